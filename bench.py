@@ -33,14 +33,23 @@ A "step" is ONE whole pass of the hot path over one sample's run stream, whole-c
 The run stream is synthetic (tools/synth.py) and is resident in HBM before the
 timed region, as the contract asks; value = records / step time, on the kernel the `pandepth`
 executable itself runs for this mode (its GPU decoder leaves the sample's runs resident and deferred,
-then pd_scan_reduce_windows takes the direct path).  BAM decode is NOT in `value`; it IS in the
-"e2e" object of the same JSON line: the executable and the reference binary on one payload BAM
-generated on this box (tools/bamgen), process wall clock, outputs compared byte for byte.  The
-reference's run there is also the contract's "cpu_baseline".  e2e["annotation"] is the same pair of executables
-in `-g` mode on that BAM (configs[2]'s annotation density: index-driven fetch of the targets' chunks, decoded on the GPU).
+then pd_scan_reduce_windows takes the direct path).  BAM decode is NOT in this step.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under torch.distributed.run,
-one rank per GPU, each rank holding its own sample ("one BAM per GPU", #.list mode).
+Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]; for N > 1 under
+torch.distributed.run, one rank per GPU, each rank holding its own sample ("one BAM per GPU", #.list mode).
+
+A plain run does only what `value` needs: the resident sample is made, W steps warm up, K steps are timed, and one
+JSON line is printed (`ms_per_step` = the time of one timed step).  --dump-outputs DIR writes what the last timed step
+handed back (the bins' offsets, CoveredSite and TotalDepth) as DIR/<name>.npy in float64; the sample is seeded, so the
+same arguments give the same inputs on every run.
+
+--full adds everything else to the same line, as before: the N > 1 sum's self-check, the compact sample's making,
+the arrays path's cross-check, configs[2] / configs[3] on the same sample, and the end-to-end legs — the executable
+and the reference binary on payload BAMs generated on this box (tools/bamgen), process wall clock, outputs compared
+byte for byte ("e2e"; the reference's run there is the contract's "cpu_baseline"; e2e["annotation"] is the same pair
+in `-g` mode on that BAM; "e2e_multi" the `#.list` run).  In a --full line `value` / `ms_per_step` / `steps` are, as
+since round 6, the executable's: records / MEDIAN process wall on the configs[1] file (N > 1: the `#.list` run), its
+runs counted by --e2e-warmup / --e2e-steps; the device step above stays beside it as "device_step".
 
 --config gff | w100a: the same contract line for BASELINE.json's other two full-size configurations on the same sample
 (they are parity-test cases, tests/test_gpu_fullsize.py; these legs give their kernels a measured roofline):
@@ -88,6 +97,30 @@ def cpu_quota():
 
 
 RUN_PAUSE_S = 2.5
+
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
+
+
+def progress(msg):
+    """--full's legs run for minutes: one line on stderr as each one starts (the result line alone goes to stdout)"""
+    sys.stderr.write("[bench] %s\n" % msg)
+    sys.stderr.flush()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as path/<name>.npy in float64 (every value
+    here is an integer below 2^53: exact).  Above DUMP_LIMIT_BYTES in all, each array keeps a fixed, seeded sample of its
+    elements, and the sampled indices go beside it as <name>_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v).ravel() for k, v in arrays.items()}
+    total = sum(8 * a.size for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.size * (DUMP_LIMIT_BYTES / 2) / total))        # half the room: the indices go beside the values
+            idx = np.sort(np.random.default_rng(20261016).choice(a.size, min(keep, a.size), replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
 
 
 def _best_wall(cmd, reps, env=None, want_stderr=False):
@@ -381,6 +414,7 @@ def e2e_multi_leg(n_bams, records, steps=3, warmup=1):
         free = os.statvfs(td).f_bavail * os.statvfs(td).f_frsize
         while records > 1e7 and n_bams * records * 56 > 0.6 * free:
             records = int(records // 2)
+        progress("e2e_multi: generating %d BAMs of %d records" % (n_bams, int(records)))
         t0 = time.perf_counter()
         lst = os.path.join(td, "s.list")
         total_bytes = 0
@@ -456,10 +490,12 @@ def e2e_leg(records, site_records, fullsize_site=False, steps=5, warmup=1):
         asked = int(records)
         while records > 2e7 and records * 56 > 0.8 * free:
             records = int(records // 2)
+        progress("e2e: generating the payload BAM (%d records)" % int(records))
         t0 = time.perf_counter()
         g = subprocess.run([gen, "-o", bam, "-n", str(int(records)), "-t", str(min(32, os.cpu_count() or 1))], check=True,
                            stderr=subprocess.PIPE, timeout=3600)
         t_gen = time.perf_counter() - t0
+        progress("e2e: %d + %d runs of the executable" % (warmup, steps))
         size = os.path.getsize(bam)
         threads = max(4, min(16, quota))
         mine = os.path.join(td, "mine")
@@ -514,6 +550,7 @@ def e2e_leg(records, site_records, fullsize_site=False, steps=5, warmup=1):
             }
         cb = None
         if os.access(ref, os.X_OK):
+            progress("e2e: the reference binary")
             # the reference at -t <the job's CPU quota> (no oversubscription on these boxes).  Rounds 4-5 also timed -t 36 (12 chromosome workers x
             # (1 + 2 BGZF threads): its best shape on an unrestricted host) and kept the faster: on the 16-CPU quota of the GPU boxes that was
             # -t 16 every time (23.5 s against 27.8-28.2 s, profiles/r05_bench*.json), so the second 28 s run is no longer made
@@ -535,11 +572,13 @@ def e2e_leg(records, site_records, fullsize_site=False, steps=5, warmup=1):
                             "cache; pandepth_ref -t %d (= the job's CPU quota; -t 36 was slower on these boxes in rounds 4-5) on a cgroup quota of %d CPUs, "
                             "%.2f s wall" % (records, size / 1e9, size / records, rthreads, quota, w_ref)}
         if os.environ.get("PD_BENCH_E2E_ANNOTATION", "1") == "1":
+            progress("e2e: annotation (-g)")
             try:                                    # an extra: whatever goes wrong here must not cost the line its e2e object
                 e2e["annotation"] = e2e_annotation(td, bam, cli, ref, threads, records)
             except Exception as ex:                 # noqa: BLE001
                 e2e["annotation"] = {"failed": repr(ex)[:300]}
         if fullsize_site and records >= 9e8 and os.statvfs(td).f_bavail * os.statvfs(td).f_frsize > 12e9:
+            progress("e2e: -w 100 -a at full size")
             try:                                    # configs[3] at full size on this very file (9.5 GB of output)
                 e2e["site_windows_fullsize"] = e2e_site_windows_fullsize(td, bam, cli, threads, records)
             except Exception as ex:                 # noqa: BLE001
@@ -551,11 +590,13 @@ def e2e_leg(records, site_records, fullsize_site=False, steps=5, warmup=1):
                                     ("q40", ["-Q", "40"], float(os.environ.get("PD_BENCH_Q40_RECORDS", "1.0e8")))):
             if recs <= 0:
                 continue
+            progress("e2e: " + key)
             try:
                 e2e[key] = e2e_variant_leg(td, gen, cli, ref, threads, key, gen_args, recs)
             except Exception as ex:                 # noqa: BLE001
                 e2e[key] = {"failed": repr(ex)[:300]}
         if site_records > 0:
+            progress("e2e: -w 100 -a")
             try:
                 e2e["site_windows"] = e2e_site_windows(td, gen, cli, ref, threads, site_records)
             except Exception as ex:                 # noqa: BLE001
@@ -629,6 +670,11 @@ def config_leg(args, which, eng, pda, synth, torch, dist, first, other, lens, ra
     keys = ("reset", "fill", "scatter_index", "scatter_tiles", "scatter_finish", "scan", "reduce_intervals", "reduce_windows")
     prof = {k: eng.profile_get(k) for k in keys}
     eng.profile(False)
+    if args.dump_outputs and rank == 0:
+        if which == "gff":
+            dump_outputs(args.dump_outputs, {"covered_sites": res[0], "total_depth": res[1]})
+        else:
+            dump_outputs(args.dump_outputs, {"window_offsets": res[0], "covered_sites": res[1], "total_depth": res[2]})
     site = None
     if which == "w100a" and rank == 0:
         # the per-site text needs every cell on the host: the largest contig's cells over PCIe (pageable destination)
@@ -719,6 +765,13 @@ def main():
                     help="records of the `-w 100 -a` end-to-end pair (configs[3]; 0 = skip)")
     ap.add_argument("--config", choices=["chr", "gff", "w100a"], default="chr",
                     help="chr = configs[1] (BASELINE.json's metric; default); gff = configs[2]; w100a = configs[3]")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to DIR/<name>.npy (float64; a seeded sample above 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and legs beyond `value`: N > 1 self-check, sample preparation, arrays path, configs[2] / [3], "
+                         "the end-to-end legs against the reference binary")
+    ap.add_argument("--e2e-steps", type=int, default=3, help="--full: timed runs of the executable in the end-to-end legs")
+    ap.add_argument("--e2e-warmup", type=int, default=1, help="--full: untimed runs of the executable before them")
     args = ap.parse_args()
     e2e_size_note = "asked for"
     if args.e2e_records < 0:
@@ -879,7 +932,7 @@ def main():
         eng.synchronize()
 
     selfcheck = None
-    if use_dist:
+    if use_dist and args.full:
         # the multi-GPU sum against what it must equal: depth sums are additive, so the bins of the summed
         # result (rank 0) = the sum over ranks of each rank's own single-GPU bins (no wrap below 2^18)
         scatter()
@@ -903,6 +956,8 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"window_offsets": res[0], "covered_sites": res[1], "total_depth": res[2]})
 
     PROF_KEYS = ("reset", "fill", "scatter_index", "scatter_tiles", "scatter_finish", "scatter_atomic", "tile_carry",
                  "scan_reduce_windows", "export_i8", "import_i8", "export_i4", "slice_sweep", "gather_windows", "direct_tiles",
@@ -916,7 +971,7 @@ def main():
     # at the end of a file: bucket starts from the marks, and the counting sort of the later runs.  value_from_decoder_output charges
     # that second part to every step — the rate of ONE pass over a sample exactly as the decoder's batches leave it.
     sample_prep = None
-    if used_compact and not use_dist:
+    if args.full and used_compact and not use_dist:
         eng.synchronize()
         eng.profile(True)
         PREP = 3
@@ -934,7 +989,7 @@ def main():
 
     # the general (materialising) path next to the direct one: a few untimed-for-`value` steps, same inputs
     arrays_path = None
-    if direct and not use_dist:
+    if args.full and direct and not use_dist:
         ASTEPS = 3
         direct = False
         eng.keep_deferred(False)
@@ -954,7 +1009,7 @@ def main():
         arrays_path = {"ms_per_step": ta / ASTEPS * 1e3, "steps": ASTEPS, "equals_direct": same, "prof": prof_a}
         direct = True
 
-    run_multi = world > 1 and args.e2e_multi_records > 0
+    run_multi = args.full and world > 1 and args.e2e_multi_records > 0
     if run_multi:
         # every rank lets go of its GPU before rank 0 starts the executable, which makes its own context on every GPU
         dist.barrier()
@@ -1082,15 +1137,16 @@ def main():
                                              if traffic else None),
                     "avg_launch_ms": kd["avg_ms"], "avg_launch_ms_rocprof": rocprof_avg, "algorithmic_bytes_per_launch": kd["algorithmic_bytes"]}
         cb, e2e = {"value": None, "unit": "records/s", "cores": 0, "kind": "reference",
-                   "sample": "not timed: the end-to-end leg runs on rank 0 of a 1-GPU invocation with --e2e-records > 0"}, None
+                   "sample": "not timed: the end-to-end leg runs on rank 0 of a 1-GPU invocation with --full and --e2e-records > 0"}, None
         # configs[2] and configs[3] on the same resident sample, three steps each after the timed region (their kernels are
         # the general path's: scatter into the arrays, write-back sweep, interval / narrow-window reductions); `--config gff |
         # w100a` runs either as a contract line of its own
         configs = None
-        if world == 1 and not use_dist and os.environ.get("PD_BENCH_CONFIG_LEGS", "1") == "1":
+        if args.full and world == 1 and not use_dist and os.environ.get("PD_BENCH_CONFIG_LEGS", "1") == "1":
+            progress("configs[2] / configs[3] on the resident sample")
             configs = {}
             sub = argparse.Namespace(**vars(args))
-            sub.steps, sub.warmup = 3, 1
+            sub.steps, sub.warmup, sub.dump_outputs = 3, 1, None
             for which in ("gff", "w100a"):
                 try:
                     ln = config_leg(sub, which, eng, pda, synth, torch, dist, first, other, lens, rank, world, use_dist)
@@ -1099,7 +1155,7 @@ def main():
                     configs[which]["check"] = ln["config"]["check"]
                 except Exception as ex:                            # noqa: BLE001 — an extra must not cost the line
                     configs[which] = {"failed": repr(ex)[:300]}
-        if world == 1 and args.e2e_records > 0:
+        if args.full and world == 1 and args.e2e_records > 0:
             try:
                 if runs8 is not None:
                     eng.reset(); eng.runs_destroy(runs8); runs8 = None
@@ -1107,14 +1163,14 @@ def main():
                 del first, other                                   # ... and the bench sample's 13 GB of runs go too
                 torch.cuda.empty_cache()
                 e2e, cb = e2e_leg(int(args.e2e_records), int(args.e2e_site_records), fullsize_site=os.environ.get("PD_BENCH_E2E_FULLSIZE_SITE", "1") == "1",
-                                  steps=args.steps, warmup=args.warmup)
+                                  steps=args.e2e_steps, warmup=args.e2e_warmup)
                 if isinstance(e2e, dict):
                     e2e["size_note"] = e2e_size_note
             except Exception as ex:                                # never lose the GPU line over this leg
                 e2e = {"failed": repr(ex)}
                 cb = {"value": None, "unit": "records/s", "cores": 0, "kind": "failed", "sample": repr(ex)}
         e2e_multi = None
-        if args.e2e_multi_records > 0 and (world > 1 or args.e2e_records > 0):
+        if args.full and args.e2e_multi_records > 0 and (world > 1 or args.e2e_records > 0):
             try:
                 if eng.h:                                          # (N > 1: this rank's context goes before the executable makes its own on every GPU)
                     if runs8 is not None:
@@ -1125,7 +1181,7 @@ def main():
                     first = other = None
                     torch.cuda.empty_cache()
                 # N > 1: the `#.list` run over N BAMs on N GPUs IS the step the line's value is quoted on (K timed runs); N = 1: a leg beside it
-                e2e_multi = e2e_multi_leg(world, int(args.e2e_multi_records), steps=(args.steps if world > 1 else 3), warmup=(min(args.warmup, 2) if world > 1 else 1))
+                e2e_multi = e2e_multi_leg(world, int(args.e2e_multi_records), steps=(args.e2e_steps if world > 1 else 3), warmup=(min(args.e2e_warmup, 2) if world > 1 else 1))
             except Exception as ex:                                # noqa: BLE001
                 e2e_multi = {"failed": repr(ex)[:300]}
         if configs is not None and isinstance(e2e, dict):
@@ -1141,7 +1197,8 @@ def main():
         # which the EXECUTABLE turns the BAM file(s) into the .stat.gz table, process wall clock.  Since round 6 that is `value` (rounds
         # 1-5 quoted the repeated device pass over a resident sample here — three orders of magnitude above what a user gets; it stays in
         # the line as `device_step`, with its roofline).  N = 1: the configs[1] file through `pandepth -i s.bam`; N > 1: N BAMs through
-        # `pandepth -i s.list` on the N GPUs.  A step = one run of the executable; `warmup` untimed runs, `steps` timed ones, MEDIAN wall.
+        # `pandepth -i s.list` on the N GPUs.  A step = one run of the executable; `warmup` untimed runs, `steps` timed ones, MEDIAN wall
+        # (--e2e-warmup / --e2e-steps of them).  Those legs run with --full only: a plain run's `value` is the device step.
         device_step = {"records_per_s": value, "ms_per_step": ms_step, "steps": args.steps, "warmup": args.warmup,
                        "what": "pd_reset + pd_push_runs (the sample resident in HBM in the decoder's compact form) + pd_scan_reduce_windows incl. copy-back: a REPEATED pass "
                                "of the statistics kernels over one resident sample; `roofline` is this step's dominant kernel",
@@ -1150,18 +1207,18 @@ def main():
         if world == 1 and isinstance(e2e, dict) and isinstance(e2e.get("pandepth"), dict):
             pe = e2e["pandepth"]
             headline = {"value": pe["records_per_s"], "ms": pe["wall_s"] * 1e3, "steps": pe["wall_s_spread"]["runs"], "spread": pe["wall_s_spread"],
-                        "records": e2e["records"], "is": "the `pandepth` executable on the configs[1] BAM (%d records, %.1f GB), exec to exit, warm page cache: "
+                        "warmup": args.e2e_warmup, "records": e2e["records"], "is": "the `pandepth` executable on the configs[1] BAM (%d records, %.1f GB), exec to exit, warm page cache: "
                         "file read + PCIe + GPU inflate + record walk + statistics + table; median of %d timed runs" % (e2e["records"], e2e["bam_bytes"] / 1e9, pe["wall_s_spread"]["runs"])}
         elif world > 1 and isinstance(e2e_multi, dict) and isinstance(e2e_multi.get("pandepth"), dict):
             pm = e2e_multi["pandepth"]
             headline = {"value": pm["records_per_s"], "ms": pm["wall_s"] * 1e3, "steps": pm["wall_s_spread"]["runs"], "spread": pm["wall_s_spread"],
-                        "records": e2e_multi["n_bams"] * e2e_multi["records_per_bam"],
+                        "warmup": min(args.e2e_warmup, 2), "records": e2e_multi["n_bams"] * e2e_multi["records_per_bam"],
                         "is": "`pandepth -i s.list` over %d BAMs of %d records on %d GPUs (one process, a context and a rank thread per GPU), exec to exit; median of %d timed runs"
                               % (e2e_multi["n_bams"], e2e_multi["records_per_bam"], world, pm["wall_s_spread"]["runs"])}
         line = {
             "metric": "alignment records/sec (whole node) + wall-clock, 3 Gb genome 50x BAM (whole-chromosome mode, BAM file -> chr.stat.gz)",
             "value": (headline["value"] if headline else value), "unit": "records/s", "n_gpus": world,
-            "steps": (headline["steps"] if headline else args.steps), "warmup": args.warmup,
+            "steps": (headline["steps"] if headline else args.steps), "warmup": (headline["warmup"] if headline else args.warmup),
             "ms_per_step": (headline["ms"] if headline else ms_step), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "int32", "data": "synthetic",
             "wall_s_spread": (headline["spread"] if headline else None),
@@ -1175,8 +1232,8 @@ def main():
                                    "whole-chromosome mode" % G,
                        "records_per_gpu": (headline["records"] // world if headline else R), "runs_sorted": n_first, "runs_unsorted": n_other,
                        "value_is": (headline["is"] if headline else
-                                    "NO end-to-end leg in this invocation (--e2e-records 0 / no room in /tmp): `value` falls back to the device step — a REPEATED pass of the "
-                                    "statistics kernels over one sample resident in HBM"),
+                                    "NO end-to-end leg in this invocation (a plain run: it comes with --full; or --e2e-records 0 / no room for the file): `value` is the "
+                                    "device step — a REPEATED pass of the statistics kernels over one sample resident in HBM"),
                        "device_step_is": device_step["what"],
                        "cells": int(n_words), "path": ("direct (difference windows stay in LDS" + (", exported as 4-bit images)" if use_dist else "; the kernel path the pandepth CLI runs in this mode)") +
                                 (" — sample resident in the compact form (8 B/run, grouped by 512-cell bucket with exact bounds), as pd_decode_end leaves it" if used_compact else "")) if direct
