@@ -160,6 +160,18 @@ int pd_scan_reduce_windows(pd_ctx *ctx, uint32_t w, uint32_t min_dep, unsigned w
                            uint32_t *cover, uint64_t *sum);
 int pd_reduce_windows(pd_ctx *ctx, uint32_t w, uint32_t min_dep, uint32_t *cover, uint64_t *sum);
 
+/* Depth distribution.  hist[t * n_bins + k] = number of counted cells of contig t whose depth is k (k < n_bins - 1);
+ * the last bin counts depth >= n_bins - 1.  2 <= n_bins <= 4097, else PD_EINVAL.  Cells [0, contig_len[t]) only.
+ *   pd_scan_depth_histogram : whole contigs, fused — reads the DIFFERENCE arrays once, writes no depth, state stays
+ *                             "accumulating"; depth wrapped to wrap_bits as pd_scan would.  A DEFERRED sample
+ *                             (pd_keep_deferred) is materialised first, as the fall-back of pd_scan_reduce_windows does;
+ *                             every later call gives the results it gave before.
+ *   pd_depth_histogram      : after pd_scan, from the depth arrays.  regs == NULL / n == 0: whole contigs; otherwise only
+ *                             the cells [first-1, second) of the given regions, which must be sorted by (tid, first) and
+ *                             must not overlap (PD_EINVAL otherwise); each region counts into its contig's row. */
+int pd_scan_depth_histogram(pd_ctx *ctx, uint32_t n_bins, unsigned wrap_bits, uint64_t *hist);
+int pd_depth_histogram(pd_ctx *ctx, const pd_region *regs, size_t n, uint32_t n_bins, uint64_t *hist);
+
 /* Replaces the per-site read loop PD:4278-4281: copies depth cells [beg, beg+n) of contig tid
  * to the host.  Requires pd_scan first. */
 int pd_read_depth(pd_ctx *ctx, int32_t tid, uint32_t beg, size_t n, uint32_t *out);

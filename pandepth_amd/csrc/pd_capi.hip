@@ -245,6 +245,7 @@ struct pd_ctx {
     uint32_t dec_max_redo = 256;                                  // ... with at most this many segments walking again per batch ("decode_max_redo")
     std::atomic<uint64_t> dec_n_fast{0}, dec_n_slow{0}, dec_n_redo{0};   // batches finished without / with the host's chain check; segments the device walked again
     uint32_t direct_sample = 256;                                 // index stride of the direct path (runs)
+    int hist_variant = 1;                                         // "hist_variant": the histogram kernels' LDS form (launch_sweep_hist): 1 = one copy per workgroup, folded (measured best)
     int direct_un = 0;                                           // 0 = the default form of the wide direct kernel (launch_direct_tiles)
     bool all_valid_host = false;
     std::vector<Pending> pend;
@@ -888,6 +889,7 @@ int pd_set_param(pd_ctx *c, const char *name, uint64_t value)
     if (!strcmp(name, "decode_h2d_lanes")) { c->dec_h2d_lanes = value > 1 ? 2 : 1; return PD_OK; }
     if (!strcmp(name, "decode_sync_event")) { c->dec_sync_event = value != 0; return PD_OK; }
     if (!strcmp(name, "decode_max_redo")) { c->dec_max_redo = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
+    if (!strcmp(name, "hist_variant")) { if (value > 3) return fail(c, PD_EINVAL, "hist_variant must be in [0, 3]"); c->hist_variant = (int)value; return PD_OK; }
     if (!strcmp(name, "decode_near_span")) { c->dec_near_span = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
     return fail(c, PD_EINVAL, std::string("unknown parameter ") + name);
 }
@@ -1253,6 +1255,109 @@ int pd_reduce_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t *cover, 
     if (int rs = need_state(c, 1, "pd_reduce_windows")) return rs;
     HIPOK(c, hipSetDevice(c->device));
     return windows_common(c, w, min_dep, 0xFFFFFFFFu, true, cover, sum);
+}
+
+// ---- depth histograms ----
+// The rows go to a zeroed uint64 array in the scratch buffer (behind `lead` bytes the caller uses), the kernels add into it, the
+// host gets it back.  Grid: eight workgroups per CU, each a run of tiles / pieces (one flush of its non-zero bins per contig).
+static int hist_finish(pd_ctx *c, uint64_t *d_hist, size_t b_hist, uint64_t *hist)
+{
+    HIPOK(c, hipGetLastError());
+    HIPOK(c, hipMemcpyAsync(hist, d_hist, b_hist, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(c, hipStreamSynchronize(c->stream));
+    return PD_OK;
+}
+
+int pd_scan_depth_histogram(pd_ctx *c, uint32_t n_bins, unsigned wrap_bits, uint64_t *hist)
+{
+    if (!c || !hist || n_bins < 2 || n_bins > 4097 || wrap_bits > 32) return PD_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int rs = need_state(c, 0, "pd_scan_depth_histogram")) return rs;
+    HIPOK(c, hipSetDevice(c->device));
+    int rc = flush_pending(c);                                   // a deferred sample is materialised (later calls see it as before)
+    if (rc) return rc;
+    rc = check_words(c);
+    if (rc) return rc;
+    const uint32_t mask = (wrap_bits == 0 || wrap_bits == 32) ? 0xFFFFFFFFu : ((1u << wrap_bits) - 1u);
+    const size_t b_hist = (size_t)c->n_contigs * n_bins * 8;
+    rc = ensure_scratch(c, b_hist + 64);
+    if (rc) return rc;
+    uint64_t *d_hist = (uint64_t *)c->scratch;
+    HIPOK(c, hipMemsetAsync(d_hist, 0, b_hist, c->stream));
+    { ProfScope ps(c, "tile_carry"); launch_tile_carry(c->stream, c->sums, c->bsum, c->carry, (uint32_t)c->n_tiles); }
+    {
+        ProfScope ps(c, "scan_depth_histogram");
+        TileMap tm{c->d_tile_contig, c->d_off, c->d_len, nullptr};
+        if (launch_sweep_hist(c->stream, c->buf, c->carry, (uint32_t)c->n_tiles, mask, tm, c->hstate, false, n_bins,
+                              (unsigned long long *)d_hist, (unsigned)c->n_cu * 8, c->hist_variant))
+            return fail(c, PD_EHIP, "histogram sweep: cannot reserve LDS");
+    }
+    return hist_finish(c, d_hist, b_hist, hist);
+}
+
+int pd_depth_histogram(pd_ctx *c, const pd_region *regs, size_t n, uint32_t n_bins, uint64_t *hist)
+{
+    if (!c || !hist || (n && !regs) || n_bins < 2 || n_bins > 4097) return PD_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int rs = need_state(c, 1, "pd_depth_histogram")) return rs;
+    HIPOK(c, hipSetDevice(c->device));
+    const size_t b_hist = (size_t)c->n_contigs * n_bins * 8, b_histr = (b_hist + 15) / 16 * 16;
+    if (!regs || n == 0) {                                       // whole contigs: the histogram sweep over the depth (int4 rows)
+        int rc = ensure_scratch(c, b_hist + 64);
+        if (rc) return rc;
+        uint64_t *d_hist = (uint64_t *)c->scratch;
+        HIPOK(c, hipMemsetAsync(d_hist, 0, b_hist, c->stream));
+        {
+            ProfScope ps(c, "depth_histogram");
+            TileMap tm{c->d_tile_contig, c->d_off, c->d_len, nullptr};
+            if (launch_sweep_hist(c->stream, c->buf, nullptr, (uint32_t)c->n_tiles, 0xFFFFFFFFu, tm, nullptr, true, n_bins,
+                                  (unsigned long long *)d_hist, (unsigned)c->n_cu * 8, c->hist_variant))
+                return fail(c, PD_EHIP, "histogram sweep: cannot reserve LDS");
+        }
+        return hist_finish(c, d_hist, b_hist, hist);
+    }
+    // regions: checked, clipped to [0, len), cut into pieces of at most 16384 cells (Piece.region = the contig)
+    constexpr uint32_t PIECE = 16384;
+    std::vector<Piece> pieces;
+    pieces.reserve(n + n / 8);
+    int32_t prev_tid = -1; int64_t prev_first = 0, prev_end = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const pd_region &r = regs[i];
+        if (r.tid < 0 || r.tid >= c->n_contigs) return fail(c, PD_EINVAL, "pd_depth_histogram: contig id out of range");
+        const int64_t b0 = (int64_t)r.first - 1, e0 = r.second;
+        if (r.tid < prev_tid || (r.tid == prev_tid && r.first < prev_first))
+            return fail(c, PD_EINVAL, "pd_depth_histogram: regions not sorted by (tid, first)");
+        if (r.tid != prev_tid) prev_end = INT64_MIN;
+        if (e0 > b0) {
+            if (b0 < prev_end) return fail(c, PD_EINVAL, "pd_depth_histogram: regions overlap");
+            prev_end = e0;
+        }
+        prev_tid = r.tid; prev_first = r.first;
+        int64_t b = b0 < 0 ? 0 : b0, e = e0;
+        if (e > (int64_t)c->len[r.tid]) e = (int64_t)c->len[r.tid];
+        for (int64_t p = b; p < e; p += PIECE) {
+            Piece pc; pc.start = c->off[r.tid] + (uint64_t)p;
+            pc.count = (uint32_t)((e - p) < PIECE ? (e - p) : PIECE); pc.region = (uint32_t)r.tid;
+            pieces.push_back(pc);
+        }
+    }
+    if (pieces.size() > 0xFFFFFFF0ull) return fail(c, PD_EINVAL, "pd_depth_histogram: too many regions");
+    const size_t b_p = pieces.size() * sizeof(Piece);
+    int rc = ensure_scratch(c, b_histr + b_p + 64);
+    if (rc) return rc;
+    unsigned char *s = (unsigned char *)c->scratch;
+    uint64_t *d_hist = (uint64_t *)s;
+    Piece *d_p = (Piece *)(s + b_histr);
+    HIPOK(c, hipMemsetAsync(d_hist, 0, b_hist, c->stream));
+    if (!pieces.empty()) HIPOK(c, hipMemcpyAsync(d_p, pieces.data(), b_p, hipMemcpyHostToDevice, c->stream));
+    HIPOK(c, hipStreamSynchronize(c->stream));          // pieces is a local
+    {
+        ProfScope ps(c, "depth_histogram_regions");
+        if (launch_hist_pieces(c->stream, c->buf, d_p, (uint32_t)pieces.size(), n_bins, (unsigned long long *)d_hist,
+                               (unsigned)c->n_cu * 8, c->hist_variant))
+            return fail(c, PD_EHIP, "histogram of regions: cannot reserve LDS");
+    }
+    return hist_finish(c, d_hist, b_hist, hist);
 }
 
 int pd_reduce_intervals(pd_ctx *c, const pd_region *regs, size_t n, uint32_t min_dep, int32_t *cover, uint64_t *sum)

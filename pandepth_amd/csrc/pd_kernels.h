@@ -132,6 +132,14 @@ void launch_window_gather(hipStream_t st, const TilePart *part, TileMap tm, int3
 void launch_reduce_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces,
                           uint32_t min_dep, int *cover, unsigned long long *sum);
 
+// depth histograms: hist[contig * n_bins + bin] (uint64, zeroed by the caller) += cells; `grid` workgroups each take a run of
+// tiles / pieces.  variant: bit 0 = one LDS copy per workgroup instead of one per wave, bit 1 = no folding of equal neighbours.
+// Pieces: Piece.region = contig id, sorted by contig.  Returns a hipError_t (LDS reservation), 0 on success.
+int launch_sweep_hist(hipStream_t st, const int *buf, const int *carry, uint32_t n_tiles, uint32_t wrap_mask, TileMap tm,
+                      const uint8_t *hstate, bool from_depth, uint32_t n_bins, unsigned long long *hist, unsigned grid, int variant);
+int launch_hist_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, uint32_t n_bins,
+                       unsigned long long *hist, unsigned grid, int variant);
+
 // GPU-side BAM decode (pd_bgzf.hip)
 void launch_bgzf_inflate(hipStream_t st, const uint8_t *comp, const pd_bgzf_block *blk, uint32_t n_blk, uint8_t *out,
                          int *status, void *scratch);

@@ -1960,18 +1960,14 @@ __global__ __launch_bounds__(1024) void k_tile_carry(const int *sums, const int 
 
 typedef int v4i_nt __attribute__((ext_vector_type(4)));
 
-template <bool WRITE, bool WIN, bool FROM_DEPTH>
-__global__ __launch_bounds__(WG) void k_sweep(int *buf, const int *carry, uint32_t wrap_mask,
-                                              const TileMap tmap, WinArgs wa, const uint8_t *hstate, uint32_t tile0)
+// Load one tile (8 rows of int4 per wave) and, unless FROM_DEPTH, turn its difference array into wrapped depth in registers:
+// the scan shared by k_sweep and k_sweep_hist.  `p4` points at this lane's first int4 of the tile, `t` is the tile's global
+// index (hstate / carry), `wtot` four ints of LDS.  Contains one __syncthreads (not FROM_DEPTH): every thread must call it.
+template <bool FROM_DEPTH>
+__device__ __forceinline__ void sweep_tile_load_scan(int4 (&v)[TILE / (WG * 4)], const int4 *p4, uint64_t t, const int *carry,
+                                                     uint32_t wrap_mask, const uint8_t *hstate, int *wtot, int lane, int wv)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ int wtot[4];
     constexpr int ROWS = TILE / (WG * 4);                        // 8
-    // tile0: the sweep of a slice (a rank's share of the summed depth in the sharded list mode): `buf` holds tiles tile0, tile0 + 1, ...
-    const uint64_t t = (uint64_t)blockIdx.x + tile0;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int4 *p4 = reinterpret_cast<int4 *>(buf + (uint64_t)blockIdx.x * TILE) + wv * (ROWS * 64) + lane;
-    int4 v[ROWS];
     // a half-tile nobody has written since the reset holds stale bytes and counts as zeros; waves
     // 0-1 cover the first 4096 cells of the tile, waves 2-3 the second (wave-uniform branch)
     const bool live = FROM_DEPTH || hstate[t * (TILE / PD_HALF) + (wv >> 1)] != 0;
@@ -2016,6 +2012,21 @@ __global__ __launch_bounds__(WG) void k_sweep(int *buf, const int *carry, uint32
             v[r].w = (int)((uint32_t)(v[r].w + b) & wrap_mask);
         }
     }
+}
+
+template <bool WRITE, bool WIN, bool FROM_DEPTH>
+__global__ __launch_bounds__(WG) void k_sweep(int *buf, const int *carry, uint32_t wrap_mask,
+                                              const TileMap tmap, WinArgs wa, const uint8_t *hstate, uint32_t tile0)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ int wtot[4];
+    constexpr int ROWS = TILE / (WG * 4);                        // 8
+    // tile0: the sweep of a slice (a rank's share of the summed depth in the sharded list mode): `buf` holds tiles tile0, tile0 + 1, ...
+    const uint64_t t = (uint64_t)blockIdx.x + tile0;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int4 *p4 = reinterpret_cast<int4 *>(buf + (uint64_t)blockIdx.x * TILE) + wv * (ROWS * 64) + lane;
+    int4 v[ROWS];
+    sweep_tile_load_scan<FROM_DEPTH>(v, p4, t, carry, wrap_mask, hstate, wtot, lane, wv);
     if (WRITE) {
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) {
@@ -2175,6 +2186,135 @@ __global__ __launch_bounds__(WG) void k_reduce_pieces(const int *depth, const Pi
 #pragma unroll
     for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0 && c) { atomicAdd(&cover[pc.region], c); atomicAdd(&sum[pc.region], s); }
+}
+
+// ------------------------------------------------------------------------------------------
+// depth histograms (pd_scan_depth_histogram / pd_depth_histogram).  Counts go into LDS, one copy of
+// the n_bins 32-bit counters per wave (COPIES = 4) or one for the workgroup (COPIES = 1); a
+// workgroup covers a RUN of tiles (or pieces) and adds its non-zero bins into the contig's uint64
+// row with 64-bit integer device atomics only when the contig changes and at the end (exact, the
+// same bits every run).  Depth clusters: at 50x a row's 256 cells fall into a few dozen bins, so
+// a lane folds equal neighbours of its four cells into one add (FOLD), and a row whose 256 cells
+// share one bin (empty stretches, piles above the last bin) is one add by lane 0.
+// ------------------------------------------------------------------------------------------
+struct HistArgs { uint32_t n_bins, nbp; unsigned long long *hist; };   // nbp: counters per LDS copy
+
+// the first n (0..4) of a lane's four consecutive cells, as bins, into LDS counters h (wave-uniform call)
+template <bool FOLD>
+__device__ __forceinline__ void hist_lane4(uint32_t *h, const uint32_t (&b)[4], uint32_t n, int lane)
+{
+    const uint32_t b0 = __builtin_amdgcn_readfirstlane(b[0]);
+    const bool uni = n == 4 && b[0] == b0 && b[1] == b0 && b[2] == b0 && b[3] == b0;
+    if (__all(uni)) { if (lane == 0) atomicAdd(&h[b0], 256u); return; }
+    if (!FOLD) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) if ((uint32_t)q < n) atomicAdd(&h[b[q]], 1u);
+        return;
+    }
+    if (!n) return;
+    uint32_t cur = b[0], c = 1;
+#pragma unroll
+    for (int q = 1; q < 4; ++q) {
+        if ((uint32_t)q >= n) break;
+        if (b[q] == cur) ++c; else { atomicAdd(&h[cur], c); cur = b[q]; c = 1; }
+    }
+    atomicAdd(&h[cur], c);
+}
+
+// Before the barrier that hands the LDS counters to hist_flush: every ds_add this wave issued has completed (s_waitcnt
+// lgkmcnt(0); vmcnt / expcnt left alone).  The compiler put no such wait in front of the barrier on the contig-change path, and
+// the workgroup-wide copy lost adds of other waves there (tools/dist_bench.py on the 3 Gb sample: profiles/r07_dist_bench_before_lds_wait.json).
+__device__ __forceinline__ void lds_drain() { __builtin_amdgcn_s_waitcnt(0xC07F); }
+
+// the workgroup's counters of one contig into its row of the histogram, zeroed behind (between two __syncthreads)
+template <int COPIES>
+__device__ __forceinline__ void hist_flush(uint32_t *hs, const HistArgs &ha, uint32_t ctg)
+{
+    unsigned long long *row = ha.hist + (uint64_t)ctg * ha.n_bins;
+    for (uint32_t j = threadIdx.x; j < ha.n_bins; j += WG) {
+        uint32_t s = 0;
+#pragma unroll
+        for (int k = 0; k < COPIES; ++k) { s += hs[k * ha.nbp + j]; hs[k * ha.nbp + j] = 0; }
+        if (s) atomicAdd(&row[j], (unsigned long long)s);
+    }
+}
+
+// The fused histogram sweep: k_sweep's load + scan (sweep_tile_load_scan: hstate skip, carry, wrap mask), then every cell of
+// [local0, clen) into the bins; no depth is written.  Workgroup g covers tiles [g * tpw, (g + 1) * tpw).  FROM_DEPTH: the
+// buffer already holds depth (pd_depth_histogram over whole contigs).
+template <bool FROM_DEPTH, int COPIES, bool FOLD>
+__global__ __launch_bounds__(WG) void k_sweep_hist(const int *buf, const int *carry, uint32_t wrap_mask, const TileMap tmap,
+                                                   const uint8_t *hstate, uint32_t n_tiles, uint32_t tpw, HistArgs ha)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ int wtot[2][4];                                   // alternate per tile: a wave one tile ahead never writes what another still reads
+    constexpr int ROWS = TILE / (WG * 4);
+    uint32_t *hs = reinterpret_cast<uint32_t *>(smem);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t *h = hs + (wv % COPIES) * ha.nbp;
+    for (uint32_t j = threadIdx.x; j < COPIES * ha.nbp; j += WG) hs[j] = 0;
+    __syncthreads();
+    const uint64_t t0 = (uint64_t)blockIdx.x * tpw;
+    const uint64_t t1 = t0 + tpw < n_tiles ? t0 + tpw : n_tiles;
+    if (t0 >= t1) return;
+    const uint32_t nb1 = ha.n_bins - 1;
+    uint32_t cur = tmap.tile_contig[t0];
+    for (uint64_t t = t0; t < t1; ++t) {
+        const uint32_t ctg = tmap.tile_contig[t];
+        if (ctg != cur) { lds_drain(); __syncthreads(); hist_flush<COPIES>(hs, ha, cur); __syncthreads(); cur = ctg; }
+        const uint64_t local0 = t * TILE - tmap.contig_off[ctg];
+        const uint32_t clen = tmap.contig_len[ctg];
+        if (local0 >= clen) continue;                            // pure padding tile (uniform)
+        const int4 *p4 = reinterpret_cast<const int4 *>(buf + t * TILE) + wv * (ROWS * 64) + lane;
+        int4 v[ROWS];
+        sweep_tile_load_scan<FROM_DEPTH>(v, p4, t, carry, wrap_mask, hstate, wtot[(t - t0) & 1], lane, wv);
+        const uint64_t rest = (uint64_t)clen - local0;
+        const uint32_t left = rest < (uint64_t)TILE ? (uint32_t)rest : (uint32_t)TILE;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const uint32_t pos = (uint32_t)(wv * (ROWS * 256) + r * 256 + lane * 4);
+            const uint32_t n = pos >= left ? 0u : (left - pos < 4u ? left - pos : 4u);
+            const uint32_t b[4] = {min((uint32_t)v[r].x, nb1), min((uint32_t)v[r].y, nb1), min((uint32_t)v[r].z, nb1), min((uint32_t)v[r].w, nb1)};
+            hist_lane4<FOLD>(h, b, n, lane);
+        }
+    }
+    lds_drain();
+    __syncthreads();
+    hist_flush<COPIES>(hs, ha, cur);
+}
+
+// Regions over the materialised depth: bounded pieces (Piece.region = the contig id), sorted by contig; workgroup g covers
+// pieces [g * ppw, (g + 1) * ppw), 1024 cells per step (four consecutive cells per lane).
+template <int COPIES, bool FOLD>
+__global__ __launch_bounds__(WG) void k_hist_pieces(const uint32_t *depth, const Piece *pieces, uint32_t n_pieces, uint32_t ppw, HistArgs ha)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *hs = reinterpret_cast<uint32_t *>(smem);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t *h = hs + (wv % COPIES) * ha.nbp;
+    for (uint32_t j = threadIdx.x; j < COPIES * ha.nbp; j += WG) hs[j] = 0;
+    __syncthreads();
+    const uint64_t p0 = (uint64_t)blockIdx.x * ppw;
+    const uint64_t p1 = p0 + ppw < n_pieces ? p0 + ppw : n_pieces;
+    if (p0 >= p1) return;
+    const uint32_t nb1 = ha.n_bins - 1;
+    uint32_t cur = pieces[p0].region;
+    for (uint64_t i = p0; i < p1; ++i) {
+        const Piece pc = pieces[i];
+        if (pc.region != cur) { lds_drain(); __syncthreads(); hist_flush<COPIES>(hs, ha, cur); __syncthreads(); cur = pc.region; }
+        const uint32_t *d = depth + pc.start;
+        for (uint32_t base = 0; base < pc.count; base += WG * 4) {
+            const uint32_t c0 = base + threadIdx.x * 4;
+            const uint32_t n = c0 >= pc.count ? 0u : (pc.count - c0 < 4u ? pc.count - c0 : 4u);
+            uint32_t b[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) b[q] = (uint32_t)q < n ? min(d[c0 + q], nb1) : 0u;
+            hist_lane4<FOLD>(h, b, n, lane);
+        }
+    }
+    lds_drain();
+    __syncthreads();
+    hist_flush<COPIES>(hs, ha, cur);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3112,6 +3252,77 @@ void launch_reduce_pieces(hipStream_t st, const int *depth, const Piece *pieces,
     if (!n_pieces) return;
     hipLaunchKernelGGL(k_reduce_pieces, dim3((n_pieces + 3) / 4), dim3(WG), 0, st, depth, pieces, n_pieces,
                        min_dep, cover, sum);
+}
+
+// LDS of the histogram kernels: `copies` copies of n_bins counters (padded to 16 B)
+static size_t hist_lds_bytes(uint32_t n_bins, int copies, uint32_t *nbp)
+{
+    *nbp = (n_bins + 3u) & ~3u;
+    return (size_t)copies * *nbp * 4;
+}
+
+template <typename K>
+static int hist_lds_reserve(K kern, size_t lds)
+{
+    if (lds <= 48 * 1024) return 0;
+    return (int)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+// variant: bit 0 = one LDS copy for the workgroup (else one per wave), bit 1 = no folding of equal neighbours
+int launch_sweep_hist(hipStream_t st, const int *buf, const int *carry, uint32_t n_tiles, uint32_t wrap_mask, TileMap tm,
+                      const uint8_t *hstate, bool from_depth, uint32_t n_bins, unsigned long long *hist, unsigned grid, int variant)
+{
+    if (!n_tiles) return 0;
+    if (grid < 1) grid = 1;
+    const uint32_t tpw = (uint32_t)((n_tiles + grid - 1) / grid);
+    grid = (n_tiles + tpw - 1) / tpw;
+    HistArgs ha; ha.n_bins = n_bins; ha.hist = hist;
+    const int copies = (variant & 1) ? 1 : 4;
+    const size_t lds = hist_lds_bytes(n_bins, copies, &ha.nbp);
+#define PD_HIST_GO(FD, C, F)                                                                                           \
+    do {                                                                                                               \
+        if (int e = hist_lds_reserve(k_sweep_hist<FD, C, F>, lds)) return e;                                           \
+        hipLaunchKernelGGL((k_sweep_hist<FD, C, F>), dim3(grid), dim3(WG), lds, st, buf, carry, wrap_mask, tm, hstate, \
+                           n_tiles, tpw, ha);                                                                          \
+    } while (0)
+    switch ((from_depth ? 4 : 0) | (variant & 3)) {
+    case 0: PD_HIST_GO(false, 4, true); break;
+    case 1: PD_HIST_GO(false, 1, true); break;
+    case 2: PD_HIST_GO(false, 4, false); break;
+    case 3: PD_HIST_GO(false, 1, false); break;
+    case 4: PD_HIST_GO(true, 4, true); break;
+    case 5: PD_HIST_GO(true, 1, true); break;
+    case 6: PD_HIST_GO(true, 4, false); break;
+    default: PD_HIST_GO(true, 1, false); break;
+    }
+#undef PD_HIST_GO
+    return 0;
+}
+
+int launch_hist_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, uint32_t n_bins,
+                       unsigned long long *hist, unsigned grid, int variant)
+{
+    if (!n_pieces) return 0;
+    if (grid < 1) grid = 1;
+    const uint32_t ppw = (n_pieces + grid - 1) / grid;
+    grid = (n_pieces + ppw - 1) / ppw;
+    HistArgs ha; ha.n_bins = n_bins; ha.hist = hist;
+    const int copies = (variant & 1) ? 1 : 4;
+    const size_t lds = hist_lds_bytes(n_bins, copies, &ha.nbp);
+    const uint32_t *d = reinterpret_cast<const uint32_t *>(depth);
+#define PD_HIST_GO(C, F)                                                                                               \
+    do {                                                                                                               \
+        if (int e = hist_lds_reserve(k_hist_pieces<C, F>, lds)) return e;                                              \
+        hipLaunchKernelGGL((k_hist_pieces<C, F>), dim3(grid), dim3(WG), lds, st, d, pieces, n_pieces, ppw, ha);        \
+    } while (0)
+    switch (variant & 3) {
+    case 0: PD_HIST_GO(4, true); break;
+    case 1: PD_HIST_GO(1, true); break;
+    case 2: PD_HIST_GO(4, false); break;
+    default: PD_HIST_GO(1, false); break;
+    }
+#undef PD_HIST_GO
+    return 0;
 }
 
 } // namespace pdk

@@ -71,6 +71,9 @@ typedef struct pd_engine_api {
     int (*comm_preinit)(const int *, int);
     /* optional (NULL = a communicator's exchange buffers are made by its first collective): see pd_comm_prepare */
     int (*comm_prepare)(pd_comm *, int);
+    /* optional (NULL = the host reads the depth back and bins it): the -dist table, see pd_scan_depth_histogram / pd_depth_histogram */
+    int (*scan_depth_histogram)(pd_ctx *, uint32_t, unsigned, uint64_t *);
+    int (*depth_histogram)(pd_ctx *, const pd_region *, size_t, uint32_t, uint64_t *);
 } pd_engine_api;
 
 /* Runs one `pandepth` invocation (argv as given to main) on the engine behind `api`. */

@@ -180,6 +180,13 @@ int parse_options(int argc, char **argv, Options *o)
         else if (flag == "s") o->use_index = false;
         else if (flag == "X") { if (!arg(&v)) return 0; tune_add(v); }          // hidden: development switches (options.h)
         else if (flag == "d") { if (!arg(&v)) return 0; o->min_dep = atoi(v.c_str()); if (o->min_dep < 1) o->min_dep = 1; }
+        else if (flag == "dist") {                                               // not in the reference: the .dist.stat.gz table (README)
+            if (!arg(&v)) return 0;
+            char *end = nullptr;
+            const long n = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end != '\0' || n < 1 || n > 4096) { std::cerr << "Error: -dist should be between 1 and 4096" << std::endl; return 0; }
+            o->dist = (int)n;
+        }
         else if (flag == "help" || flag == "h") { print_help(); return 0; }
         else { std::cerr << "Error UnKnow argument -" << flag << std::endl; return 0; }
     }

@@ -28,6 +28,7 @@ struct Options {
     bool site_out = false;               // -a
     bool use_index = true;               // hidden -s clears it
     bool gc = false;
+    int dist = 0;                        // -dist N (not in the reference): <out>.dist.stat.gz, depths 0 .. N-1 and >= N per contig
 };
 
 // Returns the number of input files (0 => nothing to do / message already printed), like

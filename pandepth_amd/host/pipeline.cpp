@@ -1213,6 +1213,8 @@ std::string footer(uint64_t L, uint64_t C, uint64_t D, int64_t gc_sum = -1)
 
 using namespace pdh;
 
+static const char DIST_HEADER[] = "#Chr\tDepth\tSites\tAtLeast\tAtLeast(%)\n";       // -dist's table
+
 extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, int device)
 {
     PhaseTimer tm;
@@ -1371,6 +1373,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
         std::cout << "INFO: Input data read done" << std::endl;
         OUT.write(footer(0, 0, 0, gc ? 0 : -1));
         OUT.close();
+        if (o.dist) { GzWriter d; if (d.open(prefix + ".dist.stat.gz")) { d.write(DIST_HEADER); d.close(); } }
         return 0;
     }
     // One context per GPU.  A `#.list` input is sharded one file per GPU (round robin) when the engine
@@ -1669,6 +1672,111 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
 
     const size_t nctg = hdr.lens.size();
     uint64_t SL = 0, SC = 0, SD = 0, SG = 0;
+    // -dist N (not in the reference): the depth distribution of the cells the tables count — every cell of the tables' contigs in
+    // the whole-contig modes, the union of the regions in -g / -b — per contig and genome-wide (Chr "*"), in <prefix>.dist.stat.gz.
+    // Made after the tables are written and the per-site job started, so that their path and timing stay as they are.
+    auto write_dist = [&]() -> bool {
+        if (!o.dist) return true;
+        const uint32_t nb = (uint32_t)o.dist + 1;                // depths 0 .. N-1 exact, the last bin >= N
+        std::vector<int32_t> tids;                               // the tables' contigs, in their order
+        std::vector<pd_region> regs;                             // region modes: the sorted, merged union of the table's regions
+        if (synthetic) {
+            if (o.mode == 6) { for (size_t t = 0; t < nctg; ++t) if (rm.has((int32_t)t)) tids.push_back((int32_t)t); }
+            else for (auto &kv : rm.bins) tids.push_back(kv.first);
+        } else {
+            for (auto &kv : rm.genes) {
+                const int64_t len = (int64_t)hdr.lens[(size_t)kv.first];
+                std::vector<std::pair<int64_t, int64_t>> sp;     // cells [b, e)
+                for (auto &g : kv.second)
+                    for (auto &c : g.second.cds) {
+                        const int64_t b = std::max<int64_t>((int64_t)c.first - 1, 0), e = std::min<int64_t>(c.second, len);
+                        if (b < e) sp.emplace_back(b, e);
+                    }
+                if (sp.empty()) continue;
+                tids.push_back(kv.first);
+                std::sort(sp.begin(), sp.end());
+                int64_t cb = sp[0].first, ce = sp[0].second;
+                for (size_t k = 1; k <= sp.size(); ++k) {
+                    if (k < sp.size() && sp[k].first <= ce) { ce = std::max(ce, sp[k].second); continue; }
+                    regs.push_back(pd_region{kv.first, (int32_t)(cb + 1), (int32_t)ce});
+                    if (k < sp.size()) { cb = sp[k].first; ce = sp[k].second; }
+                }
+            }
+        }
+        std::vector<uint64_t> hist(nctg * nb, 0);
+        if (synthetic && !scanned && api->scan_depth_histogram) {
+            if (!merge_contexts()) return false;
+            if (!eng.ck(api->scan_depth_histogram(eng.ctx, nb, wrap_bits, hist.data()), "pd_scan_depth_histogram")) return false;
+        } else if (api->depth_histogram) {
+            if (!need_scan()) return false;
+            if ((synthetic || !regs.empty()) && !eng.ck(api->depth_histogram(eng.ctx, synthetic ? nullptr : regs.data(), synthetic ? 0 : regs.size(), nb, hist.data()),
+                                                         "pd_depth_histogram")) return false;
+        } else {
+            // engines without the histogram entry points: the cells are read back and binned on the host threads
+            if (!need_scan()) return false;
+            struct Piece { int32_t tid; uint32_t beg; size_t n; };
+            std::vector<Piece> pieces;
+            constexpr size_t CH = (size_t)1 << 22;
+            auto add = [&](int32_t t, uint64_t b, uint64_t e) { for (uint64_t p = b; p < e; p += CH) pieces.push_back(Piece{t, (uint32_t)p, (size_t)std::min<uint64_t>(CH, e - p)}); };
+            if (synthetic) for (int32_t t : tids) add(t, 0, hdr.lens[(size_t)t]);
+            else for (const pd_region &r : regs) add(r.tid, (uint64_t)r.first - 1, (uint64_t)r.second);
+            std::mutex mu;
+            std::atomic<size_t> next{0};
+            bool ok = true;
+            auto work = [&]() {
+                std::vector<uint32_t> d;
+                std::vector<uint64_t> h(nb);
+                for (size_t i; (i = next.fetch_add(1)) < pieces.size();) {
+                    const Piece &pc = pieces[i];
+                    d.resize(pc.n);
+                    {
+                        std::lock_guard<std::mutex> lk(mu);
+                        if (!ok) return;
+                        if (!eng.ck(api->read_depth(eng.ctx, pc.tid, pc.beg, pc.n, d.data()), "pd_read_depth")) { ok = false; return; }
+                    }
+                    std::fill(h.begin(), h.end(), 0);
+                    for (uint32_t x : d) ++h[x < nb - 1 ? x : nb - 1];
+                    std::lock_guard<std::mutex> lk(mu);
+                    uint64_t *row = &hist[(size_t)pc.tid * nb];
+                    for (uint32_t k = 0; k < nb; ++k) row[k] += h[k];
+                }
+            };
+            const int nt = std::max(1, std::min(o.threads, 16));
+            std::vector<std::thread> th;
+            for (int k = 1; k < nt; ++k) th.emplace_back(work);
+            work();
+            for (auto &t : th) t.join();
+            if (!ok) return false;
+        }
+        std::string txt = DIST_HEADER;
+        auto block = [&](const std::string &name, const uint64_t *h) {
+            uint64_t total = 0;
+            for (uint32_t k = 0; k < nb; ++k) total += h[k];
+            uint64_t at = total;
+            for (uint32_t k = 0; k < nb; ++k) {
+                if (!h[k]) continue;
+                txt += name; txt += '\t';
+                if (k == nb - 1) txt += ">=";
+                txt += std::to_string(k); txt += '\t'; txt += std::to_string(h[k]); txt += '\t'; txt += std::to_string(at); txt += '\t';
+                txt += fmt2(at * 100.0 / total); txt += '\n';
+                at -= h[k];
+            }
+        };
+        std::vector<uint64_t> all(nb, 0);
+        for (int32_t t : tids) {
+            const uint64_t *h = &hist[(size_t)t * nb];
+            block(hdr.names[(size_t)t], h);
+            for (uint32_t k = 0; k < nb; ++k) all[k] += h[k];
+        }
+        block("*", all.data());
+        GzWriter D;
+        const std::string path = prefix + ".dist.stat.gz";
+        if (!D.open(path)) { eng.fail("cannot open " + path); return false; }
+        D.write(txt);
+        if (!D.close()) { eng.fail("cannot write " + path); return false; }
+        tm.mark("depth distribution");
+        return true;
+    };
     std::string txt;
 
     if (o.mode == 6) {
@@ -1737,6 +1845,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
             tm.mark("totals + table (rows, parse and checksums on the device)");
             OUT.close();
             tm.mark("table close");
+            if (!write_dist()) return bail();
             if (!site_done()) return bail();
             std::cout << "INFO: Input data read done" << std::endl;
             return 0;
@@ -1775,6 +1884,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
         tm.mark("scan + statistics + table text");
         OUT.close();
         tm.mark("table gzip");
+        if (!write_dist()) return bail();
         if (!site_done()) return bail();
         std::cout << "INFO: Input data read done" << std::endl;
         return 0;
@@ -1903,6 +2013,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
     tm.mark("table text");
     OUT.close();
     tm.mark("table gzip");
+    if (!write_dist()) return bail();
     if (!site_done()) return bail();
     return 0;
 }

@@ -1,0 +1,57 @@
+"""-dist on the MI355X: the `pandepth` binary on every golden case with `-dist 200` added.  The existing outputs, stdout and
+exit code stay exactly as the reference's; one extra file, o.dist.stat.gz, appears, and its text equals what the host
+fallback (the same host code on the CPU oracle engine, tests/harness/pandepth_oracle_cli) writes for the same command line."""
+import gzip
+import hashlib
+import json
+import os
+import subprocess
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CLI = os.path.join(ROOT, "pandepth_amd", "pandepth")
+ORACLE_CLI = os.path.join(HERE, "harness", "pandepth_oracle_cli")
+MANIFEST = json.load(open(os.path.join(HERE, "golden", "manifest.json")))
+
+
+@pytest.fixture(scope="module")
+def oracle_cli():
+    subprocess.run(["make", "-C", os.path.join(ROOT, "pandepth_amd"), "libpandepth_host.a"], check=True, stdout=subprocess.DEVNULL)
+    subprocess.run(["make", "-C", os.path.join(HERE, "harness"), "pandepth_oracle_cli"], check=True, stdout=subprocess.DEVNULL)
+    return ORACLE_CLI
+
+
+def run(cli, case, out_dir, extra):
+    d = os.path.join(HERE, "golden", case["fixture"])
+    os.makedirs(out_dir, exist_ok=True)
+    args = [cli] + case["args"] + extra + ["-o", os.path.join(out_dir, "o")]
+    if "-t" not in case["args"]:
+        args += ["-t", "4"]
+    return subprocess.run(args, cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+
+
+@pytest.mark.parametrize("case", MANIFEST, ids=lambda e: "%s-%s" % (e["fixture"], e["name"]))
+def test_dist_on_every_golden_case(case, oracle_cli, tmp_path):
+    assert os.access(CLI, os.X_OK), "pandepth binary not built (make -C pandepth_amd)"
+    p = run(CLI, case, str(tmp_path / "gpu"), ["-dist", "200"])
+    assert p.returncode == case["returncode"], p.stderr.decode()[-500:]
+    assert p.stdout.decode() == case["stdout"]
+    for suffix, meta in case["outputs"].items():
+        gz = (tmp_path / "gpu" / ("o." + suffix)).read_bytes()
+        assert hashlib.sha256(gz).hexdigest() == meta["gz_sha256"], suffix
+    files = sorted(os.listdir(tmp_path / "gpu"))
+    listed = sorted("o." + s for s in case["outputs"])
+    if not case["outputs"]:                                   # a run that writes no table writes no distribution either
+        assert files == [], files
+        return
+    assert files == sorted(listed + ["o.dist.stat.gz"]), files
+    q = run(oracle_cli, case, str(tmp_path / "cpu"), ["-dist", "200"])
+    assert q.returncode == case["returncode"], q.stderr.decode()[-500:]
+    got = gzip.decompress((tmp_path / "gpu" / "o.dist.stat.gz").read_bytes()).decode()
+    exp = gzip.decompress((tmp_path / "cpu" / "o.dist.stat.gz").read_bytes()).decode()
+    assert got.startswith("#Chr\tDepth\tSites\tAtLeast\tAtLeast(%)\n")
+    assert got == exp
