@@ -47,7 +47,11 @@ int pd_push_bgzf_units(pd_ctx *ctx, const void *blob, size_t n_bytes, const pd_b
  * Inflates every block of a BGZF image held in host memory on the GPU (one lane per block) and
  * copies the result back; variant 0 keeps the per-block Huffman tables in LDS, 1 in global
  * memory.  kernel_ms = average kernel time over `reps` launches.  A measuring / validation entry:
- * the production form will keep the inflated records on the device. */
+ * the production form will keep the inflated records on the device.
+ * A member the DECODER refuses is not a HIP failure: the call then returns PD_X_BGZF_REFUSED(status) =
+ * -(100 + |status|) for the first such member's status (pd_inflate_core.h / pd_inflate_wave.h: -1 .. -9
+ * corrupt stream, -20 wrong CRC-32, 1 handed to the host decoder); PD_EHIP is a failed HIP call only. */
+#define PD_X_BGZF_REFUSED(status) (-(100 + ((status) < 0 ? -(status) : (status))))
 int pd_x_bgzf_inflate(int device, const void *host_bgzf, size_t n_bytes, void *host_out, size_t out_cap,
                       size_t *out_len, int variant, int reps, double *kernel_ms, uint32_t *n_blocks);
 

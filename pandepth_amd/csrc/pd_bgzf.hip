@@ -14,6 +14,7 @@
 #include "pd_bamwalk.h"
 #include "pd_kernels.h"
 #include "../../include/pandepth_amd.h"
+#include "../../include/pandepth_amd_dev.h"
 
 namespace {
 
@@ -32,7 +33,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_inflate_blocks(const uin
     if (i >= n_blk) return;
     pdi::Fast &tf = LDS_FAST ? s_fast[threadIdx.x] : scratch[i].fast;
     const BlkDesc d = blk[i];
-    status[i] = d.out_len ? pdi::inflate_block(comp + d.in_off, d.in_len, out + d.out_off, d.out_len, tf, scratch[i].slow) : 0;
+    status[i] = pdi::inflate_block(comp + d.in_off, d.in_len, out + d.out_off, d.out_len, tf, scratch[i].slow);   // (an empty member — the EOF marker — is a stream too)
 }
 
 // One WAVE per BGZF member (pd_inflate_wave.h): persistent one-wave workgroups walk the members with a grid stride
@@ -241,7 +242,7 @@ extern "C" int pd_x_bgzf_inflate(int device, const void *host_bgzf, size_t n_byt
         if (kernel_ms) *kernel_ms = ms / (reps > 0 ? reps : 1);
         std::vector<int> st(nb);
         HIPV(hipMemcpy(st.data(), d_st, (size_t)nb * 4, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < nb; ++i) if (st[i] != 0) { rc = PD_EHIP; fprintf(stderr, "pd_x_bgzf_inflate: block %u failed with %d\n", i, st[i]); break; }
+        for (uint32_t i = 0; rc == PD_OK && i < nb; ++i) if (st[i] != 0) { rc = PD_X_BGZF_REFUSED(st[i]); fprintf(stderr, "pd_x_bgzf_inflate: block %u failed with %d\n", i, st[i]); break; }
         if (host_out && rc == PD_OK) HIPV(hipMemcpy(host_out, d_out, uo, hipMemcpyDeviceToHost));
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }

@@ -80,9 +80,12 @@ PDI_FN uint32_t rev_bits(uint32_t code, int len)
 }
 
 // builds the canonical arrays and the fast table from `n` code lengths; returns 0, or -1 for an
-// over-subscribed / incomplete code (a single distance code is allowed, as zlib does)
+// over-subscribed / incomplete code.  What zlib takes is taken, no more: of the incomplete codes only the one
+// with a single code of one bit (`incomplete` = 1: the literal/length and distance codes of a dynamic block, not
+// its code-length code) and the fixed block's 30 distance codes of five bits (`incomplete` = 2); using a
+// missing code fails in decode()
 template <class H>
-PDI_FN_NOINLINE int build(H &h, uint16_t *fast, int fast_bits, const uint8_t *len, int n)
+PDI_FN_NOINLINE int build(H &h, uint16_t *fast, int fast_bits, const uint8_t *len, int n, int incomplete)
 {
     for (int i = 0; i <= MAX_BITS; ++i) h.count[i] = 0;
     for (int i = 0; i < n; ++i) h.count[len[i]]++;
@@ -93,6 +96,7 @@ PDI_FN_NOINLINE int build(H &h, uint16_t *fast, int fast_bits, const uint8_t *le
         left <<= 1; left -= h.count[l];
         if (left < 0) return -1;
     }
+    if (left > 0 && incomplete != 2 && !(incomplete == 1 && h.count[1] == 1 && h.count[0] == n - 1)) return -1;
     uint16_t offs[MAX_BITS + 2];
     offs[1] = 0;
     for (int l = 1; l < MAX_BITS; ++l) offs[l + 1] = (uint16_t)(offs[l] + h.count[l]);
@@ -107,7 +111,7 @@ PDI_FN_NOINLINE int build(H &h, uint16_t *fast, int fast_bits, const uint8_t *le
         }
         code <<= 1;
     }
-    return 0;        // an incomplete code is tolerated here: using one of its missing codes fails in decode()
+    return 0;
 }
 
 // one symbol; -1 on an invalid code
@@ -143,7 +147,7 @@ PDI_FN_NOINLINE int inflate_block(const uint8_t *in, uint32_t in_len, uint8_t *o
     static const uint8_t CLORD[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
     Bits b; b.in = in; b.pos = 0; b.end = in_len; b.buf = 0; b.cnt = 0;
     uint32_t o = 0;
-    for (int guard = 0; guard < 70000; ++guard) {                       // a block emits >= 0 bytes; bound the block count
+    for (;;) {                                                          // (every block takes three bits or more, and a block that reads past the input is the last)
         const uint32_t last = bits_get(b, 1);
         const uint32_t type = bits_get(b, 2);
         if (type == 0) {
@@ -159,16 +163,16 @@ PDI_FN_NOINLINE int inflate_block(const uint8_t *in, uint32_t in_len, uint8_t *o
                 for (int i = 144; i < 256; ++i) t.cl[i] = 9;
                 for (int i = 256; i < 280; ++i) t.cl[i] = 7;
                 for (int i = 280; i < 288; ++i) t.cl[i] = 8;
-                if (build(t.ll, tf.ll, LL_FAST_BITS, t.cl, 288) < 0) return -3;
+                if (build(t.ll, tf.ll, LL_FAST_BITS, t.cl, 288, 0) < 0) return -3;
                 for (int i = 0; i < 30; ++i) t.cl[i] = 5;
-                if (build(t.d, tf.d, D_FAST_BITS, t.cl, 30) < 0) return -3;
+                if (build(t.d, tf.d, D_FAST_BITS, t.cl, 30, 2) < 0) return -3;
             } else {
                 const int nlen = (int)bits_get(b, 5) + 257, ndist = (int)bits_get(b, 5) + 1, ncode = (int)bits_get(b, 4) + 4;
                 if (nlen > 286 || ndist > 30) return -3;
                 for (int i = 0; i < 19; ++i) t.small[i] = 0;
                 for (int i = 0; i < ncode; ++i) t.small[CLORD[i]] = (uint8_t)bits_get(b, 3);
                 // the code-length code (<= 7 bits) borrows the distance tables until they are built
-                if (build(t.d, tf.d, D_FAST_BITS, t.small, 19) < 0) return -3;
+                if (build(t.d, tf.d, D_FAST_BITS, t.small, 19, 0) < 0) return -3;
                 int idx = 0;
                 uint8_t *cl = t.cl;
                 while (idx < nlen + ndist) {
@@ -185,8 +189,8 @@ PDI_FN_NOINLINE int inflate_block(const uint8_t *in, uint32_t in_len, uint8_t *o
                     }
                 }
                 if (cl[256] == 0) return -3;                             // no end-of-block code
-                if (build(t.ll, tf.ll, LL_FAST_BITS, cl, nlen) < 0) return -3;
-                if (build(t.d, tf.d, D_FAST_BITS, cl + nlen, ndist) < 0) return -3;
+                if (build(t.ll, tf.ll, LL_FAST_BITS, cl, nlen, 1) < 0) return -3;
+                if (build(t.d, tf.d, D_FAST_BITS, cl + nlen, ndist, 1) < 0) return -3;
             }
             for (;;) {
                 const int sym = decode(b, t.ll, tf.ll, LL_FAST_BITS);
@@ -211,9 +215,8 @@ PDI_FN_NOINLINE int inflate_block(const uint8_t *in, uint32_t in_len, uint8_t *o
             }
         } else return -1;
         if (bits_overrun(b)) return -7;
-        if (last) break;
+        if (last) return o == out_len ? 0 : -5;
     }
-    return o == out_len ? 0 : -5;
 }
 
 } // namespace pdi

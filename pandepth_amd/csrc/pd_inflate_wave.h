@@ -257,6 +257,7 @@ PW_FN int build_table(uint32_t *tab, const uint8_t *cl, int n, uint16_t *sorted,
         });
         uint32_t sub_total = 0;
         const U ex = W::excl_scan(size, &sub_total);
+        PW_MARK(MODE == 0 ? 33 : 34, sub_total);
         if (sub_total > (uint32_t)SUBCAP) return PD_W_HOST;
         W::each([&](int l) {
             uint32_t run = (1u << ROOT) + ex[l];
@@ -400,19 +401,27 @@ PW_FN bool count_step(const Tables &T, const uint8_t *in, uint32_t in_lim, uint3
         const uint32_t st = c.stage;                                      // 0 .. CK_N - 1
         uint32_t *const e = ck + st * CK_STRIDE;
         if (have_prev && e[0] == q) {
-            // same tail as before; the counts remembered from here on were relative to the old start
-            // (bytes in 17 bits | matches in 15: a pass from a wrong start may have counted anything, what is kept is kept modulo the fields' widths —
-            // the TRUE counts of a subsequence fit them, and sums and differences of counts are exact modulo a power of two)
-            const uint32_t was = e[64], d_o = c.out - (was & 0x1ffffu), d_m = c.nm - (was >> 17);
+            // same tail as before; the counts remembered from here on were relative to the old start.
+            // Every count is EXACT, in 32 bits: a pass has at most 2 S + 64 <= 32 832 symbols of at most 258 bytes.  A checkpoint packs its counts into
+            // bytes : 17 | matches : 15, which holds whatever a member that inflates can have (65 536 bytes) — but not what a pass can count: a crafted
+            // block with a one-bit code for length 258 and a one-bit distance code emits 258 bytes per two bits, 2^17 bytes in 1 016 bits of a subsequence
+            // of up to 16 384 (tests/harness/hostile_corpus.h, "wrap-targets"; counts kept modulo the fields here once let such a lane's bytes vanish from
+            // the wave's total, past the one bound in front of phases 2 and 3).  So a checkpoint whose counts do not fit is not kept (CK_NONE: nothing
+            // merges there, phase 2 hands nothing over from there), and c.n / c.m never pass through the fields.
+            const uint32_t was = e[64], d_o = c.out - (was & 0x1ffffu), d_m = c.nm - (was >> 17);       // (differences modulo 2^32 of exact counts)
 #pragma unroll
             for (uint32_t k = 0; k < (uint32_t)CK_N; ++k) if (k >= st) {
                 const uint32_t w = ck[k * CK_STRIDE + 64];
-                ck[k * CK_STRIDE + 64] = ((w + d_o) & 0x1ffffu) | (((w >> 17) + d_m) << 17);
+                const uint32_t no = (w & 0x1ffffu) + d_o, nm = (w >> 17) + d_m;
+                if (no > 0x1ffffu || nm > 0x7fffu) ck[k * CK_STRIDE] = CK_NONE;
+                else ck[k * CK_STRIDE + 64] = no | (nm << 17);
             }
-            c.n = (c.n + d_o) & 0x1ffffu; c.m = (c.m + d_m) & 0x7fffu;
+            PW_MARK(31, c.n + d_o); PW_MARK(32, c.m + d_m);               // (per lane: a merge, with the counts the pass ends up with)
+            c.n += d_o; c.m += d_m;
             return false;                                                 // e, f and the later checkpoints stay
         }
-        e[0] = q; e[64] = (c.out & 0x1ffffu) | (c.nm << 17);
+        const bool fits = c.out <= 0x1ffffu && c.nm <= 0x7fffu;          // (see above: a checkpoint is kept only with exact counts)
+        e[0] = fits ? q : (uint32_t)CK_NONE; e[64] = (c.out & 0x1ffffu) | (c.nm << 17);
         c.next_t = ck_at(nominal, S, st + 1);
         c.stage = st + 1;
     }
@@ -915,7 +924,7 @@ PW_FN int inflate_block(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32
     const uint32_t in_bits = in_len * 8;
     uint32_t q = 0, o = 0;
     if (st) st->blocks++;
-    for (int guard = 0; guard < 70000; ++guard) {
+    for (int guard = 0; guard < (1 << 17); ++guard) {                     // (a block is ten bits or more, in_bits <= 2^20: the guard is never what ends a stream)
         if (q + 3 > in_bits) return -7;
         const uint32_t hdr = peek_bits(in, q) & 7; q += 3;
         const uint32_t last = hdr & 1, type = hdr >> 1;
@@ -1063,11 +1072,10 @@ PW_FN int inflate_block(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32
             PW_MARK(24, last);
         }
         PW_MARK(25, last);
-        if (last) break;
+        if (last) { PW_MARK(27, o); return o == out_len ? 0 : -5; }
         PW_MARK(26, q);
     }
-    PW_MARK(27, o);
-    return o == out_len ? 0 : -5;
+    return -9;                                                            // (no block was the last: not a stream that ended)
 }
 
 // ---- CRC-32 of a member's inflated bytes (RFC 1952; htslib checks it for every BGZF block it reads, so a flipped bit that
@@ -1186,7 +1194,7 @@ PW_FN uint32_t crc32_wave(const uint8_t *data, uint32_t n, uint32_t *tab /* 1024
 template <class W>
 PW_FN int inflate_member(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_len, Tables &T, Token *tok, Stats *st, bool check_crc = true)
 {
-    if (out_len) {                                                        // (an empty member — the EOF marker — has nothing to inflate)
+    {                                                                     // (an empty member — the EOF marker — is a stream like any other: one empty block)
         const int rc = inflate_block<W>(in, in_len, out, out_len, T, tok, st);
         if (rc) return rc;
     }

@@ -386,15 +386,15 @@ bool parse_symbols(const uint8_t *in, size_t in_len, std::vector<Sym> &syms)
             for (int i = 144; i < 256; ++i) t.cl[i] = 9;
             for (int i = 256; i < 280; ++i) t.cl[i] = 7;
             for (int i = 280; i < 288; ++i) t.cl[i] = 8;
-            if (build(t.ll, tf.ll, LL_FAST_BITS, t.cl, 288) < 0) return false;
+            if (build(t.ll, tf.ll, LL_FAST_BITS, t.cl, 288, 2) < 0) return false;   // (2: this reads zlib's own output back — incomplete codes as they come)
             for (int i = 0; i < 30; ++i) t.cl[i] = 5;
-            if (build(t.d, tf.d, D_FAST_BITS, t.cl, 30) < 0) return false;
+            if (build(t.d, tf.d, D_FAST_BITS, t.cl, 30, 2) < 0) return false;
         } else if (type == 2) {
             const int nlen = (int)bits_get(b, 5) + 257, ndist = (int)bits_get(b, 5) + 1, ncode = (int)bits_get(b, 4) + 4;
             if (nlen > 286 || ndist > 30) return false;
             for (int i = 0; i < 19; ++i) t.small[i] = 0;
             for (int i = 0; i < ncode; ++i) t.small[CLORD[i]] = (uint8_t)bits_get(b, 3);
-            if (build(t.d, tf.d, D_FAST_BITS, t.small, 19) < 0) return false;
+            if (build(t.d, tf.d, D_FAST_BITS, t.small, 19, 2) < 0) return false;
             int idx = 0;
             uint8_t *cl = t.cl;
             while (idx < nlen + ndist) {
@@ -410,8 +410,8 @@ bool parse_symbols(const uint8_t *in, size_t in_len, std::vector<Sym> &syms)
                     while (rep--) cl[idx++] = val;
                 }
             }
-            if (build(t.ll, tf.ll, LL_FAST_BITS, cl, nlen) < 0) return false;
-            if (build(t.d, tf.d, D_FAST_BITS, cl + nlen, ndist) < 0) return false;
+            if (build(t.ll, tf.ll, LL_FAST_BITS, cl, nlen, 2) < 0) return false;
+            if (build(t.d, tf.d, D_FAST_BITS, cl + nlen, ndist, 2) < 0) return false;
         } else return false;                             // a stored block: zlib found the chunk incompressible
         for (;;) {
             const int sym = decode(b, t.ll, tf.ll, LL_FAST_BITS);

@@ -1403,6 +1403,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
             if (rcs[(size_t)k] != 0) {
                 const char *m = api->strerror(nullptr);
                 std::cerr << "Error: depth engine unavailable: " << (m ? m : "?") << std::endl;
+                OUT.abandon();                     // (no table, rather than an empty one a reader could take for a result)
                 return 2;
             }
     }
@@ -1545,6 +1546,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
     for (int k = 0; k < n_ctx; ++k) {
         if (!engs[k]->ok() || !engs[k]->ck(api->synchronize(engs[k]->ctx), "pd_synchronize")) {
             std::cerr << "Error: " << engs[k]->err << std::endl;
+            OUT.abandon();                         // (the input was damaged: no table is left behind, not even an empty one)
             return 2;
         }
     }
@@ -1572,7 +1574,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
         return eng.ck(api->scan(eng.ctx, wrap_bits), "pd_scan");
     };
     std::function<void()> abandon_site_file = [] {};           // (set below: stops a per-site writer working behind the statistics)
-    auto bail = [&]() { abandon_site_file(); std::cerr << "Error: " << eng.message() << std::endl; return 2; };
+    auto bail = [&]() { abandon_site_file(); OUT.abandon(); std::cerr << "Error: " << eng.message() << std::endl; return 2; };
     // A collective over the contexts (one thread per rank): what several GPUs' statistics have in common.  `call(k, comm)` is the
     // rank's collective; returns 1 done, 0 not applicable (no communicator, or the samples do not fit the sliced sum's 4-bit images:
     // PD_ERANGE on every rank, nothing consumed — the contexts are then added into the first one), -1 error.

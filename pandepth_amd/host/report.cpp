@@ -54,6 +54,14 @@ bool GzWriter::raw_rewind()
     return fflush(fp) == 0 && ftruncate(fileno(fp), 0) == 0 && fseek(fp, 0, SEEK_SET) == 0;
 }
 
+void GzWriter::abandon()
+{
+    if (fp_) { fclose((FILE *)fp_); fp_ = nullptr; raw_ = false; }
+    if (f_) { gzclose((gzFile)f_); f_ = nullptr; }
+    std::string().swap(text_);
+    if (!path_.empty()) ::remove(path_.c_str());
+}
+
 bool GzWriter::close()
 {
     if (fp_ && raw_) {                                           // the stream's bytes are in the file already

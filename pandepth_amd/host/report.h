@@ -29,6 +29,7 @@ public:
     bool raw_rewind();
     bool collecting() const { return fp_ != nullptr && text_.empty(); }
     bool close();
+    void abandon();                                  // the run failed: nothing is written and the file is removed (no table, rather than an empty or partial one)
     bool good() const { return f_ != nullptr || fp_ != nullptr; }
 private:
     void *f_ = nullptr;          // gzFile: streaming mode

@@ -1,6 +1,8 @@
 // tests/harness/inflate_check.cpp — TEST INFRASTRUCTURE: runs the product's DEFLATE decoder
 // (pandepth_amd/csrc/pd_inflate_core.h, the same source the gfx950 kernel compiles) on the host over
 // every BGZF block of the given files and compares each block with zlib's inflate.
+// (Constructed hostile streams for this decoder — both placements of its fast tables — are run by the other harness,
+// `inflate_wave_check -c` (hostile_corpus.h), next to the wave decoder and under the same judge and fences.)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

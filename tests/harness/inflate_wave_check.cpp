@@ -4,13 +4,22 @@
 // input made by the generator mode) and compares each block with zlib's inflate.
 //   inflate_wave_check [-s] [-f N] file...     -s: print speculation statistics   -f N: N mutated copies per block
 //   inflate_wave_check -g                     generated streams: every block type, levels 0-9, pathological inputs
+//   inflate_wave_check -c [-w FILE]           the corpus of constructed hostile streams (hostile_corpus.h) through this decoder and
+//                                             pd_inflate_core.h inside fenced memory, judged against zlib; -w: the cases that fit a BGZF
+//                                             member are also written to FILE as BGZF members, with FILE.tsv (a line per member: what
+//                                             the GPU tests need to know about it) — only when no case broke a rule
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 #include <zlib.h>
 #include <random>
 #include <vector>
+namespace hostile { static inline void mark(uint32_t code, uint32_t val); }
+#define PW_MARK(code, val) hostile::mark((uint32_t)(code), (uint32_t)(val))      /* the decoder's progress marks: counted by the corpus run */
 #include "../../pandepth_amd/csrc/pd_inflate_wave.h"
+#include "../../pandepth_amd/csrc/pd_inflate_core.h"
+#include "hostile_corpus.h"
 
 static pdw::Tables g_T;
 static pdw::Stats g_st;
@@ -125,9 +134,59 @@ static int generated()
     return bad;
 }
 
+// the corpus of hostile_corpus.h: a table of the families, 0 = no rule broken
+static int corpus(const char *members_path)
+{
+    using namespace hostile;
+    init_fences();
+    FILE *mf = nullptr, *tf = nullptr;
+    if (members_path) {
+        mf = fopen(members_path, "wb"); tf = fopen((std::string(members_path) + ".tsv").c_str(), "w");
+        if (!mf || !tf) { fprintf(stderr, "cannot write %s\n", members_path); return 2; }
+        fprintf(tf, "#offset\tsize\tisize\tzlib_accepts\tmay_decline\twrong_crc\tfamily\tname\n");
+    }
+    long bad = 0, total = 0, empty_body_family = 0, written = 0;
+    size_t index = 0, off = 0;
+    Tally wrap;
+    printf("%-20s %6s %6s %6s %8s  results of pdw::inflate_block (code: cases)\n", "family", "cases", "body", "zlib", "declined");
+    for (int f = 0; f < N_FAM; ++f) {
+        const std::vector<Case> cases = family_cases(f);
+        Tally t;
+        const clock_t t0 = clock();
+        for (const Case &c : cases) {
+            const int b = run_case(c, index++, t);
+            if (mf && !b && c.in.size() + 26 <= 65536) {                      // (18 bytes of header, 8 of trailer, BSIZE - 1 in 16 bits)
+                std::vector<uint8_t> ref; const bool zok = zlib_accepts(c.in, c.out_len, ref);
+                const uint32_t bs = (uint32_t)c.in.size() + 26 - 1;
+                const uint8_t h[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)bs, (uint8_t)(bs >> 8)};
+                fwrite(h, 1, 18, mf); if (!c.in.empty()) fwrite(c.in.data(), 1, c.in.size(), mf); fwrite(&g_crc, 4, 1, mf); fwrite(&g_isize, 4, 1, mf);
+                fprintf(tf, "%zu\t%u\t%u\t%d\t%d\t%d\t%s\t%s\n", off, bs + 1, c.out_len, (int)zok, (int)FAMILIES[f].may_decline, (int)c.wrong_crc, FAMILIES[f].name, c.name.c_str());
+                off += bs + 1; ++written;
+            }
+        }
+        printf("%-20s %6ld %6ld %6ld %8ld ", FAMILIES[f].name, t.cases, t.reached_body, t.zlib_ok, t.declined);
+        for (auto &kv : t.rc_wave) printf(" %d: %ld", kv.first, kv.second);
+        printf("   | inflate_member"); for (auto &kv : t.rc_member) printf(" %d: %ld", kv.first, kv.second);
+        printf("   | pdi"); for (auto &kv : t.rc_pdi) printf(" %d: %ld", kv.first, kv.second);
+        printf("   | sub-table entries: literal/length <= %u of %d, distance <= %u of %d, %ld over   | %.1f s\n", t.sub_ll, (int)pdw::LL_SUBCAP, t.sub_d, (int)pdw::D_SUBCAP, t.sub_over,
+               (double)(clock() - t0) / CLOCKS_PER_SEC);
+        if (t.declined && !FAMILIES[f].may_decline) ++bad;
+        if (FAMILIES[f].body_level && t.reached_body == 0) { fprintf(stderr, "family %s: no case reached decode_body\n", FAMILIES[f].name); ++empty_body_family; }
+        if (f == FAM_WRAP) wrap = t;
+        bad += t.violations; total += t.cases;
+    }
+    printf("wrap-targets: %ld merges of a re-decoded lane with its earlier pass, %ld of them with a byte count above 17 bits, %ld with a match count above 15 bits\n",
+           wrap.merges, wrap.merges_over_n, wrap.merges_over_m);
+    if (wrap.merges_over_n == 0) { fprintf(stderr, "wrap-targets: the merge path never ran with a count above its old field\n"); ++bad; }
+    printf("corpus: %ld cases, %ld families without a case in decode_body, %ld rule violations\n", total, empty_body_family, bad);
+    if (mf) { fclose(mf); fclose(tf); printf("%ld members written\n", written); if (bad || empty_body_family) { remove(members_path); remove((std::string(members_path) + ".tsv").c_str()); } }
+    return bad || empty_body_family ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     bool stats = false; int fuzz = 0; bool gen = false;
+    for (int a = 1; a < argc; ++a) if (!strcmp(argv[a], "-c")) return corpus(a + 2 < argc && !strcmp(argv[a + 1], "-w") ? argv[a + 2] : nullptr);
     std::vector<const char *> files;
     for (int a = 1; a < argc; ++a) {
         if (!strcmp(argv[a], "-s")) stats = true;
