@@ -172,6 +172,18 @@ int pd_reduce_windows(pd_ctx *ctx, uint32_t w, uint32_t min_dep, uint32_t *cover
 int pd_scan_depth_histogram(pd_ctx *ctx, uint32_t n_bins, unsigned wrap_bits, uint64_t *hist);
 int pd_depth_histogram(pd_ctx *ctx, const pd_region *regs, size_t n, uint32_t n_bins, uint64_t *hist);
 
+/* Depth as run-length intervals.  After pd_scan: the cells [beg, beg + n) of contig tid (inside the contig, n <= 2^27, else
+ * PD_EINVAL) as maximal runs.  out[j].start = contig-local first cell of run j; run j ends where run j + 1 starts, the last
+ * one at beg + n.  n_edges == 0: runs of equal depth, out[j].value = the depth.  n_edges > 0 (at most 64, strictly ascending,
+ * else PD_EINVAL): runs of equal depth CLASS, edge i opening the class [edges[i], edges[i+1]) and the last one unbounded;
+ * out[j].value = the class index, or 0xFFFFFFFF for depths below edges[0] — a class like any other, so that the runs always
+ * tile the range.  *n_levels always receives the true number of runs; when it exceeds cap only the first cap are written and
+ * the call returns PD_ERANGE (cap >= n always suffices).  Found on the device (count, scan, ordered emit over the depth
+ * arrays); only n_levels * 8 bytes come back. */
+typedef struct pd_level { uint32_t start, value; } pd_level;
+int pd_depth_levels(pd_ctx *ctx, int32_t tid, uint32_t beg, size_t n, const uint32_t *edges, uint32_t n_edges,
+                    pd_level *out, size_t cap, size_t *n_levels);
+
 /* Replaces the per-site read loop PD:4278-4281: copies depth cells [beg, beg+n) of contig tid
  * to the host.  Requires pd_scan first. */
 int pd_read_depth(pd_ctx *ctx, int32_t tid, uint32_t beg, size_t n, uint32_t *out);

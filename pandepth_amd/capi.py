@@ -69,6 +69,7 @@ def load():
         "pd_reduce_windows": (I, [P, ctypes.c_uint32, ctypes.c_uint32, P, P]),
         "pd_scan_depth_histogram": (I, [P, ctypes.c_uint32, U, P]),
         "pd_depth_histogram": (I, [P, P, SZ, ctypes.c_uint32, P]),
+        "pd_depth_levels": (I, [P, ctypes.c_int32, ctypes.c_uint32, SZ, P, ctypes.c_uint32, P, SZ, ctypes.POINTER(SZ)]),
         "pd_read_depth": (I, [P, ctypes.c_int32, ctypes.c_uint32, SZ, P]),
         "pd_format_sites": (I, [P, ctypes.c_int32, ctypes.c_uint32, SZ, ctypes.c_char_p, SZ, P, SZ, ctypes.POINTER(SZ)]),
         "pd_deflate_parse": (I, [P, P, SZ, P, ctypes.c_uint32, P, SZ, P]),
@@ -124,7 +125,7 @@ def load():
 
 EXPORTS = ["pd_abi_version", "pd_create", "pd_destroy", "pd_strerror", "pd_reset", "pd_push_intervals",
            "pd_push_intervals_device", "pd_runs_create", "pd_runs_destroy", "pd_push_runs", "pd_stage_acquire", "pd_stage_submit", "pd_set_param", "pd_keep_deferred", "pd_scan",
-           "pd_reduce_intervals", "pd_window_layout", "pd_scan_reduce_windows", "pd_reduce_windows", "pd_scan_depth_histogram", "pd_depth_histogram",
+           "pd_reduce_intervals", "pd_window_layout", "pd_scan_reduce_windows", "pd_reduce_windows", "pd_scan_depth_histogram", "pd_depth_histogram", "pd_depth_levels",
            "pd_read_depth", "pd_format_sites", "pd_deflate_parse", "pd_host_register", "pd_host_unregister", "pd_text_open", "pd_text_close", "pd_text_append_sites", "pd_text_parse", "pd_text_read", "pd_text_release", "pd_text_append_window_rows", "pd_text_append_bytes", "pd_device_buffer", "pd_device_count", "pd_accumulate_from", "pd_device_layout", "pd_export_i8", "pd_import_i8", "pd_export_i4",
            "pd_slice_sweep_i4", "pd_gather_windows", "pd_push_bgzf_units", "pd_decode_begin", "pd_decode_acquire", "pd_decode_submit", "pd_decode_queue", "pd_decode_collect", "pd_decode_end", "pd_decode_abort", "pd_comm_unique_id", "pd_comm_init", "pd_comm_init_all", "pd_comm_init_local", "pd_comm_preinit", "pd_comm_prepare", "pd_comm_destroy",
            "pd_comm_strerror", "pd_sliced_window_sum", "pd_sliced_interval_sum", "pd_sliced_sum_start", "pd_sliced_sum_finish", "pd_x_bgzf_inflate", "pd_stream", "pd_synchronize", "pd_profile",
@@ -387,6 +388,23 @@ class Engine:
             r = np.ascontiguousarray(regs, dtype=np.int32).reshape(-1, 3)
             self._ck(self.L.pd_depth_histogram(self.h, _ptr(r), r.shape[0], int(n_bins), _ptr(hist)))
         return hist[:self.n_contigs]
+
+    def depth_levels(self, tid, beg=0, n=None, edges=None, cap=None):
+        """pd_depth_levels after scan: the cells [beg, beg + n) of contig tid as maximal runs, (n_levels, 2) uint32 rows
+        (start, value); value = the depth (edges None / empty) or the index of the depth's class among the ascending edges
+        (0xFFFFFFFF below edges[0]).  cap (default n) bounds the rows the library may write."""
+        if n is None:
+            n = int(self.len[tid]) - int(beg)
+        cap = int(n) if cap is None else int(cap)
+        out = np.empty((max(cap, 1), 2), dtype=np.uint32)
+        got = ctypes.c_size_t(0)
+        if edges is None or len(edges) == 0:
+            e, ne = None, 0
+        else:
+            e = np.ascontiguousarray(edges, dtype=np.uint32)
+            ne = int(e.shape[0])
+        self._ck(self.L.pd_depth_levels(self.h, int(tid), int(beg), int(n), None if e is None else _ptr(e), ne, _ptr(out), cap, ctypes.byref(got)))
+        return out[:got.value]
 
     def read_depth(self, tid, beg=0, n=None):
         if n is None:

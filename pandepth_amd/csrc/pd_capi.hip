@@ -1456,6 +1456,62 @@ int pd_format_sites(pd_ctx *c, int32_t tid, uint32_t beg, size_t n, const char *
     return PD_OK;
 }
 
+// ---- depth levels ----
+// Scratch: the edges, the waves' run counts, their offsets, then the pairs.  The pairs' size is known only after the count, so the
+// count runs first with the head alone; when the buffer then has to grow (it is freed for that), the count is simply run again.
+int pd_depth_levels(pd_ctx *c, int32_t tid, uint32_t beg, size_t n, const uint32_t *edges, uint32_t n_edges, pd_level *out, size_t cap, size_t *n_levels)
+{
+    if (!c || !n_levels || (!out && cap) || (!edges && n_edges)) return PD_EINVAL;
+    *n_levels = 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int rs = need_state(c, 1, "pd_depth_levels")) return rs;
+    if (tid < 0 || tid >= c->n_contigs) return fail(c, PD_EINVAL, "pd_depth_levels: contig id out of range");
+    if ((uint64_t)beg + n > (uint64_t)c->len[tid]) return fail(c, PD_EINVAL, "pd_depth_levels: range past the contig's end");
+    if (n > ((size_t)1 << 27)) return fail(c, PD_EINVAL, "pd_depth_levels: at most 2^27 cells per call");
+    if (n_edges > 64) return fail(c, PD_EINVAL, "pd_depth_levels: at most 64 edges");
+    for (uint32_t k = 1; k < n_edges; ++k)
+        if (edges[k] <= edges[k - 1]) return fail(c, PD_EINVAL, "pd_depth_levels: edges not strictly ascending");
+    if (n == 0) return PD_OK;
+    HIPOK(c, hipSetDevice(c->device));
+    const uint32_t a0 = beg & ~3u, lo = beg - a0, hi = lo + (uint32_t)n;        // int4-aligned start; the range relative to it
+    const uint32_t nw = pdk::levels_waves(hi);
+    const size_t b_edge = 256, b_cnt = (size_t)nw * 4, b_off = ((size_t)nw * 4 + 4 + 15) / 16 * 16, b_head = b_edge + b_cnt + b_off;
+    const uint32_t *src = (const uint32_t *)(c->buf + c->off[tid] + a0);
+    const uint32_t kcap = (uint32_t)(cap < n ? cap : n);         // (a range of n cells has at most n runs)
+    uint32_t total = 0;
+    uint32_t *d_edge = nullptr, *d_cnt = nullptr, *d_off = nullptr;
+    for (int round = 0; ; ++round) {
+        int rc = ensure_scratch(c, round == 0 ? b_head + 64 : b_head + (size_t)(total < kcap ? total : kcap) * 8 + 64);
+        if (rc) return rc;
+        unsigned char *s = (unsigned char *)c->scratch;
+        d_edge = (uint32_t *)s; d_cnt = (uint32_t *)(s + b_edge); d_off = (uint32_t *)(s + b_edge + b_cnt);
+        if (n_edges) HIPOK(c, hipMemcpyAsync(d_edge, edges, (size_t)n_edges * 4, hipMemcpyHostToDevice, c->stream));
+        {
+            ProfScope ps(c, "depth_levels");
+            pdk::launch_levels(c->stream, src, a0, lo, hi, d_edge, n_edges, d_cnt, d_off, nullptr, 0, false);
+        }
+        HIPOK(c, hipGetLastError());
+        HIPOK(c, hipMemcpyAsync(&total, d_off + nw, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(c, hipStreamSynchronize(c->stream));
+        if (b_head + (size_t)(total < kcap ? total : kcap) * 8 + 64 <= c->scratch_bytes) break;
+        if (round) return fail(c, PD_EHIP, "pd_depth_levels: scratch did not grow");
+    }
+    *n_levels = total;
+    const uint32_t n_out = total < kcap ? total : kcap;
+    if (n_out) {
+        uint2 *d_out = (uint2 *)((unsigned char *)c->scratch + b_head);
+        {
+            ProfScope ps(c, "depth_levels");
+            pdk::launch_levels(c->stream, src, a0, lo, hi, d_edge, n_edges, d_cnt, d_off, d_out, n_out, true);
+        }
+        HIPOK(c, hipGetLastError());
+        HIPOK(c, hipMemcpyAsync(out, d_out, (size_t)n_out * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(c, hipStreamSynchronize(c->stream));
+    }
+    if ((size_t)total > cap) return fail(c, PD_ERANGE, "pd_depth_levels: more runs than the output holds");
+    return PD_OK;
+}
+
 int pd_device_buffer(pd_ctx *c, void **dev_ptr, uint64_t *n_words, uint64_t *contig_off)
 {
     if (!c) return PD_EINVAL;

@@ -140,6 +140,14 @@ int launch_sweep_hist(hipStream_t st, const int *buf, const int *carry, uint32_t
 int launch_hist_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, uint32_t n_bins,
                        unsigned long long *hist, unsigned grid, int variant);
 
+// depth levels (pd_depth_levels): runs of equal depth (n_edges == 0) or equal depth class over cells [lo, hi) behind `src`, an
+// int4-aligned cell pointer with lo < 4; first_cell = the contig-local index of src[0].  write = false: the waves' run counts and
+// their exclusive scan (wave_off[levels_waves(hi)] = the total); write = true: out[j] = (start, class) for j < cap.
+// wave_cnt: levels_waves(hi) words, wave_off: one more; edges: n_edges ascending device words.
+uint32_t levels_waves(uint64_t span);
+void launch_levels(hipStream_t st, const uint32_t *src, uint32_t first_cell, uint32_t lo, uint32_t hi, const uint32_t *edges, uint32_t n_edges,
+                   uint32_t *wave_cnt, uint32_t *wave_off, uint2 *out, uint32_t cap, bool write);
+
 // GPU-side BAM decode (pd_bgzf.hip)
 void launch_bgzf_inflate(hipStream_t st, const uint8_t *comp, const pd_bgzf_block *blk, uint32_t n_blk, uint8_t *out,
                          int *status, void *scratch);

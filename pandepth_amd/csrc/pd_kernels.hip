@@ -3325,6 +3325,159 @@ int launch_hist_pieces(hipStream_t st, const int *depth, const Piece *pieces, ui
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// depth levels (pd_depth_levels): the materialised depth of one contig range as runs of equal depth, or of equal depth class —
+// an ORDERED stream compaction.  Cell i opens a run when it is the range's first or class(d[i]) != class(d[i-1]).
+//   k_levels<EDGES, false> : every wave counts the runs that open in its 2048 cells
+//   k_levels_scan          : exclusive scan of the waves' counts (one workgroup), total behind the last
+//   k_levels<EDGES, true>  : every wave with runs writes its (start, class) pairs at its offset, in cell order
+// A wave owns 8 rows of 64 int4 (lane = four consecutive cells, non-temporal loads); waves are independent — the unit of the
+// count / offset arrays is the wave, so neither pass needs a workgroup-wide exchange, and the emit pass does not even load the
+// cells of a wave in which no run opens (quantised output: most of them).  The left neighbour of a lane's first cell comes from
+// the lane below (__shfl_up), of a row's first cell from the row before (readlane), of the wave's first cell from one extra
+// load.  `src` points at an int4-aligned cell at most three cells in front of the range; the range is [lo, hi) relative to it,
+// and nothing outside it is read (cell lo always opens a run, so it needs no neighbour).
+// class(): the identity (EDGES = false), else the index of the last edge <= d (0xFFFFFFFF below the first): a 256-entry LDS
+// table for low depths, and — for a row in which ANY lane holds a deeper cell, a wave-uniform choice — a branch-free six-step
+// search of the edges in LDS (edge[0] apart, edge[1 .. 63] padded with 0xFFFFFFFF).
+// ------------------------------------------------------------------------------------------
+namespace {
+constexpr int LV_ROWS = 8;
+constexpr uint32_t LV_WAVE = LV_ROWS * 256;          // cells per wave
+constexpr uint32_t LV_LUT = 256;                     // depths classified by table
+static_assert(LV_LUT == WG, "one table entry per thread");
+}
+
+__device__ __forceinline__ uint32_t level_search(uint32_t d, const uint32_t *edge, uint32_t n_edges)
+{
+    uint32_t pos = 0;                                            // edges among edge[1 .. 63] that are <= d
+#pragma unroll
+    for (uint32_t s = 32; s; s >>= 1) pos += edge[pos + s] <= d ? s : 0u;
+    pos = min(pos, n_edges - 1u);                                // (d = 0xFFFFFFFF meets the padding)
+    return d < edge[0] ? 0xFFFFFFFFu : pos;
+}
+
+template <bool EDGES, bool WRITE>
+__global__ __launch_bounds__(WG) void k_levels(const uint32_t *src, uint32_t first_cell, uint32_t lo, uint32_t hi, const uint32_t *edges,
+                                               uint32_t n_edges, uint32_t *wave_cnt, const uint32_t *wave_off, uint2 *out, uint32_t cap)
+{
+    __shared__ uint32_t s_edge[64];
+    __shared__ uint32_t s_lut[LV_LUT];
+    const int lane = threadIdx.x & 63;
+    const uint32_t g = blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
+    if (EDGES) {
+        if (threadIdx.x < 64) s_edge[threadIdx.x] = threadIdx.x < n_edges ? edges[threadIdx.x] : 0xFFFFFFFFu;
+        __syncthreads();
+        s_lut[threadIdx.x] = level_search(threadIdx.x, s_edge, n_edges);
+        __syncthreads();
+    }
+    const uint32_t w0 = g * LV_WAVE;                             // (wave-uniform from here on: no barrier below)
+    uint32_t run = 0;
+    if (WRITE) {
+        run = wave_off[g];
+        if (wave_off[g + 1] == run) return;                      // no run opens here (or the wave lies behind the range)
+    } else if (w0 >= hi) {
+        if (lane == 0) wave_cnt[g] = 0;
+        return;
+    }
+    uint32_t c[LV_ROWS][4];
+#pragma unroll
+    for (int r = 0; r < LV_ROWS; ++r) {
+        const uint32_t rel = w0 + r * 256 + lane * 4;
+        if (rel >= lo && rel + 4 <= hi) {
+            const v4i_nt x = __builtin_nontemporal_load(reinterpret_cast<const v4i_nt *>(src + rel));
+            c[r][0] = (uint32_t)x.x; c[r][1] = (uint32_t)x.y; c[r][2] = (uint32_t)x.z; c[r][3] = (uint32_t)x.w;
+        } else {                                                 // the range's unaligned head and tail, and what lies outside
+#pragma unroll
+            for (int k = 0; k < 4; ++k) c[r][k] = (rel + k >= lo && rel + k < hi) ? src[rel + k] : 0u;
+        }
+    }
+    uint32_t left_row = w0 > lo ? src[w0 - 1] : 0u;              // (w0 - 1 is inside [lo, hi) then)
+    if (EDGES) left_row = level_search(left_row, s_edge, n_edges);
+    uint32_t total = 0;
+#pragma unroll
+    for (int r = 0; r < LV_ROWS; ++r) {
+        if (EDGES) {
+            const uint32_t m = max(max(c[r][0], c[r][1]), max(c[r][2], c[r][3]));
+            if (__ballot(m >= LV_LUT) == 0ull) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) c[r][k] = s_lut[c[r][k]];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) c[r][k] = level_search(c[r][k], s_edge, n_edges);
+            }
+        }
+        const uint32_t rel = w0 + r * 256 + lane * 4;
+        uint32_t left = (uint32_t)__shfl_up((int)c[r][3], 1);
+        if (lane == 0) left = left_row;
+        left_row = (uint32_t)__builtin_amdgcn_readlane((int)c[r][3], 63);
+        bool f[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t x = rel + k;
+            f[k] = x >= lo && x < hi && (x == lo || c[r][k] != (k ? c[r][k - 1] : left));
+        }
+        if (!WRITE) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) total += (uint32_t)__popcll(__ballot(f[k]));
+        } else {
+            const uint32_t cnt = (uint32_t)f[0] + (uint32_t)f[1] + (uint32_t)f[2] + (uint32_t)f[3];
+            if (__ballot(cnt != 0u) == 0ull) continue;
+            const uint32_t incl = (uint32_t)wave_incl_scan((int)cnt);
+            uint32_t o = run + incl - cnt;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (f[k]) { if (o < cap) out[o] = make_uint2(first_cell + rel + k, c[r][k]); ++o; }
+            run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+    }
+    if (!WRITE && lane == 0) wave_cnt[g] = total;
+}
+
+// exclusive scan of the waves' run counts: one workgroup, 16 consecutive entries per thread and round; off[n] = the total
+__global__ __launch_bounds__(WG) void k_levels_scan(const uint32_t *cnt, uint32_t n, uint32_t *off)
+{
+    constexpr int PER = 16;
+    __shared__ uint32_t wsum[WG / 64];
+    __shared__ uint32_t carry;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (uint32_t b0 = 0; b0 < n; b0 += WG * PER) {
+        const uint32_t i0 = b0 + threadIdx.x * PER;
+        uint32_t v[PER], mine = 0;
+#pragma unroll
+        for (int k = 0; k < PER; ++k) { v[k] = i0 + k < n ? cnt[i0 + k] : 0u; mine += v[k]; }
+        const uint32_t incl = (uint32_t)wave_incl_scan((int)mine);
+        if (lane == 63) wsum[wv] = incl;
+        __syncthreads();
+        uint32_t base = carry + incl - mine;
+        for (int k = 0; k < wv; ++k) base += wsum[k];
+#pragma unroll
+        for (int k = 0; k < PER; ++k) { if (i0 + k < n) off[i0 + k] = base; base += v[k]; }
+        __syncthreads();
+        if (threadIdx.x == WG - 1) carry = base;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) off[n] = carry;
+}
+
+uint32_t levels_waves(uint64_t span) { return (uint32_t)((span + LV_WAVE - 1) / LV_WAVE + 3) / 4 * 4; }
+
+void launch_levels(hipStream_t st, const uint32_t *src, uint32_t first_cell, uint32_t lo, uint32_t hi, const uint32_t *edges, uint32_t n_edges,
+                   uint32_t *wave_cnt, uint32_t *wave_off, uint2 *out, uint32_t cap, bool write)
+{
+    const uint32_t nw = levels_waves(hi), nb = nw / 4;
+    if (!write) {
+        if (n_edges) hipLaunchKernelGGL((k_levels<true, false>), dim3(nb), dim3(WG), 0, st, src, first_cell, lo, hi, edges, n_edges, wave_cnt, wave_off, out, cap);
+        else hipLaunchKernelGGL((k_levels<false, false>), dim3(nb), dim3(WG), 0, st, src, first_cell, lo, hi, edges, n_edges, wave_cnt, wave_off, out, cap);
+        hipLaunchKernelGGL(k_levels_scan, dim3(1), dim3(WG), 0, st, wave_cnt, nw, wave_off);
+    } else {
+        if (n_edges) hipLaunchKernelGGL((k_levels<true, true>), dim3(nb), dim3(WG), 0, st, src, first_cell, lo, hi, edges, n_edges, wave_cnt, wave_off, out, cap);
+        else hipLaunchKernelGGL((k_levels<false, true>), dim3(nb), dim3(WG), 0, st, src, first_cell, lo, hi, edges, n_edges, wave_cnt, wave_off, out, cap);
+    }
+}
+
 } // namespace pdk
 
 #ifdef PD_WIDE3_TICKS

@@ -74,6 +74,8 @@ typedef struct pd_engine_api {
     /* optional (NULL = the host reads the depth back and bins it): the -dist table, see pd_scan_depth_histogram / pd_depth_histogram */
     int (*scan_depth_histogram)(pd_ctx *, uint32_t, unsigned, uint64_t *);
     int (*depth_histogram)(pd_ctx *, const pd_region *, size_t, uint32_t, uint64_t *);
+    /* optional (NULL = the host reads the depth back and finds the runs): the -levels file, see pd_depth_levels */
+    int (*depth_levels)(pd_ctx *, int32_t, uint32_t, size_t, const uint32_t *, uint32_t, pd_level *, size_t, size_t *);
 } pd_engine_api;
 
 /* Runs one `pandepth` invocation (argv as given to main) on the engine behind `api`. */

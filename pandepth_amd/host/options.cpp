@@ -187,6 +187,23 @@ int parse_options(int argc, char **argv, Options *o)
             if (v.empty() || *end != '\0' || n < 1 || n > 4096) { std::cerr << "Error: -dist should be between 1 and 4096" << std::endl; return 0; }
             o->dist = (int)n;
         }
+        else if (flag == "levels") {                                             // not in the reference: the .levels.bed.gz intervals (README)
+            if (!arg(&v)) return 0;
+            bool good = !v.empty();
+            o->levels_edges.clear();
+            if (v != "exact") {
+                uint64_t x = 0; size_t digits = 0;
+                for (size_t k = 0; good && k <= v.size(); ++k) {
+                    if (k < v.size() && v[k] >= '0' && v[k] <= '9') { x = x * 10 + (uint64_t)(v[k] - '0'); if (++digits > 10) good = false; continue; }
+                    if ((k < v.size() && v[k] != ',') || digits == 0 || x >= (1ull << 31) || o->levels_edges.size() == 64 ||
+                        (!o->levels_edges.empty() && x <= o->levels_edges.back())) { good = false; break; }
+                    o->levels_edges.push_back((uint32_t)x);
+                    x = 0; digits = 0;
+                }
+            }
+            if (!good) { std::cerr << "Error: -levels should be 'exact' or up to 64 ascending depths such as 0,1,5,15" << std::endl; return 0; }
+            o->levels = true;
+        }
         else if (flag == "help" || flag == "h") { print_help(); return 0; }
         else { std::cerr << "Error UnKnow argument -" << flag << std::endl; return 0; }
     }

@@ -29,6 +29,8 @@ struct Options {
     bool use_index = true;               // hidden -s clears it
     bool gc = false;
     int dist = 0;                        // -dist N (not in the reference): <out>.dist.stat.gz, depths 0 .. N-1 and >= N per contig
+    bool levels = false;                 // -levels SPEC (not in the reference): <out>.levels.bed.gz, runs of equal depth ('exact': levels_edges empty) or depth class
+    std::vector<uint32_t> levels_edges;  // the classes' lower edges, strictly ascending, at most 64
 };
 
 // Returns the number of input files (0 => nothing to do / message already printed), like
@@ -50,6 +52,7 @@ void print_help();
 //   sync_event=0 (collect waits for the batch's stream instead of its last event)  h2d_lanes=2 (two copies on the link at a time)
 //   dd_trace=1 (with PANDEPTH_TIMING: a [trace] line per batch, tools/feeder_trace.py)  dd_inflight=N (at most N batches queued at a time)
 //   dd_pin_ahead=N (buffers page-locked before the readers start)  decode_warm=1 (the slots made ready by a helper thread)  lz_calls=4 (provider calls of a gzip round in flight)
+//   levels_chunk=N (cells per pd_depth_levels call of the -levels writer; default 2^24)
 //   environment: PANDEPTH_DEVTRACE=1 (a [devtrace] line per batch: host-clock times of its stage events; first batches: what pd_decode_queue's own time went to)
 // -X is not part of the reference's command line (which answers an unknown flag with "Error UnKnow argument"): it is accepted only in this
 // spelling, is not listed by -h, and a PANDEPTH_* variable of the earlier rounds that is still set gets a note on stderr.

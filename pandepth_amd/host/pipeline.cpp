@@ -1374,6 +1374,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
         OUT.write(footer(0, 0, 0, gc ? 0 : -1));
         OUT.close();
         if (o.dist) { GzWriter d; if (d.open(prefix + ".dist.stat.gz")) { d.write(DIST_HEADER); d.close(); } }
+        if (o.levels) { GzWriter l; if (l.open(prefix + ".levels.bed.gz")) l.close(); }
         return 0;
     }
     // One context per GPU.  A `#.list` input is sharded one file per GPU (round robin) when the engine
@@ -1674,14 +1675,9 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
 
     const size_t nctg = hdr.lens.size();
     uint64_t SL = 0, SC = 0, SD = 0, SG = 0;
-    // -dist N (not in the reference): the depth distribution of the cells the tables count — every cell of the tables' contigs in
-    // the whole-contig modes, the union of the regions in -g / -b — per contig and genome-wide (Chr "*"), in <prefix>.dist.stat.gz.
-    // Made after the tables are written and the per-site job started, so that their path and timing stay as they are.
-    auto write_dist = [&]() -> bool {
-        if (!o.dist) return true;
-        const uint32_t nb = (uint32_t)o.dist + 1;                // depths 0 .. N-1 exact, the last bin >= N
-        std::vector<int32_t> tids;                               // the tables' contigs, in their order
-        std::vector<pd_region> regs;                             // region modes: the sorted, merged union of the table's regions
+    // The cells the tables count, shared by -dist and -levels: the tables' contigs in their order and, in the region modes, the
+    // sorted, merged union of the table's regions (1-based first, as pd_region has it; merged regions neither overlap nor touch).
+    auto covered_cells = [&](std::vector<int32_t> &tids, std::vector<pd_region> &regs) {
         if (synthetic) {
             if (o.mode == 6) { for (size_t t = 0; t < nctg; ++t) if (rm.has((int32_t)t)) tids.push_back((int32_t)t); }
             else for (auto &kv : rm.bins) tids.push_back(kv.first);
@@ -1705,6 +1701,16 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
                 }
             }
         }
+    };
+    // -dist N (not in the reference): the depth distribution of the cells the tables count — every cell of the tables' contigs in
+    // the whole-contig modes, the union of the regions in -g / -b — per contig and genome-wide (Chr "*"), in <prefix>.dist.stat.gz.
+    // Made after the tables are written and the per-site job started, so that their path and timing stay as they are.
+    auto write_dist = [&]() -> bool {
+        if (!o.dist) return true;
+        const uint32_t nb = (uint32_t)o.dist + 1;                // depths 0 .. N-1 exact, the last bin >= N
+        std::vector<int32_t> tids;                               // the tables' contigs, in their order
+        std::vector<pd_region> regs;                             // region modes: the sorted, merged union of the table's regions
+        covered_cells(tids, regs);
         std::vector<uint64_t> hist(nctg * nb, 0);
         if (synthetic && !scanned && api->scan_depth_histogram) {
             if (!merge_contexts()) return false;
@@ -1779,6 +1785,97 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
         tm.mark("depth distribution");
         return true;
     };
+    // -levels SPEC (not in the reference): the same cells as runs, in <prefix>.levels.bed.gz — "<contig>\t<start>\t<end>\t<value>\n",
+    // 0-based half-open, maximal stretches of equal depth ("exact": value = the depth) or of equal depth class (value "lo:hi",
+    // the last class "lo:inf"; cells below the first edge are not written).  The runs of a chunk of cells come from the engine
+    // (pd_depth_levels: 8 bytes per run cross the link) or, without that member, from the cells read back; the host joins a
+    // chunk's first run to the run left open by the chunk before, and formats the rows on its threads.  A chunk is 2^24 cells
+    // (-X levels_chunk=N): 64 MiB of depth on the device, at most 128 MiB of runs on the host, 12 calls for a 200 Mb contig.
+    // Quantised text is small and goes through the table writer's threaded gzip; exact text can be as long as the per-site file
+    // and is streamed through zlib as it is made, never held.
+    auto write_levels = [&]() -> bool {
+        if (!o.levels) return true;
+        std::vector<int32_t> tids;
+        std::vector<pd_region> regs;
+        covered_cells(tids, regs);
+        if (!need_scan()) return false;
+        const std::vector<uint32_t> &edges = o.levels_edges;
+        const bool exact = edges.empty();
+        std::vector<std::string> label(edges.size());
+        for (size_t k = 0; k < edges.size(); ++k) label[k] = std::to_string(edges[k]) + ":" + (k + 1 < edges.size() ? std::to_string(edges[k + 1]) : std::string("inf"));
+        const long long chunk_ll = tune_int("levels_chunk", (long long)1 << 24);
+        const size_t CH = (size_t)std::min<long long>(std::max<long long>(chunk_ll, 1), (long long)1 << 27);
+        GzWriter LV;
+        if (!exact) LV.set_threads(o.threads);
+        const std::string path = prefix + ".levels.bed.gz";
+        if (!LV.open(path)) { eng.fail("cannot open " + path); return false; }
+        struct Row { uint32_t start, end, value; };
+        std::vector<Row> rows;
+        std::unique_ptr<pd_level[]> runs;
+        size_t runs_cap = 0;
+        std::vector<uint32_t> cells;
+        const int nt = std::max(1, std::min(o.threads, 16));
+        std::vector<std::string> part((size_t)nt);
+        auto flush_rows = [&](const std::string &name) {
+            if (rows.empty()) return;
+            auto fmt = [&](size_t a, size_t b, std::string *out) {
+                out->clear();
+                for (size_t i = a; i < b; ++i) {
+                    *out += name; *out += '\t'; append_u64(out, rows[i].start); *out += '\t'; append_u64(out, rows[i].end); *out += '\t';
+                    if (exact) append_u64(out, rows[i].value); else *out += label[rows[i].value];
+                    *out += '\n';
+                }
+            };
+            const size_t n = rows.size(), k = n < 65536 ? 1 : (size_t)nt, per = (n + k - 1) / k;
+            std::vector<std::thread> th;
+            for (size_t j = 1; j < k; ++j) th.emplace_back(fmt, std::min(n, j * per), std::min(n, (j + 1) * per), &part[j]);
+            fmt(0, std::min(n, per), &part[0]);
+            for (auto &t : th) t.join();
+            for (size_t j = 0; j < k; ++j) LV.write(part[j]);
+            rows.clear();
+        };
+        size_t ri = 0;
+        for (int32_t t : tids) {
+            const std::string &name = hdr.names[(size_t)t];
+            std::vector<std::pair<uint64_t, uint64_t>> spans;    // cells [b, e) of this contig, ascending, not touching
+            if (synthetic) { if (hdr.lens[(size_t)t]) spans.emplace_back(0, hdr.lens[(size_t)t]); }
+            else for (; ri < regs.size() && regs[ri].tid == t; ++ri) spans.emplace_back((uint64_t)regs[ri].first - 1, (uint64_t)regs[ri].second);
+            for (auto &sp : spans) {
+                bool open = false; uint32_t ostart = 0, ovalue = 0;                // the run left open by the cells so far
+                auto close_run = [&](uint32_t end) { if (open && (exact || ovalue != 0xFFFFFFFFu)) rows.push_back(Row{ostart, end, ovalue}); };
+                for (uint64_t p = sp.first; p < sp.second; p += CH) {
+                    const size_t n = (size_t)std::min<uint64_t>(CH, sp.second - p);
+                    if (runs_cap < n) { runs.reset(); runs.reset(new pd_level[n]); runs_cap = n; }
+                    size_t nr = 0;
+                    if (api->depth_levels) {
+                        if (!eng.ck(api->depth_levels(eng.ctx, t, (uint32_t)p, n, exact ? nullptr : edges.data(), (uint32_t)edges.size(), runs.get(), n, &nr),
+                                    "pd_depth_levels")) { LV.abandon(); return false; }
+                    } else {
+                        // engines without the entry point: the cells are read back and the runs found here
+                        cells.resize(n);
+                        if (!eng.ck(api->read_depth(eng.ctx, t, (uint32_t)p, n, cells.data()), "pd_read_depth")) { LV.abandon(); return false; }
+                        uint32_t prev = 0;
+                        for (size_t i = 0; i < n; ++i) {
+                            const uint32_t v = exact ? cells[i] : (uint32_t)(std::upper_bound(edges.begin(), edges.end(), cells[i]) - edges.begin()) - 1u;
+                            if (i == 0 || v != prev) runs[nr++] = pd_level{(uint32_t)(p + i), v};
+                            prev = v;
+                        }
+                    }
+                    for (size_t j = 0; j < nr; ++j) {
+                        if (open && runs[j].value == ovalue) continue;             // (a chunk's first run continuing the one before)
+                        close_run(runs[j].start);
+                        open = true; ostart = runs[j].start; ovalue = runs[j].value;
+                    }
+                    if (rows.size() >= ((size_t)1 << 20)) flush_rows(name);
+                }
+                close_run((uint32_t)sp.second);
+            }
+            flush_rows(name);
+        }
+        if (!LV.close()) { ::remove(path.c_str()); eng.fail("cannot write " + path); return false; }
+        tm.mark("depth levels");
+        return true;
+    };
     std::string txt;
 
     if (o.mode == 6) {
@@ -1848,6 +1945,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
             OUT.close();
             tm.mark("table close");
             if (!write_dist()) return bail();
+            if (!write_levels()) return bail();
             if (!site_done()) return bail();
             std::cout << "INFO: Input data read done" << std::endl;
             return 0;
@@ -1887,6 +1985,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
         OUT.close();
         tm.mark("table gzip");
         if (!write_dist()) return bail();
+        if (!write_levels()) return bail();
         if (!site_done()) return bail();
         std::cout << "INFO: Input data read done" << std::endl;
         return 0;
@@ -2016,6 +2115,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
     OUT.close();
     tm.mark("table gzip");
     if (!write_dist()) return bail();
+    if (!write_levels()) return bail();
     if (!site_done()) return bail();
     return 0;
 }
