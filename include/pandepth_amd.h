@@ -184,6 +184,19 @@ typedef struct pd_level { uint32_t start, value; } pd_level;
 int pd_depth_levels(pd_ctx *ctx, int32_t tid, uint32_t beg, size_t n, const uint32_t *edges, uint32_t n_edges,
                     pd_level *out, size_t cap, size_t *n_levels);
 
+/* Depth percentiles of many rows at once, selected on the device.  After pd_scan.  Row i = segs[row_off[i] .. row_off[i+1])
+ * (row_off: n_rows + 1 entries, non-decreasing, row_off[0] = 0, row_off[n_rows] = n_segs, else PD_EINVAL; at most 2^21 segments
+ * in one row).  Segments are cells [first-1, second) clipped to their contig, in any order, may overlap (a multiset) and may lie
+ * on different contigs; tid out of range: PD_EINVAL.  pct: 1..16 values in 0..100, strictly ascending, else PD_EINVAL.
+ * cells[i] = cells of row i (may be NULL); q[i * n_pct + j] = the nearest-rank pct[j] quantile of row i's cell values — the r-th
+ * smallest with r = max(1, ceil(pct[j] * cells[i] / 100)) — and 0xFFFFFFFF when cells[i] == 0.  Exact for any uint32 cell value.
+ * Only n_rows * 4 * n_pct bytes come back; device scratch stays below 256 MiB whatever the number of rows (rows are served in
+ * batches).  The context is left as it was found. */
+int pd_depth_quantiles(pd_ctx *ctx, const pd_region *segs, size_t n_segs, const uint64_t *row_off, size_t n_rows,
+                       const uint32_t *pct, uint32_t n_pct, uint64_t *cells, uint32_t *q);
+/* the same for the windows of pd_window_layout(w) (row = window win_off[t] + k), without a region list crossing the link */
+int pd_window_quantiles(pd_ctx *ctx, uint32_t w, const uint32_t *pct, uint32_t n_pct, uint32_t *q);
+
 /* Replaces the per-site read loop PD:4278-4281: copies depth cells [beg, beg+n) of contig tid
  * to the host.  Requires pd_scan first. */
 int pd_read_depth(pd_ctx *ctx, int32_t tid, uint32_t beg, size_t n, uint32_t *out);
@@ -373,7 +386,8 @@ int pd_synchronize(pd_ctx *ctx);
  * pd_profile_get returns the accumulated milliseconds and launch count of kernel `name`
  * ("reset", "fill", "scatter_index", "scatter_tiles", "scatter_finish", "scatter_atomic", "tile_carry",
  * "scan", "scan_reduce_windows", "reduce_intervals", "reduce_windows", "direct_tiles", "direct_export",
- * "export_i4", "export_i8", "import_i8", "slice_sweep", "gather_windows", "accumulate_from");
+ * "export_i4", "export_i8", "import_i8", "slice_sweep", "gather_windows", "accumulate_from",
+ * "quantile_narrow", "quantile_block", "quantile_pieces", "quantile_pick");
  * pd_profile(ctx, 0/1) switches it (and clears the accumulators). */
 int pd_profile(pd_ctx *ctx, int enable);
 int pd_profile_get(pd_ctx *ctx, const char *name, double *ms, uint64_t *launches);

@@ -20,7 +20,10 @@ extern "C" {
  * text from memory), "lz_slots" (2 | 4 parse calls in flight).  Round 6, the decode pipeline: "decode_h2d_fifo" (default 1: the batches' host-to-device copies
  * first come, first served on the context's main stream, one copy per batch; 0: on the batch's own stream), "decode_h2d_lanes" (1 | 2 copies on the link at a
  * time), "decode_sync_event" (default 1: pd_decode_collect waits for the batch's last event; 0: for its stream), "decode_h2d_kernel" (1..3: a copy kernel /
- * + the tables / the members read in place: all measured slower), "decode_warm" (1: the session's first slots made ready by a helper thread). */
+ * + the tables / the members read in place: all measured slower), "decode_warm" (1: the session's first slots made ready by a helper thread).
+ * Quantiles: "quantile_wave_max" (0..2048, default 512: rows of up to that many cells are selected by a group of lanes from LDS),
+ * "quantile_split_cells" (default 262144: rows of up to that many cells are one workgroup's LDS histogram; longer rows are cut into pieces
+ * over many workgroups).  0 / 0 sends every row through the pieces, 0 / 2^32-1 every row through one workgroup. */
 int pd_set_param(pd_ctx *ctx, const char *name, uint64_t value);
 
 /* ---- GPU-side BAM decode, the one-call synchronous form (round 1's entry point, kept on top of

@@ -70,6 +70,8 @@ def load():
         "pd_scan_depth_histogram": (I, [P, ctypes.c_uint32, U, P]),
         "pd_depth_histogram": (I, [P, P, SZ, ctypes.c_uint32, P]),
         "pd_depth_levels": (I, [P, ctypes.c_int32, ctypes.c_uint32, SZ, P, ctypes.c_uint32, P, SZ, ctypes.POINTER(SZ)]),
+        "pd_depth_quantiles": (I, [P, P, SZ, P, SZ, P, ctypes.c_uint32, P, P]),
+        "pd_window_quantiles": (I, [P, ctypes.c_uint32, P, ctypes.c_uint32, P]),
         "pd_read_depth": (I, [P, ctypes.c_int32, ctypes.c_uint32, SZ, P]),
         "pd_format_sites": (I, [P, ctypes.c_int32, ctypes.c_uint32, SZ, ctypes.c_char_p, SZ, P, SZ, ctypes.POINTER(SZ)]),
         "pd_deflate_parse": (I, [P, P, SZ, P, ctypes.c_uint32, P, SZ, P]),
@@ -125,7 +127,7 @@ def load():
 
 EXPORTS = ["pd_abi_version", "pd_create", "pd_destroy", "pd_strerror", "pd_reset", "pd_push_intervals",
            "pd_push_intervals_device", "pd_runs_create", "pd_runs_destroy", "pd_push_runs", "pd_stage_acquire", "pd_stage_submit", "pd_set_param", "pd_keep_deferred", "pd_scan",
-           "pd_reduce_intervals", "pd_window_layout", "pd_scan_reduce_windows", "pd_reduce_windows", "pd_scan_depth_histogram", "pd_depth_histogram", "pd_depth_levels",
+           "pd_reduce_intervals", "pd_window_layout", "pd_scan_reduce_windows", "pd_reduce_windows", "pd_scan_depth_histogram", "pd_depth_histogram", "pd_depth_levels", "pd_depth_quantiles", "pd_window_quantiles",
            "pd_read_depth", "pd_format_sites", "pd_deflate_parse", "pd_host_register", "pd_host_unregister", "pd_text_open", "pd_text_close", "pd_text_append_sites", "pd_text_parse", "pd_text_read", "pd_text_release", "pd_text_append_window_rows", "pd_text_append_bytes", "pd_device_buffer", "pd_device_count", "pd_accumulate_from", "pd_device_layout", "pd_export_i8", "pd_import_i8", "pd_export_i4",
            "pd_slice_sweep_i4", "pd_gather_windows", "pd_push_bgzf_units", "pd_decode_begin", "pd_decode_acquire", "pd_decode_submit", "pd_decode_queue", "pd_decode_collect", "pd_decode_end", "pd_decode_abort", "pd_comm_unique_id", "pd_comm_init", "pd_comm_init_all", "pd_comm_init_local", "pd_comm_preinit", "pd_comm_prepare", "pd_comm_destroy",
            "pd_comm_strerror", "pd_sliced_window_sum", "pd_sliced_interval_sum", "pd_sliced_sum_start", "pd_sliced_sum_finish", "pd_x_bgzf_inflate", "pd_stream", "pd_synchronize", "pd_profile",
@@ -405,6 +407,31 @@ class Engine:
             ne = int(e.shape[0])
         self._ck(self.L.pd_depth_levels(self.h, int(tid), int(beg), int(n), None if e is None else _ptr(e), ne, _ptr(out), cap, ctypes.byref(got)))
         return out[:got.value]
+
+    def depth_quantiles(self, segs, row_off, pct):
+        """pd_depth_quantiles after scan: row i = the segments segs[row_off[i]:row_off[i + 1]] ((n, 3) int32: tid, first, second —
+        cells [first-1, second) clipped to the contig, a multiset); returns (cells uint64 (n_rows,), q uint32 (n_rows, len(pct))),
+        q[i, j] = the nearest-rank pct[j] percentile of row i's cells, 0xFFFFFFFF for a row without cells."""
+        sg = np.ascontiguousarray(segs, dtype=np.int32).reshape(-1, 3)
+        ro = np.ascontiguousarray(row_off, dtype=np.uint64)
+        pc = np.ascontiguousarray(pct, dtype=np.uint32)
+        n_rows, npc = int(ro.size) - 1, int(pc.size)
+        cells = np.zeros(max(n_rows, 1), dtype=np.uint64)
+        q = np.zeros((max(n_rows, 1), max(npc, 1)), dtype=np.uint32)
+        pcb = pc if npc else np.zeros(1, dtype=np.uint32)
+        self._ck(self.L.pd_depth_quantiles(self.h, _ptr(sg) if sg.shape[0] else None, sg.shape[0], _ptr(ro), n_rows, _ptr(pcb), npc, _ptr(cells), _ptr(q)))
+        return cells[:n_rows], q[:n_rows]
+
+    def window_quantiles(self, w, pct):
+        """pd_window_quantiles after scan: (win_off, q uint32 (n_windows, len(pct))) for the windows of window_layout(w)."""
+        off = self.window_layout(w)
+        n = int(off[-1])
+        pc = np.ascontiguousarray(pct, dtype=np.uint32)
+        npc = int(pc.size)
+        q = np.zeros((max(n, 1), max(npc, 1)), dtype=np.uint32)
+        pcb = pc if npc else np.zeros(1, dtype=np.uint32)
+        self._ck(self.L.pd_window_quantiles(self.h, int(w), _ptr(pcb), npc, _ptr(q)))
+        return off, q[:n]
 
     def read_depth(self, tid, beg=0, n=None):
         if n is None:

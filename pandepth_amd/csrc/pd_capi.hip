@@ -245,6 +245,7 @@ struct pd_ctx {
     uint32_t dec_max_redo = 256;                                  // ... with at most this many segments walking again per batch ("decode_max_redo")
     std::atomic<uint64_t> dec_n_fast{0}, dec_n_slow{0}, dec_n_redo{0};   // batches finished without / with the host's chain check; segments the device walked again
     uint32_t direct_sample = 256;                                 // index stride of the direct path (runs)
+    uint32_t q_wave_max = 512, q_split = 262144;                  // "quantile_wave_max" / "quantile_split_cells": the cell counts up to which a quantile row takes the narrow / the workgroup kernel
     int hist_variant = 1;                                         // "hist_variant": the histogram kernels' LDS form (launch_sweep_hist): 1 = one copy per workgroup, folded (measured best)
     int direct_un = 0;                                           // 0 = the default form of the wide direct kernel (launch_direct_tiles)
     bool all_valid_host = false;
@@ -890,6 +891,8 @@ int pd_set_param(pd_ctx *c, const char *name, uint64_t value)
     if (!strcmp(name, "decode_sync_event")) { c->dec_sync_event = value != 0; return PD_OK; }
     if (!strcmp(name, "decode_max_redo")) { c->dec_max_redo = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "hist_variant")) { if (value > 3) return fail(c, PD_EINVAL, "hist_variant must be in [0, 3]"); c->hist_variant = (int)value; return PD_OK; }
+    if (!strcmp(name, "quantile_wave_max")) { if (value > 2048) return fail(c, PD_EINVAL, "quantile_wave_max must be in [0, 2048]"); c->q_wave_max = (uint32_t)value; return PD_OK; }
+    if (!strcmp(name, "quantile_split_cells")) { if (value > 0xFFFFFFFFull) return fail(c, PD_EINVAL, "quantile_split_cells must be below 2^32"); c->q_split = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "decode_near_span")) { c->dec_near_span = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
     return fail(c, PD_EINVAL, std::string("unknown parameter ") + name);
 }
@@ -1509,6 +1512,211 @@ int pd_depth_levels(pd_ctx *c, int32_t tid, uint32_t beg, size_t n, const uint32
         HIPOK(c, hipStreamSynchronize(c->stream));
     }
     if ((size_t)total > cap) return fail(c, PD_ERANGE, "pd_depth_levels: more runs than the output holds");
+    return PD_OK;
+}
+
+} // extern "C"
+
+// ---- depth quantiles ----
+// Rows go to the device in batches whose scratch does not grow with the row count: at most 2^20 rows (2^22 windows) and 2^21
+// segments a batch, 1024 histogram rows and 2^21 pieces a wide launch.  A row takes the narrow kernel up to "quantile_wave_max"
+// cells, the workgroup kernel up to "quantile_split_cells", and is cut into pieces over many workgroups above that.
+namespace {
+constexpr uint32_t Q_PIECE = 16384, Q_WIDE_ROWS = 1024;
+constexpr size_t Q_PIECE_CHUNK = (size_t)1 << 21, Q_SEG_BATCH = (size_t)1 << 21;
+inline size_t q_al(size_t b) { return (b + 255) / 256 * 256; }
+
+int quant_pct(pd_ctx *c, const uint32_t *pct, uint32_t n_pct, const char *fn, pdk::QPct *P)
+{
+    if (!pct || n_pct < 1 || n_pct > 16) return fail(c, PD_EINVAL, std::string(fn) + ": 1 to 16 percentages");
+    P->n = n_pct;
+    for (uint32_t j = 0; j < 16; ++j) P->p[j] = 0;
+    for (uint32_t j = 0; j < n_pct; ++j) {
+        if (pct[j] > 100 || (j && pct[j] <= pct[j - 1])) return fail(c, PD_EINVAL, std::string(fn) + ": percentages must be 0..100, strictly ascending");
+        P->p[j] = pct[j];
+    }
+    return PD_OK;
+}
+
+// the pieces collected so far into the histograms (Piece.region = the row's number in the wide launch)
+int quant_flush_pieces(pd_ctx *c, std::vector<Piece> &pieces, Piece *d_pieces, unsigned long long *d_hist)
+{
+    if (pieces.empty()) return PD_OK;
+    HIPOK(c, hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(Piece), hipMemcpyHostToDevice, c->stream));
+    HIPOK(c, hipStreamSynchronize(c->stream));          // pieces is refilled by the caller
+    {
+        ProfScope ps(c, "quantile_pieces");
+        if (launch_hist_pieces(c->stream, c->buf, d_pieces, (uint32_t)pieces.size(), 4096, d_hist, (unsigned)c->n_cu * 8, c->hist_variant))
+            return fail(c, PD_EHIP, "quantile histograms: cannot reserve LDS");
+    }
+    HIPOK(c, hipGetLastError());
+    pieces.clear();
+    return PD_OK;
+}
+inline int quant_add_pieces(pd_ctx *c, std::vector<Piece> &pieces, uint64_t start, uint64_t count, uint32_t slot, Piece *d_pieces, unsigned long long *d_hist)
+{
+    for (uint64_t p = 0; p < count; p += Q_PIECE) {
+        Piece pc; pc.start = start + p; pc.count = (uint32_t)std::min<uint64_t>(Q_PIECE, count - p); pc.region = slot;
+        pieces.push_back(pc);
+        if (pieces.size() == Q_PIECE_CHUNK) if (int rc = quant_flush_pieces(c, pieces, d_pieces, d_hist)) return rc;
+    }
+    return PD_OK;
+}
+} // namespace
+
+extern "C" {
+
+int pd_window_quantiles(pd_ctx *c, uint32_t w, const uint32_t *pct, uint32_t n_pct, uint32_t *q)
+{
+    if (!c || !q || w == 0) return PD_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int rs = need_state(c, 1, "pd_window_quantiles")) return rs;
+    pdk::QPct P;
+    if (int rc = quant_pct(c, pct, n_pct, "pd_window_quantiles", &P)) return rc;
+    std::vector<uint64_t> wo((size_t)c->n_contigs + 1);
+    pd_window_layout(c, w, wo.data());
+    const uint64_t nw = wo[c->n_contigs];
+    if (nw == 0) return PD_OK;
+    HIPOK(c, hipSetDevice(c->device));
+    uint32_t maxlen = 0;
+    for (uint32_t l : c->len) maxlen = std::max(maxlen, l);
+    const uint32_t weff = std::min(w, maxlen);
+    const int regime = weff <= c->q_wave_max ? 0 : weff <= c->q_split ? 1 : 2;
+    const uint64_t BR = regime == 2 ? Q_WIDE_ROWS : std::min<uint64_t>((uint64_t)1 << 22, ((uint64_t)1 << 24) / n_pct);
+    const uint64_t nbmax = std::min(BR, nw);
+    const size_t b_wo = q_al(wo.size() * 8), b_q = q_al((size_t)nbmax * n_pct * 4);
+    const size_t b_hist = regime == 2 ? q_al((size_t)nbmax * 4096 * 8) : 0, b_pc = regime == 2 ? Q_PIECE_CHUNK * sizeof(Piece) : 0;
+    if (int rc = ensure_scratch(c, b_wo + b_q + b_hist + b_pc + 256)) return rc;
+    unsigned char *s = (unsigned char *)c->scratch;
+    uint64_t *d_wo = (uint64_t *)s; uint32_t *d_q = (uint32_t *)(s + b_wo);
+    unsigned long long *d_hist = (unsigned long long *)(s + b_wo + b_q); Piece *d_pc = (Piece *)(s + b_wo + b_q + b_hist);
+    HIPOK(c, hipMemcpyAsync(d_wo, wo.data(), wo.size() * 8, hipMemcpyHostToDevice, c->stream));
+    std::vector<Piece> pieces;
+    int32_t t = 0;
+    for (uint64_t row0 = 0; row0 < nw; row0 += BR) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(BR, nw - row0);
+        pdk::QRows R{nullptr, nullptr, d_wo, c->d_off, c->d_len, row0, w, c->n_contigs};
+        if (regime == 0) {
+            uint32_t gshift = 3; while (gshift < 6 && (1u << gshift) < weff) ++gshift;
+            ProfScope ps(c, "quantile_narrow");
+            if (pdk::launch_quant_narrow(c->stream, c->buf, R, nullptr, nb, weff, gshift, P, d_q)) return fail(c, PD_EHIP, "quantile kernel: cannot reserve LDS");
+        } else if (regime == 1) {
+            ProfScope ps(c, "quantile_block");
+            pdk::launch_quant_block(c->stream, c->buf, R, nullptr, nb, P, d_q, nullptr);
+        } else {
+            HIPOK(c, hipMemsetAsync(d_hist, 0, (size_t)nb * 4096 * 8, c->stream));
+            for (uint64_t g = row0; g < row0 + nb; ++g) {
+                while (wo[(size_t)t + 1] <= g) ++t;
+                const uint64_t b = (g - wo[(size_t)t]) * w, e = std::min<uint64_t>(b + w, c->len[(size_t)t]);
+                if (int rc = quant_add_pieces(c, pieces, c->off[(size_t)t] + b, e - b, (uint32_t)(g - row0), d_pc, d_hist)) return rc;
+            }
+            if (int rc = quant_flush_pieces(c, pieces, d_pc, d_hist)) return rc;
+            ProfScope ps(c, "quantile_pick");
+            pdk::launch_quant_block(c->stream, c->buf, R, nullptr, nb, P, d_q, d_hist);
+        }
+        HIPOK(c, hipGetLastError());
+        HIPOK(c, hipMemcpyAsync(q + row0 * n_pct, d_q, (size_t)nb * n_pct * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(c, hipStreamSynchronize(c->stream));
+    }
+    return PD_OK;
+}
+
+int pd_depth_quantiles(pd_ctx *c, const pd_region *segs, size_t n_segs, const uint64_t *row_off, size_t n_rows,
+                       const uint32_t *pct, uint32_t n_pct, uint64_t *cells, uint32_t *q)
+{
+    if (!c || (n_segs && !segs) || !row_off || (n_rows && !q)) return PD_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int rs = need_state(c, 1, "pd_depth_quantiles")) return rs;
+    pdk::QPct P;
+    if (int rc = quant_pct(c, pct, n_pct, "pd_depth_quantiles", &P)) return rc;
+    if (row_off[0] != 0 || row_off[n_rows] != n_segs) return fail(c, PD_EINVAL, "pd_depth_quantiles: row_off must run from 0 to n_segs");
+    for (size_t i = 0; i < n_rows; ++i) {
+        if (row_off[i + 1] < row_off[i] || row_off[i + 1] > n_segs) return fail(c, PD_EINVAL, "pd_depth_quantiles: row_off must not decrease");
+        if (row_off[i + 1] - row_off[i] > Q_SEG_BATCH) return fail(c, PD_EINVAL, "pd_depth_quantiles: at most 2^21 segments per row");
+    }
+    for (size_t i = 0; i < n_segs; ++i)
+        if (segs[i].tid < 0 || segs[i].tid >= c->n_contigs) return fail(c, PD_EINVAL, "pd_depth_quantiles: contig id out of range");
+    if (n_rows == 0) return PD_OK;
+    HIPOK(c, hipSetDevice(c->device));
+    auto clip = [&](const pd_region &r, uint64_t *start, uint64_t *count) {
+        int64_t b = (int64_t)r.first - 1, e = r.second;
+        if (b < 0) b = 0;
+        if (e > (int64_t)c->len[(size_t)r.tid]) e = (int64_t)c->len[(size_t)r.tid];
+        *start = c->off[(size_t)r.tid] + (uint64_t)b; *count = e > b ? (uint64_t)(e - b) : 0;
+    };
+    std::vector<uint64_t> own_cells;
+    if (!cells) { own_cells.resize(n_rows); cells = own_cells.data(); }
+    size_t n_wide = 0; uint64_t wide_pieces = 0;
+    for (size_t i = 0; i < n_rows; ++i) {
+        uint64_t C = 0, np = 0;
+        for (uint64_t k = row_off[i]; k < row_off[i + 1]; ++k) { uint64_t st, cn; clip(segs[k], &st, &cn); C += cn; np += (cn + Q_PIECE - 1) / Q_PIECE; }
+        cells[i] = C;
+        if (C > c->q_wave_max && C > c->q_split) { ++n_wide; wide_pieces += np; }
+    }
+    const size_t BR = (size_t)1 << 20, nbmax = std::min(BR, n_rows), sgmax = std::min<size_t>(Q_SEG_BATCH, n_segs), nwmax = std::min<size_t>(Q_WIDE_ROWS, n_wide);
+    const size_t b_seg = q_al(sgmax * sizeof(Piece)), b_off = q_al((nbmax + 1) * 8), b_list = q_al(nbmax * 4), b_q = q_al(nbmax * n_pct * 4);
+    const size_t b_hist = q_al(nwmax * 4096 * 8), b_pc = q_al((size_t)std::min<uint64_t>(Q_PIECE_CHUNK, wide_pieces) * sizeof(Piece));
+    if (int rc = ensure_scratch(c, b_seg + b_off + 3 * b_list + b_q + b_hist + b_pc + 256)) return rc;
+    unsigned char *s = (unsigned char *)c->scratch;
+    Piece *d_seg = (Piece *)s; s += b_seg;
+    uint64_t *d_off = (uint64_t *)s; s += b_off;
+    uint32_t *d_list[3]; for (int k = 0; k < 3; ++k) { d_list[k] = (uint32_t *)s; s += b_list; }
+    uint32_t *d_q = (uint32_t *)s; s += b_q;
+    unsigned long long *d_hist = (unsigned long long *)s; s += b_hist;
+    Piece *d_pc = (Piece *)s;
+    std::vector<Piece> hseg, pieces;
+    std::vector<uint64_t> hoff;
+    std::vector<uint32_t> list[3];
+    for (size_t r0 = 0; r0 < n_rows;) {
+        size_t r1 = r0;
+        while (r1 < n_rows && r1 - r0 < BR && row_off[r1 + 1] - row_off[r0] <= Q_SEG_BATCH) ++r1;     // (a row alone always fits)
+        const uint32_t nb = (uint32_t)(r1 - r0);
+        hseg.clear(); hoff.clear(); for (auto &l : list) l.clear();
+        uint32_t cap = 0;
+        for (size_t i = r0; i < r1; ++i) {
+            hoff.push_back(hseg.size());
+            for (uint64_t k = row_off[i]; k < row_off[i + 1]; ++k) {
+                uint64_t st, cn; clip(segs[k], &st, &cn);
+                Piece pc; pc.start = st; pc.count = (uint32_t)cn; pc.region = 0;
+                hseg.push_back(pc);
+            }
+            const uint64_t C = cells[i];
+            const int regime = C <= c->q_wave_max ? 0 : C <= c->q_split ? 1 : 2;
+            if (regime == 0) cap = std::max(cap, (uint32_t)C);
+            list[regime].push_back((uint32_t)(i - r0));
+        }
+        hoff.push_back(hseg.size());
+        if (!hseg.empty()) HIPOK(c, hipMemcpyAsync(d_seg, hseg.data(), hseg.size() * sizeof(Piece), hipMemcpyHostToDevice, c->stream));
+        HIPOK(c, hipMemcpyAsync(d_off, hoff.data(), hoff.size() * 8, hipMemcpyHostToDevice, c->stream));
+        for (int k = 0; k < 3; ++k)
+            if (!list[k].empty()) HIPOK(c, hipMemcpyAsync(d_list[k], list[k].data(), list[k].size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(c, hipStreamSynchronize(c->stream));          // the host arrays are refilled by the next batch
+        pdk::QRows R{d_seg, d_off, nullptr, c->d_off, c->d_len, 0, 0, c->n_contigs};
+        if (!list[0].empty()) {
+            ProfScope ps(c, "quantile_narrow");
+            if (pdk::launch_quant_narrow(c->stream, c->buf, R, d_list[0], (uint32_t)list[0].size(), cap, 6, P, d_q)) return fail(c, PD_EHIP, "quantile kernel: cannot reserve LDS");
+        }
+        if (!list[1].empty()) {
+            ProfScope ps(c, "quantile_block");
+            pdk::launch_quant_block(c->stream, c->buf, R, d_list[1], (uint32_t)list[1].size(), P, d_q, nullptr);
+        }
+        for (size_t w0 = 0; w0 < list[2].size(); w0 += Q_WIDE_ROWS) {
+            const uint32_t nwr = (uint32_t)std::min<size_t>(Q_WIDE_ROWS, list[2].size() - w0);
+            HIPOK(c, hipMemsetAsync(d_hist, 0, (size_t)nwr * 4096 * 8, c->stream));
+            for (uint32_t k = 0; k < nwr; ++k) {
+                const uint32_t lr = list[2][w0 + k];
+                for (uint64_t j = hoff[lr]; j < hoff[lr + 1]; ++j)
+                    if (int rc = quant_add_pieces(c, pieces, hseg[j].start, hseg[j].count, k, d_pc, d_hist)) return rc;
+            }
+            if (int rc = quant_flush_pieces(c, pieces, d_pc, d_hist)) return rc;
+            ProfScope ps(c, "quantile_pick");
+            pdk::launch_quant_block(c->stream, c->buf, R, d_list[2] + w0, nwr, P, d_q, d_hist);
+        }
+        HIPOK(c, hipGetLastError());
+        HIPOK(c, hipMemcpyAsync(q + r0 * n_pct, d_q, (size_t)nb * n_pct * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(c, hipStreamSynchronize(c->stream));
+        r0 = r1;
+    }
     return PD_OK;
 }
 

@@ -148,6 +148,24 @@ uint32_t levels_waves(uint64_t span);
 void launch_levels(hipStream_t st, const uint32_t *src, uint32_t first_cell, uint32_t lo, uint32_t hi, const uint32_t *edges, uint32_t n_edges,
                    uint32_t *wave_cnt, uint32_t *wave_off, uint2 *out, uint32_t cap, bool write);
 
+// depth quantiles (pd_depth_quantiles / pd_window_quantiles) over the depth left by pd_scan.  Row r of a batch is the segments
+// segs[seg_off[r] .. seg_off[r + 1]) (Piece.start = flat cell, Piece.count; region unused) or, with segs == nullptr, window
+// row0 + r of pd_window_layout(w), found on the device.  `list` (may be null: rows 0 .. n - 1) names the rows a launch takes;
+// q[r * P.n + j] = the nearest-rank P.p[j] quantile, 0xFFFFFFFF for a row without cells.
+//   launch_quant_narrow : rows of at most `cap` cells, a group of 1 << gshift lanes (3 .. 6) per row; returns a hipError_t (LDS)
+//   launch_quant_block  : a workgroup per row; ghist != nullptr: the row's 4096 bins (last: >= 4095) were counted by
+//                         launch_hist_pieces into ghist[slot * 4096 ..) with Piece.region = slot, the launch's row number
+struct QRows {
+    const Piece *segs; const uint64_t *seg_off;
+    const uint64_t *win_off, *contig_off; const uint32_t *contig_len;
+    uint64_t row0; uint32_t w; int32_t n_contigs;
+};
+struct QPct { uint32_t n; uint32_t p[16]; };
+int launch_quant_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t cap, uint32_t gshift,
+                        const QPct &P, uint32_t *q);
+void launch_quant_block(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, const QPct &P, uint32_t *q,
+                        const unsigned long long *ghist);
+
 // GPU-side BAM decode (pd_bgzf.hip)
 void launch_bgzf_inflate(hipStream_t st, const uint8_t *comp, const pd_bgzf_block *blk, uint32_t n_blk, uint8_t *out,
                          int *status, void *scratch);

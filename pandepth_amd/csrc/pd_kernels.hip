@@ -3478,6 +3478,221 @@ void launch_levels(hipStream_t st, const uint32_t *src, uint32_t first_cell, uin
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// depth quantiles (pd_depth_quantiles / pd_window_quantiles): exact nearest-rank order statistics of the cells of many rows.
+// A row is a multiset of segments of the materialised depth (QRows: a segment list, or the windows of pd_window_layout(w) found
+// on the device).  Three launch shapes, chosen per row by its cell count on the host:
+//   k_quant_narrow        a GROUP of 8 .. 64 lanes per row: the cells go to LDS once, every rank is found by a bitwise radix
+//                         descent from the highest bit set in the row (ballot + popcount per 64 cells and bit); exact for any uint32
+//   k_quant_block<.., 0>  a workgroup per row: LDS histogram of min(v, 4095), block prefix, every rank picked from it
+//   k_hist_pieces + k_quant_block<.., 1>   rows cut into pieces over many workgroups, added into the row's uint64 histogram in
+//                         memory (the -dist kernel, one row of 4096 bins per quantile row), then a workgroup per row picks
+// A rank that falls into the last bin (v >= 4095) is refined by the workgroup that found it (q_deep): three more passes over the
+// row's cells, histograms of bits 31..20, 19..8 and 7..0 of the cells that are >= 4095 and share the bits fixed so far.
+// ------------------------------------------------------------------------------------------
+struct QSel { unsigned long long below[16], total, dbelow; uint32_t bin[16], dbin; };
+
+// the cells of row r: segments [s0, s0 + ns) of R.segs, or (window mode) the one stretch (ws, wc)
+__device__ __forceinline__ void q_row_begin(const QRows &R, uint64_t r, uint64_t *s0, uint32_t *ns, uint64_t *ws, uint32_t *wc)
+{
+    if (R.segs) { *s0 = R.seg_off[r]; *ns = (uint32_t)(R.seg_off[r + 1] - *s0); *ws = 0; *wc = 0; return; }
+    const uint64_t g = R.row0 + r;
+    int lo = 0, hi = R.n_contigs - 1;                            // the last contig whose first window is <= g
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (R.win_off[mid] <= g) lo = mid; else hi = mid - 1; }
+    const uint64_t b = (g - R.win_off[lo]) * R.w, clen = R.contig_len[lo];
+    *s0 = 0; *ns = 1; *ws = R.contig_off[lo] + b;
+    *wc = b >= clen ? 0u : (uint32_t)(clen - b < (uint64_t)R.w ? clen - b : (uint64_t)R.w);
+}
+__device__ __forceinline__ void q_seg(const QRows &R, uint64_t s0, uint32_t i, uint64_t ws, uint32_t wc, uint64_t *start, uint32_t *count)
+{
+    if (R.segs) { const Piece pc = R.segs[s0 + i]; *start = pc.start; *count = pc.count; }
+    else { *start = ws; *count = wc; }
+}
+__device__ __forceinline__ unsigned long long q_rank(uint32_t p, unsigned long long cells)
+{
+    const unsigned long long r = ((unsigned long long)p * cells + 99ull) / 100ull;
+    return r ? r : 1ull;
+}
+
+__global__ __launch_bounds__(WG) void k_quant_narrow(const uint32_t *depth, const QRows R, const uint32_t *list, uint32_t n, uint32_t cap,
+                                                     uint32_t gshift, const QPct P, uint32_t *q)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const uint32_t G = 1u << gshift, gl = threadIdx.x & (G - 1), grp = threadIdx.x >> gshift;
+    const uint64_t slot = (uint64_t)blockIdx.x * (WG >> gshift) + grp;
+    if (slot >= n) return;                                       // (whole groups leave; nothing below synchronises the workgroup)
+    const uint64_t r = list ? list[slot] : slot;
+    uint32_t *v = reinterpret_cast<uint32_t *>(smem) + (size_t)grp * cap;
+    uint64_t s0, ws; uint32_t ns, wc;
+    q_row_begin(R, r, &s0, &ns, &ws, &wc);
+    uint32_t C = 0, any = 0;
+    for (uint32_t i = 0; i < ns; ++i) {
+        uint64_t start; uint32_t count;
+        q_seg(R, s0, i, ws, wc, &start, &count);
+        const uint32_t *d = depth + start;
+        for (uint32_t k = gl; k < count && C + k < cap; k += G) { const uint32_t x = d[k]; v[C + k] = x; any |= x; }
+        C += count;
+    }
+    if (C > cap) C = cap;                                        // (the host sends no such row here)
+    __threadfence_block();                                       // the group's lanes read each other's cells: same wave, LDS writes drained
+    for (uint32_t o = G >> 1; o; o >>= 1) any |= (uint32_t)__shfl_xor((int)any, (int)o);
+    uint32_t *out = q + r * P.n;
+    if (C == 0) { if (gl < P.n) out[gl] = 0xFFFFFFFFu; return; }
+    const int hb = any ? 31 - __clz((int)any) : -1;
+    const uint32_t gbase = (threadIdx.x & 63u) & ~(G - 1);
+    const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << G) - 1ull);
+    for (uint32_t j = 0; j < P.n; ++j) {
+        uint32_t rank = (uint32_t)q_rank(P.p[j], C), prefix = 0;
+        for (int bit = hb; bit >= 0; --bit) {
+            uint32_t cnt = 0;                                    // cells that share the bits fixed so far and have this one clear
+            for (uint32_t k0 = 0; k0 < C; k0 += G) {
+                const uint32_t k = k0 + gl;
+                const bool z = k < C && ((v[k] ^ prefix) >> bit) == 0;
+                cnt += (uint32_t)__popcll((__ballot(z) >> gbase) & gmask);
+            }
+            if (rank > cnt) { rank -= cnt; prefix |= 1u << bit; }
+        }
+        if (gl == 0) out[j] = prefix;
+    }
+}
+
+__device__ __forceinline__ unsigned long long q_block_scan(unsigned long long mine, unsigned long long *sc, unsigned long long *total)
+{
+    sc[threadIdx.x] = mine;
+    __syncthreads();
+    for (int o = 1; o < WG; o <<= 1) {
+        const unsigned long long a = (int)threadIdx.x >= o ? sc[threadIdx.x - o] : 0ull;
+        __syncthreads();
+        sc[threadIdx.x] += a;
+        __syncthreads();
+    }
+    const unsigned long long incl = sc[threadIdx.x];
+    *total = sc[WG - 1];
+    __syncthreads();
+    return incl;
+}
+
+// the thread whose `per` bins hold the r-th smallest writes the bin and the number of cells below it
+template <typename T>
+__device__ __forceinline__ void q_pick(const T *h, uint32_t per, unsigned long long excl, unsigned long long mine, unsigned long long r,
+                                       uint32_t *bin, unsigned long long *below)
+{
+    if (r <= excl || r > excl + mine) return;
+    unsigned long long acc = excl;
+    for (uint32_t k = 0; k < per; ++k) {
+        const unsigned long long x = h[threadIdx.x * per + k];
+        if (r <= acc + x) { *bin = threadIdx.x * per + k; *below = acc; return; }
+        acc += x;
+    }
+}
+
+// the r-th smallest of the row's cells that are >= 4095 (whole workgroup; h: 4096 LDS counters)
+template <typename T>
+__device__ uint32_t q_deep(const uint32_t *depth, const QRows &R, uint64_t s0, uint32_t ns, uint64_t ws, uint32_t wc, unsigned long long r,
+                           T *h, unsigned long long *sc, QSel *sel)
+{
+    uint32_t prefix = 0;
+    for (int pass = 0; pass < 3; ++pass) {
+        const uint32_t shift = pass == 0 ? 20u : pass == 1 ? 8u : 0u, nb = pass == 2 ? 256u : 4096u, fixed = pass == 1 ? 20u : 8u;
+        for (uint32_t j = threadIdx.x; j < 4096; j += WG) h[j] = 0;
+        __syncthreads();
+        for (uint32_t i = 0; i < ns; ++i) {
+            uint64_t start; uint32_t count;
+            q_seg(R, s0, i, ws, wc, &start, &count);
+            const uint32_t *d = depth + start;
+            for (uint32_t k = threadIdx.x; k < count; k += WG) {
+                const uint32_t x = d[k];
+                if (x >= 4095u && (pass == 0 || (x >> fixed) == (prefix >> fixed))) atomicAdd(&h[(x >> shift) & (nb - 1)], (T)1);
+            }
+        }
+        lds_drain();
+        __syncthreads();
+        const uint32_t per = nb / WG;
+        unsigned long long mine = 0, total;
+        for (uint32_t k = 0; k < per; ++k) mine += h[threadIdx.x * per + k];
+        const unsigned long long incl = q_block_scan(mine, sc, &total);
+        q_pick(h, per, incl - mine, mine, r, &sel->dbin, &sel->dbelow);
+        __syncthreads();
+        prefix |= sel->dbin << shift;
+        r -= sel->dbelow;
+        __syncthreads();
+    }
+    return prefix;
+}
+
+// A workgroup per row.  FROM_HIST: the row's 4096 uint64 bins are in memory already (ghist + slot * 4096); else they are counted here.
+template <typename T, bool FROM_HIST>
+__global__ __launch_bounds__(WG) void k_quant_block(const uint32_t *depth, const QRows R, const uint32_t *list, const QPct P, uint32_t *q,
+                                                    const unsigned long long *ghist)
+{
+    __shared__ T h[4096];
+    __shared__ unsigned long long sc[WG];
+    __shared__ QSel sel;
+    const int lane = threadIdx.x & 63;
+    const uint64_t r = list ? list[blockIdx.x] : blockIdx.x;
+    uint64_t s0, ws; uint32_t ns, wc;
+    q_row_begin(R, r, &s0, &ns, &ws, &wc);
+    const T *src = h;
+    if constexpr (FROM_HIST) src = reinterpret_cast<const T *>(ghist) + (size_t)blockIdx.x * 4096;
+    else {
+        for (uint32_t j = threadIdx.x; j < 4096; j += WG) h[j] = 0;
+        __syncthreads();
+        for (uint32_t i = 0; i < ns; ++i) {
+            uint64_t start; uint32_t count;
+            q_seg(R, s0, i, ws, wc, &start, &count);
+            const uint32_t *d = depth + start;
+            for (uint32_t base = 0; base < count; base += WG * 4) {
+                const uint32_t c0 = base + threadIdx.x * 4;
+                const uint32_t n = c0 >= count ? 0u : (count - c0 < 4u ? count - c0 : 4u);
+                uint32_t b[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) b[k] = (uint32_t)k < n ? min(d[c0 + k], 4095u) : 0u;
+                hist_lane4<true>(reinterpret_cast<uint32_t *>(h), b, n, lane);
+            }
+        }
+        lds_drain();
+        __syncthreads();
+    }
+    unsigned long long mine = 0, total;
+    for (uint32_t k = 0; k < 16; ++k) mine += src[threadIdx.x * 16 + k];
+    const unsigned long long incl = q_block_scan(mine, sc, &total);
+    uint32_t *out = q + r * P.n;
+    if (total == 0) { if (threadIdx.x < P.n) out[threadIdx.x] = 0xFFFFFFFFu; return; }
+    for (uint32_t j = 0; j < P.n; ++j) q_pick(src, 16, incl - mine, mine, q_rank(P.p[j], total), &sel.bin[j], &sel.below[j]);
+    __syncthreads();
+    unsigned long long last_r = 0; uint32_t last_v = 0;
+    for (uint32_t j = 0; j < P.n; ++j) {
+        uint32_t val = sel.bin[j];
+        if (val == 4095u) {                                      // cells >= 4095: refine (uniform over the workgroup; q_deep leaves bin[] / below[] alone)
+            const unsigned long long rd = q_rank(P.p[j], total) - sel.below[j];
+            if (rd != last_r) { last_v = q_deep<T>(depth, R, s0, ns, ws, wc, rd, h, sc, &sel); last_r = rd; }
+            val = last_v;
+        }
+        if (threadIdx.x == 0) out[j] = val;
+    }
+}
+
+int launch_quant_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t cap, uint32_t gshift,
+                        const QPct &P, uint32_t *q)
+{
+    if (!n) return 0;
+    if (cap < 1) cap = 1;
+    const uint32_t gpb = (uint32_t)WG >> gshift;
+    const size_t lds = (size_t)gpb * cap * 4;
+    if (int e = hist_lds_reserve(k_quant_narrow, lds)) return e;
+    hipLaunchKernelGGL(k_quant_narrow, dim3((n + gpb - 1) / gpb), dim3(WG), lds, st, reinterpret_cast<const uint32_t *>(depth), R, list, n, cap, gshift, P, q);
+    return 0;
+}
+
+void launch_quant_block(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, const QPct &P, uint32_t *q,
+                        const unsigned long long *ghist)
+{
+    if (!n) return;
+    const uint32_t *d = reinterpret_cast<const uint32_t *>(depth);
+    if (ghist) hipLaunchKernelGGL((k_quant_block<unsigned long long, true>), dim3(n), dim3(WG), 0, st, d, R, list, P, q, ghist);
+    else hipLaunchKernelGGL((k_quant_block<uint32_t, false>), dim3(n), dim3(WG), 0, st, d, R, list, P, q, ghist);
+}
+
 } // namespace pdk
 
 #ifdef PD_WIDE3_TICKS

@@ -204,6 +204,20 @@ int parse_options(int argc, char **argv, Options *o)
             if (!good) { std::cerr << "Error: -levels should be 'exact' or up to 64 ascending depths such as 0,1,5,15" << std::endl; return 0; }
             o->levels = true;
         }
+        else if (flag == "quantile") {                                           // not in the reference: the .quantile.stat.gz percentiles (README)
+            if (!arg(&v)) return 0;
+            bool good = !v.empty();
+            o->quantile.clear();
+            uint32_t x = 0; size_t digits = 0;
+            for (size_t k = 0; good && k <= v.size(); ++k) {
+                if (k < v.size() && v[k] >= '0' && v[k] <= '9') { x = x * 10 + (uint32_t)(v[k] - '0'); if (++digits > 3) good = false; continue; }
+                if ((k < v.size() && v[k] != ',') || digits == 0 || x > 100 || o->quantile.size() == 16 ||
+                    (!o->quantile.empty() && x <= o->quantile.back())) { good = false; break; }
+                o->quantile.push_back(x);
+                x = 0; digits = 0;
+            }
+            if (!good) { o->quantile.clear(); std::cerr << "Error: -quantile should be 1 to 16 ascending percentages between 0 and 100, such as 25,50,75" << std::endl; return 0; }
+        }
         else if (flag == "help" || flag == "h") { print_help(); return 0; }
         else { std::cerr << "Error UnKnow argument -" << flag << std::endl; return 0; }
     }

@@ -1361,6 +1361,16 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
         const size_t at = header_line.find("\tCoverage(%)");
         header_line.insert(at, "\tGC(%)");
     }
+    // -quantile's table: the main table's identity columns under the main table's names, the row's cell count, one column per percentage
+    auto quantile_header = [&]() {
+        std::string h = "#Chr";
+        if (o.mode != 0) h += "\tStart\tEnd";
+        if (!synthetic) h += o.mode == 3 ? "\tRegionID" : "\tGeneID";
+        h += "\tCells";
+        for (uint32_t p : o.quantile) { h += "\tQ"; h += std::to_string(p); }
+        h += '\n';
+        return h;
+    };
     GzWriter OUT;
     OUT.set_threads(o.threads);                          // large tables: same bytes, LZ77 parse on all threads (host/pgzip.h)
     if (!OUT.open(stat_path)) { std::cerr << "open OUT File error: " << stat_path << std::endl; return 0; }
@@ -1375,6 +1385,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
         OUT.close();
         if (o.dist) { GzWriter d; if (d.open(prefix + ".dist.stat.gz")) { d.write(DIST_HEADER); d.close(); } }
         if (o.levels) { GzWriter l; if (l.open(prefix + ".levels.bed.gz")) l.close(); }
+        if (!o.quantile.empty()) { GzWriter qf; if (qf.open(prefix + ".quantile.stat.gz")) { qf.write(quantile_header()); qf.close(); } }
         return 0;
     }
     // One context per GPU.  A `#.list` input is sharded one file per GPU (round robin) when the engine
@@ -1876,6 +1887,138 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
         tm.mark("depth levels");
         return true;
     };
+    // -quantile SPEC (not in the reference): nearest-rank depth percentiles of the cells of every row of the main table, in the
+    // table's row order, in <prefix>.quantile.stat.gz.  A row's cells: the whole contig, the window, or — in -g / -b — the multiset
+    // union of the id's entries clipped to the contig (overlapping entries count twice, as in Length / TotalDepth).  Q<p> is the
+    // r-th smallest cell, r = max(1, ceil(p * Cells / 100)); a row without cells prints NA.  The rows are selected on the engine
+    // (pd_window_quantiles / pd_depth_quantiles: only the results come back) or, without those members, on the host threads from
+    // the cells read back contig by contig.  Made after the tables, like -dist and -levels.
+    auto write_quantile = [&]() -> bool {
+        if (o.quantile.empty()) return true;
+        if (!need_scan()) return false;
+        const std::vector<uint32_t> &pct = o.quantile;
+        const uint32_t np = (uint32_t)pct.size();
+        struct QRow { int32_t tid; int64_t start, end; const std::string *id; uint64_t cells, qi; };      // qi: the row's place in qv
+        std::vector<QRow> rows;
+        std::vector<uint32_t> qv;
+        const bool dev = api->depth_quantiles && api->window_quantiles && !(tune("quantile_device") && tune("quantile_device")[0] == '0');
+        if (dev && api->set_param)
+            for (const char *k : {"quantile_wave_max", "quantile_split_cells"})
+                if (const char *e = tune(k)) (void)api->set_param(eng.ctx, k, (uint64_t)strtoull(e, nullptr, 10));
+        std::vector<pd_region> segs;
+        std::vector<uint64_t> roff(1, 0);
+        bool by_window = false;
+        if (o.mode == 5 || o.mode == 6) {
+            const uint32_t w = (uint32_t)o.win;
+            std::vector<uint64_t> woff(nctg + 1);
+            api->window_layout(eng.ctx, w, woff.data());
+            if (o.mode == 6) {
+                for (size_t t = 0; t < nctg; ++t) {
+                    if (!rm.has((int32_t)t)) continue;
+                    const int64_t len = hdr.lens[t];
+                    const size_t n_rows = len > 1 ? (size_t)((len - 1 + (int64_t)w - 1) / (int64_t)w) : 0;   // (a final 1-base window is dropped, as in the table)
+                    for (size_t k = 0; k < n_rows; ++k) {
+                        const int64_t j = 1 + (int64_t)k * w, end = std::min<int64_t>(j - 1 + w, len);
+                        rows.push_back(QRow{(int32_t)t, j, end, nullptr, (uint64_t)(end - j + 1), woff[t] + k});
+                    }
+                }
+            } else {
+                for (auto &kv : rm.bins)
+                    for (const Bin &b : kv.second)
+                        rows.push_back(QRow{kv.first, b.start, b.end, nullptr, (uint64_t)(b.end - b.start + 1), woff[(size_t)kv.first] + (uint64_t)(b.start - 1) / w});
+            }
+            if (dev) {
+                by_window = true;
+                qv.resize((size_t)std::max<uint64_t>(1, woff[nctg] * np));
+                if (!eng.ck(api->window_quantiles(eng.ctx, w, pct.data(), np, qv.data()), "pd_window_quantiles")) return false;
+            } else {
+                for (size_t i = 0; i < rows.size(); ++i) { segs.push_back(pd_region{rows[i].tid, (int32_t)rows[i].start, (int32_t)rows[i].end}); roff.push_back(segs.size()); rows[i].qi = i; }
+            }
+        } else if (o.mode == 0) {
+            for (auto &kv : rm.bins) {
+                const int64_t len = hdr.lens[(size_t)kv.first];
+                rows.push_back(QRow{kv.first, 1, len, nullptr, 0, rows.size()});
+                segs.push_back(pd_region{kv.first, 1, (int32_t)len}); roff.push_back(segs.size());
+            }
+        } else {
+            for (auto &kv : rm.genes) {
+                std::vector<std::pair<int32_t, const std::pair<const std::string, Gene> *>> order;       // by start; equal starts keep the id order (PD:5032-5041)
+                for (auto &g : kv.second) order.emplace_back(g.second.start, &g);
+                std::stable_sort(order.begin(), order.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+                for (auto &og : order) {
+                    const Gene &x = og.second->second;
+                    rows.push_back(QRow{kv.first, x.start, x.end, &og.second->first, 0, rows.size()});
+                    for (auto &cd : x.cds) segs.push_back(pd_region{kv.first, cd.first, cd.second});
+                    roff.push_back(segs.size());
+                }
+            }
+        }
+        if (!by_window) {
+            const size_t n_rows = rows.size();
+            std::vector<uint64_t> cells(n_rows ? n_rows : 1);
+            qv.assign(n_rows ? n_rows * np : 1, 0xFFFFFFFFu);
+            if (dev) {
+                if (!eng.ck(api->depth_quantiles(eng.ctx, segs.data(), segs.size(), roff.data(), n_rows, pct.data(), np, cells.data(), qv.data()), "pd_depth_quantiles")) return false;
+            } else {
+                // engines without the entry points: a contig's cells are read back once, its rows selected on the threads
+                std::vector<uint32_t> d;
+                for (size_t r0 = 0; r0 < n_rows;) {
+                    const int32_t t = rows[r0].tid;
+                    size_t r1 = r0;
+                    while (r1 < n_rows && rows[r1].tid == t) ++r1;
+                    const uint64_t len = hdr.lens[(size_t)t];
+                    d.resize(len);
+                    for (uint64_t p = 0; p < len; p += (uint64_t)1 << 22)
+                        if (!eng.ck(api->read_depth(eng.ctx, t, (uint32_t)p, (size_t)std::min<uint64_t>((uint64_t)1 << 22, len - p), d.data() + p), "pd_read_depth")) return false;
+                    std::atomic<size_t> next{r0};
+                    auto work = [&]() {
+                        std::vector<uint32_t> v;
+                        for (size_t i; (i = next.fetch_add(1)) < r1;) {
+                            v.clear();
+                            for (uint64_t k = roff[i]; k < roff[i + 1]; ++k) {
+                                const int64_t b = std::max<int64_t>((int64_t)segs[k].first - 1, 0), e = std::min<int64_t>(segs[k].second, (int64_t)len);
+                                if (b < e) v.insert(v.end(), d.begin() + b, d.begin() + e);
+                            }
+                            cells[i] = v.size();
+                            for (uint32_t j = 0; j < np && !v.empty(); ++j) {
+                                const uint64_t r = std::max<uint64_t>(1, ((uint64_t)pct[j] * v.size() + 99) / 100);
+                                std::nth_element(v.begin(), v.begin() + (ptrdiff_t)(r - 1), v.end());
+                                qv[i * np + j] = v[r - 1];
+                            }
+                        }
+                    };
+                    const int nt = std::max(1, std::min<int>(std::min(o.threads, 16), (int)(r1 - r0)));
+                    std::vector<std::thread> th;
+                    for (int k = 1; k < nt; ++k) th.emplace_back(work);
+                    work();
+                    for (auto &x : th) x.join();
+                    r0 = r1;
+                }
+            }
+            for (size_t i = 0; i < n_rows; ++i) rows[i].cells = cells[i];
+        }
+        GzWriter Q;
+        Q.set_threads(o.threads);
+        const std::string path = prefix + ".quantile.stat.gz";
+        if (!Q.open(path)) { eng.fail("cannot open " + path); return false; }
+        std::string out = quantile_header();
+        for (const QRow &r : rows) {
+            out += hdr.names[(size_t)r.tid];
+            if (o.mode != 0) { out += '\t'; append_i64(&out, r.start); out += '\t'; append_i64(&out, r.end); }
+            if (r.id) { out += '\t'; out += *r.id; }
+            out += '\t'; append_u64(&out, r.cells);
+            for (uint32_t j = 0; j < np; ++j) {
+                out += '\t';
+                if (r.cells) append_u64(&out, qv[r.qi * np + j]); else out += "NA";
+            }
+            out += '\n';
+            if (out.size() > (1u << 22)) { Q.write(out); out.clear(); }
+        }
+        Q.write(out);
+        if (!Q.close()) { ::remove(path.c_str()); eng.fail("cannot write " + path); return false; }
+        tm.mark("depth quantiles");
+        return true;
+    };
     std::string txt;
 
     if (o.mode == 6) {
@@ -1946,6 +2089,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
             tm.mark("table close");
             if (!write_dist()) return bail();
             if (!write_levels()) return bail();
+            if (!write_quantile()) return bail();
             if (!site_done()) return bail();
             std::cout << "INFO: Input data read done" << std::endl;
             return 0;
@@ -1986,6 +2130,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
         tm.mark("table gzip");
         if (!write_dist()) return bail();
         if (!write_levels()) return bail();
+        if (!write_quantile()) return bail();
         if (!site_done()) return bail();
         std::cout << "INFO: Input data read done" << std::endl;
         return 0;
@@ -2116,6 +2261,7 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
     tm.mark("table gzip");
     if (!write_dist()) return bail();
     if (!write_levels()) return bail();
+    if (!write_quantile()) return bail();
     if (!site_done()) return bail();
     return 0;
 }
