@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include "pd_kernels.h"
 #include "pd_lz77.h"
+#include "pd_lz77_devwave.h"
 
 namespace pdk {
 
@@ -21,24 +22,7 @@ namespace {
 constexpr int WGZ = 256;
 constexpr uint32_t RBLK = 2048;                 // elements per wave-block of the radix passes
 
-struct DevWaveZ {                               // the hardware wavefront (pd_lz77.h's W)
-    template <class T> struct Var { T v; __device__ T &operator[](int) { return v; } __device__ const T &operator[](int) const { return v; } };
-    template <class F> __device__ static __forceinline__ void each(F f) { f((int)(threadIdx.x & 63)); }
-    __device__ static __forceinline__ uint64_t ballot_eq(const Var<uint32_t> &x, uint32_t v) { return __ballot(x.v == v); }
-    __device__ static __forceinline__ uint64_t ballot_ne(const Var<uint32_t> &x, uint32_t v) { return __ballot(x.v != v); }
-    __device__ static __forceinline__ uint32_t reduce_max(const Var<uint32_t> &x)
-    {
-        uint32_t m = x.v;
-#pragma unroll
-        for (int o = 32; o; o >>= 1) { const uint32_t y = (uint32_t)__shfl_xor((int)m, o); m = y > m ? y : m; }
-        return m;
-    }
-    // (lane is the same in every lane: a lane read through a scalar register instead of a trip through the LDS crossbar)
-    __device__ static __forceinline__ uint32_t bcast(const Var<uint32_t> &x, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)x.v, __builtin_amdgcn_readfirstlane(lane)); }
-    __device__ static __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-    __device__ static __forceinline__ void loads_landed() { __builtin_amdgcn_s_waitcnt(0x0F70); }            // s_waitcnt vmcnt(0)
-    __device__ static __forceinline__ bool lead() { return (threadIdx.x & 63) == 0; }
-};
+using pdz::DevWaveZ;                            // the hardware wavefront (pd_lz77_devwave.h)
 
 // ---- keys: hash << 32 | position, for every position with 3 bytes left ----
 __global__ __launch_bounds__(WGZ) void k_lz_keys(const uint8_t *text, uint32_t np, uint64_t *keys)
