@@ -222,3 +222,23 @@ def test_together_with_dist_and_levels(cli, fixture, args, tmp_path):
         alone.update({f: got[f] for f in got if f not in plain})
     assert sorted(alone) == ["o.dist.stat.gz", "o.levels.bed.gz", "o.quantile.stat.gz"]
     assert both == {**plain, **alone}
+
+
+def test_empty_paf_writes_every_extra_empty(cli, tmp_path):
+    """a PAF without a single line has no targets: the main table is its header and last line, and every extra output is
+    what it holds without rows — -dist and -quantile their header, -levels nothing"""
+    (tmp_path / "in").mkdir()
+    (tmp_path / "in" / "e.paf").write_bytes(b"")
+    out = tmp_path / "out"
+    out.mkdir()
+    p = subprocess.run([cli, "-i", "e.paf", "-dist", "8", "-levels", "exact", "-quantile", "50", "-o", str(out / "o"), "-t", "2"],
+                       cwd=str(tmp_path / "in"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)
+    assert p.returncode == 0, p.stderr.decode()[-500:]
+    text = {f: gzip.decompress((out / f).read_bytes()).decode() for f in os.listdir(out)}
+    assert sorted(text) == ["o.chr.stat.gz", "o.dist.stat.gz", "o.levels.bed.gz", "o.quantile.stat.gz"]
+    main = text["o.chr.stat.gz"].splitlines()
+    assert len(main) == 2 and main[0] == "#Chr\tLength\tCoveredSite\tTotalDepth\tCoverage(%)\tMeanDepth"
+    assert main[1].startswith("##RegionLength: 0\tCoveredSite: 0\t")
+    assert text["o.dist.stat.gz"] == "#Chr\tDepth\tSites\tAtLeast\tAtLeast(%)\n"
+    assert text["o.levels.bed.gz"] == ""
+    assert text["o.quantile.stat.gz"] == "#Chr\tCells\tQ50\n"
