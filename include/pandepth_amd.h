@@ -388,7 +388,14 @@ int pd_synchronize(pd_ctx *ctx);
  * "scan", "scan_reduce_windows", "reduce_intervals", "reduce_windows", "direct_tiles", "direct_export",
  * "export_i4", "export_i8", "import_i8", "slice_sweep", "gather_windows", "accumulate_from",
  * "quantile_narrow", "quantile_block", "quantile_pieces", "quantile_pick");
- * pd_profile(ctx, 0/1) switches it (and clears the accumulators). */
+ * pd_profile(ctx, 0/1) switches it (and clears the accumulators).
+ * Names that begin with "decode_" are counters of the last decode session (counted whether or not profiling is on, cleared by
+ * pd_decode_begin; *ms is 0): which way pd_decode_end went — "decode_end_compact" (the compact session's sample), "decode_end_c8_fallback"
+ * (a compact session back to 12-byte runs), "decode_end_runs_make" (12-byte batches made one compact sample), "decode_end_scatter" (the
+ * general path), "decode_end_unsorted" (the first runs pushed as PD_PUSH_DEFAULT: the records were not in order), "decode_end_pending"
+ * (a compact session that found other runs deferred) —, "decode_c8_grow" (times the compact sample's arrays grew and moved),
+ * "decode_chain_device" / "decode_chain_host" (batches whose record chain the device / the host confirmed), "decode_segments_redone",
+ * "decode_guess_units" (units submitted with PD_UNIT_GUESS). */
 int pd_profile(pd_ctx *ctx, int enable);
 int pd_profile_get(pd_ctx *ctx, const char *name, double *ms, uint64_t *launches);
 
@@ -412,6 +419,10 @@ typedef struct pd_bgzf_block { uint64_t in_off, out_off; uint32_t in_len, out_le
  *   tag, a Huffman code this decoder leaves to zlib); 2 a member read for the unit does not inflate or fails
  *   its CRC-32; 3 the record chain could not be followed: in both cases decode the unit on the host, which reads only what the
  *   unit needs and reports the corruption if it is one.
+ *   A PD_UNIT_GUESS unit takes the first bytes at or after `start` that pass for a record header as its first record; nothing
+ *   before it confirms them.  Where those bytes are no record (a start inside data that looks like a header) the unit comes back
+ *   with 3, or with 1 when the supposed record's block size runs past the unit's bytes — which cannot be told from a real record
+ *   that does; it is never counted from there.  The caller treats 1 and 3 alike.
  * pd_decode_acquire / submit may be called from several threads (one batch each); submit returns when the batch's
  * runs are in HBM — batches of different threads overlap on the device. */
 #define PD_UNIT_GUESS 1u

@@ -18,6 +18,41 @@ def PD_PUSH_DISORDER(cells):
     return ((int(cells) + 255) // 256) << 8
 
 PD_TILE = 8192
+PD_UNIT_GUESS = 1
+PD_DECODE_COMPACT = 1
+PD_NONE = 0xFFFFFFFFFFFFFFFF                     # pd_decode_result::first_start / next_start: no such record
+
+
+# ---- the decode session's structs (include/pandepth_amd.h; tests/test_capi_layout.py holds them to the header's sizeof / offsetof) ----
+class pd_bgzf_block(ctypes.Structure):
+    _fields_ = [("in_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("in_len", ctypes.c_uint32), ("out_len", ctypes.c_uint32)]
+
+
+class pd_decode_cfg(ctypes.Structure):
+    _fields_ = [("flag_mask", ctypes.c_uint32), ("min_mapq", ctypes.c_int32), ("contig_on", ctypes.c_void_p), ("span_off", ctypes.c_void_p),
+                ("spans", ctypes.c_void_p), ("sorted", ctypes.c_int32), ("bytes_hint", ctypes.c_uint64), ("batch_bytes", ctypes.c_uint64),
+                ("batches_in_flight", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_batches", ctypes.c_uint64)]
+
+
+class pd_decode_unit(ctypes.Structure):
+    _fields_ = [("start", ctypes.c_uint64), ("stop", ctypes.c_uint64), ("avail", ctypes.c_uint64), ("first_block", ctypes.c_uint32),
+                ("n_blocks", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class pd_decode_batch(ctypes.Structure):
+    _fields_ = [("host_buf", ctypes.c_void_p), ("n_bytes", ctypes.c_size_t), ("blocks", ctypes.POINTER(pd_bgzf_block)), ("n_blocks", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32), ("inflated_bytes", ctypes.c_uint64), ("units", ctypes.POINTER(pd_decode_unit)), ("n_units", ctypes.c_uint32),
+                ("pad2", ctypes.c_uint32), ("order", ctypes.c_uint64)]
+
+
+class pd_decode_result(ctypes.Structure):
+    _fields_ = [("n_reads", ctypes.c_uint64), ("n_first", ctypes.c_uint64), ("n_other", ctypes.c_uint64), ("first_start", ctypes.c_uint64),
+                ("next_start", ctypes.c_uint64), ("ms_h2d", ctypes.c_double), ("ms_inflate", ctypes.c_double), ("ms_walk", ctypes.c_double),
+                ("ms_emit", ctypes.c_double), ("first_key", ctypes.c_uint64), ("last_key", ctypes.c_uint64), ("unsorted", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+
+DECODE_STRUCTS = [pd_bgzf_block, pd_decode_cfg, pd_decode_unit, pd_decode_batch, pd_decode_result]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -109,6 +144,13 @@ def load():
         "pd_sliced_sum_finish": (I, [P, I, ctypes.c_uint32, ctypes.c_uint32, U, I, P, P]),
         "pd_push_bgzf_units": (I, [P, P, SZ, P, ctypes.c_uint32, P, ctypes.c_uint32, U64, ctypes.c_uint32, ctypes.c_int32, P,
                                ctypes.POINTER(U64)]),
+        "pd_decode_begin": (I, [P, ctypes.POINTER(pd_decode_cfg)]),
+        "pd_decode_acquire": (I, [P, SZ, ctypes.POINTER(P)]),
+        "pd_decode_submit": (I, [P, ctypes.POINTER(pd_decode_batch), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(pd_decode_result)]),
+        "pd_decode_queue": (I, [P, ctypes.POINTER(pd_decode_batch), ctypes.POINTER(U64)]),
+        "pd_decode_collect": (I, [P, U64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(pd_decode_result)]),
+        "pd_decode_end": (I, [P]),
+        "pd_decode_abort": (I, [P]),
         "pd_x_bgzf_inflate": (I, [I, P, SZ, P, SZ, ctypes.POINTER(SZ), I, I, ctypes.POINTER(ctypes.c_double),
                               ctypes.POINTER(ctypes.c_uint32)]),
         "pd_stream": (P, [P]),
@@ -512,6 +554,10 @@ class Engine:
                                            int(inflated_bytes), int(flag_mask), int(min_mapq), _ptr(st), ctypes.byref(nrec)))
         return st[:len(units)], int(nrec.value)
 
+    def decode_session(self):
+        """The pd_decode_* calls of this context: see DecodeSession."""
+        return DecodeSession(self)
+
     def stream(self):
         return int(self.L.pd_stream(self.h) or 0)
 
@@ -526,6 +572,111 @@ class Engine:
         n = ctypes.c_uint64()
         self._ck(self.L.pd_profile_get(self.h, name.encode(), ctypes.byref(ms), ctypes.byref(n)))
         return float(ms.value), int(n.value)
+
+
+class DecodeSession:
+    """pd_decode_begin / acquire / submit / queue / collect / end / abort on one Engine, one method per call and nothing between them.
+    A batch is the tuple (bytes, blocks, units, inflated_bytes, order): blocks rows (in_off, out_off, in_len, out_len), units rows
+    (start, stop, avail, first_block, n_blocks[, flags]).  `acquire` hands out a pinned buffer; `submit` / `queue` copy the batch's
+    bytes into the buffer given (default: the one acquired longest ago and not yet used).  `submit` and `collect` return
+    (unit_status int32 array, result dict of pd_decode_result's fields).  A call that fails raises PdError, which leaves the session
+    as the library left it."""
+
+    def __init__(self, eng):
+        self.e, self.L = eng, eng.L
+        self._keep = []                      # arrays the C side reads during a call (and, for begin, until it returns)
+        self.held = []                       # buffers acquired and not yet handed to submit / queue
+
+    def begin(self, flag_mask=1796, min_mapq=-1, contig_on=None, span_off=None, spans=None, sorted=1, bytes_hint=0, batch_bytes=0,
+              batches_in_flight=0, flags=0, n_batches=0):
+        cfg = pd_decode_cfg()
+        cfg.flag_mask, cfg.min_mapq, cfg.sorted = int(flag_mask), int(min_mapq), int(sorted)
+        cfg.bytes_hint, cfg.batch_bytes, cfg.batches_in_flight, cfg.flags, cfg.n_batches = int(bytes_hint), int(batch_bytes), int(batches_in_flight), int(flags), int(n_batches)
+        keep = [cfg]
+        if contig_on is not None:
+            on = np.ascontiguousarray(contig_on, dtype=np.uint8)
+            assert on.size == self.e.n_contigs
+            keep.append(on); cfg.contig_on = on.ctypes.data
+        if (spans is None) != (span_off is None):
+            raise ValueError("span_off and spans go together (spans of contig t are spans[span_off[t]:span_off[t + 1]])")
+        if spans is not None:
+            so = np.ascontiguousarray(span_off, dtype=np.uint32)
+            sp = np.ascontiguousarray(np.asarray(spans, dtype=np.int32).reshape(-1, 2))
+            assert so.size == self.e.n_contigs + 1 and int(so[-1]) == sp.shape[0]
+            pad = np.zeros((max(sp.shape[0], 1), 2), dtype=np.int32)         # (never a NULL pointer for an empty list: NULL means "every read")
+            pad[:sp.shape[0]] = sp
+            keep += [so, pad]; cfg.span_off = so.ctypes.data; cfg.spans = pad.ctypes.data
+        self._keep = keep
+        self.e._ck(self.L.pd_decode_begin(self.e.h, ctypes.byref(cfg)))
+
+    def acquire(self, nbytes):
+        """-> the address of a pinned buffer of at least nbytes bytes (held until a batch is submitted or queued with it)"""
+        p = ctypes.c_void_p()
+        self.e._ck(self.L.pd_decode_acquire(self.e.h, int(nbytes), ctypes.byref(p)))
+        self.held.append(int(p.value))
+        return int(p.value)
+
+    def _take(self, buf):
+        if buf is None:
+            buf = self.held[0]
+        if buf in self.held:
+            self.held.remove(buf)
+        return buf
+
+    def _batch(self, buf, batch):
+        data, blocks, units, inflated, order = batch
+        data = bytes(data)
+        if data:
+            ctypes.memmove(buf, data, len(data))
+        nb, nu = len(blocks), len(units)
+        bd = (pd_bgzf_block * max(nb, 1))()
+        for k, b in enumerate(blocks):
+            bd[k].in_off, bd[k].out_off, bd[k].in_len, bd[k].out_len = (int(x) for x in b[:4])
+        ud = (pd_decode_unit * max(nu, 1))()
+        for k, u in enumerate(units):
+            ud[k].start, ud[k].stop, ud[k].avail, ud[k].first_block, ud[k].n_blocks = (int(x) for x in u[:5])
+            ud[k].flags = int(u[5]) if len(u) > 5 else 0
+        bt = pd_decode_batch()
+        bt.host_buf, bt.n_bytes, bt.n_blocks, bt.n_units, bt.inflated_bytes, bt.order = buf, len(data), nb, nu, int(inflated), int(order)
+        bt.blocks = ctypes.cast(bd, ctypes.POINTER(pd_bgzf_block)) if nb else None
+        bt.units = ctypes.cast(ud, ctypes.POINTER(pd_decode_unit)) if nu else None
+        return bt, (bd, ud)
+
+    @staticmethod
+    def _result(st, n_units, res):
+        return np.array(st[:n_units], dtype=np.int32), {name: getattr(res, name) for name, _ in pd_decode_result._fields_ if name != "pad"}
+
+    def submit(self, batch, buf=None):
+        bt, keep = self._batch(self._take(buf), batch)
+        st = (ctypes.c_int32 * max(bt.n_units, 1))()
+        res = pd_decode_result()
+        self.e._ck(self.L.pd_decode_submit(self.e.h, ctypes.byref(bt), st, ctypes.byref(res)))
+        del keep
+        return self._result(st, bt.n_units, res)
+
+    def queue(self, batch, buf=None):
+        """-> ticket (pd_decode_queue copies the batch's tables; the buffer stays the engine's until the batch is collected)"""
+        bt, keep = self._batch(self._take(buf), batch)
+        t = ctypes.c_uint64()
+        self.e._ck(self.L.pd_decode_queue(self.e.h, ctypes.byref(bt), ctypes.byref(t)))
+        del keep
+        return int(t.value)
+
+    def collect(self, ticket, n_units):
+        st = (ctypes.c_int32 * max(int(n_units), 1))()
+        res = pd_decode_result()
+        self.e._ck(self.L.pd_decode_collect(self.e.h, int(ticket), st, ctypes.byref(res)))
+        return self._result(st, int(n_units), res)
+
+    def end(self):
+        self.held = []
+        self.e._ck(self.L.pd_decode_end(self.e.h))
+        self._keep = []
+
+    def abort(self):
+        self.held = []
+        self.e._ck(self.L.pd_decode_abort(self.e.h))
+        self._keep = []
 
 
 class TextStream:

@@ -562,11 +562,14 @@ inline uint32_t check_chain(Vec &segs, Redo *redo)
     uint64_t E = 0;
     bool known = true;
     uint32_t dead = 0;                                   // flags for the rest of a unit whose chain has stopped
+    bool guessed = false;                                // the unit's start was guessed (PD_UNIT_GUESS: its first segment has no hint)
     for (size_t j = 0; j < segs.size(); ++j) {
         Seg &s = segs[j];
         bool confirmed = true;
-        if (s.unit_first) { E = 0; known = true; dead = 0; }
+        if (s.unit_first) { E = 0; known = true; dead = 0; guessed = s.hint == NONE; }
         else if (dead) { s.flags = dead; s.n_first = s.n_other = s.n_far = s.n_rec = 0; continue; }
+        else if (guessed && known && E == 0) { }         // no record found in the unit yet (it began inside a record longer than a segment):
+                                                         // there is no chain to hold this segment to, its own guess stands like the first one's
         else if (known) {
             const bool none_expected = E >= s.end;
             const bool ok = none_expected ? s.used_start == NONE : s.used_start == E;

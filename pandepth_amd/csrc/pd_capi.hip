@@ -243,6 +243,11 @@ struct pd_ctx {
     bool dec_fast = true;                                         // the record chain of a batch is confirmed on the device where the session allows it ("decode_fast")
     uint32_t dec_spoil = 0;                                       // test hook: every k-th segment's guess is spoilt after pass 1 ("decode_spoil")
     uint32_t dec_max_redo = 256;                                  // ... with at most this many segments walking again per batch ("decode_max_redo")
+    uint64_t dec_c8_reserve = 0;                                  // test hook ("decode_c8_reserve" = n > 0): a compact session's first estimate is at most n first runs and its sample grows
+                                                                  // without the 2^16 runs of slack, so that files of a few thousand records make the sample grow and move (0: off)
+    // which way the last session went (read through pd_profile_get, names "decode_*"; cleared by pd_decode_begin)
+    enum { DN_GROW, DN_END_COMPACT, DN_END_C8_FALLBACK, DN_END_RUNS_MAKE, DN_END_SCATTER, DN_END_UNSORTED, DN_END_PEND, DN_GUESS, DN_COUNT };
+    std::atomic<uint64_t> dec_n[DN_COUNT] = {};
     std::atomic<uint64_t> dec_n_fast{0}, dec_n_slow{0}, dec_n_redo{0};   // batches finished without / with the host's chain check; segments the device walked again
     uint32_t direct_sample = 256;                                 // index stride of the direct path (runs)
     uint32_t q_wave_max = 512, q_split = 262144;                  // "quantile_wave_max" / "quantile_split_cells": the cell counts up to which a quantile row takes the narrow / the workgroup kernel
@@ -889,6 +894,7 @@ int pd_set_param(pd_ctx *c, const char *name, uint64_t value)
     if (!strcmp(name, "lz_slots")) { c->lz_slots = value >= 4 ? 4 : 2; return PD_OK; }
     if (!strcmp(name, "decode_h2d_lanes")) { c->dec_h2d_lanes = value > 1 ? 2 : 1; return PD_OK; }
     if (!strcmp(name, "decode_sync_event")) { c->dec_sync_event = value != 0; return PD_OK; }
+    if (!strcmp(name, "decode_c8_reserve")) { c->dec_c8_reserve = value; return PD_OK; }
     if (!strcmp(name, "decode_max_redo")) { c->dec_max_redo = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "hist_variant")) { if (value > 3) return fail(c, PD_EINVAL, "hist_variant must be in [0, 3]"); c->hist_variant = (int)value; return PD_OK; }
     if (!strcmp(name, "quantile_wave_max")) { if (value > 2048) return fail(c, PD_EINVAL, "quantile_wave_max must be in [0, 2048]"); c->q_wave_max = (uint32_t)value; return PD_OK; }
@@ -1796,12 +1802,14 @@ int c8_reserve(pd_ctx *c, uint64_t n_s, uint64_t n_o, bool exact = false)
 {
     pd_ctx::C8Dec &x = c->c8;
     if (n_s <= x.cap_s && n_o <= x.cap_o && x.base) return PD_OK;
-    const size_t ns = std::max<size_t>((size_t)n_s + (exact ? 0 : (size_t)n_s / 2) + ((size_t)1 << 16), x.cap_s), no = std::max<size_t>((size_t)n_o + (exact ? 0 : (size_t)n_o / 2) + ((size_t)1 << 16), x.cap_o);
+    const size_t slack = c->dec_c8_reserve ? 0 : (size_t)1 << 16;
+    const size_t ns = std::max<size_t>((size_t)n_s + (exact ? 0 : (size_t)n_s / 2) + slack, x.cap_s), no = std::max<size_t>((size_t)n_o + (exact ? 0 : (size_t)n_o / 2) + slack, x.cap_o);
     const size_t bytes = (ns + no) * sizeof(Run8) + no * sizeof(pd_iv) + 256;
     uint8_t *nb = nullptr;
     if (x.base) (void)hipDeviceSynchronize();
     if (hipMalloc(&nb, bytes) != hipSuccess) { (void)hipGetLastError(); return PD_ENOMEM; }
     if (x.base) {
+        ++c->dec_n[pd_ctx::DN_GROW];
         hipError_t e = hipSuccess;
         if (x.n_s) e = hipMemcpy(nb, x.base, (size_t)x.n_s * sizeof(Run8), hipMemcpyDeviceToDevice);
         if (e == hipSuccess && x.n_o) e = hipMemcpy(nb + (ns + no) * sizeof(Run8), x.oth(), (size_t)x.n_o * sizeof(pd_iv), hipMemcpyDeviceToDevice);
@@ -1903,7 +1911,8 @@ int pd_decode_begin(pd_ctx *c, const pd_decode_cfg *cfg)
             tb[2] = tb[3] = dec_now_us();
             // (>= 32 B of BGZF per record of a real short-read file: a first run per record, a later run for every fourth; c8_reserve adds
             // half again when the sample has to GROW, not to this first estimate — a 70 GB file would otherwise ask for 50 GB up front.)
-            const uint64_t est = std::min<uint64_t>(cfg->bytes_hint ? cfg->bytes_hint / 32 + (1u << 20) : (uint64_t)8 << 20, DEV_BATCH_MAX);
+            uint64_t est = std::min<uint64_t>(cfg->bytes_hint ? cfg->bytes_hint / 32 + (1u << 20) : (uint64_t)8 << 20, DEV_BATCH_MAX);
+            if (c->dec_c8_reserve) est = std::min<uint64_t>(est, c->dec_c8_reserve);
             const int rsv = c8_reserve(c, est, est / 4, /*exact=*/true);
             tb[3] = dec_now_us();
             if (rsv == PD_OK) {
@@ -1934,6 +1943,7 @@ int pd_decode_begin(pd_ctx *c, const pd_decode_cfg *cfg)
     c->arena_used = 0;
     tb[4] = tb[5] = dec_now_us();
     c->dec_n_fast = 0; c->dec_n_slow = 0; c->dec_n_redo = 0;
+    for (auto &n : c->dec_n) n = 0;
     for (auto &g : g_dec_us) g = 0;
     if (c->dec_warm.joinable()) c->dec_warm.join();
     if (cfg->batch_bytes && cfg->batches_in_flight) {
@@ -2111,7 +2121,7 @@ int dec_queue(pd_ctx *c, pd_ctx::DecSlot &sl, const pd_decode_batch *bt)
         const pd_decode_unit &un = J.units[u];
         if (un.start > un.stop || un.start > un.avail || un.avail > bt->inflated_bytes || (uint64_t)un.first_block + un.n_blocks > bt->n_blocks)
             return dec_fail(c, PD_EINVAL, "pd_decode_submit: unit outside the inflated buffer");
-        if (un.flags & PD_UNIT_GUESS) guess = true;
+        if (un.flags & PD_UNIT_GUESS) { guess = true; ++c->dec_n[pd_ctx::DN_GUESS]; }
         J.seg0[u] = (uint32_t)segs.size();
         for (uint64_t b = un.start; b < un.stop; b += pdb2::SEG_BYTES) {
             pdb2::Seg sg; memset(&sg, 0, sizeof sg);
@@ -2608,6 +2618,7 @@ int pd_decode_end(pd_ctx *c)
         if (ok_order && x.n_s && x.n_s + x.n_o <= DEV_BATCH_MAX && !c->pend.empty()) {
             // the context holds other runs already (units the device handed back and the host decoded meanwhile, an earlier file of a list):
             // they go into the arrays now, and the compact sample is pushed behind them like any other deferred batch
+            ++c->dec_n[pd_ctx::DN_END_PEND];
             const int rf = flush_pending(c);
             if (rf) { (void)hipDeviceSynchronize(); c8_drop(c); return rf; }
         }
@@ -2642,6 +2653,7 @@ int pd_decode_end(pd_ctx *c)
             if (e != hipSuccess) { runs_free(r); return fail(c, PD_EHIP, std::string("pd_decode_end: ") + hipGetErrorString(e)); }
             r->n_long = (uint32_t)std::min<uint64_t>(n_long + h[1], 0xFFFFFFFFull);
             c->dec_runs = r;
+            ++c->dec_n[pd_ctx::DN_END_COMPACT];
             Pending p{nullptr, r->n, 0u, -1};
             p.cr = r;
             c->pend.push_back(p);
@@ -2650,6 +2662,8 @@ int pd_decode_end(pd_ctx *c)
         // not usable as a compact sample after all (the records are not in the order the header promised, more than 2^32 runs):
         // back to 12-byte arrays, which take the general paths below
         nf = x.n_s; no = x.n_o; nfar = 0;
+        ++c->dec_n[pd_ctx::DN_END_C8_FALLBACK];
+        if (!ok_order) ++c->dec_n[pd_ctx::DN_END_UNSORTED];
         if (nf && c->n_cells >= (1ull << 32)) {
             // 32 bits of a flat begin name a cell only below 2^32 cells; above, it takes the sample's own bucket index to say which contig a
             // run lies in, and that index is exactly what an unordered stream does not have.  (The executable never gets here: it gives a
@@ -2715,12 +2729,15 @@ int pd_decode_end(pd_ctx *c)
         if (runs_make(c, c->run_first, (size_t)nf, o, non, 2, &r) == PD_OK) {
             for (pd_iv **q : {&c->run_first, &c->run_other, &c->run_far}) if (*q) { (void)hipFree(*q); *q = nullptr; }
             c->dec_runs = r;
+            ++c->dec_n[pd_ctx::DN_END_RUNS_MAKE];
             Pending p{nullptr, r->n, 0u, -1};
             p.cr = r;
             c->pend.push_back(p);
             return PD_OK;
         }
     }
+    ++c->dec_n[pd_ctx::DN_END_SCATTER];
+    if (c->dec_cfg.sorted && !sorted) ++c->dec_n[pd_ctx::DN_END_UNSORTED];
     if (nf) rc = scatter_device(c, c->run_first, (size_t)nf, sorted ? (PD_PUSH_SORTED | PD_PUSH_MORE) : PD_PUSH_DEFAULT, -1, nullptr);
     if (rc == PD_OK && no) rc = scatter_device(c, c->run_other, (size_t)no, near_sorted ? (PD_PUSH_SORTED | PD_PUSH_MORE | PD_PUSH_DISORDER(near_dis + 1)) : PD_PUSH_DEFAULT, -1, nullptr);
     if (rc == PD_OK && nfar) rc = scatter_device(c, c->run_far, (size_t)nfar, far_sorted ? (PD_PUSH_SORTED | PD_PUSH_MORE | PD_PUSH_DISORDER(span + 1)) : PD_PUSH_DEFAULT, -1, nullptr);
@@ -3505,6 +3522,18 @@ int pd_profile_get(pd_ctx *c, const char *name, double *ms, uint64_t *launches)
     HIPOK(c, hipSetDevice(c->device));
     int rc = prof_collect(c);
     if (rc) return rc;
+    {   // the decode session's counters (launches only; counted whether or not profiling is on)
+        static const struct { const char *name; int k; } dn[] = {
+            {"decode_c8_grow", pd_ctx::DN_GROW}, {"decode_end_compact", pd_ctx::DN_END_COMPACT}, {"decode_end_c8_fallback", pd_ctx::DN_END_C8_FALLBACK},
+            {"decode_end_runs_make", pd_ctx::DN_END_RUNS_MAKE}, {"decode_end_scatter", pd_ctx::DN_END_SCATTER}, {"decode_end_unsorted", pd_ctx::DN_END_UNSORTED},
+            {"decode_end_pending", pd_ctx::DN_END_PEND}, {"decode_guess_units", pd_ctx::DN_GUESS}};
+        uint64_t v = 0; bool hit = false;
+        for (auto &d : dn) if (!strcmp(name, d.name)) { v = c->dec_n[d.k].load(); hit = true; }
+        if (!strcmp(name, "decode_chain_device")) { v = c->dec_n_fast.load(); hit = true; }
+        if (!strcmp(name, "decode_chain_host")) { v = c->dec_n_slow.load(); hit = true; }
+        if (!strcmp(name, "decode_segments_redone")) { v = c->dec_n_redo.load(); hit = true; }
+        if (hit) { if (ms) *ms = 0.0; if (launches) *launches = v; return PD_OK; }
+    }
     auto it = c->prof_acc.find(name);
     if (ms) *ms = it == c->prof_acc.end() ? 0.0 : it->second.first;
     if (launches) *launches = it == c->prof_acc.end() ? 0 : it->second.second;

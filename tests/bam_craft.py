@@ -168,6 +168,120 @@ def split_units(blocks, offs, total, n_units):
     return units_from_stops(blocks, offs, total, [offs[(len(offs) * k) // n_units] for k in range(1, n_units)])
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# batches (pd_decode_submit / pd_decode_queue: whole members, tables in the batch's own coordinates)
+# ---------------------------------------------------------------------------------------------------------------------
+def member_spans(f):
+    """file offsets [begin, end) of every BGZF member of a corpus file (header and trailer included)"""
+    ends = [b[0] + b[2] + 8 for b in f["blocks"]]
+    return list(zip([0] + ends[:-1], ends))
+
+
+def unit_at(f, start, stop, flags=0):
+    """The unit [start, stop) of a corpus file in FILE coordinates, for any start: (start, stop, avail, first_block, n_blocks, flags).
+    It owns the records that start in [start, stop); its members run from the one that holds `start` to the one that holds the last
+    byte of its last record (of `stop - 1` when it owns none)."""
+    offs = np.asarray(f["offs"], dtype=np.int64)
+    total = len(f["inf"])
+    ends = np.append(offs[1:], total)
+    bstart = np.array([b[1] for b in f["blocks"]], dtype=np.int64)
+    bend = np.array([b[1] + b[3] for b in f["blocks"]], dtype=np.int64)
+    stop = min(int(stop), total)
+    lo, hi = int(np.searchsorted(offs, start, side="left")), int(np.searchsorted(offs, stop, side="left"))
+    last_byte = int(ends[hi - 1]) - 1 if hi > lo else max(stop - 1, start)
+    fb = int(np.searchsorted(bend, start, side="right"))
+    lb = int(np.searchsorted(bstart, last_byte, side="right")) - 1
+    return (int(start), stop, int(bend[lb]), fb, lb - fb + 1, int(flags))
+
+
+def batch_of_units(f, units, order=0):
+    """One batch from units in FILE coordinates (rows of units_from_stops / unit_at), the way the executable's readers build theirs
+    (host/pipeline.cpp): the whole members from the first unit's first to the last one any unit needs, in_off pointing at the deflate
+    payload inside the batch's own bytes, out_off restarting at 0, the units' start / stop / avail in the batch's inflated space and
+    first_block counted from the batch's first member.
+    -> dict(data, blocks, units, inflated, order — what DecodeSession takes — and base: the file's inflated offset of the batch's byte
+    0, members: (first, last) member of the file, units_file)"""
+    span = member_spans(f)
+    m0 = min(u[3] for u in units)
+    m1 = max(u[3] + u[4] - 1 for u in units)
+    f0 = span[m0][0]
+    base = f["blocks"][m0][1]
+    blocks = [(b[0] - f0, b[1] - base, b[2], b[3]) for b in f["blocks"][m0:m1 + 1]]
+    inflated = f["blocks"][m1][1] + f["blocks"][m1][3] - base
+    rows = [(u[0] - base, u[1] - base, u[2] - base, u[3] - m0, u[4], u[5] if len(u) > 5 else 0) for u in units]
+    for r in rows:
+        assert 0 <= r[0] <= r[2] <= inflated and r[3] + r[4] <= len(blocks), r
+    return dict(data=f["data"][f0:span[m1][1]], blocks=blocks, units=rows, inflated=inflated, order=order, base=base, members=(m0, m1),
+                units_file=[tuple(u) for u in units])
+
+
+def cut_batches(f, stops, units_per_batch, guess=False):
+    """A corpus file as the batches of a decode session: the units of units_from_stops(stops), units_per_batch to a batch, orders
+    0, 1, ... in file order.  Neighbouring batches share the members their edge records straddle.
+    guess: the no-index form — the stops are moved down to member starts, and every batch is ONE unit that begins at its member's first
+    byte with PD_UNIT_GUESS (batch 0 at the first record, without the flag) and ends where the next one begins; stops that would leave
+    a unit without a record are dropped."""
+    total = len(f["inf"])
+    if not guess:
+        units = units_from_stops(f["blocks"], f["offs"], total, stops)
+        return [batch_of_units(f, units[k:k + units_per_batch], k // units_per_batch) for k in range(0, len(units), units_per_batch)]
+    assert units_per_batch == 1
+    offs = np.asarray(f["offs"], dtype=np.int64)
+    bstart = np.array([b[1] for b in f["blocks"]], dtype=np.int64)
+    cuts, prev = [], int(offs[0])
+    for s in sorted(set(int(bstart[np.searchsorted(bstart, s, side="right") - 1]) for s in stops)) + [total]:
+        if s > prev and np.searchsorted(offs, s, side="left") > np.searchsorted(offs, prev, side="left"):
+            cuts.append((prev, s)); prev = s
+    return [batch_of_units(f, [unit_at(f, a, b, 0 if k == 0 else 1)], k) for k, (a, b) in enumerate(cuts)]
+
+
+def session_cuts(f, name):
+    """{label: batches}: the cuts of a corpus file that the decode-session tests use — on the CPU (tests/test_decode_batches.py) and on
+    the device (tests/test_gpu_decode_session.py) alike: 1, 3 and 16 batches of two units cut at record starts, the crafted stops of
+    `layout` one unit to a batch, and the no-index form cut at eighths of the file ("guess")"""
+    total, offs = len(f["inf"]), f["offs"]
+    out = {}
+    for nb in (1, 3, 16):
+        out["%d" % nb] = cut_batches(f, [offs[(len(offs) * k) // (2 * nb)] for k in range(1, 2 * nb)], 2)
+        assert len(out["%d" % nb]) == nb, (name, nb)
+    if name == "layout":
+        out["crafted"] = cut_batches(f, layout_crafted_stops(offs, walk_geometry()[1]), 1)
+    out["guess"] = cut_batches(f, [total * k // 8 for k in range(1, 8)], 1, guess=True)
+    return out
+
+
+def long_decoy_file(d, seg):
+    """A file of its own for guessed starts: ordinary reads, ONE record of more than two segments whose Z tag holds a decoy header
+    (decoy_tag) one and a half segments into the record, ordinary reads again.
+    -> the file (as build_corpus describes one), the long record's offset, the decoy's offset"""
+    size, at = 2 * seg + 70000, seg + seg // 2
+    recs = [_sized(150 + k, 100 + 9 * k, k) for k in range(20)]
+    long_rec = bytearray(_sized(size, 400, 20, tag=b"XL"))
+    s = decoy_tag()
+    long_rec[at:at + len(s)] = s
+    recs.append(bytes(long_rec))
+    recs += [_sized(150 + k % 40, 500 + 9 * k, k) for k in range(21, 400)]
+    path = os.path.join(str(d), "long_decoy.bam")
+    blocks, inf, offs = write_bam(path, NAMES, LENS, recs)
+    lens, parsed = parse_bam(inf)
+    assert [r["off"] for r in parsed] == offs and parsed[20]["size"] == size
+    f = dict(path=path, blocks=blocks, inf=inf, offs=offs, lens=lens, recs=parsed, data=open(path, "rb").read(), cases={})
+    assert inf[offs[20] + at:offs[20] + at + len(s)] == s and inf.count(s) == 1
+    return f, offs[20], offs[20] + at
+
+
+def owners(f, batches):
+    """how many units of `batches` own each record of the file (a record belongs to the unit in whose [start, stop) it starts)"""
+    offs = np.asarray(f["offs"], dtype=np.int64)
+    n = np.zeros(offs.size, dtype=np.int64)
+    for b in batches:
+        for (start, stop, avail, fb, nb, flags), (fs, fe, fa) in zip(b["units"], [u[:3] for u in b["units_file"]]):
+            assert (start + b["base"], stop + b["base"], avail + b["base"]) == (fs, fe, fa)
+            mine = (offs >= fs) & (offs < fe)
+            n += mine
+    return n
+
+
 def census(offs, total, units, sub, seg):
     """Where the records of a file lie against the lanes, segments and units of a split — from the offsets alone.
     -> dict: lane_end / seg_end / unit_end: sets of distances (<= 64) from a record start to the end of its lane's stretch / its
