@@ -20,29 +20,15 @@
 #include <string>
 #include <vector>
 #include <map>
-#include "pd_kernels.h"
-#include "pd_local_comm.h"
-#include "../../include/pandepth_amd_dev.h"
-#include "pd_bamwalk.h"
-#include <condition_variable>
-#include <algorithm>
-#include <atomic>
 #include <deque>
-#include <chrono>
+#include "pd_local_comm.h"
+#include "pd_ctx.h"            // (behind pd_local_comm.h, whose staging buffer is not one of the guarded allocations)
 
-using namespace pdk;
-
-// ---- guarded device allocations (PANDEPTH_GUARD=1; pd_guard_check in include/pandepth_amd_dev.h) ---------------------------
-// Every device buffer this file allocates goes through the two functions below.  Normally they ARE hipMalloc / hipFree.  With
-// PANDEPTH_GUARD set, a buffer of n bytes is allocated as [256 B canary | n bytes | 256 B canary] (the second canary starting at
-// byte n exactly, not at a rounded size), the canaries are filled with a pattern, and they are compared — after a device
-// synchronize — whenever the buffer is freed and whenever pd_guard_check runs (pd_reset, pd_destroy, pd_comm_destroy call it):
-// a kernel that writes in front of or behind its buffer is named by the line that allocated the buffer, instead of landing in
-// the allocator's padding unseen.
+// ---- guarded device allocations: what pd_ctx.h declares (the bookkeeping is this file's alone) ----
 namespace pdguard {
 constexpr size_t G = 256;
 constexpr unsigned char PAT = 0xC5;
-struct Rec { size_t bytes; int line; };
+struct Rec { size_t bytes; const char *file; int line; };
 std::mutex mu;
 std::map<void *, Rec> live;
 std::atomic<uint64_t> n_bad{0};
@@ -63,8 +49,8 @@ uint64_t check_one(void *user, const Rec &r)
     for (size_t i = 0; i < G; ++i) if (h[G + i] != PAT) { ++back; if (first_back < 0) first_back = (int)i; last_back = (int)i; }
     if (!front && !back) return 0;
     char m[320];
-    snprintf(m, sizeof m, "[guard] device buffer of %zu bytes allocated at pd_capi.hip:%d was written out of bounds: %d byte(s) in front (first at -%d), "
-             "%d byte(s) behind (offsets +%d .. +%d past the end)", r.bytes, r.line, front, first_front < 0 ? 0 : (int)G - first_front, back, first_back, last_back);
+    snprintf(m, sizeof m, "[guard] device buffer of %zu bytes allocated at %s:%d was written out of bounds: %d byte(s) in front (first at -%d), "
+             "%d byte(s) behind (offsets +%d .. +%d past the end)", r.bytes, r.file, r.line, front, first_front < 0 ? 0 : (int)G - first_front, back, first_back, last_back);
     fprintf(stderr, "%s\n", m);
     last_msg = m;
     // repair the canaries so that one overrun is reported once
@@ -72,43 +58,43 @@ uint64_t check_one(void *user, const Rec &r)
     return 1;
 }
 
-hipError_t gmalloc(void **out, size_t bytes, int line)
+hipError_t gmalloc(void **out, size_t bytes, const char *file, int line)
 {
-    if (!on()) return hipMalloc(out, bytes);
+    if (!on()) return (hipMalloc)(out, bytes);              // (in parentheses: the runtime's own, not pd_ctx.h's macro)
     uint8_t *raw = nullptr;
-    const hipError_t e = hipMalloc((void **)&raw, bytes + 2 * G);
+    const hipError_t e = (hipMalloc)((void **)&raw, bytes + 2 * G);
     if (e != hipSuccess) return e;
     (void)hipMemset(raw, PAT, G);
     (void)hipMemset(raw + G + bytes, PAT, G);
     (void)hipDeviceSynchronize();
     *out = raw + G;
     std::lock_guard<std::mutex> g(mu);
-    live[raw + G] = Rec{bytes, line};
+    live[raw + G] = Rec{bytes, file, line};
     return hipSuccess;
 }
 
 hipError_t gfree(void *user)
 {
-    if (!on() || !user) return hipFree(user);
+    if (!on() || !user) return (hipFree)(user);
     std::lock_guard<std::mutex> g(mu);
     auto it = live.find(user);
-    if (it == live.end()) return hipFree(user);          // not one of ours (cannot happen; stay safe)
+    if (it == live.end()) return (hipFree)(user);          // not one of ours (cannot happen; stay safe)
     (void)hipDeviceSynchronize();
     n_bad += check_one(user, it->second);
     live.erase(it);
-    return hipFree((uint8_t *)user - G);
+    return (hipFree)((uint8_t *)user - G);
 }
 
 // a sub-buffer of a larger allocation (pd_create packs the context's small buffers into one): the caller has left G bytes in front of
 // and behind it; they become canaries, checked like everybody else's until drop()
-void adopt(void *user, size_t bytes, int line)
+void adopt(void *user, size_t bytes, const char *file, int line)
 {
     if (!on()) return;
     (void)hipMemset((uint8_t *)user - G, PAT, G);
     (void)hipMemset((uint8_t *)user + bytes, PAT, G);
     (void)hipDeviceSynchronize();
     std::lock_guard<std::mutex> g(mu);
-    live[user] = Rec{bytes, line};
+    live[user] = Rec{bytes, file, line};
 }
 void drop(void *user)
 {
@@ -136,10 +122,6 @@ uint64_t check_all()
     return n_bad.load();
 }
 } // namespace pdguard
-
-template <class T> static inline hipError_t pd_dmalloc(T **out, size_t bytes, int line) { return pdguard::gmalloc((void **)out, bytes, line); }
-#define hipMalloc(p, n) pd_dmalloc((p), (n), __LINE__)
-#define hipFree(p) pdguard::gfree((void *)(p))
 
 extern "C" int pd_guard_check(char *msg, size_t cap)
 {
@@ -171,194 +153,12 @@ extern "C" int pd_guard_selftest(void)
 
 namespace {
 
-constexpr int N_STAGE = 1024;                       // upper bound; slots are created on demand
-constexpr size_t STAGE_CAP = (size_t)1 << 18;        // runs per staging slot (3 MiB pinned + 3 MiB HBM)
-constexpr size_t DEV_BATCH_MAX = 0xFFFFFF00ull;       // runs per sorted batch (32-bit run indices)
-constexpr uint64_t OVF_MAX = (uint64_t)64 << 20;     // overflow-list entries (ends of runs longer than lmax) per tile pass
-constexpr uint32_t LMAX_DEFAULT = 512;               // look-back bound for owner tiles (cells)
-constexpr uint32_t SAMPLE_DEFAULT = 64;              // sparse index stride (runs)
-
 std::string g_create_err;                   // why the last pd_create failed (contexts may be created on several threads at once:
 std::mutex g_create_err_mu;                 // written and read under this lock, handed out as a copy of the calling thread's own)
 
-struct Stage {
-    pd_iv *host = nullptr, *dev = nullptr;
-    hipEvent_t copied = nullptr, done = nullptr;
-    int state = 0;                                   // 0 free, 1 held by caller, 2 in flight
-    uint64_t seq = 0;
-};
-
-struct ProfRec { std::string name; hipEvent_t a, b; };
-
-struct Pending { const pd_iv *iv; uint32_t n; uint32_t disorder; int slot; pd_runs *cr = nullptr; };   // slot: staging slot or -1; cr: a compact sample (iv NULL until expanded)
-
 } // namespace
 
-// a whole sample in the compact form (include/pandepth_amd.h: pd_runs_create; layout: C8Sample in pd_kernels.h)
-struct pd_runs {
-    pd_ctx *ctx = nullptr;
-    Run8 *r8 = nullptr;                                          // [sorted stream: n_s runs, file order | ... | other runs by bucket at o_base]
-    uint32_t n_s = 0, n_o = 0, o_base = 0, n = 0;                // n = n_s + n_o
-    uint32_t *b1 = nullptr, *o1 = nullptr;                       // (n_tiles << bshift) + 1 bucket starts per stream (one allocation: b1 | o1)
-    uint32_t bshift = 4;                                         // 16 buckets of 512 cells per tile
-    uint32_t n_long = 0;                                         // runs longer than a bucket: the direct kernels cannot use the sample
-    pd_iv *iv12 = nullptr;                                       // the expanded copy, made on first need
-    bool own_r8 = true;                                          // r8 is this object's allocation (false: it lives in the decode session's arena)
-    C8Sample view() const { return C8Sample{r8, b1, o1, o_base, bshift}; }
-};
-
-static inline size_t slice_flag_bytes(uint64_t n_tiles) { return (size_t)((n_tiles + 16 + 15) / 16 * 16); }
-
-struct pd_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr, copy_stream = nullptr;
-    int32_t n_contigs = 0;
-    std::vector<uint32_t> len;
-    std::vector<uint64_t> off;                       // first cell of each slot
-    uint64_t n_cells = 0, n_tiles = 0, n_words = 0;
-    int *buf = nullptr;                              // [n_cells diff | n_tiles sums | pad]
-    uint8_t *slab = nullptr;                         // ONE allocation behind the seventeen small buffers below (carry .. chk)
-    int *sums = nullptr, *carry = nullptr, *bsum = nullptr;
-    uint64_t *d_off = nullptr; uint32_t *d_len = nullptr; uint32_t *d_tile_contig = nullptr;
-    uint32_t *ub_a[PD_MAXPEND] = {}, *cand_lo[PD_MAXPEND] = {};   // per pending batch, indexed by 4096-cell tile
-    BatchDesc *desc = nullptr; CheckWords *chk = nullptr;         // desc: PD_MAXPEND entries
-    uint8_t *hstate = nullptr; uint32_t n_half = 0;               // "written since reset" per 4096 cells
-    uint8_t *slice_flags = nullptr;                               // pd_slice_sweep_i4: tiles that own exceptions
-    bool accumulate_packed = true;                                // pd_accumulate_from: 4-bit transport
-    bool direct_windows = false;                                  // pd_keep_deferred: a whole deferred sample stays deferred, the direct kernels may read it
-    bool pristine = true;                                         // nothing materialised in the arrays since the last reset
-    bool sums_stale = false;                                      // the tile sums hold what a direct export wrote while the sample is still deferred
-    uint32_t *direct_words = nullptr;                             // [n_long, fail, heavy_count, pad | heavy tile list]
-    bool dec_crc = true;                                          // the decoder checks every member's CRC-32 ("decode_crc")
-    unsigned lz_group = 16;                                       // chunks per workgroup of the LDS parse ("lz_group", up to 16; 0: every chunk parses with its text in memory).  Round 5's default: sixteen
-                                                                  // chunks of 8 + 2 KiB share a CU's LDS (158 KB: 32 KiB of history + their text), 16 waves per CU — 8.6 ms against 11.8 for the 60 MB call of
-                                                                  // profiles/r04_lz_parse_ab.txt, and the text is fetched once instead of ~1 000 times; chunks of 16 KiB fit seven to a CU and lose
-    unsigned dec_waves = 20;                                      // one-wave inflate workgroups per CU and launch ("inflate_waves")
-    std::atomic<uint32_t> dec_oth_div{41};                        // inflated bytes per slot for a later run in a batch's arrays: 41 (a kept record's minimum size) until a batch
-                                                                  // does not fit (long reads: a later run per 8 bytes of CIGAR), then 8 for the batches that follow
-    int dec_sync_event = 1;                                       // "decode_sync_event": pd_decode_collect waits for the batch's last event (0: for its stream, as until round 6)
-    int dec_h2d_fifo = 1;                                         // "decode_h2d_fifo": the batches' compressed bytes go up ONE after the other on a copy stream of their own (see pd_decode_queue)
-    std::mutex dec_copy_mu; int dec_h2d_lanes = 1; uint64_t dec_copy_seq = 0; hipStream_t dec_copy_st2 = nullptr;   // "decode_h2d_lanes": 2 = the batches' copies alternate between the main stream and a second one (two on the link at a time)
-    int dec_h2d_kernel = 0;                                       // "decode_h2d_kernel": a batch's compressed bytes fetched from the pinned buffer by a copy KERNEL on the batch's stream instead of the copy engine
-    bool dec_fast = true;                                         // the record chain of a batch is confirmed on the device where the session allows it ("decode_fast")
-    uint32_t dec_spoil = 0;                                       // test hook: every k-th segment's guess is spoilt after pass 1 ("decode_spoil")
-    uint32_t dec_max_redo = 256;                                  // ... with at most this many segments walking again per batch ("decode_max_redo")
-    uint64_t dec_c8_reserve = 0;                                  // test hook ("decode_c8_reserve" = n > 0): a compact session's first estimate is at most n first runs and its sample grows
-                                                                  // without the 2^16 runs of slack, so that files of a few thousand records make the sample grow and move (0: off)
-    // which way the last session went (read through pd_profile_get, names "decode_*"; cleared by pd_decode_begin)
-    enum { DN_GROW, DN_END_COMPACT, DN_END_C8_FALLBACK, DN_END_RUNS_MAKE, DN_END_SCATTER, DN_END_UNSORTED, DN_END_PEND, DN_GUESS, DN_COUNT };
-    std::atomic<uint64_t> dec_n[DN_COUNT] = {};
-    std::atomic<uint64_t> dec_n_fast{0}, dec_n_slow{0}, dec_n_redo{0};   // batches finished without / with the host's chain check; segments the device walked again
-    uint32_t direct_sample = 256;                                 // index stride of the direct path (runs)
-    uint32_t q_wave_max = 512, q_split = 262144;                  // "quantile_wave_max" / "quantile_split_cells": the cell counts up to which a quantile row takes the narrow / the workgroup kernel
-    int hist_variant = 1;                                         // "hist_variant": the histogram kernels' LDS form (launch_sweep_hist): 1 = one copy per workgroup, folded (measured best)
-    int direct_un = 0;                                           // 0 = the default form of the wide direct kernel (launch_direct_tiles)
-    bool all_valid_host = false;
-    std::vector<Pending> pend;
-    // ---- device decode (pd_decode_*): a few batch slots, each with its own stream and buffers ----
-    struct DecSlot {
-        bool busy = false;
-        bool warming = false;                                     // the session's warm-up thread is still making this slot's buffer and stream (dec_mu)
-        hipStream_t st = nullptr;
-        hipEvent_t ev[6] = {};
-        hipEvent_t ev_done = nullptr;                             // recorded behind everything pd_decode_queue puts on the stream: what pd_decode_collect waits for
-        uint8_t *h_blob = nullptr; size_t h_cap = 0;              // page-locked (pin_alloc)
-        bool h_mapped = false;                                    // ... as huge pages of its own registered with the runtime (freed by pin_free)
-        uint8_t *h_small = nullptr; size_t h_small_cap = 0;       // pinned: the batch's small tables on their way to and from the device
-        void *d[10] = {}; size_t cap[10] = {};                    // blob, inflated, tables (members | segments | member counter), status, -, lanes, redo list,
-                                                                  // ChainOut + per-segment keys (compact emission), and the runs of a batch whose chain the device
-                                                                  // confirms itself: first runs (8 B), later runs (12 B) — copied to exact arrays when the batch is collected
-        void *d_tok = nullptr; unsigned tok_wg = 0;               // wave scratch (match tokens) and the number of workgroups it was sized for
-        // a batch between pd_decode_queue and pd_decode_collect (pd_decode_submit: the two back to back)
-        struct Job {
-            bool open = false, queued = false, c8 = false, fast = false, owes_count = false, timed = false;
-            bool collecting = false;                               // some thread is inside dec_collect on this slot (set and tested under dec_mu): one ticket, one collect
-            uint64_t order = 0; size_t n_bytes = 0; uint64_t inflated = 0; uint32_t n_seg = 0;
-            std::vector<pd_bgzf_block> blocks; std::vector<pd_decode_unit> units; std::vector<pdb2::Seg> segs; std::vector<uint32_t> seg0;
-            size_t o_blk = 0, o_seg = 0, o_next = 0, o_up = 0, o_bst = 0, o_co = 0, o_so = 0, o_ord = 0;
-            pdb2::Cfg cfg{};
-            uint8_t *d_tab = nullptr;                              // the batch's tables on the device: the slot's table buffer, or behind the members in the blob buffer (one copy)
-            uint64_t cap_first = 0, cap_other = 0, t_mark = 0, t_q0 = 0, t_q1 = 0;      // (t_q0 / t_q1: PANDEPTH_DEVTRACE)
-        } job;
-        uint32_t gen = 0;
-    };
-    struct RunSeg { uint64_t order; pd_iv *first; uint64_t n_first; pd_iv *other; uint64_t n_other; pd_iv *far; uint64_t n_far; uint32_t max_span; uint32_t unsorted; uint64_t first_key, last_key; uint64_t n_long = 0; };
-    static constexpr int N_DEC = 12;
-    uint8_t *arena = nullptr; size_t arena_cap = 0; std::atomic<size_t> arena_used{0};   // the batches' run arrays (bump allocated)
-    DecSlot dec[N_DEC];
-    std::mutex dec_mu; std::condition_variable dec_cv;
-    bool dec_open = false;
-    bool dec_warm_on = false;                                     // "decode_warm"
-    std::thread dec_warm;                                         // pd_decode_begin's helper: the first slots' page-locked buffers, streams and hardware queues, one after the other, beside the caller
-    void *dec_warm_word = nullptr;
-    uint32_t dec_near_span = 0xFFFFFFFFu;                         // "decode_near_span": split the later runs into two streams (off)
-    pd_decode_cfg dec_cfg{}; uint8_t *d_contig_on = nullptr; uint32_t *d_span_off = nullptr; int32_t *d_spans = nullptr;
-    std::vector<RunSeg> run_segs;
-    pd_iv *run_first = nullptr, *run_other = nullptr, *run_far = nullptr;   // the concatenated sample (owned until the next reset)
-    pd_runs *dec_runs = nullptr;                                  // ... or the whole of it as a compact sample (PD_DECODE_COMPACT)
-    // A decode session that emits the compact form directly (PD_DECODE_COMPACT + pd_decode_cfg::n_batches): every batch's pass 2 writes its
-    // first runs as 8-byte compact runs (and marks the buckets' first runs, keyed by (batch, index in the batch)); as soon as every
-    // earlier batch has been counted, a batch's runs are copied — on a stream of their own, behind the decode — to their FINAL places in
-    // the sample's sorted stream, and its later runs behind those of the batches before it.  No feeder ever waits for another one, and at
-    // the end nothing is concatenated or converted: only the marks become indices and the later runs are sorted by bucket.
-    struct C8Dec {
-        bool on = false;
-        uint8_t *base = nullptr; size_t bytes = 0;               // ONE allocation: [Run8 x (cap_s + cap_o) | pd_iv x cap_o]
-        size_t cap_s = 0, cap_o = 0;
-        uint32_t *b1 = nullptr; size_t nbw = 0;                  // bucket starts: b1 | o1, nbw words each
-        unsigned long long *marks = nullptr;                     // per bucket: min (batch << 32 | index in the batch) of a run that begins there
-        uint32_t bshift = 4;
-        uint64_t n_s = 0, n_o = 0, turn = 0, n_batches = 0;
-        struct Batch { bool counted = false; uint64_t nf = 0, no = 0; Run8 *seg_s = nullptr; pd_iv *seg_o = nullptr; hipEvent_t ev = nullptr; };
-        std::vector<Batch> batch;                                // by order
-        std::vector<uint32_t> base_s;                            // first place of every batch's first runs in the sorted stream
-        hipStream_t compose = nullptr;
-        std::string err;                                         // what went wrong while runs were being placed (reported by pd_decode_end)
-        std::mutex mu;
-        Run8 *r8() const { return (Run8 *)base; }
-        pd_iv *oth() const { return (pd_iv *)(base + (cap_s + cap_o) * sizeof(Run8)); }
-    } c8;
-    uint64_t *ovf = nullptr; uint32_t ovf_cap = 0;    // ends of runs longer than lmax (grown on demand)
-    std::vector<Stage> stage;                        // grows on demand, up to N_STAGE
-    uint64_t seq = 0;
-    void *scratch = nullptr; size_t scratch_bytes = 0;
-    int state = 0;                                   // 0 accumulating (diff), 1 depth
-    uint32_t lmax = LMAX_DEFAULT, sample = SAMPLE_DEFAULT;
-    unsigned grid_tiles = 0;                         // 0 = sized per pass from the number of runs
-    int stile = 8192; int n_cu = 256;
-    // pd_deflate_parse's work buffers (device memory, grown on demand, kept until pd_destroy): two slots, each with its stream, so that
-    // two calls overlap (one's copies under the other's kernels)
-    struct LzWork {
-        static constexpr int N = 16;
-        void *p[N] = {}; size_t cap[N] = {};
-        bool fit(int k, size_t bytes)
-        {
-            if (bytes <= cap[k]) return true;
-            if (p[k]) { (void)hipFree(p[k]); p[k] = nullptr; cap[k] = 0; }
-            const size_t want = bytes + bytes / 8 + 4096;
-            if (hipMalloc(&p[k], want) != hipSuccess) return false;
-            cap[k] = want;
-            return true;
-        }
-        void release() { for (int k = 0; k < N; ++k) { if (p[k]) (void)hipFree(p[k]); p[k] = nullptr; cap[k] = 0; } if (st) { (void)hipStreamDestroy(st); st = nullptr; }
-                         if (h_stage) { (void)hipHostFree(h_stage); h_stage = nullptr; } for (auto &e : ev_stage) if (e) { (void)hipEventDestroy(e); e = nullptr; } }
-        hipStream_t st = nullptr;
-        void *h_stage = nullptr; hipEvent_t ev_stage[2] = {nullptr, nullptr};     // page-locked staging of the symbols' way back
-        std::mutex mu;
-    } lz[4];                                                      // (a round's provider calls in flight at once: two until round 6, up to four)
-    std::atomic<unsigned> lz_turn{0}; unsigned lz_slots = 2;         // "lz_slots": 2 or 4 of lz[] in use
-    bool lz_mix = false;                                          // "lz_mix": see lz_run
-    // the statistics of the last window call stay on the device (pd_text_append_window_rows formats the table's rows from them)
-    unsigned char *wk = nullptr; size_t wk_bytes = 0; uint32_t wk_w = 0; uint64_t wk_nw = 0; bool wk_valid = false; std::vector<uint64_t> wk_woff;
-    bool prof = false;
-    std::vector<ProfRec> prof_pending;
-    std::vector<hipEvent_t> ev_pool;
-    std::map<std::string, std::pair<double, uint64_t>> prof_acc;
-    std::mutex mu;
-    std::string err;
-};
-
-namespace {
+namespace pdi {
 
 int fail(pd_ctx *c, int code, const std::string &msg)
 {
@@ -375,13 +175,6 @@ int need_state(pd_ctx *c, int want, const char *fn)
     return fail(c, PD_ESTATE, std::string(fn) + ": " + why);
 }
 
-#define HIPOK(ctx, call)                                                                         \
-    do {                                                                                         \
-        hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(ctx, PD_EHIP, std::string(#call) + ": " + hipGetErrorString(e_));        \
-    } while (0)
-
 ContigTab tab_of(pd_ctx *c) { return ContigTab{c->d_off, c->d_len, c->n_contigs}; }
 
 hipEvent_t get_event(pd_ctx *c)
@@ -392,17 +185,9 @@ hipEvent_t get_event(pd_ctx *c)
     return e;
 }
 
-struct ProfScope {
-    pd_ctx *c; ProfRec r; bool on;
-    ProfScope(pd_ctx *ctx, const char *name) : c(ctx), on(ctx->prof)
-    {
-        if (on) { r.name = name; r.a = get_event(c); r.b = get_event(c); (void)hipEventRecord(r.a, c->stream); }
-    }
-    ~ProfScope()
-    {
-        if (on) { (void)hipEventRecord(r.b, c->stream); c->prof_pending.push_back(r); }
-    }
-};
+} // namespace pdi
+
+namespace {
 
 int prof_collect(pd_ctx *c)
 {
@@ -471,6 +256,10 @@ int expand_compact(pd_ctx *c, Pending &p)
     p.disorder = (uint32_t)PD_TILE >> r->bshift;
     return PD_OK;
 }
+
+} // namespace
+
+namespace pdi {
 
 // one owner-tile pass over all pending sorted batches
 int flush_pending(pd_ctx *c)
@@ -563,6 +352,10 @@ int scatter_device(pd_ctx *c, const pd_iv *d, size_t n, unsigned flags, int slot
     return PD_OK;
 }
 
+} // namespace pdi
+
+namespace {
+
 int check_words(pd_ctx *c)
 {
     CheckWords h;
@@ -630,23 +423,13 @@ int stage_submit(pd_ctx *c, int slot, size_t n, unsigned flags)
 
 } // namespace
 
-extern "C" {
-
-int pd_abi_version(void) { return PD_ABI_VERSION; }
-
-const char *pd_strerror(const pd_ctx *ctx)
-{
-    if (ctx) return ctx->err.c_str();
-    static thread_local std::string mine;
-    { std::lock_guard<std::mutex> lk(g_create_err_mu); mine = g_create_err; }
-    return mine.c_str();
-}
+namespace pdi {
 
 // A page-locked host buffer for a decode slot.  hipHostMalloc of 34 MB takes 7-8 ms (the runtime allocates and maps it 4 KiB page by page): six of them were
 // 46 ms in front of every run's first read.  Anonymous memory the kernel backs with 2 MiB pages (MADV_HUGEPAGE; where transparent huge pages are off it is
 // ordinary memory), touched, then registered with the runtime (hipHostRegister) takes 1.5 ms and copies at the same 56 GB/s (tools/ubench/pin_cost.hip,
 // profiles/r06_h2d_fill.txt).  Falls back to hipHostMalloc.
-static uint8_t *pin_alloc(size_t bytes, bool *mapped)
+uint8_t *pin_alloc(size_t bytes, bool *mapped)
 {
     *mapped = false;
     if (!getenv("PANDEPTH_NO_HUGE_PIN")) {
@@ -668,13 +451,27 @@ static uint8_t *pin_alloc(size_t bytes, bool *mapped)
     if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     return (uint8_t *)p;
 }
-static void pin_free(uint8_t *p, size_t bytes, bool mapped)
+void pin_free(uint8_t *p, size_t bytes, bool mapped)
 {
     if (!p) return;
     if (!mapped) { (void)hipHostFree(p); return; }
     const size_t al = (size_t)2 << 20, len = (bytes + al - 1) / al * al;
     (void)hipHostUnregister(p);
     munmap(p, len);
+}
+
+} // namespace pdi
+
+extern "C" {
+
+int pd_abi_version(void) { return PD_ABI_VERSION; }
+
+const char *pd_strerror(const pd_ctx *ctx)
+{
+    if (ctx) return ctx->err.c_str();
+    static thread_local std::string mine;
+    { std::lock_guard<std::mutex> lk(g_create_err_mu); mine = g_create_err; }
+    return mine.c_str();
 }
 
 int pd_create(int device, int32_t n_contigs, const uint32_t *contig_len, pd_ctx **out)
@@ -751,7 +548,7 @@ int pd_create(int device, int32_t n_contigs, const uint32_t *contig_len, pd_ctx 
         size_t total = 0;
         for (size_t k = 0; k < wants.size(); ++k) { total += gap; at[k] = total; total = (total + wants[k].bytes + gap + 255) / 256 * 256; }
         CREATE_OK(hipMalloc(&c->slab, total + 256));
-        for (size_t k = 0; k < wants.size(); ++k) { *wants[k].pp = c->slab + at[k]; pdguard::adopt(*wants[k].pp, wants[k].bytes, wants[k].line); }
+        for (size_t k = 0; k < wants.size(); ++k) { *wants[k].pp = c->slab + at[k]; pdguard::adopt(*wants[k].pp, wants[k].bytes, __FILE_NAME__, wants[k].line); }
     }
     {
         std::vector<uint32_t> tc(c->n_tiles + 1, 0);
@@ -772,11 +569,6 @@ int pd_create(int device, int32_t n_contigs, const uint32_t *contig_len, pd_ctx 
     *out = c;
     return PD_OK;
 }
-
-static void runs_free(pd_runs *r);
-static int runs_make(pd_ctx *c, const pd_iv *sorted, size_t n_sorted, const pd_iv *const *others, const size_t *n_others, int n_arr, pd_runs **out);
-
-static inline uint64_t dec_now_us() { return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int pd_destroy(pd_ctx *c)
 {
@@ -812,12 +604,7 @@ int pd_destroy(pd_ctx *c)
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
         if (sl.st) (void)hipStreamDestroy(sl.st);
     }
-    for (auto &r : c->run_segs) {
-        const auto ina = [&](const void *p) { return c->arena && (const uint8_t *)p >= c->arena && (const uint8_t *)p < c->arena + c->arena_cap; };
-        if (r.first && !ina(r.first)) (void)hipFree(r.first);
-        if (r.other && !ina(r.other)) (void)hipFree(r.other);
-        if (r.far && !ina(r.far)) (void)hipFree(r.far);
-    }
+    for (auto &r : c->run_segs) r.release(c);
     for (void *p : {(void *)c->d_contig_on, (void *)c->d_span_off, (void *)c->d_spans, (void *)c->run_first, (void *)c->run_other, (void *)c->run_far, (void *)c->arena}) if (p) (void)hipFree(p);
     runs_free(c->dec_runs);
     for (void *p : {(void *)c->c8.base, (void *)c->c8.b1}) if (p) (void)hipFree(p);
@@ -903,7 +690,11 @@ int pd_set_param(pd_ctx *c, const char *name, uint64_t value)
     return fail(c, PD_EINVAL, std::string("unknown parameter ") + name);
 }
 
-static void runs_free(pd_runs *r)
+} // extern "C"
+
+namespace pdi {
+
+void runs_free(pd_runs *r)
 {
     if (!r) return;
     if (r->own_r8 && r->r8) (void)hipFree(r->r8);
@@ -911,7 +702,7 @@ static void runs_free(pd_runs *r)
     delete r;
 }
 
-static uint32_t runs_bshift(const pd_ctx *c)
+uint32_t runs_bshift(const pd_ctx *c)
 {
     // buckets as wide as the look-back bound ("lmax", a power of two between 256 and 8192 cells; default 512)
     uint32_t cells = 256; while (cells < c->lmax && cells < (uint32_t)PD_TILE) cells <<= 1;
@@ -924,7 +715,7 @@ static uint32_t runs_bshift(const pd_ctx *c)
 // order.  Fills the bucket starts of the sorted stream (a suffix minimum over the marks), counts the other runs per bucket, places them
 // behind o_base.  words (device, 2 x uint32, already holding the sorted stream's flags): [0] bad contig id, [1] runs longer than a bucket.
 // Only enqueues on c->stream; `tmp` must hold 2 x (nb + 2) + (nb / 1024 + 4) words.
-static void runs_finish(pd_ctx *c, pd_runs *r, const pd_iv *const *others, const size_t *n_others, int n_arr, uint32_t *tmp, uint32_t *words)
+void runs_finish(pd_ctx *c, pd_runs *r, const pd_iv *const *others, const size_t *n_others, int n_arr, uint32_t *tmp, uint32_t *words)
 {
     hipStream_t st = c->stream;
     const uint32_t nb = (uint32_t)((uint64_t)c->n_tiles << r->bshift);
@@ -940,7 +731,7 @@ static void runs_finish(pd_ctx *c, pd_runs *r, const pd_iv *const *others, const
 }
 
 // caller holds c->mu and has set the device.  `sorted` must be sorted by (tid, beg) — checked; the `others` may be in any order.
-static int runs_make(pd_ctx *c, const pd_iv *sorted, size_t n_sorted, const pd_iv *const *others, const size_t *n_others, int n_arr, pd_runs **out)
+int runs_make(pd_ctx *c, const pd_iv *sorted, size_t n_sorted, const pd_iv *const *others, const size_t *n_others, int n_arr, pd_runs **out)
 {
     *out = nullptr;
     size_t n = n_sorted, n_o = 0;
@@ -984,6 +775,10 @@ static int runs_make(pd_ctx *c, const pd_iv *sorted, size_t n_sorted, const pd_i
     *out = r;
     return PD_OK;
 }
+
+} // namespace pdi
+
+extern "C" {
 
 int pd_runs_create(pd_ctx *c, const pd_iv *dev_sorted, size_t n_sorted, const pd_iv *dev_other, size_t n_other, pd_runs **out)
 {
@@ -1744,1070 +1539,6 @@ int pd_device_buffer(pd_ctx *c, void **dev_ptr, uint64_t *n_words, uint64_t *con
 
 } // extern "C"
 
-// ---------------------------------------------------------------------------------------------------------------
-// GPU-side BAM decode in asynchronous batches (include/pandepth_amd.h: pd_decode_*)
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-
-enum { DS_BLOB, DS_INF, DS_BLK, DS_ST, DS_SEG /* (unused since the tables travel as one) */, DS_LANE, DS_ONLY, DS_SEGOUT, DS_R8, DS_OTH };
-
-// PANDEPTH_TIMING=1: where the host side of the decode path spends its time (thread-microseconds, summed)
-std::atomic<uint64_t> g_dec_us[8];
-inline uint64_t dec_now() { return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-struct DecTimer { int k; uint64_t t0; explicit DecTimer(int k_) : k(k_), t0(dec_now()) {} ~DecTimer() { g_dec_us[k] += dec_now() - t0; } };
-
-int dec_fail(pd_ctx *c, int code, const std::string &msg) { std::lock_guard<std::mutex> lk(c->mu); return fail(c, code, msg); }
-
-#define HIPDEC(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return dec_fail(c, PD_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
-std::mutex g_alloc_mu;                   // pinned / device allocations of the decode slots, one at a time
-
-int dec_ensure(pd_ctx *c, pd_ctx::DecSlot &sl, int k, size_t bytes)
-{
-    if (bytes <= sl.cap[k]) return PD_OK;
-    std::lock_guard<std::mutex> al(g_alloc_mu);
-    if (sl.d[k]) { HIPDEC(hipStreamSynchronize(sl.st)); HIPDEC(hipFree(sl.d[k])); sl.d[k] = nullptr; sl.cap[k] = 0; }
-    const size_t want = bytes + bytes / 8 + 4096;
-    if (hipMalloc(&sl.d[k], want) != hipSuccess) return dec_fail(c, PD_ENOMEM, "device-decode buffer allocation failed");
-    sl.cap[k] = want;
-    return PD_OK;
-}
-
-// the host side of a batch after pass 1: pdb2::check_chain (pd_bamwalk.h)
-uint32_t dec_finish(std::vector<pdb2::Seg> &segs, std::vector<uint32_t> *redo) { return pdb2::check_chain(segs, redo); }
-
-static_assert(sizeof(pdb2::R8) == sizeof(Run8), "the decoder's 8-byte run is the kernels' Run8");
-
-// ---- compact decode sessions (pd_ctx::C8Dec) ----
-void c8_drop(pd_ctx *c)
-{
-    pd_ctx::C8Dec &x = c->c8;
-    if (x.compose) (void)hipStreamSynchronize(x.compose);
-    if (x.base) { (void)hipFree(x.base); x.base = nullptr; }
-    if (x.b1) { (void)hipFree(x.b1); x.b1 = nullptr; }
-    if (x.marks) { (void)hipFree(x.marks); x.marks = nullptr; }
-    const auto ina = [&](const void *p) { return c->arena && (const uint8_t *)p >= c->arena && (const uint8_t *)p < c->arena + c->arena_cap; };
-    for (auto &b : x.batch) {
-        if (b.seg_s && !ina(b.seg_s)) (void)hipFree(b.seg_s);
-        if (b.seg_o && !ina(b.seg_o)) (void)hipFree(b.seg_o);
-        if (b.ev) (void)hipEventDestroy(b.ev);
-    }
-    x.batch.clear(); x.base_s.clear();
-    x.on = false; x.bytes = 0; x.cap_s = x.cap_o = 0; x.n_s = x.n_o = x.turn = x.n_batches = 0;
-}
-
-// room for n_s first runs and n_o later runs in the sample's final arrays (the caller holds c8.mu; copies placed earlier may still be
-// running — the device is waited for before anything moves).  Returns PD_OK / PD_ENOMEM / PD_EHIP, no message.
-int c8_reserve(pd_ctx *c, uint64_t n_s, uint64_t n_o, bool exact = false)
-{
-    pd_ctx::C8Dec &x = c->c8;
-    if (n_s <= x.cap_s && n_o <= x.cap_o && x.base) return PD_OK;
-    const size_t slack = c->dec_c8_reserve ? 0 : (size_t)1 << 16;
-    const size_t ns = std::max<size_t>((size_t)n_s + (exact ? 0 : (size_t)n_s / 2) + slack, x.cap_s), no = std::max<size_t>((size_t)n_o + (exact ? 0 : (size_t)n_o / 2) + slack, x.cap_o);
-    const size_t bytes = (ns + no) * sizeof(Run8) + no * sizeof(pd_iv) + 256;
-    uint8_t *nb = nullptr;
-    if (x.base) (void)hipDeviceSynchronize();
-    if (hipMalloc(&nb, bytes) != hipSuccess) { (void)hipGetLastError(); return PD_ENOMEM; }
-    if (x.base) {
-        ++c->dec_n[pd_ctx::DN_GROW];
-        hipError_t e = hipSuccess;
-        if (x.n_s) e = hipMemcpy(nb, x.base, (size_t)x.n_s * sizeof(Run8), hipMemcpyDeviceToDevice);
-        if (e == hipSuccess && x.n_o) e = hipMemcpy(nb + (ns + no) * sizeof(Run8), x.oth(), (size_t)x.n_o * sizeof(pd_iv), hipMemcpyDeviceToDevice);
-        (void)hipFree(x.base);
-        if (e != hipSuccess) { (void)hipFree(nb); x.base = nullptr; return PD_EHIP; }
-    }
-    x.base = nb; x.bytes = bytes; x.cap_s = ns; x.cap_o = no;
-    return PD_OK;
-}
-
-// A batch has been counted (its runs are being written to its own segment, `ev` follows that kernel): it and every batch behind it whose
-// predecessors are all counted now get their final places, and the copies there are queued on the compose stream.  Nobody waits.
-void c8_counted(pd_ctx *c, uint64_t order, uint64_t nf, uint64_t no, Run8 *seg_s, pd_iv *seg_o, hipEvent_t ev)
-{
-    pd_ctx::C8Dec &x = c->c8;
-    std::lock_guard<std::mutex> lk(x.mu);
-    if (order >= x.batch.size() || x.batch[(size_t)order].counted) { if (x.err.empty()) x.err = "a batch number was submitted twice or lies outside the session"; return; }
-    pd_ctx::C8Dec::Batch &me = x.batch[(size_t)order];
-    me.counted = true; me.nf = nf; me.no = no; me.seg_s = seg_s; me.seg_o = seg_o; me.ev = ev;
-    while (x.turn < x.n_batches && x.batch[(size_t)x.turn].counted) {
-        pd_ctx::C8Dec::Batch &b = x.batch[(size_t)x.turn];
-        x.base_s[(size_t)x.turn] = (uint32_t)x.n_s;
-        if (b.nf + b.no) {
-            hipError_t e = hipSuccess;
-            // (when the sample outgrows its arrays — every growth waits for the device and moves what is there — they are made large enough for
-            // the REST of the file at the rate seen so far, not half again: a long-read file has 1 600 later runs per first run where the first
-            // estimate assumed one in four, and eight growths of gigabytes stalled every feeder — 8 thread-seconds on 128 batches)
-            uint64_t want_s = x.n_s + b.nf, want_o = x.n_o + b.no;
-            if ((want_s > x.cap_s || want_o > x.cap_o) && x.n_batches > x.turn + 1) {
-                const double f = 1.05 * (double)x.n_batches / (double)(x.turn + 1);
-                want_s = std::max<uint64_t>(want_s, (uint64_t)((double)want_s * f)); want_o = std::max<uint64_t>(want_o, (uint64_t)((double)want_o * f));
-                if (c8_reserve(c, want_s, want_o, /*exact=*/true) != PD_OK) { want_s = x.n_s + b.nf; want_o = x.n_o + b.no; }      // (no room for the projection: what is needed now)
-            }
-            if (c8_reserve(c, x.n_s + b.nf, x.n_o + b.no) != PD_OK) e = hipErrorOutOfMemory;
-            if (e == hipSuccess && b.ev) e = hipStreamWaitEvent(x.compose, b.ev, 0);
-            if (e == hipSuccess && b.nf) launch_copy_words(x.compose, x.r8() + x.n_s, b.seg_s, b.nf * (sizeof(Run8) / 4));
-            if (e == hipSuccess && b.no) launch_copy_words(x.compose, x.oth() + x.n_o, b.seg_o, b.no * (sizeof(pd_iv) / 4));
-            if (e == hipSuccess) e = hipGetLastError();
-            if (e != hipSuccess && x.err.empty()) x.err = std::string("placing a batch's runs: ") + hipGetErrorString(e);
-            x.n_s += b.nf; x.n_o += b.no;
-        }
-        ++x.turn;
-    }
-}
-
-} // namespace
-
-extern "C" {
-
-int pd_decode_begin(pd_ctx *c, const pd_decode_cfg *cfg)
-{
-    if (!c || !cfg) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 0, "pd_decode_begin")) return rs;
-    HIPOK(c, hipSetDevice(c->device));
-    const uint64_t tb0 = dec_now_us(); uint64_t tb[6] = {tb0, tb0, tb0, tb0, tb0, tb0};
-    struct BeginMarks { const uint64_t *t; ~BeginMarks() { if (getenv("PANDEPTH_TIMING") && t[5] - t[0] > 20000) fprintf(stderr, "[timing]   pd_decode_begin: tables %.3f s, marks + compose stream %.3f s, sample arrays %.3f s, arena %.3f s, buffers %.3f s\n", (t[1] - t[0]) / 1e6, (t[2] - t[1]) / 1e6, (t[3] - t[2]) / 1e6, (t[4] - t[3]) / 1e6, (t[5] - t[4]) / 1e6); } } begin_marks{tb};
-    c->dec_cfg = *cfg;
-    std::vector<uint8_t> on((size_t)c->n_contigs, 1);
-    for (int32_t t = 0; t < c->n_contigs; ++t) on[(size_t)t] = cfg->contig_on ? (cfg->contig_on[t] != 0) : (c->len[(size_t)t] >= 2);
-    if (!c->d_contig_on && hipMalloc(&c->d_contig_on, (size_t)c->n_contigs + 16) != hipSuccess) return fail(c, PD_ENOMEM, "pd_decode_begin: allocation failed");
-    HIPOK(c, hipMemcpyAsync(c->d_contig_on, on.data(), on.size(), hipMemcpyHostToDevice, c->stream));
-    if (c->d_span_off) { (void)hipFree(c->d_span_off); c->d_span_off = nullptr; }
-    if (c->d_spans) { (void)hipFree(c->d_spans); c->d_spans = nullptr; }
-    if (cfg->span_off && cfg->spans) {
-        const size_t ns = cfg->span_off[c->n_contigs];
-        if (hipMalloc(&c->d_span_off, ((size_t)c->n_contigs + 1) * 4) != hipSuccess || hipMalloc(&c->d_spans, ns * 8 + 16) != hipSuccess)
-            return fail(c, PD_ENOMEM, "pd_decode_begin: allocation failed");
-        HIPOK(c, hipMemcpyAsync(c->d_span_off, cfg->span_off, ((size_t)c->n_contigs + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        if (ns) HIPOK(c, hipMemcpyAsync(c->d_spans, cfg->spans, ns * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    c->dec_cfg.contig_on = nullptr; c->dec_cfg.span_off = nullptr; c->dec_cfg.spans = nullptr;      // (the caller's arrays are not kept)
-    // A sorted file read for whole-contig statistics (PD_DECODE_COMPACT), its batches numbered 0 .. n_batches - 1: the batches' runs go
-    // straight to their final places in a compact sample (C8Dec).  Sized from the compressed bytes
-    // (>= 32 B of BGZF per record of a real file; denser files make it grow): a first run per record, a later run for every fourth.
-    HIPOK(c, hipStreamSynchronize(c->stream));                        // (the caller's arrays have been read)
-    tb[1] = tb[2] = tb[3] = dec_now_us();
-    {
-        std::lock_guard<std::mutex> l8(c->c8.mu);
-        pd_ctx::C8Dec &x = c->c8;
-        if (x.on || !x.batch.empty()) { (void)hipDeviceSynchronize(); c8_drop(c); }     // (a session that was never ended)
-        x.on = false; x.n_s = x.n_o = x.turn = 0; x.n_batches = 0; x.err.clear();
-        const uint64_t nb64 = (uint64_t)c->n_tiles << runs_bshift(c);
-        // (any genome size: a compact run keeps the low 32 bits of its flat begin and every consumer works relative to a tile; what is bounded is
-        // the number of runs — 32-bit indices — so a file that promises more than that many records keeps 12-byte runs per batch)
-        if ((cfg->flags & PD_DECODE_COMPACT) && cfg->n_batches && cfg->n_batches < (1ull << 31) && cfg->sorted && !cfg->spans && c->pend.empty() &&
-            cfg->bytes_hint / 16 < DEV_BATCH_MAX && nb64 <= 0xFFFFFF00ull &&
-            // (above 2^32 cells a compact session that outgrows its 32-bit run indices cannot fall back to 12-byte runs afterwards — pd_decode_end
-            // would have to refuse a file already decoded — so there the caller must have said how large the file is; the executable always does)
-            (c->n_cells < (1ull << 32) || cfg->bytes_hint != 0)) {
-            x.bshift = runs_bshift(c);
-            x.nbw = (size_t)nb64 + 2;
-            if (x.b1) { (void)hipFree(x.b1); x.b1 = nullptr; }
-            if (x.marks) { (void)hipFree(x.marks); x.marks = nullptr; }
-            if (hipMalloc(&x.b1, 2 * x.nbw * 4) != hipSuccess || hipMalloc(&x.marks, x.nbw * 8) != hipSuccess) { (void)hipGetLastError(); return fail(c, PD_ENOMEM, "pd_decode_begin: allocation failed"); }
-            HIPOK(c, hipMemsetAsync(x.marks, 0xFF, x.nbw * 8, c->stream));
-            HIPOK(c, hipStreamSynchronize(c->stream));                // (the batches' kernels run on other streams)
-            if (!x.compose) HIPOK(c, hipStreamCreateWithFlags(&x.compose, hipStreamNonBlocking));
-            tb[2] = tb[3] = dec_now_us();
-            // (>= 32 B of BGZF per record of a real short-read file: a first run per record, a later run for every fourth; c8_reserve adds
-            // half again when the sample has to GROW, not to this first estimate — a 70 GB file would otherwise ask for 50 GB up front.)
-            uint64_t est = std::min<uint64_t>(cfg->bytes_hint ? cfg->bytes_hint / 32 + (1u << 20) : (uint64_t)8 << 20, DEV_BATCH_MAX);
-            if (c->dec_c8_reserve) est = std::min<uint64_t>(est, c->dec_c8_reserve);
-            const int rsv = c8_reserve(c, est, est / 4, /*exact=*/true);
-            tb[3] = dec_now_us();
-            if (rsv == PD_OK) {
-                x.n_batches = cfg->n_batches;
-                x.batch.assign((size_t)cfg->n_batches, pd_ctx::C8Dec::Batch());
-                x.base_s.assign((size_t)cfg->n_batches, 0u);
-                x.on = true;
-            } else {
-                // not enough memory for the compact sample's arrays: the session goes on with 12-byte runs per batch, as sessions without
-                // PD_DECODE_COMPACT do (pd_decode_end then takes the general paths)
-                (void)hipGetLastError();
-                if (x.b1) { (void)hipFree(x.b1); x.b1 = nullptr; }
-                if (x.marks) { (void)hipFree(x.marks); x.marks = nullptr; }
-            }
-        }
-    }
-    // one arena for the batches' run arrays (a hipMalloc per batch waits for the other streams): about half the compressed
-    // bytes is plenty for short reads (12 B per run against >= 30 B of BGZF per record); what does not fit is allocated singly
-    // (a compact session's segments are 8-byte first runs + 12-byte later runs: a third less)
-    // (round 6: a fifth in a compact session — 8 bytes per record and 12 per later run are 0.18 of a 53-bytes-per-record file — instead of a third: device
-    // memory a process HOLDS is wiped when it leaves, and the next process's large allocations wait for that: 1.0-1.8 s now and then in this very call when
-    // one run followed another within a second, tools/calls/r6_call27.sh)
-    const size_t want = cfg->bytes_hint ? (size_t)(cfg->bytes_hint / (c->c8.on ? 5 : 2)) + ((size_t)16 << 20) : (size_t)256 << 20;
-    if (c->arena_cap < want) {
-        if (c->arena) { (void)hipFree(c->arena); c->arena = nullptr; c->arena_cap = 0; }
-        if (hipMalloc(&c->arena, want) == hipSuccess) c->arena_cap = want; else (void)hipGetLastError();
-    }
-    c->arena_used = 0;
-    tb[4] = tb[5] = dec_now_us();
-    c->dec_n_fast = 0; c->dec_n_slow = 0; c->dec_n_redo = 0;
-    for (auto &n : c->dec_n) n = 0;
-    for (auto &g : g_dec_us) g = 0;
-    if (c->dec_warm.joinable()) c->dec_warm.join();
-    if (cfg->batch_bytes && cfg->batches_in_flight) {
-        const size_t need = std::max<size_t>((size_t)cfg->batch_bytes + 128, (size_t)8 << 20);
-        const size_t want = need + std::max<size_t>((size_t)1 << 20, need / 32);            // (room for the batch's tables behind its bytes: pd_decode_acquire)
-        if (!c->dec_warm_on) {
-            // the first buffers page-locked here, from ONE thread (six readers pinning at once took 75-100 ms EACH, 5-8 ms alone)
-            DecTimer ta(1);
-            uint32_t k = 0;
-            for (auto &sl : c->dec) {
-                if (k++ >= cfg->batches_in_flight) break;
-                if (sl.h_cap >= need) continue;
-                if (sl.h_blob) { pin_free(sl.h_blob, sl.h_cap, sl.h_mapped); sl.h_blob = nullptr; sl.h_cap = 0; }
-                if ((sl.h_blob = pin_alloc(want, &sl.h_mapped)) != nullptr) sl.h_cap = want;
-            }
-        } else {
-        // "decode_warm" (measured and left off, tools/calls/r6_call26.sh): the first slots made ready by a helper thread, one after the other, while the caller
-        // goes on — a slot's page-locked buffer, its stream and events, and by a first, empty launch the stream's hardware queue (the runtime makes it when
-        // something is launched: 9 ms each, one after the other whoever asks); pd_decode_acquire hands a slot out when it is ready.  The first reader does
-        // start after 20 ms — and its kernels wait until the LAST queue is made: every queue the process makes stops the ones it has (first batches collected
-        // after 140-155 ms instead of 58-66 after a 50 ms pd_decode_begin).
-        uint32_t n_warm = 0;
-        {
-            std::lock_guard<std::mutex> l2(c->dec_mu);
-            for (auto &sl : c->dec) { if (n_warm >= cfg->batches_in_flight) break; sl.warming = true; ++n_warm; }
-        }
-        if (!c->dec_warm_word && hipMalloc(&c->dec_warm_word, 256) != hipSuccess) { (void)hipGetLastError(); c->dec_warm_word = nullptr; }
-        c->dec_warm = std::thread([c, n_warm, need, want]() {
-            (void)hipSetDevice(c->device);
-            for (uint32_t k = 0; k < n_warm; ++k) {
-                pd_ctx::DecSlot &sl = c->dec[k];
-                {
-                    DecTimer ta(1);
-                    if (sl.h_cap < need) {
-                        std::lock_guard<std::mutex> al(g_alloc_mu);
-                        if (sl.h_blob) { pin_free(sl.h_blob, sl.h_cap, sl.h_mapped); sl.h_blob = nullptr; sl.h_cap = 0; }
-                        if ((sl.h_blob = pin_alloc(want, &sl.h_mapped)) != nullptr) sl.h_cap = want;
-                    }
-                }
-                if (!sl.st) {
-                    bool ok = hipStreamCreateWithFlags(&sl.st, hipStreamNonBlocking) == hipSuccess;
-                    for (auto &e : sl.ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-                    ok = ok && hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming) == hipSuccess;
-                    if (!ok) {                                              // (dec_queue makes what is missing and reports what cannot be made)
-                        (void)hipGetLastError();
-                        for (auto &e : sl.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-                        if (sl.ev_done) { (void)hipEventDestroy(sl.ev_done); sl.ev_done = nullptr; }
-                        if (sl.st) { (void)hipStreamDestroy(sl.st); sl.st = nullptr; }
-                    } else if (c->dec_warm_word) {
-                        (void)hipMemsetAsync(c->dec_warm_word, 0, 4, sl.st);      // the stream's first launch: its hardware queue is made now
-                        (void)hipStreamSynchronize(sl.st);
-                    }
-                }
-                { std::lock_guard<std::mutex> l2(c->dec_mu); sl.warming = false; }
-                c->dec_cv.notify_all();
-            }
-        });
-        }
-    }
-    tb[5] = dec_now_us();
-    c->dec_open = true;
-    return PD_OK;
-}
-
-int pd_decode_acquire(pd_ctx *c, size_t bytes, void **host_buf)
-{
-    if (!c || !host_buf) return PD_EINVAL;
-    *host_buf = nullptr;
-    std::unique_lock<std::mutex> lk(c->dec_mu);
-    if (!c->dec_open) return dec_fail(c, PD_ESTATE, "pd_decode_acquire: call pd_decode_begin first");
-    pd_ctx::DecSlot *sl = nullptr;
-    { DecTimer tw(0); c->dec_cv.wait(lk, [&] { for (auto &x : c->dec) if (!x.busy && !x.warming) { sl = &x; return true; } return false; }); }
-    sl->busy = true;
-    lk.unlock();
-    {
-        DecTimer tsd(7);
-        if (hipSetDevice(c->device) != hipSuccess) {
-            { std::lock_guard<std::mutex> l2(c->dec_mu); sl->busy = false; }
-            c->dec_cv.notify_one();
-            return dec_fail(c, PD_EHIP, "hipSetDevice failed");
-        }
-    }
-    DecTimer ta(1);
-    if (bytes + 64 > sl->h_cap) {
-        if (sl->h_blob) { pin_free(sl->h_blob, sl->h_cap, sl->h_mapped); sl->h_blob = nullptr; sl->h_cap = 0; }
-        // (room behind the caller's bytes for the batch's small tables, which then travel with them in ONE copy: dec_queue)
-        const size_t want = std::max<size_t>(bytes + 64, (size_t)8 << 20) + std::max<size_t>((size_t)1 << 20, bytes / 32);
-        // one allocation at a time: six feeders pinning their first buffers at once took 75-100 ms EACH (4-5 ms alone)
-        std::lock_guard<std::mutex> al(g_alloc_mu);
-        if ((sl->h_blob = pin_alloc(want, &sl->h_mapped)) == nullptr) {
-            { std::lock_guard<std::mutex> l2(c->dec_mu); sl->busy = false; }
-            c->dec_cv.notify_one();
-            return dec_fail(c, PD_ENOMEM, "pinned batch buffer allocation failed");
-        }
-        sl->h_cap = want;
-    }
-    *host_buf = sl->h_blob;
-    return PD_OK;
-}
-
-} // extern "C"
-
-namespace {
-
-const bool g_dec_devtrace = getenv("PANDEPTH_DEVTRACE") != nullptr;  // (development: host-clock times at which a batch's stages were seen to end, a line per batch)
-const bool g_dec_timing = getenv("PANDEPTH_TIMING") != nullptr || g_dec_devtrace;     // the per-batch device events are recorded only when somebody reads them
-
-inline bool in_arena(const pd_ctx *c, const void *p) { return c->arena && (const uint8_t *)p >= c->arena && (const uint8_t *)p < c->arena + c->arena_cap; }
-
-// room for a batch's runs: the arena first, an allocation of its own when that is full
-bool dec_grab(pd_ctx *c, size_t bytes, void **out)
-{
-    bytes = (bytes + 255) & ~(size_t)255;
-    const size_t at = c->arena_used.fetch_add(bytes);
-    if (at + bytes <= c->arena_cap) { *out = c->arena + at; return true; }
-    if (hipMalloc(out, bytes) == hipSuccess) return true;
-    (void)hipGetLastError(); *out = nullptr;
-    return false;
-}
-
-// a compact batch's segments and event belong to the call that made them until c8_counted has taken them
-struct C8Segs {
-    pd_ctx *c; Run8 *seg_s = nullptr; pd_iv *seg_o = nullptr; hipEvent_t ev = nullptr; bool kept = false;
-    ~C8Segs()
-    {
-        if (kept) return;
-        if (seg_s && !in_arena(c, seg_s)) (void)hipFree(seg_s);
-        if (seg_o && !in_arena(c, seg_o)) (void)hipFree(seg_o);
-        if (ev) (void)hipEventDestroy(ev);
-    }
-};
-
-// every batch with an order below n_batches is counted exactly once, whatever way its calls end; a batch that had something queued
-// and is counted empty through an error path leaves the session in error (its totals would silently disagree with the file)
-struct C8Owes {
-    pd_ctx *c; pd_ctx::DecSlot::Job *j; bool armed = true;
-    ~C8Owes()
-    {
-        if (!armed || !j->owes_count) return;
-        j->owes_count = false;
-        if (j->queued) { std::lock_guard<std::mutex> lk(c->c8.mu); if (c->c8.err.empty()) c->c8.err = "a batch of the session failed on the device"; }
-        c8_counted(c, j->order, 0, 0, nullptr, nullptr, nullptr);
-    }
-};
-
-// ---- first half: everything the batch needs is put on the slot's stream; nothing is waited for -------------------------------------
-int dec_queue(pd_ctx *c, pd_ctx::DecSlot &sl, const pd_decode_batch *bt)
-{
-    pd_ctx::DecSlot::Job &J = sl.job;                                 // (claimed by dec_slot_of: J.open is set)
-    J.queued = false; J.fast = false; J.timed = false; J.t_q0 = dec_now_us(); J.order = bt->order; J.n_bytes = bt->n_bytes; J.inflated = bt->inflated_bytes; J.n_seg = 0;
-    J.blocks.clear(); J.units.clear(); J.segs.clear(); J.seg0.clear();
-    const bool c8 = J.c8 = c->c8.on;
-    J.owes_count = c8 && bt->order < c->c8.n_batches;
-    C8Owes owes{c, &J};
-    if (c8 && bt->order >= c->c8.n_batches && bt->n_units) return dec_fail(c, PD_EINVAL, "pd_decode_submit: batch order outside [0, n_batches) of this session");
-    if (!bt->n_units || !bt->n_blocks) return PD_OK;                  // (nothing to decode: the order is counted, empty)
-    if (!bt->units || !bt->blocks) return dec_fail(c, PD_EINVAL, "pd_decode_submit: a batch with units needs its unit and member tables");
-    if (bt->n_bytes + 64 > sl.h_cap) return dec_fail(c, PD_EINVAL, "pd_decode_submit: more bytes than were acquired");
-    HIPDEC(hipSetDevice(c->device));
-    uint64_t dq[8] = {}; int dqn = 0;                                  // (PANDEPTH_DEVTRACE: where the call's own time goes, first batches)
-    auto dq_mark = [&]() { if (g_dec_devtrace && dqn < 8) dq[dqn++] = dec_now_us(); };
-    dq_mark();
-    if (!sl.st) {
-        HIPDEC(hipStreamCreateWithFlags(&sl.st, hipStreamNonBlocking));
-        for (auto &e : sl.ev) HIPDEC(hipEventCreate(&e));
-        HIPDEC(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
-    }
-    J.units.assign(bt->units, bt->units + bt->n_units);
-    J.blocks.assign(bt->blocks, bt->blocks + bt->n_blocks);
-    // ---- segments of every unit (host) ----
-    std::vector<pdb2::Seg> &segs = J.segs;
-    J.seg0.assign(bt->n_units + 1, 0);
-    bool guess = false;
-    for (uint32_t u = 0; u < bt->n_units; ++u) {
-        const pd_decode_unit &un = J.units[u];
-        if (un.start > un.stop || un.start > un.avail || un.avail > bt->inflated_bytes || (uint64_t)un.first_block + un.n_blocks > bt->n_blocks)
-            return dec_fail(c, PD_EINVAL, "pd_decode_submit: unit outside the inflated buffer");
-        if (un.flags & PD_UNIT_GUESS) { guess = true; ++c->dec_n[pd_ctx::DN_GUESS]; }
-        J.seg0[u] = (uint32_t)segs.size();
-        for (uint64_t b = un.start; b < un.stop; b += pdb2::SEG_BYTES) {
-            pdb2::Seg sg; memset(&sg, 0, sizeof sg);
-            sg.begin = b; sg.end = std::min<uint64_t>(b + pdb2::SEG_BYTES, un.stop); sg.avail = un.avail;
-            sg.unit_first = b == un.start;
-            sg.hint = (b == un.start && !(un.flags & PD_UNIT_GUESS)) ? un.start : pdb2::NONE;
-            segs.push_back(sg);
-        }
-    }
-    J.seg0[bt->n_units] = (uint32_t)segs.size();
-    for (uint32_t b = 0; b < bt->n_blocks; ++b)
-        if (J.blocks[b].in_off + J.blocks[b].in_len + 8 > bt->n_bytes + 8 || J.blocks[b].out_off + J.blocks[b].out_len > bt->inflated_bytes)
-            return dec_fail(c, PD_EINVAL, "pd_decode_submit: block outside its buffer");
-    const uint32_t n_seg = J.n_seg = (uint32_t)segs.size();
-    if (!n_seg) return PD_OK;
-    // The device confirms the record chain itself — no host round trip between the two passes — in sessions whose units all start at
-    // known records (index cuts and index chunks: everything but no-index streams).  A kept read has at least one CIGAR operation, so its record is at least 41 bytes (4 + 32 fixed, a name of
-    // one byte, one operation): inflated / 41 first runs is a bound, not an estimate.  Later runs are bounded only by the CIGAR bytes;
-    // the same number of slots (several times what real reads need) is given and the chain kernel checks that they suffice.
-    J.fast = c->dec_fast && !guess && (c8 || c->dec_near_span == 0xFFFFFFFFu);      // (every session whose units start at known records and whose later runs are one stream)
-    J.cap_first = J.fast ? bt->inflated_bytes / 41 + 64 : 0;
-    J.cap_other = J.fast ? bt->inflated_bytes / c->dec_oth_div.load() + 64 : 0;
-    // (the inflate kernel's LDS lets 20 one-wave workgroups share a CU; "inflate_waves": fewer per launch, so that several batches' launches share the GPU)
-    const unsigned n_wg = (unsigned)c->n_cu * c->dec_waves;
-    int rc;
-    dq_mark();
-    J.t_mark = dec_now();
-    auto lap = [&](int k) { const uint64_t n = dec_now(); g_dec_us[k] += n - J.t_mark; J.t_mark = n; };
-    // The batch's small tables travel through a page-locked staging area of the slot — an "asynchronous" copy from or to pageable memory
-    // is staged by the runtime on the calling thread, under a lock all streams share — and since round 5 as ONE copy each way: members,
-    // segments and the (zeroed) member counter go up together into one device buffer laid out the same way; ChainOut + the segments'
-    // keys (or, on the host's path, the member statuses and the segments) come back together.
-    const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    J.o_blk = 0; J.o_seg = J.o_blk + al((size_t)bt->n_blocks * sizeof(pd_bgzf_block)); J.o_next = J.o_seg + al((size_t)n_seg * sizeof(pdb2::Seg)); J.o_up = J.o_next + 256;
-    J.o_bst = J.o_up; J.o_co = J.o_bst + al((size_t)bt->n_blocks * 4); J.o_so = J.o_co + sizeof(pdb2::ChainOut);
-    J.o_ord = J.o_so + al((size_t)n_seg * sizeof(pdb2::SegOut));
-    const size_t small_need = J.o_ord + 256;
-    // the tables behind the members in the caller's (page-locked) buffer when it has the room: one host-to-device copy per batch instead of two
-    const size_t tab_at = (bt->n_bytes + 64 + 255) & ~(size_t)255;
-    const bool one_copy = c->dec_h2d_kernel == 0 && c->dec_h2d_fifo && tab_at + J.o_up <= sl.h_cap;
-    if ((rc = dec_ensure(c, sl, DS_BLOB, one_copy ? tab_at + J.o_up : bt->n_bytes + 64)) || (rc = dec_ensure(c, sl, DS_INF, (size_t)bt->inflated_bytes + 256)) ||
-        (rc = dec_ensure(c, sl, DS_BLK, J.o_up)) || (rc = dec_ensure(c, sl, DS_ST, (size_t)bt->n_blocks * 4 + 16)) ||
-        (rc = dec_ensure(c, sl, DS_LANE, (size_t)n_seg * 64 * sizeof(pdb2::LaneOut))) ||
-        (rc = dec_ensure(c, sl, DS_ONLY, (size_t)n_seg * 4 + 16)) || ((c8 || J.fast) && (rc = dec_ensure(c, sl, DS_SEGOUT, sizeof(pdb2::ChainOut) + (size_t)n_seg * sizeof(pdb2::SegOut)))) ||
-        (J.fast && ((rc = dec_ensure(c, sl, DS_R8, (size_t)J.cap_first * (c8 ? sizeof(Run8) : sizeof(pd_iv)))) || (rc = dec_ensure(c, sl, DS_OTH, (size_t)J.cap_other * sizeof(pd_iv)))))) return rc;
-    if (!sl.d_tok || sl.tok_wg < n_wg) {
-        // (the scratch is indexed by workgroup: "inflate_waves" may have been raised since it was sized)
-        std::lock_guard<std::mutex> al2(g_alloc_mu);
-        if (sl.d_tok) { HIPDEC(hipStreamSynchronize(sl.st)); HIPDEC(hipFree(sl.d_tok)); sl.d_tok = nullptr; sl.tok_wg = 0; }
-        if (hipMalloc(&sl.d_tok, bgzf_wave_scratch_bytes(n_wg)) != hipSuccess) { (void)hipGetLastError(); return dec_fail(c, PD_ENOMEM, "device-decode scratch allocation failed"); }
-        sl.tok_wg = n_wg;
-    }
-    if (small_need > sl.h_small_cap) {
-        std::lock_guard<std::mutex> al2(g_alloc_mu);
-        if (sl.h_small) { HIPDEC(hipStreamSynchronize(sl.st)); (void)hipHostFree(sl.h_small); sl.h_small = nullptr; sl.h_small_cap = 0; }
-        const size_t want = small_need + small_need / 4 + 4096;
-        if (hipHostMalloc((void **)&sl.h_small, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return dec_fail(c, PD_ENOMEM, "pinned staging allocation failed"); }
-        sl.h_small_cap = want;
-    }
-    uint8_t *const pin = sl.h_small;
-    lap(2);                                                               // device buffers
-    hipStream_t st = sl.st;
-    dq_mark();
-    uint8_t *d_blob = (uint8_t *)sl.d[DS_BLOB], *d_inf = (uint8_t *)sl.d[DS_INF], *d_tab = one_copy ? (uint8_t *)sl.d[DS_BLOB] + tab_at : (uint8_t *)sl.d[DS_BLK];
-    J.d_tab = d_tab;
-    pdb2::Seg *d_seg = (pdb2::Seg *)(d_tab + J.o_seg);
-    pdb2::LaneOut *d_lane = (pdb2::LaneOut *)sl.d[DS_LANE];
-    pdb2::Cfg &cfg = J.cfg;
-    cfg = pdb2::Cfg{};
-    cfg.buf = d_inf; cfg.avail = bt->inflated_bytes; cfg.n_ref = c->n_contigs; cfg.contig_len = c->d_len; cfg.contig_on = c->d_contig_on;
-    cfg.flag_mask = c->dec_cfg.flag_mask; cfg.min_mapq = c->dec_cfg.min_mapq; cfg.span_off = c->d_span_off; cfg.spans = c->d_spans;
-    cfg.near_span = c8 ? 0xFFFFFFFFu : c->dec_near_span;                   // (a compact session has one stream of later runs)
-    cfg.c8 = pdb2::C8Out{};
-    // ---- H2D, inflate, pass 1 ----
-    // (from here on the device may be reading the caller's buffer and the slot's staging area: a call that fails half way waits for
-    // what it has queued before the slot goes back)
-    struct Settle { hipStream_t st; bool armed = true; ~Settle() { if (armed) (void)hipStreamSynchronize(st); } } settle{st};
-    J.timed = g_dec_timing;
-    memset((uint8_t *)bt->host_buf + bt->n_bytes, 0, 64);                  // (the decoder reads up to 8 bytes past a member's end)
-    uint8_t *const up = one_copy ? (uint8_t *)bt->host_buf + tab_at : pin;    // where the tables are put together
-    memcpy(up + J.o_blk, J.blocks.data(), (size_t)bt->n_blocks * sizeof(pd_bgzf_block));
-    memcpy(up + J.o_seg, segs.data(), (size_t)n_seg * sizeof(pdb2::Seg));
-    memset(up + J.o_next, 0, 256);
-    // ("decode_h2d_kernel": the copy engine's transfer and the kernel behind it are ordered by a signal between two engines — 2.2 ms of idle queue per
-    // batch in profiles/r05_decode_timeline.txt; a copy kernel reads the pinned bytes over the link itself and the inflate kernel follows it in the same queue)
-    // (3: no copy at all — the inflate kernel reads the members straight out of the pinned buffer, which the slot holds until the batch is collected)
-    if (c->dec_h2d_kernel == 0 && c->dec_h2d_fifo) {
-        // ONE batch's bytes on the link at a time, in the order the batches were queued (round 6).  Copies issued on the batches' own streams share the
-        // link: six readers that happen to queue together get their bytes together, six times later than the first of them could have had them, their
-        // kernels then share the GPU and finish together, and the readers come back together — a convoy in which reading, copying and decoding take
-        // turns instead of overlapping (tools/feeder_trace.py, profiles/r06_feeder_trace.txt: 1.25-1.35 ms per batch whatever the readers x buffers).
-        // First come, first served, the first batch decodes while the second is on the link.  The copies ride on the context's main stream, which has
-        // nothing else to do while a file is decoded (a stream of their own would be one more hardware queue to make: 10 ms).
-        std::lock_guard<std::mutex> lk(c->dec_copy_mu);
-        hipStream_t cs = c->stream;
-        if (c->dec_h2d_lanes > 1 && (c->dec_copy_seq++ & 1)) {
-            if (!c->dec_copy_st2) HIPDEC(hipStreamCreateWithFlags(&c->dec_copy_st2, hipStreamNonBlocking));
-            cs = c->dec_copy_st2;
-        }
-        if (J.timed) HIPDEC(hipEventRecord(sl.ev[0], cs));
-        if (one_copy) HIPDEC(hipMemcpyAsync(d_blob, bt->host_buf, tab_at + J.o_up, hipMemcpyHostToDevice, cs));
-        else {
-            HIPDEC(hipMemcpyAsync(d_tab, pin, J.o_up, hipMemcpyHostToDevice, cs));
-            HIPDEC(hipMemcpyAsync(d_blob, bt->host_buf, bt->n_bytes + 64, hipMemcpyHostToDevice, cs));
-        }
-        if (J.timed) HIPDEC(hipEventRecord(sl.ev[1], cs));
-        HIPDEC(hipEventRecord(sl.ev[5], cs));
-        HIPDEC(hipStreamWaitEvent(st, sl.ev[5], 0));
-    } else {
-        if (J.timed) HIPDEC(hipEventRecord(sl.ev[0], st));
-        if (c->dec_h2d_kernel == 3) d_blob = (uint8_t *)bt->host_buf;
-        else if (c->dec_h2d_kernel) launch_copy_words(st, d_blob, bt->host_buf, (bt->n_bytes + 64 + 3) / 4);
-        else HIPDEC(hipMemcpyAsync(d_blob, bt->host_buf, bt->n_bytes + 64, hipMemcpyHostToDevice, st));
-        if (c->dec_h2d_kernel >= 2) launch_copy_words(st, d_tab, pin, (J.o_up + 3) / 4);
-        else HIPDEC(hipMemcpyAsync(d_tab, pin, J.o_up, hipMemcpyHostToDevice, st));
-        if (J.timed) HIPDEC(hipEventRecord(sl.ev[1], st));
-    }
-    dq_mark();
-    launch_bgzf_inflate_wave(st, d_blob, (const pd_bgzf_block *)(d_tab + J.o_blk), bt->n_blocks, d_inf, (int *)sl.d[DS_ST], sl.d_tok, n_wg, c->dec_crc,
-                             (uint32_t *)(d_tab + J.o_next), false);
-    dq_mark();
-    if (J.timed) HIPDEC(hipEventRecord(sl.ev[2], st));
-    launch_walk_segments(st, cfg, d_seg, n_seg, d_lane, nullptr, 0);
-    if (c->dec_spoil) launch_spoil_segments(st, cfg, d_seg, n_seg, d_lane, c->dec_spoil);     // (test hook)
-    if (J.fast) {
-        pd_ctx::C8Dec &x = c->c8;
-        pdb2::ChainOut *d_co = (pdb2::ChainOut *)sl.d[DS_SEGOUT];
-        launch_chain_segments(st, cfg, d_seg, n_seg, d_lane, (const int *)sl.d[DS_ST], bt->n_blocks, J.cap_first, J.cap_other, c->dec_max_redo, d_co);
-        if (J.timed) HIPDEC(hipEventRecord(sl.ev[3], st));
-        pdb2::Cfg c2 = cfg;
-        if (c8) c2.c8 = pdb2::C8Out{(pdb2::R8 *)sl.d[DS_R8], x.marks, c->d_off, 13u - x.bshift, (pdb2::SegOut *)(d_co + 1), (uint32_t)bt->order};
-        else { c2.c8 = pdb2::C8Out{}; c2.c8.seg_out = (pdb2::SegOut *)(d_co + 1); }      // (12-byte runs; the order keys ride along)
-        launch_emit_segments(st, c2, d_seg, n_seg, d_lane, c8 ? nullptr : (pd_iv *)sl.d[DS_R8], (pd_iv *)sl.d[DS_OTH], nullptr, d_co);
-        HIPDEC(hipMemcpyAsync(pin + J.o_co, d_co, sizeof(pdb2::ChainOut) + (size_t)n_seg * sizeof(pdb2::SegOut), hipMemcpyDeviceToHost, st));
-        if (J.timed) HIPDEC(hipEventRecord(sl.ev[4], st));
-    } else {
-        HIPDEC(hipMemcpyAsync(pin + J.o_bst, sl.d[DS_ST], (size_t)bt->n_blocks * 4, hipMemcpyDeviceToHost, st));
-        HIPDEC(hipMemcpyAsync(pin + J.o_seg, d_seg, (size_t)n_seg * sizeof(pdb2::Seg), hipMemcpyDeviceToHost, st));
-        if (J.timed) HIPDEC(hipEventRecord(sl.ev[3], st));
-    }
-    // (what the collecting call waits for.  hipStreamSynchronize would put a marker of its own into the stream's HARDWARE queue at the time of the call — and
-    // the process's streams share eight of those: the marker landed behind whatever another batch's stream had in the same queue, and a batch that had long
-    // finished was "collected" 2 ms later, when the other batch was through: tools/calls/r6_call14.sh, profiles/r06_devtrace.txt)
-    HIPDEC(hipEventRecord(sl.ev_done, st));
-    HIPDEC(hipGetLastError());
-    dq_mark();
-    if (g_dec_devtrace && bt->order < 14)
-        fprintf(stderr, "[devtrace] batch %llu pd_decode_queue: stream + events + segments %llu us, buffers %llu, copies issued %llu, inflate launched %llu, the rest launched %llu\n", (unsigned long long)bt->order,
-                (unsigned long long)(dq[1] - dq[0]), (unsigned long long)(dq[2] - dq[1]), (unsigned long long)(dq[3] - dq[2]), (unsigned long long)(dq[4] - dq[3]), (unsigned long long)(dq[5] - dq[4]));
-    J.queued = true; J.t_q1 = dec_now_us();
-    owes.armed = false;                                                   // (the second half counts the order)
-    settle.armed = false;
-    return PD_OK;
-}
-
-// ---- second half: wait for the batch, finish it, report what pd_decode_submit reports ------------------------------------------------
-int dec_collect(pd_ctx *c, pd_ctx::DecSlot &sl, int32_t *unit_status, pd_decode_result *res)
-{
-    pd_ctx::DecSlot::Job &J = sl.job;                                 // (J.open goes with the slot: dec_release)
-    if (res) { memset(res, 0, sizeof *res); res->first_start = res->next_start = ~0ull; }
-    const uint32_t n_units = (uint32_t)J.units.size(), n_blocks = (uint32_t)J.blocks.size(), n_seg = J.n_seg;
-    if (unit_status) for (uint32_t u = 0; u < n_units; ++u) unit_status[u] = 0;
-    C8Owes owes{c, &J};
-    if (!J.queued) return PD_OK;
-    if (!unit_status) return dec_fail(c, PD_EINVAL, "pd_decode_collect: unit_status is required for a batch with units");
-    const bool c8 = J.c8;
-    std::vector<pdb2::Seg> &segs = J.segs;
-    const std::vector<uint32_t> &seg0 = J.seg0;
-    HIPDEC(hipSetDevice(c->device));
-    hipStream_t st = sl.st;
-    uint8_t *const pin = sl.h_small;
-    uint8_t *d_tab = J.d_tab ? J.d_tab : (uint8_t *)sl.d[DS_BLK];
-    pdb2::Seg *d_seg = (pdb2::Seg *)(d_tab + J.o_seg);
-    pdb2::LaneOut *d_lane = (pdb2::LaneOut *)sl.d[DS_LANE];
-    pdb2::SegOut *d_so = c8 ? (pdb2::SegOut *)((uint8_t *)sl.d[DS_SEGOUT] + sizeof(pdb2::ChainOut)) : nullptr;
-    pdb2::Cfg cfg = J.cfg;
-    J.t_mark = dec_now();
-    auto lap = [&](int k) { const uint64_t n = dec_now(); g_dec_us[k] += n - J.t_mark; J.t_mark = n; };
-    if (g_dec_devtrace && J.timed) {
-        uint64_t t[6] = {};
-        for (int k = 0; k < 5; ++k) { if (k < 4 || J.fast) (void)hipEventSynchronize(sl.ev[k]); t[k] = dec_now_us(); }
-        (void)hipEventSynchronize(sl.ev_done); t[5] = dec_now_us();
-        fprintf(stderr, "[devtrace] batch %llu queue call %llu us; since its start: collect entered %llu, copy begun %llu, copied %llu, inflated %llu, walked %llu, emitted %llu, stream idle %llu\n",
-                (unsigned long long)J.order, (unsigned long long)(J.t_q1 - J.t_q0), (unsigned long long)(J.t_mark - J.t_q0), (unsigned long long)(t[0] - J.t_q0), (unsigned long long)(t[1] - J.t_q0),
-                (unsigned long long)(t[2] - J.t_q0), (unsigned long long)(t[3] - J.t_q0), (unsigned long long)(t[4] - J.t_q0), (unsigned long long)(t[5] - J.t_q0));
-    }
-    HIPDEC(c->dec_sync_event ? hipEventSynchronize(sl.ev_done) : hipStreamSynchronize(st));
-    HIPDEC(hipGetLastError());
-    lap(3);                                                               // waiting for the device
-    auto times = [&](bool emitted) {
-        if (!res || !J.timed) return;
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, sl.ev[0], sl.ev[1]) == hipSuccess) res->ms_h2d = ms;
-        if (hipEventElapsedTime(&ms, sl.ev[1], sl.ev[2]) == hipSuccess) res->ms_inflate = ms;
-        if (hipEventElapsedTime(&ms, sl.ev[2], sl.ev[3]) == hipSuccess) res->ms_walk = ms;
-        if (emitted && hipEventElapsedTime(&ms, sl.ev[3], sl.ev[4]) == hipSuccess) res->ms_emit = ms;
-    };
-    // the order of a compact batch's first runs across its segments (inside a lane and across the lanes of a segment the emission checked it)
-    auto order_of = [&](const pdb2::SegOut *so, pd_ctx::RunSeg *rs) {
-        uint64_t prev = 0, first = pdb2::NONE, n_long = 0; uint32_t bad = 0;
-        for (uint32_t j = 0; j < n_seg; ++j) {
-            bad |= so[j].unsorted; n_long += so[j].n_long;
-            if (so[j].first_key == pdb2::NONE) continue;
-            if (first == pdb2::NONE) first = so[j].first_key; else if (so[j].first_key < prev) bad = 1;
-            prev = so[j].last_key;
-        }
-        rs->unsorted = bad ? 1u : 0u; rs->first_key = first; rs->last_key = prev; rs->n_long = n_long;
-    };
-    if (J.fast) {
-        pdb2::ChainOut co;
-        memcpy(&co, pin + J.o_co, sizeof co);
-        c->dec_n_redo += co.n_redo;
-        if (!co.slow) {
-            // ---- the device has confirmed the chain and written the runs to the slot's arrays: exact arrays for them, copied behind the
-            // emission on this stream (the slot's arrays are free again when its next batch gets there), and the batch is counted
-            ++c->dec_n_fast;
-            const uint64_t nf = co.n_first, no = co.n_other;
-            pd_ctx::RunSeg rs{J.order, nullptr, nf, nullptr, no, nullptr, 0, co.max_span, 0u, 0ull, 0ull};
-            if (!c8) {
-                // 12-byte runs (every mode that needs the arrays): exact arrays from the arena, the batch listed for pd_decode_end
-                struct Guard { pd_ctx *c; pd_ctx::RunSeg *r; bool keep = false;
-                               ~Guard() { if (keep) return; for (pd_iv *q : {r->first, r->other}) if (q && !in_arena(c, q)) (void)hipFree(q); } } guard{c, &rs};
-                if (nf + no) {
-                    if ((nf && !dec_grab(c, (size_t)nf * sizeof(pd_iv), (void **)&rs.first)) || (no && !dec_grab(c, (size_t)no * sizeof(pd_iv), (void **)&rs.other)))
-                        return dec_fail(c, PD_ENOMEM, "run array allocation failed");
-                    if (nf) launch_copy_words(st, rs.first, sl.d[DS_R8], nf * (sizeof(pd_iv) / 4));
-                    if (no) launch_copy_words(st, rs.other, sl.d[DS_OTH], no * (sizeof(pd_iv) / 4));
-                    HIPDEC(hipGetLastError());                       // (pd_decode_end waits for the slots' streams before it reads these arrays)
-                    order_of((const pdb2::SegOut *)(pin + J.o_so), &rs);
-                    rs.n_long = 0;
-                }
-                if (res) { res->n_first = nf; res->n_other = no; res->n_reads = co.n_rec; res->unsorted = rs.unsorted; res->first_key = rs.first_key; res->last_key = rs.last_key;
-                           res->first_start = co.first_start; res->next_start = co.next_start; }
-                times(true);
-                lap(5);
-                if (nf + no) { std::lock_guard<std::mutex> lk(c->dec_mu); c->run_segs.push_back(rs); }
-                guard.keep = true;
-                return PD_OK;
-            }
-            C8Segs g{c};
-            if (nf + no) {
-                if ((nf && !dec_grab(c, (size_t)nf * sizeof(Run8), (void **)&g.seg_s)) || (no && !dec_grab(c, (size_t)no * sizeof(pd_iv), (void **)&g.seg_o)) ||
-                    hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return dec_fail(c, PD_ENOMEM, "run segment allocation failed"); }
-                if (nf) launch_copy_words(st, g.seg_s, sl.d[DS_R8], nf * (sizeof(Run8) / 4));
-                if (no) launch_copy_words(st, g.seg_o, sl.d[DS_OTH], no * (sizeof(pd_iv) / 4));
-                HIPDEC(hipGetLastError());
-                HIPDEC(hipEventRecord(g.ev, st));
-            }
-            J.owes_count = false; g.kept = true;
-            c8_counted(c, J.order, nf, no, g.seg_s, g.seg_o, g.ev);
-            if (nf + no) order_of((const pdb2::SegOut *)(pin + J.o_so), &rs);
-            if (res) { res->n_first = nf; res->n_other = no; res->n_reads = co.n_rec; res->unsorted = rs.unsorted; res->first_key = rs.first_key; res->last_key = rs.last_key;
-                       res->first_start = co.first_start; res->next_start = co.next_start; }
-            times(true);
-            lap(5);
-            if (nf + no) { std::lock_guard<std::mutex> lk(c->dec_mu); c->run_segs.push_back(rs); }
-            return PD_OK;
-        }
-        // ---- out of the ordinary (ChainOut::slow says why; nothing was emitted): the member statuses and the segments as they stand come
-        // to the host, which goes through the batch the way it always has
-        ++c->dec_n_slow;
-        // (more later runs than the batch's array holds — reads with thousands of CIGAR operations: the batches queued from now on get
-        // a slot per 8 inflated bytes, which an alternation of matches and gaps cannot exceed)
-        if ((co.slow & pdb2::CH_ROOM) && co.n_first <= J.cap_first) c->dec_oth_div.store(8);
-        HIPDEC(hipMemcpyAsync(pin + J.o_bst, sl.d[DS_ST], (size_t)n_blocks * 4, hipMemcpyDeviceToHost, st));
-        HIPDEC(hipMemcpyAsync(pin + J.o_seg, d_seg, (size_t)n_seg * sizeof(pdb2::Seg), hipMemcpyDeviceToHost, st));
-        HIPDEC(hipStreamSynchronize(st));
-    }
-    if (!J.fast) ++c->dec_n_slow;
-    std::vector<int> bst(n_blocks);
-    memcpy(bst.data(), pin + J.o_bst, (size_t)n_blocks * 4);
-    memcpy(segs.data(), pin + J.o_seg, (size_t)n_seg * sizeof(pdb2::Seg));
-    // ---- the chain across segments; segments whose guess was wrong walk again from the corrected start ----
-    std::vector<uint32_t> redo;
-    for (int round = 0; dec_finish(segs, &redo) > 0; ++round) {
-        if (round >= 24) { for (uint32_t j : redo) segs[j].flags |= pdb2::WF_BAD; break; }
-        for (uint32_t j : redo) HIPDEC(hipMemcpyAsync(&d_seg[j].hint, &segs[j].hint, 8, hipMemcpyHostToDevice, st));
-        HIPDEC(hipMemcpyAsync(sl.d[DS_ONLY], redo.data(), redo.size() * 4, hipMemcpyHostToDevice, st));
-        launch_walk_segments(st, cfg, d_seg, n_seg, d_lane, (const uint32_t *)sl.d[DS_ONLY], (uint32_t)redo.size());
-        HIPDEC(hipMemcpyAsync(pin + J.o_seg, d_seg, (size_t)n_seg * sizeof(pdb2::Seg), hipMemcpyDeviceToHost, st));
-        HIPDEC(hipStreamSynchronize(st));
-        memcpy(segs.data(), pin + J.o_seg, (size_t)n_seg * sizeof(pdb2::Seg));
-    }
-    // ---- unit outcomes; units handed back emit nothing ----
-    uint64_t nf = 0, no = 0, nfar = 0, nrec = 0; uint32_t max_span = 0;
-    for (uint32_t u = 0; u < n_units; ++u) {
-        int stt = 0;
-        const pd_decode_unit &un = J.units[u];
-        for (uint32_t b = 0; b < un.n_blocks; ++b) { const int v = bst[un.first_block + b]; if (v < 0) stt = 2; else if (v > 0 && stt == 0) stt = 1; }
-        for (uint32_t j = seg0[u]; j < seg0[u + 1]; ++j) {
-            if (segs[j].flags & pdb2::WF_BAD) { if (stt != 2) stt = 3; }
-            else if ((segs[j].flags & (pdb2::WF_MORE | pdb2::WF_HOST)) && stt == 0) stt = 1;
-        }
-        unit_status[u] = stt;
-        for (uint32_t j = seg0[u]; j < seg0[u + 1]; ++j) {
-            if (stt) { segs[j].n_first = segs[j].n_other = segs[j].n_far = 0; } else nrec += segs[j].n_rec;
-            segs[j].base_first = nf; segs[j].base_other = no; segs[j].base_far = nfar;
-            nf += segs[j].n_first; no += segs[j].n_other; nfar += segs[j].n_far;
-            if (!stt && segs[j].max_span > max_span) max_span = segs[j].max_span;
-        }
-    }
-    if (res) {
-        res->n_first = nf; res->n_other = no + nfar; res->n_reads = nrec;
-        uint64_t fs = ~0ull, E = 0;
-        for (uint32_t j = seg0[0]; j < seg0[1]; ++j) { if (fs == ~0ull && segs[j].used_start != pdb2::NONE) fs = segs[j].used_start; if (segs[j].e_last > E) E = segs[j].e_last; }
-        res->first_start = fs; res->next_start = E ? E : ~0ull;
-    }
-    // ---- pass 2: the runs ----
-    pd_ctx::RunSeg rs{J.order, nullptr, nf, nullptr, no, nullptr, nfar, max_span, 0u, 0ull, 0ull};
-    // run arrays taken outside the arena belong to this call until the batch is listed: every early return gives them back
-    struct RunGuard {
-        pd_ctx *c; pd_ctx::RunSeg *r; bool keep = false;
-        ~RunGuard() { if (keep) return; for (pd_iv *q : {r->first, r->other, r->far}) if (q && !in_arena(c, q)) (void)hipFree(q); }
-    } run_guard{c, &rs};
-    lap(4);                                                               // host: chain check, unit outcomes
-    bool have_so = false;
-    if (c8) {
-        // compact session: pass 2 writes the batch's first runs as 8-byte runs into a segment of its own and marks the buckets' first runs;
-        // c8_counted then queues the copies to the runs' final places for every batch whose predecessors are all counted
-        pd_ctx::C8Dec &x = c->c8;
-        C8Segs g{c};
-        if (nf + no) {
-            if ((nf && !dec_grab(c, (size_t)nf * sizeof(Run8), (void **)&g.seg_s)) || (no && !dec_grab(c, (size_t)no * sizeof(pd_iv), (void **)&g.seg_o)) ||
-                hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return dec_fail(c, PD_ENOMEM, "run segment allocation failed"); }
-            memcpy(pin + J.o_seg, segs.data(), (size_t)n_seg * sizeof(pdb2::Seg));
-            HIPDEC(hipMemcpyAsync(d_seg, pin + J.o_seg, (size_t)n_seg * sizeof(pdb2::Seg), hipMemcpyHostToDevice, st));
-            cfg.c8 = pdb2::C8Out{(pdb2::R8 *)g.seg_s, x.marks, c->d_off, 13u - x.bshift, d_so, (uint32_t)J.order};
-            launch_emit_segments(st, cfg, d_seg, n_seg, d_lane, nullptr, g.seg_o, nullptr, nullptr);
-            HIPDEC(hipEventRecord(g.ev, st));
-        }
-        J.owes_count = false; g.kept = true;
-        c8_counted(c, J.order, nf, no, g.seg_s, g.seg_o, g.ev);
-        if (nf + no) {
-            have_so = true;
-            HIPDEC(hipMemcpyAsync(pin + J.o_so, d_so, (size_t)n_seg * sizeof(pdb2::SegOut), hipMemcpyDeviceToHost, st));
-        }
-        lap(5);
-    } else if (nf + no + nfar) {
-        if ((nf && !dec_grab(c, (size_t)nf * sizeof(pd_iv), (void **)&rs.first)) || (no && !dec_grab(c, (size_t)no * sizeof(pd_iv), (void **)&rs.other)) ||
-            (nfar && !dec_grab(c, (size_t)nfar * sizeof(pd_iv), (void **)&rs.far))) return dec_fail(c, PD_ENOMEM, "run array allocation failed");
-        memcpy(pin + J.o_seg, segs.data(), (size_t)n_seg * sizeof(pdb2::Seg));
-        HIPDEC(hipMemcpyAsync(d_seg, pin + J.o_seg, (size_t)n_seg * sizeof(pdb2::Seg), hipMemcpyHostToDevice, st));
-        lap(5);                                                           // run array allocation
-        launch_emit_segments(st, cfg, d_seg, n_seg, d_lane, rs.first, rs.other, rs.far, nullptr);
-    }
-    // are the first runs in (tid, begin) order, as the header's SO:coordinate promises?  (DS_ONLY is free again: 6 words)
-    uint32_t order_words[6] = {0, 0, 0, 0, 0, 0};
-    if (nf && !c8) {
-        HIPDEC(hipMemsetAsync(sl.d[DS_ONLY], 0, 24, st));
-        launch_runs_sorted(st, rs.first, nf, (uint32_t *)sl.d[DS_ONLY]);
-        HIPDEC(hipMemcpyAsync(pin + J.o_ord, sl.d[DS_ONLY], 24, hipMemcpyDeviceToHost, st));
-    }
-    if (J.timed) HIPDEC(hipEventRecord(sl.ev[4], st));
-    HIPDEC(hipStreamSynchronize(st));
-    HIPDEC(hipGetLastError());
-    if (nf && !c8) {
-        memcpy(order_words, pin + J.o_ord, 24);
-        rs.unsorted = order_words[0];
-        rs.first_key = (uint64_t)order_words[2] | ((uint64_t)order_words[3] << 32);
-        rs.last_key = (uint64_t)order_words[4] | ((uint64_t)order_words[5] << 32);
-    }
-    if (have_so) order_of((const pdb2::SegOut *)(pin + J.o_so), &rs);
-    if (res) { res->unsorted = rs.unsorted; res->first_key = rs.first_key; res->last_key = rs.last_key; }
-    lap(6);                                                               // pass 2 (waiting)
-    times(!J.fast);
-    if (nf + no + nfar) { std::lock_guard<std::mutex> lk(c->dec_mu); c->run_segs.push_back(rs); }
-    run_guard.keep = true;
-    return PD_OK;
-}
-
-pd_ctx::DecSlot *dec_slot_of(pd_ctx *c, const void *host_buf)
-{
-    // (other feeders may be in pd_decode_acquire, re-allocating THEIR slots' pinned buffers: look the slot up under the lock)
-    std::lock_guard<std::mutex> l0(c->dec_mu);
-    for (auto &x : c->dec) if (x.busy && !x.job.open && x.h_blob == host_buf) { x.job.open = true; return &x; }      // (claimed: a batch is under way in this slot)
-    return nullptr;
-}
-void dec_release(pd_ctx *c, pd_ctx::DecSlot *s) { { std::lock_guard<std::mutex> l(c->dec_mu); s->busy = false; s->job.open = false; s->job.collecting = false; } c->dec_cv.notify_all(); }
-
-} // namespace
-
-extern "C" {
-
-int pd_decode_submit(pd_ctx *c, const pd_decode_batch *bt, int32_t *unit_status, pd_decode_result *res)
-{
-    if (!c || !bt || !bt->host_buf || !unit_status) return PD_EINVAL;
-    pd_ctx::DecSlot *slp = dec_slot_of(c, bt->host_buf);
-    if (!slp) return dec_fail(c, PD_EINVAL, "pd_decode_submit: buffer was not handed out by pd_decode_acquire");
-    struct Release { pd_ctx *c; pd_ctx::DecSlot *s; ~Release() { dec_release(c, s); } } rel{c, slp};
-    if (res) { memset(res, 0, sizeof *res); res->first_start = res->next_start = ~0ull; }
-    for (uint32_t u = 0; u < bt->n_units; ++u) unit_status[u] = 0;
-    // (a ticket of an earlier batch on this slot is stale from here on, and nobody else may collect or drain the batch about to be queued)
-    { std::lock_guard<std::mutex> l0(c->dec_mu); ++slp->gen; slp->job.collecting = true; }
-    const int rc = dec_queue(c, *slp, bt);
-    if (rc) return rc;
-    return dec_collect(c, *slp, unit_status, res);
-}
-
-int pd_decode_queue(pd_ctx *c, const pd_decode_batch *bt, uint64_t *ticket)
-{
-    if (!c || !bt || !bt->host_buf || !ticket) return PD_EINVAL;
-    *ticket = 0;
-    pd_ctx::DecSlot *slp = dec_slot_of(c, bt->host_buf);
-    if (!slp) return dec_fail(c, PD_EINVAL, "pd_decode_queue: buffer was not handed out by pd_decode_acquire");
-    const int rc = dec_queue(c, *slp, bt);
-    if (rc) { dec_release(c, slp); return rc; }
-    { std::lock_guard<std::mutex> l0(c->dec_mu); *ticket = ((uint64_t)++slp->gen << 8) | (uint64_t)(slp - c->dec + 1); }
-    return PD_OK;
-}
-
-int pd_decode_collect(pd_ctx *c, uint64_t ticket, int32_t *unit_status, pd_decode_result *res)
-{
-    if (!c) return PD_EINVAL;
-    const uint64_t k = ticket & 0xff;
-    pd_ctx::DecSlot *slp = k >= 1 && k <= (uint64_t)pd_ctx::N_DEC ? &c->dec[k - 1] : nullptr;
-    {
-        std::lock_guard<std::mutex> l0(c->dec_mu);
-        if (!slp || !slp->busy || !slp->job.open || slp->job.collecting || slp->gen != (uint32_t)(ticket >> 8)) slp = nullptr;
-        else slp->job.collecting = true;
-    }
-    if (!slp) return dec_fail(c, PD_EINVAL, "pd_decode_collect: not the ticket of a queued batch (or the batch is being collected already)");
-    struct Release { pd_ctx *c; pd_ctx::DecSlot *s; ~Release() { dec_release(c, s); } } rel{c, slp};
-    return dec_collect(c, *slp, unit_status, res);
-}
-
-// batches that were queued and never collected: finished here (pd_decode_end: they count) or waited for and dropped (pd_decode_abort)
-static void dec_drain(pd_ctx *c, bool finish)
-{
-    for (auto &sl : c->dec) {
-        bool mine = false;
-        // (a slot some thread is collecting, or is inside pd_decode_submit on, is left to that thread: the callers wait on dec_cv for it)
-        { std::lock_guard<std::mutex> lk(c->dec_mu); mine = sl.busy && sl.job.open && !sl.job.collecting; if (mine) sl.job.collecting = true; }
-        if (!mine) continue;
-        if (finish) { std::vector<int32_t> st(sl.job.units.size() + 1, 0); (void)dec_collect(c, sl, st.data(), nullptr); }
-        else { (void)hipSetDevice(c->device); if (sl.st) (void)hipStreamSynchronize(sl.st); C8Owes owes{c, &sl.job}; sl.job.queued = false; }
-        dec_release(c, &sl);
-    }
-}
-
-int pd_decode_end(pd_ctx *c)
-{
-    if (!c) return PD_EINVAL;
-    if (c->dec_warm.joinable()) c->dec_warm.join();
-    dec_drain(c, true);
-    {   // every batch has returned; wait for stragglers that still hold a slot
-        std::unique_lock<std::mutex> lk(c->dec_mu);
-        c->dec_cv.wait(lk, [&] { for (auto &x : c->dec) if (x.busy) return false; return true; });
-        c->dec_open = false;
-    }
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 0, "pd_decode_end")) return rs;
-    HIPOK(c, hipSetDevice(c->device));
-    for (auto &sl : c->dec) if (sl.st) HIPOK(c, hipStreamSynchronize(sl.st));      // (the last copies of the batches' runs to their arrays)
-    std::vector<pd_ctx::RunSeg> segs;
-    { std::lock_guard<std::mutex> l2(c->dec_mu); segs.swap(c->run_segs); }
-    std::sort(segs.begin(), segs.end(), [](const pd_ctx::RunSeg &a, const pd_ctx::RunSeg &b) { return a.order < b.order; });
-    uint64_t nf = 0, no = 0, nfar = 0; uint32_t span = 0;
-    for (auto &r : segs) { nf += r.n_first; no += r.n_other; nfar += r.n_far; if (r.max_span > span) span = r.max_span; }
-    auto in_arena = [&](const void *p) { return c->arena && (const uint8_t *)p >= c->arena && (const uint8_t *)p < c->arena + c->arena_cap; };
-    auto drop = [&]() { for (auto &r : segs) for (pd_iv *q : {r.first, r.other, r.far}) if (q && !in_arena(q)) (void)hipFree(q); };
-    if (c->run_first || c->run_other || c->run_far || c->dec_runs) {
-        // an earlier sample of this context (#.list: one file after another) may still be deferred on these arrays
-        int rf = flush_pending(c);
-        if (rf) { drop(); return rf; }
-        HIPOK(c, hipStreamSynchronize(c->stream));
-        for (pd_iv **q : {&c->run_first, &c->run_other, &c->run_far}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-        runs_free(c->dec_runs); c->dec_runs = nullptr;
-    }
-    if (c->c8.on) {
-        // ---- a compact session: the runs are where they belong already (or on their way there, on the compose stream) ----
-        pd_ctx::C8Dec &x = c->c8;
-        std::lock_guard<std::mutex> l8(x.mu);
-        x.on = false;
-        if (x.turn != x.n_batches || !x.err.empty()) {
-            const std::string why = x.err.empty() ? "not every batch of the compact session was submitted" : x.err;
-            (void)hipDeviceSynchronize(); c8_drop(c);
-            return fail(c, PD_ESTATE, "pd_decode_end: " + why);
-        }
-        bool ok_order = true; uint64_t prev = 0, n_long = 0; bool have = false;
-        for (auto &r : segs) {
-            n_long += r.n_long;
-            if (!r.n_first) continue;
-            if (r.unsorted || (have && r.first_key < prev)) ok_order = false;
-            prev = r.last_key; have = true;
-        }
-        if (getenv("PANDEPTH_TIMING"))
-            fprintf(stderr, "[timing]   decode entry points, thread-seconds: slot wait %.3f, pinned alloc %.3f, device buffers + queueing %.3f, waiting for the device %.3f, "
-                            "host chain check %.3f, runs to their arrays %.3f, wait emit (host's path) %.3f, first HIP call of the feeder threads %.3f; %zu batches; runs (compact session): %llu first, %llu later (span %u); "
-                            "chain confirmed on the device for %llu batches, by the host for %llu; segments the device walked again: %llu\n",
-                    g_dec_us[0] / 1e6, g_dec_us[1] / 1e6, g_dec_us[2] / 1e6, g_dec_us[3] / 1e6, g_dec_us[4] / 1e6, g_dec_us[5] / 1e6, g_dec_us[6] / 1e6, g_dec_us[7] / 1e6, segs.size(),
-                    (unsigned long long)x.n_s, (unsigned long long)x.n_o, span, (unsigned long long)c->dec_n_fast.load(), (unsigned long long)c->dec_n_slow.load(), (unsigned long long)c->dec_n_redo.load());
-        if (x.n_s + x.n_o == 0) { (void)hipStreamSynchronize(x.compose); c8_drop(c); return PD_OK; }
-        HIPOK(c, hipStreamSynchronize(x.compose));                 // every batch's runs have reached their places
-        if (ok_order && x.n_s && x.n_s + x.n_o <= DEV_BATCH_MAX && !c->pend.empty()) {
-            // the context holds other runs already (units the device handed back and the host decoded meanwhile, an earlier file of a list):
-            // they go into the arrays now, and the compact sample is pushed behind them like any other deferred batch
-            ++c->dec_n[pd_ctx::DN_END_PEND];
-            const int rf = flush_pending(c);
-            if (rf) { (void)hipDeviceSynchronize(); c8_drop(c); return rf; }
-        }
-        if (ok_order && x.n_s && c->pend.empty() && x.n_s + x.n_o <= DEV_BATCH_MAX) {
-            pd_runs *r = new pd_runs;
-            r->ctx = c; r->r8 = x.r8(); r->own_r8 = true; r->n_s = (uint32_t)x.n_s; r->n_o = (uint32_t)x.n_o; r->n = r->n_s + r->n_o; r->o_base = r->n_s;      // (the later runs go right behind the sorted stream, as in pd_runs_create: what counts is how many runs there ARE, not how many were reserved)
-            r->b1 = x.b1; r->o1 = x.b1 + x.nbw; r->bshift = x.bshift;
-            const pd_iv *oth = x.oth(); const size_t no1 = (size_t)x.n_o;
-            uint32_t *tmp = nullptr, *words = nullptr, *d_base = nullptr;
-            const size_t nbw = x.nbw;
-            unsigned long long *marks = x.marks;
-            const std::vector<uint32_t> base_s = x.base_s;
-            x.base = nullptr; x.b1 = nullptr; x.marks = nullptr; x.bytes = 0; x.cap_s = x.cap_o = 0;       // (they belong to the sample now; the marks go below)
-            c8_drop(c);                                                                                        // the batches' segments and events
-            if (hipMalloc(&tmp, (2 * nbw + nbw / 1024 + 8) * 4) != hipSuccess || hipMalloc(&words, 16) != hipSuccess || hipMalloc(&d_base, base_s.size() * 4 + 16) != hipSuccess) {
-                (void)hipGetLastError(); for (void *q : {(void *)tmp, (void *)words, (void *)d_base, (void *)marks}) if (q) (void)hipFree(q); runs_free(r);
-                return fail(c, PD_ENOMEM, "pd_decode_end: allocation failed");
-            }
-            uint32_t h[2] = {0, 0};
-            hipError_t e = hipMemsetAsync(words, 0, 16, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_base, base_s.data(), base_s.size() * 4, hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) {
-                // the marks (batch, index in the batch) of the buckets' first runs become indices into the sorted stream
-                { ProfScope ps(c, "compact_finish"); launch_c8_marks_to_index(c->stream, marks, (uint32_t)(nbw - 1), d_base, r->b1); }
-                const pd_iv *o[1] = {oth}; const size_t non[1] = {no1};
-                runs_finish(c, r, o, non, no1 ? 1 : 0, tmp, words);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(h, words, 8, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            (void)hipFree(tmp); (void)hipFree(words); (void)hipFree(d_base); (void)hipFree(marks);
-            if (e != hipSuccess) { runs_free(r); return fail(c, PD_EHIP, std::string("pd_decode_end: ") + hipGetErrorString(e)); }
-            r->n_long = (uint32_t)std::min<uint64_t>(n_long + h[1], 0xFFFFFFFFull);
-            c->dec_runs = r;
-            ++c->dec_n[pd_ctx::DN_END_COMPACT];
-            Pending p{nullptr, r->n, 0u, -1};
-            p.cr = r;
-            c->pend.push_back(p);
-            return PD_OK;
-        }
-        // not usable as a compact sample after all (the records are not in the order the header promised, more than 2^32 runs):
-        // back to 12-byte arrays, which take the general paths below
-        nf = x.n_s; no = x.n_o; nfar = 0;
-        ++c->dec_n[pd_ctx::DN_END_C8_FALLBACK];
-        if (!ok_order) ++c->dec_n[pd_ctx::DN_END_UNSORTED];
-        if (nf && c->n_cells >= (1ull << 32)) {
-            // 32 bits of a flat begin name a cell only below 2^32 cells; above, it takes the sample's own bucket index to say which contig a
-            // run lies in, and that index is exactly what an unordered stream does not have.  (The executable never gets here: it gives a
-            // file whose records are not in the promised order to the host readers before anything is counted.)
-            (void)hipDeviceSynchronize(); c8_drop(c);
-            return fail(c, PD_ESTATE, "pd_decode_end: the records of this compact session are not in coordinate order (or are more than 2^32 - 256 runs) on a genome of 2^32 cells or more: "
-                                      "decode it again without PD_DECODE_COMPACT");
-        }
-        if ((nf && hipMalloc(&c->run_first, (size_t)nf * sizeof(pd_iv)) != hipSuccess) || (no && hipMalloc(&c->run_other, (size_t)no * sizeof(pd_iv)) != hipSuccess)) {
-            c8_drop(c); return fail(c, PD_ENOMEM, "pd_decode_end: run array allocation failed"); }
-        if (nf) launch_r8_to_iv(c->stream, x.r8(), nf, tab_of(c), c->run_first);
-        if (no) HIPOK(c, hipMemcpyAsync(c->run_other, x.oth(), (size_t)no * sizeof(pd_iv), hipMemcpyDeviceToDevice, c->stream));
-        HIPOK(c, hipGetLastError());
-        HIPOK(c, hipStreamSynchronize(c->stream));
-        c8_drop(c);
-        int rc = PD_OK;
-        const bool near_ok = ok_order && span <= (1u << 14);
-        if (nf) rc = scatter_device(c, c->run_first, (size_t)nf, ok_order ? (PD_PUSH_SORTED | PD_PUSH_MORE) : PD_PUSH_DEFAULT, -1, nullptr);
-        if (rc == PD_OK && no) rc = scatter_device(c, c->run_other, (size_t)no, near_ok ? (PD_PUSH_SORTED | PD_PUSH_MORE | PD_PUSH_DISORDER(span + 1)) : PD_PUSH_DEFAULT, -1, nullptr);
-        return rc;
-    }
-    if ((nf && hipMalloc(&c->run_first, (size_t)nf * sizeof(pd_iv)) != hipSuccess) || (no && hipMalloc(&c->run_other, (size_t)no * sizeof(pd_iv)) != hipSuccess) ||
-        (nfar && hipMalloc(&c->run_far, (size_t)nfar * sizeof(pd_iv)) != hipSuccess)) { drop(); return fail(c, PD_ENOMEM, "pd_decode_end: run array allocation failed"); }
-    uint64_t of = 0, oo = 0, ofar = 0;
-    for (auto &r : segs) {
-        if (r.n_first) HIPOK(c, hipMemcpyAsync(c->run_first + of, r.first, (size_t)r.n_first * sizeof(pd_iv), hipMemcpyDeviceToDevice, c->stream));
-        if (r.n_other) HIPOK(c, hipMemcpyAsync(c->run_other + oo, r.other, (size_t)r.n_other * sizeof(pd_iv), hipMemcpyDeviceToDevice, c->stream));
-        if (r.n_far) HIPOK(c, hipMemcpyAsync(c->run_far + ofar, r.far, (size_t)r.n_far * sizeof(pd_iv), hipMemcpyDeviceToDevice, c->stream));
-        of += r.n_first; oo += r.n_other; ofar += r.n_far;
-    }
-    HIPOK(c, hipStreamSynchronize(c->stream));
-    drop();
-    // the sample, deferred, as up to three streams in file order: every read's first run (position sorted for a
-    // coordinate-sorted file: exact tile bounds), its later runs that begin within NEAR_SPAN bases of its start (they trail
-    // the sorted order by at most that), and the few that follow a long gap (N operations: they trail by up to `span`).
-    // An unsorted file, or gaps of more than a few tiles, take the atomic path.
-    bool sorted = c->dec_cfg.sorted != 0;
-    if (sorted) {                                        // ... and only if the records really are in that order (the header may lie)
-        uint64_t prev = 0; bool have = false;
-        for (auto &r : segs) {
-            if (!r.n_first) continue;
-            if (r.unsorted || (have && r.first_key < prev)) { sorted = false; break; }
-            prev = r.last_key; have = true;
-        }
-    }
-    if (getenv("PANDEPTH_TIMING"))
-        fprintf(stderr, "[timing]   decode entry points, thread-seconds: slot wait %.3f, pinned alloc %.3f, device buffers %.3f, wait H2D+inflate+walk %.3f, "
-                        "host chain check %.3f, run arrays %.3f, wait emit %.3f, first HIP call of the feeder threads %.3f; %zu batches; runs: %llu first, %llu near, %llu far (span %u); "
-                        "chain confirmed on the device for %llu batches, by the host for %llu; segments the device walked again: %llu\n", g_dec_us[0] / 1e6,
-                g_dec_us[1] / 1e6, g_dec_us[2] / 1e6, g_dec_us[3] / 1e6, g_dec_us[4] / 1e6, g_dec_us[5] / 1e6, g_dec_us[6] / 1e6, g_dec_us[7] / 1e6, segs.size(),
-                (unsigned long long)nf, (unsigned long long)no, (unsigned long long)nfar, span, (unsigned long long)c->dec_n_fast.load(), (unsigned long long)c->dec_n_slow.load(), (unsigned long long)c->dec_n_redo.load());
-    int rc = PD_OK;
-    // disorder of a stream = how far its runs may trail the sorted order: the near stream by near_span (when the split is on,
-    // otherwise by the longest gap seen, like the far stream)
-    const uint32_t near_dis = nfar ? (c->dec_near_span < span ? c->dec_near_span : span) : span;
-    const bool near_sorted = sorted && near_dis <= (1u << 14), far_sorted = sorted && span <= (1u << 14);
-    if (nf && sorted && (c->dec_cfg.flags & PD_DECODE_COMPACT) && c->pend.empty() && nf + no + nfar <= DEV_BATCH_MAX) {
-        // the whole-contig modes: the sample stays as ONE compact sample (8 bytes per run, grouped by 512-cell bucket: the first
-        // runs keep their order — checked again —, the later runs of multi-run reads are dropped into their buckets), the
-        // 12-byte arrays go
-        pd_runs *r = nullptr;
-        const pd_iv *o[2] = {c->run_other, c->run_far}; const size_t non[2] = {(size_t)no, (size_t)nfar};
-        if (runs_make(c, c->run_first, (size_t)nf, o, non, 2, &r) == PD_OK) {
-            for (pd_iv **q : {&c->run_first, &c->run_other, &c->run_far}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-            c->dec_runs = r;
-            ++c->dec_n[pd_ctx::DN_END_RUNS_MAKE];
-            Pending p{nullptr, r->n, 0u, -1};
-            p.cr = r;
-            c->pend.push_back(p);
-            return PD_OK;
-        }
-    }
-    ++c->dec_n[pd_ctx::DN_END_SCATTER];
-    if (c->dec_cfg.sorted && !sorted) ++c->dec_n[pd_ctx::DN_END_UNSORTED];
-    if (nf) rc = scatter_device(c, c->run_first, (size_t)nf, sorted ? (PD_PUSH_SORTED | PD_PUSH_MORE) : PD_PUSH_DEFAULT, -1, nullptr);
-    if (rc == PD_OK && no) rc = scatter_device(c, c->run_other, (size_t)no, near_sorted ? (PD_PUSH_SORTED | PD_PUSH_MORE | PD_PUSH_DISORDER(near_dis + 1)) : PD_PUSH_DEFAULT, -1, nullptr);
-    if (rc == PD_OK && nfar) rc = scatter_device(c, c->run_far, (size_t)nfar, far_sorted ? (PD_PUSH_SORTED | PD_PUSH_MORE | PD_PUSH_DISORDER(span + 1)) : PD_PUSH_DEFAULT, -1, nullptr);
-    return rc;
-}
-
-int pd_decode_abort(pd_ctx *c)
-{
-    if (!c) return PD_EINVAL;
-    if (c->dec_warm.joinable()) c->dec_warm.join();
-    dec_drain(c, false);
-    std::unique_lock<std::mutex> lk(c->dec_mu);
-    c->dec_cv.wait(lk, [&] { for (auto &x : c->dec) if (x.busy) return false; return true; });
-    c->dec_open = false;
-    (void)hipSetDevice(c->device);
-    auto in_arena = [&](const void *p) { return c->arena && (const uint8_t *)p >= c->arena && (const uint8_t *)p < c->arena + c->arena_cap; };
-    for (auto &r : c->run_segs) for (pd_iv *q : {r.first, r.other, r.far}) if (q && !in_arena(q)) (void)hipFree(q);
-    c->run_segs.clear();
-    { std::lock_guard<std::mutex> l8(c->c8.mu); if (c->c8.on || c->c8.base) { (void)hipDeviceSynchronize(); c8_drop(c); } }
-    return PD_OK;
-}
-
-// The synchronous single-batch form (round 1's entry point, kept for its callers): one batch through the pipeline
-// above, its runs scattered at once (first runs: owner tiles; the others: atomics).
-int pd_push_bgzf_units(pd_ctx *c, const void *blob, size_t n_bytes, const pd_bgzf_block *blocks, uint32_t n_blocks,
-                       const pd_bgzf_unit *units, uint32_t n_units, uint64_t inflated_bytes, uint32_t flag_mask,
-                       int32_t min_mapq, int32_t *unit_status, uint64_t *n_records)
-{
-    if (!c || !blob || !blocks || !units || !unit_status) return PD_EINVAL;
-    if (n_records) *n_records = 0;
-    if (n_units == 0 || n_blocks == 0) return PD_OK;
-    pd_decode_cfg cfg{}; cfg.flag_mask = flag_mask; cfg.min_mapq = min_mapq; cfg.sorted = 1;
-    int rc = pd_decode_begin(c, &cfg);
-    if (rc) return rc;
-    // the session this call opens is closed on every path out of it (its batch is taken out of the list below, so the
-    // abort drops nothing that was counted)
-    struct Close { pd_ctx *c; ~Close() { (void)pd_decode_abort(c); } } close_session{c};
-    void *hb = nullptr;
-    if ((rc = pd_decode_acquire(c, n_bytes, &hb))) return rc;
-    memcpy(hb, blob, n_bytes);
-    std::vector<pd_decode_unit> du(n_units);
-    for (uint32_t u = 0; u < n_units; ++u) du[u] = pd_decode_unit{units[u].start, units[u].stop, units[u].avail, units[u].first_block, units[u].n_blocks, 0, 0};
-    static std::atomic<uint64_t> key{0};
-    pd_decode_batch bt{}; bt.host_buf = hb; bt.n_bytes = n_bytes; bt.blocks = blocks; bt.n_blocks = n_blocks; bt.inflated_bytes = inflated_bytes;
-    bt.units = du.data(); bt.n_units = n_units; bt.order = ((uint64_t)1 << 63) + key.fetch_add(1);
-    pd_decode_result res;
-    if ((rc = pd_decode_submit(c, &bt, unit_status, &res))) return rc;
-    for (auto &sl : c->dec) if (sl.st) (void)hipStreamSynchronize(sl.st);           // (the batch's runs are scattered from another stream below)
-    if (n_records) *n_records = res.n_reads;
-    pd_ctx::RunSeg mine{0, nullptr, 0, nullptr, 0, nullptr, 0, 0};
-    {
-        std::lock_guard<std::mutex> lk(c->dec_mu);
-        for (size_t i = 0; i < c->run_segs.size(); ++i)
-            if (c->run_segs[i].order == bt.order) { mine = c->run_segs[i]; c->run_segs.erase(c->run_segs.begin() + (long)i); break; }
-    }
-    if (mine.n_first + mine.n_other + mine.n_far) {
-        std::unique_lock<std::mutex> lk(c->mu);
-        if (int rs = need_state(c, 0, "pd_push_bgzf_units")) return rs;
-        HIPOK(c, hipSetDevice(c->device));
-        if (mine.n_first) { rc = scatter_device(c, mine.first, (size_t)mine.n_first, PD_PUSH_SORTED, -1, nullptr); if (rc) return rc; }
-        if (mine.n_other) { rc = scatter_device(c, mine.other, (size_t)mine.n_other, PD_PUSH_DEFAULT, -1, nullptr); if (rc) return rc; }
-        if (mine.n_far) { rc = scatter_device(c, mine.far, (size_t)mine.n_far, PD_PUSH_DEFAULT, -1, nullptr); if (rc) return rc; }
-        HIPOK(c, hipStreamSynchronize(c->stream));
-        const auto ina = [&](const void *p) { return c->arena && (const uint8_t *)p >= c->arena && (const uint8_t *)p < c->arena + c->arena_cap; };
-        for (pd_iv *q : {mine.first, mine.other, mine.far}) if (q && !ina(q)) (void)hipFree(q);
-    }
-    return PD_OK;
-}
-
-} // extern "C"
 
 extern "C" {
 
@@ -3130,7 +1861,7 @@ static int lz_run(pd_ctx *c, const void *text, pd_text *tx, uint64_t tx_off, siz
     if (prof) for (auto &e : ev) (void)hipEventCreate(&e);
     const bool dbg = getenv("PD_LZ_DEBUG") != nullptr;
     double tm[8] = {}; int ti = 0;
-    auto tick = [&]() { if (dbg && ti < 8) tm[ti++] = dec_now() * 1e-6; };
+    auto tick = [&]() { if (dbg && ti < 8) tm[ti++] = dec_now_us() * 1e-6; };
     tick();
     const uint32_t np = (uint32_t)(n_text - 2);
     const uint32_t n_blocks = (np + 2047) / 2048;

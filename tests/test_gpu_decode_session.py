@@ -1,10 +1,10 @@
 """The batched decode session (pd_decode_begin / acquire / submit | queue + collect / end | abort: include/pandepth_amd.h,
-pandepth_amd/csrc/pd_capi.hip) called directly, on the crafted corpus of tests/bam_craft.py cut into batches the way the executable's
+pandepth_amd/csrc/pd_decode.hip) called directly, on the crafted corpus of tests/bam_craft.py cut into batches the way the executable's
 readers cut a file (bam_craft.cut_batches; held to the file on the CPU in tests/test_decode_batches.py), against the per-base depth of
 the reference written from the SAM specification (bam_craft.reference_depth).  Every comparison is of exact integers, per base or per
 window; no unit may be handed back except where a guessed start lies inside a decoy record.
 
-Which branch of pd_capi.hip a group reaches is shown by the session's counters (pd_profile_get "decode_*": which way pd_decode_end
+Which branch of pd_decode.hip a group reaches is shown by the session's counters (pd_profile_get "decode_*": which way pd_decode_end
 went, who confirmed the record chains, how often the compact sample grew), by the kernels' launch counts, by a status or by the
 library's own message."""
 import ctypes
@@ -189,6 +189,26 @@ def test_session_gives_the_per_base_depth(corpus, name, cut, mode, flt):
         e.profile(True)
         check_results(f, run_mode(e, mode, batches, flt))
         check_windows(e, f, flt, compact_direct=(mode == "compact"))
+
+
+TRANSPORTS = [("decode_h2d_fifo", 0), ("decode_h2d_lanes", 2), ("decode_h2d_kernel", 1), ("decode_h2d_kernel", 2), ("decode_h2d_kernel", 3),
+              ("decode_sync_event", 0)]
+
+
+@pytest.mark.parametrize("mode", ["plain", "compact"])
+@pytest.mark.parametrize("param,value", TRANSPORTS, ids=["%s_%d" % t for t in TRANSPORTS])
+def test_transport_variants_give_the_per_base_depth(corpus, param, value, mode):
+    """the ways a batch's bytes reach the device and a collect waits for it that are off by default (dec_queue's upload, dec_collect's
+    wait): the batches' own streams instead of the copy FIFO, two copy lanes, the three copy-kernel forms, the stream wait"""
+    f = corpus["packed"]
+    flt = B.FILTERS[0]
+    batches = f["cuts"]["3"]
+    with pda.Engine(f["lens"]) as e:
+        e.set_param(param, value)
+        check_results(f, run_mode(e, mode, batches, flt))
+        assert counter(e, "decode_end_compact" if mode == "compact" else "decode_end_scatter") == 1
+        assert counter(e, "decode_chain_device") + counter(e, "decode_chain_host") == len(batches)
+        check_depth(e, f["lens"], f["depth"][flt])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
