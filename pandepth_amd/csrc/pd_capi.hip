@@ -713,7 +713,8 @@ uint32_t runs_bshift(const pd_ctx *c)
 // The second half of making a compact sample, shared by pd_runs_create and pd_decode_end: the sorted stream is in r->r8[0 .. n_s) and the
 // first run of every bucket has left its index in r->b1 (everything else 0xFFFFFFFF); `others` are the remaining runs as 12-byte arrays, any
 // order.  Fills the bucket starts of the sorted stream (a suffix minimum over the marks), counts the other runs per bucket, places them
-// behind o_base.  words (device, 2 x uint32, already holding the sorted stream's flags): [0] bad contig id, [1] runs longer than a bucket.
+// behind o_base, and writes the per-tile descriptors (r->td) from the finished bucket starts.  words (device, 2 x uint32, already holding
+// the sorted stream's flags): [0] bad contig id, [1] runs longer than a bucket.
 // Only enqueues on c->stream; `tmp` must hold 2 x (nb + 2) + (nb / 1024 + 4) words.
 void runs_finish(pd_ctx *c, pd_runs *r, const pd_iv *const *others, const size_t *n_others, int n_arr, uint32_t *tmp, uint32_t *words)
 {
@@ -728,6 +729,7 @@ void runs_finish(pd_ctx *c, pd_runs *r, const pd_iv *const *others, const size_t
     for (int k = 0; k < n_arr; ++k) launch_c8_hist(st, others[k], (uint32_t)n_others[k], tab, r->bshift, hist, words);
     launch_excl_scan_u32(st, hist, r->o1, nb + 1, bs);
     for (int k = 0; k < n_arr; ++k) launch_c8_place_other(st, others[k], (uint32_t)n_others[k], tab, r->bshift, r->o1, cursor, r->r8 + r->o_base);
+    launch_c8_tile_desc(st, r->view(), tab, c->d_tile_contig, (uint32_t)c->n_tiles, r->td);       // both streams' bucket starts are final
 }
 
 // caller holds c->mu and has set the device.  `sorted` must be sorted by (tid, beg) — checked; the `others` may be in any order.
@@ -747,14 +749,14 @@ int runs_make(pd_ctx *c, const pd_iv *sorted, size_t n_sorted, const pd_iv *cons
     const uint32_t nb = (uint32_t)nb64;
     const size_t nbw = (size_t)nb + 2;
     uint32_t *tmp = nullptr, *words = nullptr;
-    if (hipMalloc(&r->r8, n * sizeof(Run8) + 64) != hipSuccess || hipMalloc(&r->b1, 2 * nbw * 4) != hipSuccess ||
+    if (hipMalloc(&r->r8, n * sizeof(Run8) + 64) != hipSuccess || hipMalloc(&r->b1, c8_index_bytes(nbw, c->n_tiles)) != hipSuccess ||
         hipMalloc(&tmp, (2 * nbw + nb / 1024 + 8) * 4) != hipSuccess || hipMalloc(&words, 16) != hipSuccess) {
         (void)hipGetLastError();
         for (void *q : {(void *)tmp, (void *)words}) if (q) (void)hipFree(q);
         runs_free(r);
         return fail(c, PD_ENOMEM, "pd_runs_create: allocation failed");
     }
-    r->o1 = r->b1 + nbw;
+    r->o1 = r->b1 + nbw; r->td = (TileDesc *)((uint8_t *)r->b1 + c8_desc_offset(nbw));
     uint32_t h[2] = {0, 0};
     hipStream_t st = c->stream;
     hipError_t e = hipMemsetAsync(words, 0, 16, st);
@@ -1005,7 +1007,7 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
     }
     if (grid > c->n_tiles) grid = (unsigned)c->n_tiles;
     { ProfScope sc(c, "direct_tiles");
-      if (c8) launch_direct_c8(c->stream, c->pend[0].cr->view(), tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part,
+      if (c8) launch_direct_c8(c->stream, c->pend[0].cr->view(), c->pend[0].cr->td, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part,
                                c->direct_words + 16, c->direct_words + 2, grid, c->direct_un);
       else launch_direct_tiles(c->stream, ps, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, d_wo,
                                d_cov, d_sum, c->direct_words, c->direct_words + 1, c->direct_words + 16, c->direct_words + 2, grid, c->direct_un); }
@@ -1714,7 +1716,7 @@ static int direct_export(pd_ctx *c, void *dev_i4, pd_exc *dev_exc, uint32_t exc_
     }
     if (grid > c->n_tiles) grid = (unsigned)c->n_tiles;
     { ProfScope sc(c, "direct_export");
-      if (c8) launch_direct_c8_export(c->stream, c->pend[0].cr->view(), tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, dev_i4, dev_exc, exc_cap,
+      if (c8) launch_direct_c8_export(c->stream, c->pend[0].cr->view(), c->pend[0].cr->td, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, dev_i4, dev_exc, exc_cap,
                                       dev_count, c->sums, c->direct_words + 16, c->direct_words + 2, grid);
       else launch_direct_export(c->stream, ps, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, dev_i4, dev_exc, exc_cap, dev_count,
                                 c->sums, c->direct_words, c->direct_words + 1, c->direct_words + 16, c->direct_words + 2, grid); }

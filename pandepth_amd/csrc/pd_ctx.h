@@ -72,7 +72,8 @@ struct pd_runs {
     pd_ctx *ctx = nullptr;
     Run8 *r8 = nullptr;                                          // [sorted stream: n_s runs, file order | ... | other runs by bucket at o_base]
     uint32_t n_s = 0, n_o = 0, o_base = 0, n = 0;                // n = n_s + n_o
-    uint32_t *b1 = nullptr, *o1 = nullptr;                       // (n_tiles << bshift) + 1 bucket starts per stream (one allocation: b1 | o1)
+    uint32_t *b1 = nullptr, *o1 = nullptr;                       // (n_tiles << bshift) + 1 bucket starts per stream (one allocation: b1 | o1 | td, c8_index_bytes)
+    TileDesc *td = nullptr;                                      // per tile: what k_direct_c8 reads before the tile's runs (made by runs_finish)
     uint32_t bshift = 4;                                         // 16 buckets of 512 cells per tile
     uint32_t n_long = 0;                                         // runs longer than a bucket: the direct kernels cannot use the sample
     pd_iv *iv12 = nullptr;                                       // the expanded copy, made on first need
@@ -181,7 +182,7 @@ struct pd_ctx {
         bool on = false;
         uint8_t *base = nullptr; size_t bytes = 0;               // ONE allocation: [Run8 x (cap_s + cap_o) | pd_iv x cap_o]
         size_t cap_s = 0, cap_o = 0;
-        uint32_t *b1 = nullptr; size_t nbw = 0;                  // bucket starts: b1 | o1, nbw words each
+        uint32_t *b1 = nullptr; size_t nbw = 0;                  // bucket starts: b1 | o1, nbw words each, then the sample's tile descriptors (c8_index_bytes)
         unsigned long long *marks = nullptr;                     // per bucket: min (batch << 32 | index in the batch) of a run that begins there
         uint32_t bshift = 4;
         uint64_t n_s = 0, n_o = 0, turn = 0, n_batches = 0;

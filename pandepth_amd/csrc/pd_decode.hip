@@ -258,7 +258,7 @@ int begin_compact(pd_ctx *c, const pd_decode_cfg *cfg, uint64_t *tb)
     x.nbw = (size_t)nb64 + 2;
     if (x.b1) { (void)hipFree(x.b1); x.b1 = nullptr; }
     if (x.marks) { (void)hipFree(x.marks); x.marks = nullptr; }
-    if (hipMalloc(&x.b1, 2 * x.nbw * 4) != hipSuccess || hipMalloc(&x.marks, x.nbw * 8) != hipSuccess) { (void)hipGetLastError(); return fail(c, PD_ENOMEM, "pd_decode_begin: allocation failed"); }
+    if (hipMalloc(&x.b1, c8_index_bytes(x.nbw, c->n_tiles)) != hipSuccess || hipMalloc(&x.marks, x.nbw * 8) != hipSuccess) { (void)hipGetLastError(); return fail(c, PD_ENOMEM, "pd_decode_begin: allocation failed"); }
     HIPOK(c, hipMemsetAsync(x.marks, 0xFF, x.nbw * 8, c->stream));
     HIPOK(c, hipStreamSynchronize(c->stream));                // (the batches' kernels run on other streams)
     if (!x.compose) HIPOK(c, hipStreamCreateWithFlags(&x.compose, hipStreamNonBlocking));
@@ -1007,7 +1007,7 @@ int compact_to_sample(pd_ctx *c, uint64_t n_long)
     pd_ctx::C8Dec &x = c->c8;
     pd_runs *r = new pd_runs;
     r->ctx = c; r->r8 = x.r8(); r->own_r8 = true; r->n_s = (uint32_t)x.n_s; r->n_o = (uint32_t)x.n_o; r->n = r->n_s + r->n_o; r->o_base = r->n_s;      // (the later runs go right behind the sorted stream, as in pd_runs_create: what counts is how many runs there ARE, not how many were reserved)
-    r->b1 = x.b1; r->o1 = x.b1 + x.nbw; r->bshift = x.bshift;
+    r->b1 = x.b1; r->o1 = x.b1 + x.nbw; r->td = (TileDesc *)((uint8_t *)x.b1 + c8_desc_offset(x.nbw)); r->bshift = x.bshift;
     const pd_iv *oth = x.oth(); const size_t no1 = (size_t)x.n_o;
     uint32_t *tmp = nullptr, *words = nullptr, *d_base = nullptr;
     const size_t nbw = x.nbw;

@@ -56,6 +56,14 @@ struct CheckWords {           // context-wide, read back at pd_scan / pd_synchro
 // longer than a bucket, so the only other runs that can reach into tile t are those of the bucket right before it.
 struct Run8 { uint32_t b; uint32_t len; };
 struct C8Sample { const Run8 *r8; const uint32_t *b1, *o1; uint32_t o_base, bshift; };
+// What k_direct_c8 needs to know about a tile before it can fetch the tile's runs, worked out once when the sample is finished (its inputs —
+// b1, o1, the context's contig layout, bshift — are fixed for the sample's life): the candidates' ranges in the two streams ([slo, shi) of
+// b1's numbering, [olo, ohi) of o1's; a contig's first tile does not look back), the tile's first cell inside its contig and the contig's
+// length.  One 32-byte record per tile, read through a pointer of its own, so that the kernel's loop gets it with scalar loads.
+struct alignas(32) TileDesc { uint32_t slo, shi, olo, ohi, pc, clen, spare0, spare1; };
+// a compact sample's index arrays are ONE allocation: b1 | o1 (nbw words each) | pad to 32 bytes | TileDesc x n_tiles
+static inline size_t c8_desc_offset(size_t nbw) { return (2 * nbw * 4 + 31) / 32 * 32; }
+static inline size_t c8_index_bytes(size_t nbw, uint64_t n_tiles) { return c8_desc_offset(nbw) + (size_t)n_tiles * sizeof(TileDesc); }
 
 struct PendBatch {            // one sorted batch of a tile pass (device pointers)
     const pd_iv *iv;
@@ -88,12 +96,15 @@ void launch_excl_scan_u32(hipStream_t st, const uint32_t *in, uint32_t *out, uin
 void launch_c8_fill_starts(hipStream_t st, uint32_t *b1, uint32_t n_buckets, uint32_t n_runs, uint32_t *tmp /* n_buckets / 1024 + 2 words */);
 void launch_c8_marks_to_index(hipStream_t st, const unsigned long long *marks, uint32_t n_buckets, const uint32_t *base, uint32_t *b1);
 void launch_c8_place_other(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, const uint32_t *o1, uint32_t *cursor, Run8 *out);
+void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc);
 void launch_c8_expand(hipStream_t st, C8Sample cs, const uint32_t *tile_contig, const uint64_t *contig_off, uint32_t n_tiles, pd_iv *out);
 void launch_r8_to_iv(hipStream_t st, const Run8 *r8, uint64_t n, ContigTab tab, pd_iv *out);
 void launch_copy_words(hipStream_t st, void *dst, const void *src, uint64_t n_words);      // device-to-device, 4-byte words (both pointers 4-byte aligned)
-void launch_direct_c8(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
+// (k_direct_c8 itself reads cs.r8, cs.o_base and desc only; tab, tile_contig and the bucket starts in cs serve the int-window pass launched
+// behind it for the pile-up tiles)
+void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
                       uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un);
-void launch_direct_c8_export(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, void *img, pd_exc *exc,
+void launch_direct_c8_export(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, void *img, pd_exc *exc,
                              uint32_t cap, uint32_t *count, int *sums, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles);
 void launch_direct_export(hipStream_t st, const PendSet &ps, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles,
                           void *img, pd_exc *exc, uint32_t cap, uint32_t *count, int *sums, uint32_t *n_long, uint32_t *fail,

@@ -1563,6 +1563,24 @@ __global__ __launch_bounds__(256) void k_copy_words(uint32_t *__restrict__ dst, 
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) dst[i] = src[i];
 }
 
+// The per-tile descriptors of a finished compact sample (TileDesc in pd_kernels.h): one thread per tile reads the bucket starts around the
+// tile in both streams and the tile's contig, so that k_direct_c8 finds them in one record instead of a chain of dependent loads.
+__global__ __launch_bounds__(WG) void k_c8_tile_desc(const C8Sample cs, const ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc)
+{
+    const uint32_t t = blockIdx.x * WG + threadIdx.x;
+    if (t >= n_tiles) return;
+    const uint32_t k0 = t << cs.bshift, nbk = 1u << cs.bshift;
+    const uint32_t ctg = tile_contig[t];
+    TileDesc d;
+    d.pc = (uint32_t)((uint64_t)t * TILE - tab.off[ctg]);         // the tile's first cell inside its contig
+    d.clen = tab.len[ctg];
+    const uint32_t lo = d.pc ? k0 - 1 : k0;                       // a contig's first tile has nothing before it
+    d.slo = cs.b1[lo]; d.shi = cs.b1[k0 + nbk];
+    d.olo = cs.o1[lo]; d.ohi = cs.o1[k0 + nbk];
+    d.spare0 = d.spare1 = 0;
+    desc[t] = d;
+}
+
 // a sorted stream of compact runs whose sample turned out not to be usable as one (the file's order does not hold after all): back to
 // 12-byte runs; the contig of a flat begin by bisection over the slots (genomes below 2^32 cells only: the caller has made sure)
 __global__ __launch_bounds__(WG) void k_r8_to_iv(const Run8 *r8, uint64_t n, ContigTab tab, pd_iv *out)
@@ -1583,14 +1601,15 @@ __global__ __launch_bounds__(WG) void k_r8_to_iv(const Run8 *r8, uint64_t n, Con
 //   its first cell or further (the carry-in).
 // A run without cells adds and subtracts at the same cell.  The tile's candidates are its own buckets and the one before them, in
 // BOTH streams of the sample (the file's sorted first runs as the decoder wrote them, and the later runs counting-sorted by bucket):
-// one loop over the two ranges laid end to end.  Same window arithmetic, prefix sum and statistics as k_direct_wide3; tiles with more
-// than 32 000 candidates go to the int-window kernel through the same list.
+// one loop over the two ranges laid end to end.  Same window arithmetic and prefix sum as k_direct_wide3; the statistics of an interior tile
+// take a packed minimum and a packed sum per word (exact loops for the waves that hold a cell below the threshold, and for edge tiles); tiles
+// with more than 32 000 candidates go to the int-window kernel through the same list.
 // V4 (round 6, JOIN only, UN8 even): the full chunks of the sorted stream are fetched 16 bytes per lane — two runs per load, a kilobyte per wave and
 // instruction instead of 512 bytes; which thread works on which run changes, nothing else (the window's updates commute).
 template <int WPE, int UN8, bool EXPORT, bool JOIN = false, bool V4 = false>
-__global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, uint32_t n_tiles, ContigTab tab, const uint32_t *tile_contig,
-                                                     uint32_t wrap_mask, const DirectWide args, uint32_t *heavy_list, uint32_t *heavy_count,
-                                                     const DirectExport ex)
+__global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const TileDesc *__restrict__ desc, uint32_t n_tiles,
+                                                     uint32_t wrap_mask, const DirectWide args, uint32_t *__restrict__ heavy_list,
+                                                     uint32_t *__restrict__ heavy_count, const DirectExport ex)
 {
     const uint32_t w = args.w, min_dep = args.min_dep; TilePart *const part = args.part;
     constexpr uint32_t ST = TILE, HT = TILE / 2;
@@ -1601,42 +1620,27 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, uint32
     __shared__ unsigned long long red_s[4][2];
     __shared__ int red_c[4][2];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t bsh = cs.bshift;
-    // the bounds of a tile are three entries of each stream's bucket starts (scalar loads); the sorted stream's are fetched a tile ahead,
-    // the other stream's at the top of the tile (they are not needed before the sorted stream's runs are through)
-    auto bounds = [&](const uint64_t t, uint32_t &slo, uint32_t &shi) {
-        slo = shi = 0;
-        if (t < n_tiles) {
-            const uint32_t k0 = (uint32_t)t << bsh;
-            shi = cs.b1[k0 + (1u << bsh)];
-            const uint32_t ctg = tile_contig[t];
-            slo = cs.b1[(uint64_t)t * ST > tab.off[ctg] ? k0 - 1 : k0];            // a contig's first tile has nothing before it
-        }
-    };
-    uint32_t nslo, nshi;
-    bounds(blockIdx.x, nslo, nshi);
+    // a tile's bounds, its place in its contig and the contig's length are ONE record of the sample's descriptor table (TileDesc), read
+    // through a pointer nothing is stored through: scalar loads, issued a tile ahead behind the first run loads, so that no tile waits
+    // for metadata and nothing at the top of a tile depends on another load's result but the run loads themselves
+    TileDesc nxt = TileDesc{};
+    if (blockIdx.x < n_tiles) nxt = desc[blockIdx.x];
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         const uint64_t a = t * ST;
-        const uint32_t ns = nshi - nslo, s_at = nslo;             // the tile's candidates in the sorted stream
-        uint4 *w4 = reinterpret_cast<uint4 *>(win);
-        for (uint32_t j = threadIdx.x; j < HT / 4; j += WG) w4[j] = make_uint4(0u, 0u, 0u, 0u);
-        if (threadIdx.x == 0) s_carry = 0;
-        const int32_t ctg = (int32_t)tile_contig[t];
-        const uint32_t clen = tab.len[ctg];
-        const uint32_t p0 = (uint32_t)a;                          // the runs' begins are flat (mod 2^32), like this
-        const uint32_t pc = (uint32_t)(a - tab.off[ctg]);         // the tile's first cell inside its contig
-        const uint32_t k0 = (uint32_t)t << bsh;
-        // ... and in the other stream (both possible lower bounds are fetched, so that the loads do not wait for the contig's offset)
-        const uint32_t o_prev = cs.o1[k0 ? k0 - 1 : 0], o_own = cs.o1[k0], ohi = cs.o1[k0 + (1u << bsh)];
-        bounds(t + gridDim.x, nslo, nshi);
-        __syncthreads();
-        const uint32_t olo = pc ? o_prev : o_own, no = ohi - olo;
+        const TileDesc cur = nxt;
+        const uint64_t t_next = t + gridDim.x;
+        const uint32_t ns = cur.shi - cur.slo, s_at = cur.slo;    // the tile's candidates in the sorted stream
+        const uint32_t olo = cur.olo, no = cur.ohi - olo;         // ... and in the other stream
         const uint32_t cand = ns + no;
-        if (cand > 32000u) {                                      // workgroup-uniform: the int-window kernel does this tile
+        const uint32_t clen = cur.clen;
+        const uint32_t p0 = (uint32_t)a;                          // the runs' begins are flat (mod 2^32), like this
+        const uint32_t pc = cur.pc;                               // the tile's first cell inside its contig
+        if (cand > 32000u) {                                      // workgroup-uniform: the int-window kernel does this tile (no LDS touched: no barrier)
             if (threadIdx.x == 0) heavy_list[atomicAdd(heavy_count, 1u)] = (uint32_t)t;
-            __syncthreads();
+            if (t_next < n_tiles) nxt = desc[t_next];
             continue;
         }
+        uint4 *w4 = reinterpret_cast<uint4 *>(win);
         int carry_s = 0;
         {
             // ONE sequence of chunks: those of the sorted stream's candidates, then those of the other stream's — which stream a chunk
@@ -1699,10 +1703,18 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, uint32
                     }
                 }
             };
-            if (nq) {
+            auto clear_window = [&]() {                           // ... and the next tile's descriptor: behind the run loads, so that the wait in front of the barrier covers both
+                for (uint32_t j = threadIdx.x; j < HT / 4; j += WG) w4[j] = make_uint4(0u, 0u, 0u, 0u);
+                if (threadIdx.x == 0) s_carry = 0;
+                if (t_next < n_tiles) nxt = desc[t_next];
+                __syncthreads();
+            };
+            if (!nq) clear_window();                              // (workgroup-uniform: every thread meets one of the two barriers)
+            else {
                 uint2 A[UN8], B[UN8];
                 uint32_t q = 0;
-                load8(A, q);
+                load8(A, q);                                      // the first chunk is on its way before the window is cleared: nothing it needs is in LDS
+                clear_window();
 #pragma unroll 1
                 for (;;) {                                        // two buffers, no register copies: B is in flight while A is worked on
                     if (q + 1 < nq) load8(B, q + 1);
@@ -1756,26 +1768,32 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, uint32
             const uint64_t left = (uint64_t)clen - local0;
             const uint32_t lim = left > (uint64_t)ST ? ST : (uint32_t)left;
             const uint64_t dmax = (uint64_t)(uint32_t)carry_l + cand;     // no depth in this tile exceeds carry + begins
-            if (nb >= ST && lim >= ST && min_dep <= 1u && dmax < (1u << 27) && dmax <= wrap_mask) {
-                // the common tile — inside one window, inside the contig, no wrap possible, threshold <= 1: the sum is the
-                // sum of the local prefixes + 16 x (carry_l + carry_h) per lane; a cell is covered unless its prefix = -carry
-                int sl = 0; int cnt = 0;
-                const int zl = -carry_l, zh = -carry_h;
+            const bool inner = nb >= ST && lim >= ST;             // inside one window, inside the contig
+            bool settled = false;                                 // wave-uniform
+            if (inner && dmax <= 0xFFFFu && dmax <= wrap_mask) {
+                // every depth of the tile fits 16 bits and cannot wrap: with both carries folded into the row's addend a packed word IS
+                // two depths (the low half is >= 0, so nothing is borrowed from the high one).  Per word: a packed minimum and a sum of
+                // both halves.  A wave whose least depth reaches the threshold has counted all its cells; any other takes the exact loops.
+                typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+                const uint32_t both = ((uint32_t)carry_h << 16) + (uint32_t)carry_l;
+                uint32_t mn = 0xFFFFFFFFu, acc = 0;
 #pragma unroll
                 for (int r = 0; r < ROWS; ++r) {
-                    const int add = basep + ex[r];
-                    const int pw[4] = {v[r].x + add, v[r].y + add, v[r].z + add, v[r].w + add};
+                    const uint32_t add = (uint32_t)(basep + ex[r]) + both;
+                    const uint32_t pw[4] = {(uint32_t)v[r].x + add, (uint32_t)v[r].y + add, (uint32_t)v[r].z + add, (uint32_t)v[r].w + add};
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const int L = (int)(short)(pw[q] & 0xffff), H = (pw[q] - L) >> 16;
-                        sl += L + H;
-                        if (min_dep) cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(L != zl)) + __builtin_popcountll(__builtin_amdgcn_ballot_w64(H != zh));
+                        mn = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(us2, mn), __builtin_bit_cast(us2, pw[q])));
+                        acc = __builtin_amdgcn_sad_u16(pw[q], 0u, acc);
                     }
                 }
-                c0 = min_dep ? cnt : (int)(ROWS * 8 * 64);
-                s0 = (uint32_t)sl + (uint32_t)(ROWS * 4) * ((uint32_t)carry_l + (uint32_t)carry_h);
-                uniform_counts = true;
-            } else if (nb >= ST && lim >= ST && dmax < (1u << 27)) {
+                const uint32_t least = (mn & 0xFFFFu) < (mn >> 16) ? (mn & 0xFFFFu) : (mn >> 16);
+                if (__builtin_amdgcn_ballot_w64(least < min_dep) == 0ull) {
+                    c0 = (int)(ROWS * 8 * 64); s0 = acc; settled = true;
+                }
+            }
+            if (settled) uniform_counts = true;
+            else if (inner && dmax < (1u << 27)) {
                 uint32_t s32 = 0; int cnt = 0;
 #pragma unroll
                 for (int r = 0; r < ROWS; ++r) {
@@ -3077,6 +3095,11 @@ void launch_copy_words(hipStream_t st, void *dst, const void *src, uint64_t n_wo
     hipLaunchKernelGGL(k_copy_words, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, st, (uint32_t *)dst, (const uint32_t *)src, n_words);
 }
 
+void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc)
+{
+    if (n_tiles) hipLaunchKernelGGL(k_c8_tile_desc, dim3((n_tiles + WG - 1) / WG), dim3(WG), 0, st, cs, tab, tile_contig, n_tiles, desc);
+}
+
 void launch_r8_to_iv(hipStream_t st, const Run8 *r8, uint64_t n, ContigTab tab, pd_iv *out)
 {
     if (!n) return;
@@ -3084,12 +3107,12 @@ void launch_r8_to_iv(hipStream_t st, const Run8 *r8, uint64_t n, ContigTab tab, 
     hipLaunchKernelGGL(k_r8_to_iv, dim3((unsigned)(g > 65536 ? 65536 : g)), dim3(WG), 0, st, r8, n, tab, out);
 }
 
-void launch_direct_c8(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
+void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
                       uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un)
 {
     const DirectWide dw{w, min_dep, part};
     // "direct_un" for a compact sample: 100 x waves-per-SIMD target + loads in flight per thread (0 = default)
-#define PD_C8(WPE_, UN8_) hipLaunchKernelGGL((k_direct_c8<WPE_, UN8_, false>), dim3(grid_tiles), dim3(WG), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, dw, heavy_list, heavy_count, DirectExport{})
+#define PD_C8(WPE_, UN8_) hipLaunchKernelGGL((k_direct_c8<WPE_, UN8_, false>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{})
     switch (un) {
     case 502: PD_C8(5, 2); break;
     case 504: PD_C8(5, 4); break;
@@ -3107,17 +3130,17 @@ void launch_direct_c8(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t
     // <8, 1> 2.42, <5, 2> 2.70 — k_direct_wide3 on the same sample as 12-byte streams: 3.11
     case 704: PD_C8(7, 4); break;
     // the joined tail (JOIN): 1000 + the numbers above
-    case 1803: hipLaunchKernelGGL((k_direct_c8<8, 3, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 1703: hipLaunchKernelGGL((k_direct_c8<7, 3, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 1704: hipLaunchKernelGGL((k_direct_c8<7, 4, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 1802: hipLaunchKernelGGL((k_direct_c8<8, 2, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
+    case 1803: hipLaunchKernelGGL((k_direct_c8<8, 3, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
+    case 1703: hipLaunchKernelGGL((k_direct_c8<7, 3, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
+    case 1704: hipLaunchKernelGGL((k_direct_c8<7, 4, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
+    case 1802: hipLaunchKernelGGL((k_direct_c8<8, 2, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
     // 5000 +: 16-byte loads (two runs per lane and load) for the sorted stream's full chunks
-    case 5704: hipLaunchKernelGGL((k_direct_c8<7, 4, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 5702: hipLaunchKernelGGL((k_direct_c8<7, 2, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 5802: hipLaunchKernelGGL((k_direct_c8<8, 2, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 5706: hipLaunchKernelGGL((k_direct_c8<7, 6, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
+    case 5704: hipLaunchKernelGGL((k_direct_c8<7, 4, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
+    case 5702: hipLaunchKernelGGL((k_direct_c8<7, 2, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
+    case 5802: hipLaunchKernelGGL((k_direct_c8<8, 2, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
+    case 5706: hipLaunchKernelGGL((k_direct_c8<7, 6, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
     // round 4, two streams (ms by the context's events, which also bracket the pile-up and finish launches): <8, 3> 2.35; joined tail: <8, 3> 2.33, <8, 2> 2.07, <7, 3> 2.07, <7, 4> 2.04
-    default: hipLaunchKernelGGL((k_direct_c8<7, 4, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
+    default: hipLaunchKernelGGL((k_direct_c8<7, 4, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
     }
 #undef PD_C8
     WinArgs wa; wa.w = w; wa.min_dep = min_dep; wa.inv_w = 1.0f / (float)w; wa.cover = nullptr; wa.sum = nullptr; wa.part = part;
@@ -3126,11 +3149,11 @@ void launch_direct_c8(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t
                        heavy_count + 1 /* n_long: unused here */, (const uint32_t *)heavy_list, (const uint32_t *)heavy_count, DirectExport{}, cs);
 }
 
-void launch_direct_c8_export(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, void *img, pd_exc *exc,
+void launch_direct_c8_export(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, void *img, pd_exc *exc,
                              uint32_t cap, uint32_t *count, int *sums, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles)
 {
     const DirectExport de{(unsigned short *)img, exc, cap, count, sums};
-    hipLaunchKernelGGL((k_direct_c8<7, 4, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, n_tiles, tab, tile_contig, 0xFFFFFFFFu,
+    hipLaunchKernelGGL((k_direct_c8<7, 4, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, 0xFFFFFFFFu,
                        DirectWide{(uint32_t)TILE, 1u, nullptr}, heavy_list, heavy_count, de);
     WinArgs wa; wa.w = (uint32_t)TILE; wa.min_dep = 1; wa.inv_w = 0.f; wa.cover = nullptr; wa.sum = nullptr; wa.part = nullptr;
     PendSet none{}; none.nb = 0; none.lmax = 0;
