@@ -98,9 +98,11 @@ int pd_push_intervals_device(pd_ctx *ctx, const pd_iv *dev_iv, size_t n, unsigne
 /* A whole sample kept in the engine's COMPACT form (what the GPU decoder leaves for the whole-contig modes): 8 bytes per
  * run — begin inside its contig, already clipped to [0, len] as PD:449-452's cells are, and length — grouped by bucket of
  * 512 cells (the "lmax" look-back bound) with the exact index of every bucket's first run, the contig implied by the run's
- * place.  The direct window path (pd_scan_reduce_windows after pd_keep_deferred, windows of >= 8192 cells; pd_export_i4)
- * then reads a third fewer bytes, tests no contig ids and no bounds, and visits only a tile's own runs and those of the one
- * bucket before it.  pd_runs_create takes the sample as the decoder has it — `dev_sorted`, sorted by (tid, beg) (every read's
+ * place.  The 8 bytes are kept as two arrays of 4-byte words with the same index (one allocation): the low 16 bits of begin
+ * and length in one, the high 16 bits of both in the other.  The direct window path (pd_scan_reduce_windows after
+ * pd_keep_deferred, windows of >= 8192 cells; pd_export_i4) reads the first array only — 4 bytes per run, a third of what
+ * 12-byte runs cost —, tests no contig ids and no bounds, and visits only a tile's own runs and those of the one bucket
+ * before it (a run it takes is no longer than a bucket, so 16 + 16 bits relative to the tile say everything).  pd_runs_create takes the sample as the decoder has it — `dev_sorted`, sorted by (tid, beg) (every read's
  * first run; the order is CHECKED: PD_EINVAL if it does not hold or a contig id is out of range — push such runs the ordinary
  * way), and `dev_other` in any order (the later runs of reads with deletions / skips; may be NULL / 0) — and makes it in a
  * few passes over the runs; both arrays may be freed afterwards.  The object belongs to ctx, stays valid across pd_reset, and

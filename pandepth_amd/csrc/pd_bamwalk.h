@@ -43,7 +43,8 @@ static const uint64_t NONE = ~0ull, STOPPED = 1ull << 62;
 
 // Compact emission (whole-contig modes of a coordinate-sorted file, PD_DECODE_COMPACT): pass 2 writes every read's first run straight to
 // the batch's segment of the sample's sorted stream as 8 bytes — the low 32 bits of its flat begin (cell index in the engine's buffer, the
-// begin clamped to [0, len] as PD:449-452's cells are) and its clamped length —, the first run a lane writes and every run that opens
+// begin clamped to [0, len] as PD:449-452's cells are) and its clamped length, as one R8 or, where the plane pointers are set, as two 4-byte
+// words (lo: the two low halves, hi: the two high halves; pdk::C8Sample) —, the first run a lane writes and every run that opens
 // a new 512-cell bucket leave (batch, index) in marks[bucket] (an atomic minimum: the buckets' first runs in file order, which is all the
 // direct kernels need to find a tile's runs), and the order of the stream is checked on the way: inside a lane, across the lanes of a
 // segment, and (by the host, from SegOut) across segments and batches.
@@ -56,6 +57,7 @@ struct C8Out {
     uint32_t cshift = 0;                  // log2(cells per bucket)
     SegOut *seg_out = nullptr;            // one per segment of the batch (also without r8: 12-byte first runs, keys (tid << 32 | begin))
     uint32_t batch = 0;                   // the batch's number in file order
+    uint32_t *lo = nullptr, *hi = nullptr; // set (r8 null): the first runs leave as two planes of 4-byte words, same index as r8's
 };
 
 struct Cfg {                              // wave-uniform
@@ -206,13 +208,14 @@ struct Pending { uint64_t cig_off, next_p; uint32_t n_cig; int32_t tid, pos; };
 template <bool EMIT>
 PW_FN void first_run(const Cfg &c, LaneWalk &w, int32_t tid, int32_t beg, int32_t end, pd_iv *first, uint64_t of)
 {
-    if (EMIT && c.c8.r8) {                            // compact emission (wave-uniform choice)
+    if (EMIT && (c.c8.r8 || c.c8.lo)) {               // compact emission (wave-uniform choice)
         const uint32_t clen = c.contig_len[tid];
         uint32_t cb = beg < 0 ? 0u : (uint32_t)beg; if (cb > clen) cb = clen;
         uint32_t ce = end < 0 ? 0u : (uint32_t)end; if (ce > clen) ce = clen;
         const uint32_t len = ce > cb ? ce - cb : 0u;
         const uint64_t flat = c.c8.contig_off[tid] + cb, G = of + w.n_first;
-        c.c8.r8[G] = R8{(uint32_t)flat, len};
+        if (c.c8.lo) { c.c8.lo[G] = ((uint32_t)flat & 0xFFFFu) | (len << 16); c.c8.hi[G] = ((uint32_t)flat >> 16) | (len & 0xFFFF0000u); }
+        else c.c8.r8[G] = R8{(uint32_t)flat, len};
         if (w.key_first == NONE || (w.key_last >> c.c8.cshift) != (flat >> c.c8.cshift))
             min_u64(&c.c8.marks[flat >> c.c8.cshift], ((unsigned long long)c.c8.batch << 32) | (uint32_t)G);
         if (w.key_first == NONE) w.key_first = flat; else if (flat < w.key_last) w.unsorted = 1;

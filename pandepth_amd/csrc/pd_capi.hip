@@ -697,7 +697,7 @@ namespace pdi {
 void runs_free(pd_runs *r)
 {
     if (!r) return;
-    if (r->own_r8 && r->r8) (void)hipFree(r->r8);
+    if (r->own_lo && r->lo) (void)hipFree(r->lo);                 // (both planes)
     for (void *q : {(void *)r->b1, (void *)r->iv12}) if (q) (void)hipFree(q);
     delete r;
 }
@@ -710,7 +710,7 @@ uint32_t runs_bshift(const pd_ctx *c)
     return bs;
 }
 
-// The second half of making a compact sample, shared by pd_runs_create and pd_decode_end: the sorted stream is in r->r8[0 .. n_s) and the
+// The second half of making a compact sample, shared by pd_runs_create and pd_decode_end: the sorted stream is in r->lo / r->hi[0 .. n_s) and the
 // first run of every bucket has left its index in r->b1 (everything else 0xFFFFFFFF); `others` are the remaining runs as 12-byte arrays, any
 // order.  Fills the bucket starts of the sorted stream (a suffix minimum over the marks), counts the other runs per bucket, places them
 // behind o_base, and writes the per-tile descriptors (r->td) from the finished bucket starts.  words (device, 2 x uint32, already holding
@@ -728,7 +728,7 @@ void runs_finish(pd_ctx *c, pd_runs *r, const pd_iv *const *others, const size_t
     (void)hipMemsetAsync(hist, 0, 2 * nbw * 4, st);                       // the histogram and the buckets' cursors
     for (int k = 0; k < n_arr; ++k) launch_c8_hist(st, others[k], (uint32_t)n_others[k], tab, r->bshift, hist, words);
     launch_excl_scan_u32(st, hist, r->o1, nb + 1, bs);
-    for (int k = 0; k < n_arr; ++k) launch_c8_place_other(st, others[k], (uint32_t)n_others[k], tab, r->bshift, r->o1, cursor, r->r8 + r->o_base);
+    for (int k = 0; k < n_arr; ++k) launch_c8_place_other(st, others[k], (uint32_t)n_others[k], tab, r->bshift, r->o1, cursor, r->lo + r->o_base, r->hi + r->o_base);
     launch_c8_tile_desc(st, r->view(), tab, c->d_tile_contig, (uint32_t)c->n_tiles, r->td);       // both streams' bucket starts are final
 }
 
@@ -749,22 +749,23 @@ int runs_make(pd_ctx *c, const pd_iv *sorted, size_t n_sorted, const pd_iv *cons
     const uint32_t nb = (uint32_t)nb64;
     const size_t nbw = (size_t)nb + 2;
     uint32_t *tmp = nullptr, *words = nullptr;
-    if (hipMalloc(&r->r8, n * sizeof(Run8) + 64) != hipSuccess || hipMalloc(&r->b1, c8_index_bytes(nbw, c->n_tiles)) != hipSuccess ||
+    if (hipMalloc(&r->lo, n * sizeof(Run8) + 64) != hipSuccess || hipMalloc(&r->b1, c8_index_bytes(nbw, c->n_tiles)) != hipSuccess ||
         hipMalloc(&tmp, (2 * nbw + nb / 1024 + 8) * 4) != hipSuccess || hipMalloc(&words, 16) != hipSuccess) {
         (void)hipGetLastError();
         for (void *q : {(void *)tmp, (void *)words}) if (q) (void)hipFree(q);
         runs_free(r);
         return fail(c, PD_ENOMEM, "pd_runs_create: allocation failed");
     }
+    r->hi = r->lo + n;                                            // one allocation: lo | hi, n words each
     r->o1 = r->b1 + nbw; r->td = (TileDesc *)((uint8_t *)r->b1 + c8_desc_offset(nbw));
     uint32_t h[2] = {0, 0};
     hipStream_t st = c->stream;
     hipError_t e = hipMemsetAsync(words, 0, 16, st);
     if (e == hipSuccess) e = hipMemsetAsync(r->b1, 0xFF, nbw * 4, st);
     if (e == hipSuccess) {
-        // (this first pass is what the GPU decoder's emit kernel does as it writes a file's runs: 8-byte runs in file order, the buckets'
+        // (this first pass is what the GPU decoder's emit kernel does as it writes a file's runs: 8-byte runs in file order as two planes, the buckets'
         // first runs marked)
-        { ProfScope ps(c, "compact_runs"); launch_c8_from_sorted(st, sorted, (uint32_t)n_sorted, tab_of(c), r->bshift, r->r8, r->b1, words); }
+        { ProfScope ps(c, "compact_runs"); launch_c8_from_sorted(st, sorted, (uint32_t)n_sorted, tab_of(c), r->bshift, r->lo, r->hi, r->b1, words); }
         runs_finish(c, r, others, n_others, n_arr, tmp, words);
         e = hipGetLastError();
     }

@@ -70,15 +70,15 @@ using namespace pdi;
 // a whole sample in the compact form (include/pandepth_amd.h: pd_runs_create; layout: C8Sample in pd_kernels.h)
 struct pd_runs {
     pd_ctx *ctx = nullptr;
-    Run8 *r8 = nullptr;                                          // [sorted stream: n_s runs, file order | ... | other runs by bucket at o_base]
+    uint32_t *lo = nullptr, *hi = nullptr;                       // the runs' two planes (C8Sample), one allocation with lo first; each [sorted stream: n_s runs, file order | ... | other runs by bucket at o_base]
     uint32_t n_s = 0, n_o = 0, o_base = 0, n = 0;                // n = n_s + n_o
     uint32_t *b1 = nullptr, *o1 = nullptr;                       // (n_tiles << bshift) + 1 bucket starts per stream (one allocation: b1 | o1 | td, c8_index_bytes)
     TileDesc *td = nullptr;                                      // per tile: what k_direct_c8 reads before the tile's runs (made by runs_finish)
     uint32_t bshift = 4;                                         // 16 buckets of 512 cells per tile
     uint32_t n_long = 0;                                         // runs longer than a bucket: the direct kernels cannot use the sample
     pd_iv *iv12 = nullptr;                                       // the expanded copy, made on first need
-    bool own_r8 = true;                                          // r8 is this object's allocation (false: it lives in the decode session's arena)
-    C8Sample view() const { return C8Sample{r8, b1, o1, o_base, bshift}; }
+    bool own_lo = true;                                          // the planes are this object's allocation (false: they live in the decode session's arena)
+    C8Sample view() const { return C8Sample{lo, hi, b1, o1, o_base, bshift}; }
 };
 
 static inline size_t slice_flag_bytes(uint64_t n_tiles) { return (size_t)((n_tiles + 16 + 15) / 16 * 16); }
@@ -141,7 +141,7 @@ struct pd_ctx {
         uint8_t *h_small = nullptr; size_t h_small_cap = 0;       // pinned: the batch's small tables on their way to and from the device
         void *d[9] = {}; size_t cap[9] = {};                      // (DS_* of pd_decode.hip) blob, inflated, tables (members | segments | member counter), status, lanes, redo list,
                                                                   // ChainOut + per-segment keys (compact emission), and the runs of a batch whose chain the device
-                                                                  // confirms itself: first runs (8 B), later runs (12 B) — copied to exact arrays when the batch is collected
+                                                                  // confirms itself: first runs (8 B; a compact session's as two planes), later runs (12 B) — copied to exact arrays when the batch is collected
         void *d_tok = nullptr; unsigned tok_wg = 0;               // wave scratch (match tokens) and the number of workgroups it was sized for
         // a batch between pd_decode_queue and pd_decode_collect (pd_decode_submit: the two back to back)
         struct Job {
@@ -180,19 +180,20 @@ struct pd_ctx {
     // the end nothing is concatenated or converted: only the marks become indices and the later runs are sorted by bucket.
     struct C8Dec {
         bool on = false;
-        uint8_t *base = nullptr; size_t bytes = 0;               // ONE allocation: [Run8 x (cap_s + cap_o) | pd_iv x cap_o]
+        uint8_t *base = nullptr; size_t bytes = 0;               // ONE allocation: [lo plane x (cap_s + cap_o) | hi plane x (cap_s + cap_o) | pd_iv x cap_o]
         size_t cap_s = 0, cap_o = 0;
         uint32_t *b1 = nullptr; size_t nbw = 0;                  // bucket starts: b1 | o1, nbw words each, then the sample's tile descriptors (c8_index_bytes)
         unsigned long long *marks = nullptr;                     // per bucket: min (batch << 32 | index in the batch) of a run that begins there
         uint32_t bshift = 4;
         uint64_t n_s = 0, n_o = 0, turn = 0, n_batches = 0;
-        struct Batch { bool counted = false; uint64_t nf = 0, no = 0; Run8 *seg_s = nullptr; pd_iv *seg_o = nullptr; hipEvent_t ev = nullptr; };
+        struct Batch { bool counted = false; uint64_t nf = 0, no = 0; uint32_t *seg_s = nullptr; pd_iv *seg_o = nullptr; hipEvent_t ev = nullptr; };   // seg_s: the nf first runs' lo plane, their hi plane c8_plane_words(nf) behind it
         std::vector<Batch> batch;                                // by order
         std::vector<uint32_t> base_s;                            // first place of every batch's first runs in the sorted stream
         hipStream_t compose = nullptr;
         std::string err;                                         // what went wrong while runs were being placed (reported by pd_decode_end)
         std::mutex mu;
-        Run8 *r8() const { return (Run8 *)base; }
+        uint32_t *lo() const { return (uint32_t *)base; }
+        uint32_t *hi() const { return (uint32_t *)base + cap_s + cap_o; }
         pd_iv *oth() const { return (pd_iv *)(base + (cap_s + cap_o) * sizeof(Run8)); }
     } c8;
     uint64_t *ovf = nullptr; uint32_t ovf_cap = 0;    // ends of runs longer than lmax (grown on demand)

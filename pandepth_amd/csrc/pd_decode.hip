@@ -48,6 +48,7 @@ int dec_ensure(pd_ctx *c, DecSlot &sl, int k, size_t bytes)
 uint32_t dec_finish(std::vector<pdb2::Seg> &segs, std::vector<uint32_t> *redo) { return pdb2::check_chain(segs, redo); }
 
 static_assert(sizeof(pdb2::R8) == sizeof(Run8), "the decoder's 8-byte run is the kernels' Run8");
+size_t c8_seg_bytes(uint64_t nf) { return 2 * c8_plane_words((size_t)nf) * 4; }      // a batch's first runs as two planes
 
 // ---- who owns a batch's run arrays: the session's arena (bump allocated, given back as a whole) or an allocation of their own ----
 bool arena_owns(const pd_ctx *c, const void *p) { return c->arena && (const uint8_t *)p >= c->arena && (const uint8_t *)p < c->arena + c->arena_cap; }
@@ -115,7 +116,8 @@ int c8_reserve(pd_ctx *c, uint64_t n_s, uint64_t n_o, bool exact = false)
     if (x.base) {
         ++c->dec_n[pd_ctx::DN_GROW];
         hipError_t e = hipSuccess;
-        if (x.n_s) e = hipMemcpy(nb, x.base, (size_t)x.n_s * sizeof(Run8), hipMemcpyDeviceToDevice);
+        if (x.n_s) e = hipMemcpy(nb, x.lo(), (size_t)x.n_s * 4, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess && x.n_s) e = hipMemcpy(nb + (ns + no) * 4, x.hi(), (size_t)x.n_s * 4, hipMemcpyDeviceToDevice);
         if (e == hipSuccess && x.n_o) e = hipMemcpy(nb + (ns + no) * sizeof(Run8), x.oth(), (size_t)x.n_o * sizeof(pd_iv), hipMemcpyDeviceToDevice);
         (void)hipFree(x.base);
         if (e != hipSuccess) { (void)hipFree(nb); x.base = nullptr; return PD_EHIP; }
@@ -126,7 +128,7 @@ int c8_reserve(pd_ctx *c, uint64_t n_s, uint64_t n_o, bool exact = false)
 
 // A batch has been counted (its runs are being written to its own segment, `ev` follows that kernel): it and every batch behind it whose
 // predecessors are all counted now get their final places, and the copies there are queued on the compose stream.  Nobody waits.
-void c8_counted(pd_ctx *c, uint64_t order, uint64_t nf, uint64_t no, Run8 *seg_s, pd_iv *seg_o, hipEvent_t ev)
+void c8_counted(pd_ctx *c, uint64_t order, uint64_t nf, uint64_t no, uint32_t *seg_s, pd_iv *seg_o, hipEvent_t ev)
 {
     pd_ctx::C8Dec &x = c->c8;
     std::lock_guard<std::mutex> lk(x.mu);
@@ -149,7 +151,7 @@ void c8_counted(pd_ctx *c, uint64_t order, uint64_t nf, uint64_t no, Run8 *seg_s
             }
             if (c8_reserve(c, x.n_s + b.nf, x.n_o + b.no) != PD_OK) e = hipErrorOutOfMemory;
             if (e == hipSuccess && b.ev) e = hipStreamWaitEvent(x.compose, b.ev, 0);
-            if (e == hipSuccess && b.nf) launch_copy_words(x.compose, x.r8() + x.n_s, b.seg_s, b.nf * (sizeof(Run8) / 4));
+            if (e == hipSuccess && b.nf) launch_copy_planes(x.compose, x.lo() + x.n_s, x.hi() + x.n_s, b.seg_s, b.seg_s + c8_plane_words((size_t)b.nf), b.nf);
             if (e == hipSuccess && b.no) launch_copy_words(x.compose, x.oth() + x.n_o, b.seg_o, b.no * (sizeof(pd_iv) / 4));
             if (e == hipSuccess) e = hipGetLastError();
             if (e != hipSuccess && x.err.empty()) x.err = std::string("placing a batch's runs: ") + hipGetErrorString(e);
@@ -172,7 +174,7 @@ struct C8Owes {
     }
 };
 
-// A compact batch's runs are handed to the session: segments of their own for the nf first runs (8 bytes each) and the no later runs
+// A compact batch's runs are handed to the session: segments of their own for the nf first runs (8 bytes each, as two planes) and the no later runs
 // (12 bytes), an event; `fill(seg_s, seg_o)` puts on the slot's stream what writes them (a copy of what the device emitted, or the
 // emission itself) and the event follows it; c8_counted then queues the copies to the runs' final places for every batch whose
 // predecessors are all counted.  The segments and the event are this call's until c8_counted has taken them.
@@ -181,13 +183,13 @@ int c8_hand_over(pd_ctx *c, DecSlot &sl, uint64_t nf, uint64_t no, Fill fill)
 {
     Owned g{c};
     if (nf + no) {
-        if ((nf && !g.grab(0, (size_t)nf * sizeof(Run8))) || (no && !g.grab(1, (size_t)no * sizeof(pd_iv))) ||
+        if ((nf && !g.grab(0, c8_seg_bytes(nf))) || (no && !g.grab(1, (size_t)no * sizeof(pd_iv))) ||
             hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return dec_fail(c, PD_ENOMEM, "run segment allocation failed"); }
-        if (const int rc = fill((Run8 *)g.p[0], (pd_iv *)g.p[1])) return rc;
+        if (const int rc = fill((uint32_t *)g.p[0], (pd_iv *)g.p[1])) return rc;
         HIPDEC(hipEventRecord(g.ev, sl.st));
     }
     sl.job.owes_count = false; g.kept = true;
-    c8_counted(c, sl.job.order, nf, no, (Run8 *)g.p[0], (pd_iv *)g.p[1], g.ev);
+    c8_counted(c, sl.job.order, nf, no, (uint32_t *)g.p[0], (pd_iv *)g.p[1], g.ev);
     return PD_OK;
 }
 
@@ -464,7 +466,7 @@ int dec_size_slot(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, size_t blob
         (rc = dec_ensure(c, sl, DS_BLK, J.o.up)) || (rc = dec_ensure(c, sl, DS_ST, (size_t)bt->n_blocks * 4 + 16)) ||
         (rc = dec_ensure(c, sl, DS_LANE, (size_t)n_seg * 64 * sizeof(pdb2::LaneOut))) ||
         (rc = dec_ensure(c, sl, DS_ONLY, (size_t)n_seg * 4 + 16)) || ((J.c8 || J.fast) && (rc = dec_ensure(c, sl, DS_SEGOUT, sizeof(pdb2::ChainOut) + (size_t)n_seg * sizeof(pdb2::SegOut)))) ||
-        (J.fast && ((rc = dec_ensure(c, sl, DS_R8, (size_t)J.cap_first * (J.c8 ? sizeof(Run8) : sizeof(pd_iv)))) || (rc = dec_ensure(c, sl, DS_OTH, (size_t)J.cap_other * sizeof(pd_iv)))))) return rc;
+        (J.fast && ((rc = dec_ensure(c, sl, DS_R8, J.c8 ? c8_seg_bytes(J.cap_first) : (size_t)J.cap_first * sizeof(pd_iv))) || (rc = dec_ensure(c, sl, DS_OTH, (size_t)J.cap_other * sizeof(pd_iv)))))) return rc;
     if (!sl.d_tok || sl.tok_wg < n_wg) {
         // (the scratch is indexed by workgroup: "inflate_waves" may have been raised since it was sized)
         std::lock_guard<std::mutex> al2(g_alloc_mu);
@@ -565,7 +567,8 @@ int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t 
         launch_chain_segments(st, cfg, d_seg, n_seg, d_lane, (const int *)sl.d[DS_ST], bt->n_blocks, J.cap_first, J.cap_other, c->dec_max_redo, d_co);
         if (J.timed) HIPDEC(hipEventRecord(sl.ev[3], st));
         pdb2::Cfg c2 = cfg;
-        if (c8) c2.c8 = pdb2::C8Out{(pdb2::R8 *)sl.d[DS_R8], x.marks, c->d_off, 13u - x.bshift, (pdb2::SegOut *)(d_co + 1), (uint32_t)bt->order};
+        if (c8) c2.c8 = pdb2::C8Out{nullptr, x.marks, c->d_off, 13u - x.bshift, (pdb2::SegOut *)(d_co + 1), (uint32_t)bt->order,
+                                    (uint32_t *)sl.d[DS_R8], (uint32_t *)sl.d[DS_R8] + c8_plane_words((size_t)J.cap_first)};      // (the slot's array as two planes of cap_first words)
         else { c2.c8 = pdb2::C8Out{}; c2.c8.seg_out = (pdb2::SegOut *)(d_co + 1); }      // (12-byte runs; the order keys ride along)
         launch_emit_segments(st, c2, d_seg, n_seg, d_lane, c8 ? nullptr : (pd_iv *)sl.d[DS_R8], (pd_iv *)sl.d[DS_OTH], nullptr, d_co);
         HIPDEC(hipMemcpyAsync(pin + J.o.co, d_co, sizeof(pdb2::ChainOut) + (size_t)n_seg * sizeof(pdb2::SegOut), hipMemcpyDeviceToHost, st));
@@ -693,13 +696,15 @@ int collect_confirmed(pd_ctx *c, DecSlot &sl, const pdb2::ChainOut &co, pd_decod
     RunSeg rs{J.order, nullptr, nf, nullptr, no, nullptr, 0, co.max_span, 0u, 0ull, 0ull};
     Owned own{c};
     const auto copy_out = [&](void *first, size_t run_bytes, void *other) -> int {
-        if (nf) launch_copy_words(sl.st, first, sl.d[DS_R8], nf * (run_bytes / 4));
+        if (nf && J.c8) launch_copy_planes(sl.st, (uint32_t *)first, (uint32_t *)first + c8_plane_words((size_t)nf), (const uint32_t *)sl.d[DS_R8],
+                                           (const uint32_t *)sl.d[DS_R8] + c8_plane_words((size_t)J.cap_first), nf);      // both planes, one launch
+        else if (nf) launch_copy_words(sl.st, first, sl.d[DS_R8], nf * (run_bytes / 4));
         if (no) launch_copy_words(sl.st, other, sl.d[DS_OTH], no * (sizeof(pd_iv) / 4));
         HIPDEC(hipGetLastError());                                   // (pd_decode_end waits for the slots' streams before it reads these arrays)
         return PD_OK;
     };
     if (J.c8) {
-        if (int rc = c8_hand_over(c, sl, nf, no, [&](Run8 *seg_s, pd_iv *seg_o) { return copy_out(seg_s, sizeof(Run8), seg_o); })) return rc;
+        if (int rc = c8_hand_over(c, sl, nf, no, [&](uint32_t *seg_s, pd_iv *seg_o) { return copy_out(seg_s, sizeof(Run8), seg_o); })) return rc;
     } else if (nf + no) {
         if ((nf && !own.grab(0, (size_t)nf * sizeof(pd_iv))) || (no && !own.grab(1, (size_t)no * sizeof(pd_iv)))) return dec_fail(c, PD_ENOMEM, "run array allocation failed");
         rs.first = (pd_iv *)own.p[0]; rs.other = (pd_iv *)own.p[1];
@@ -771,7 +776,7 @@ RunSeg unit_outcomes(Job &J, const int *bst, int32_t *unit_status, pd_decode_res
     return RunSeg{J.order, nullptr, nf, nullptr, no, nullptr, nfar, max_span, 0u, 0ull, 0ull};
 }
 
-// Pass 2 behind the host's chain check: the runs.  A compact session's pass 2 writes the batch's first runs as 8-byte runs into a segment
+// Pass 2 behind the host's chain check: the runs.  A compact session's pass 2 writes the batch's first runs as 8-byte runs (two planes) into a segment
 // of its own and marks the buckets' first runs (*have_so: the segments' keys are on their way back); otherwise the runs go to 12-byte
 // arrays, which are `own`'s until the batch is listed.
 int collect_emit(pd_ctx *c, DecSlot &sl, RunSeg &rs, Owned &own, bool *have_so)
@@ -790,10 +795,10 @@ int collect_emit(pd_ctx *c, DecSlot &sl, RunSeg &rs, Owned &own, bool *have_so)
     };
     if (J.c8) {
         pdb2::SegOut *d_so = (pdb2::SegOut *)((uint8_t *)sl.d[DS_SEGOUT] + sizeof(pdb2::ChainOut));
-        const int rc = c8_hand_over(c, sl, nf, no, [&](Run8 *seg_s, pd_iv *seg_o) -> int {
+        const int rc = c8_hand_over(c, sl, nf, no, [&](uint32_t *seg_s, pd_iv *seg_o) -> int {
             if (const int ru = segs_up()) return ru;
             pdb2::Cfg cfg = J.cfg;
-            cfg.c8 = pdb2::C8Out{(pdb2::R8 *)seg_s, c->c8.marks, c->d_off, 13u - c->c8.bshift, d_so, (uint32_t)J.order};
+            cfg.c8 = pdb2::C8Out{nullptr, c->c8.marks, c->d_off, 13u - c->c8.bshift, d_so, (uint32_t)J.order, seg_s, seg_s + c8_plane_words((size_t)nf)};
             launch_emit_segments(st, cfg, d_seg, n_seg, d_lane, nullptr, seg_o, nullptr, nullptr);
             return PD_OK;
         });
@@ -1006,7 +1011,7 @@ int compact_to_sample(pd_ctx *c, uint64_t n_long)
 {
     pd_ctx::C8Dec &x = c->c8;
     pd_runs *r = new pd_runs;
-    r->ctx = c; r->r8 = x.r8(); r->own_r8 = true; r->n_s = (uint32_t)x.n_s; r->n_o = (uint32_t)x.n_o; r->n = r->n_s + r->n_o; r->o_base = r->n_s;      // (the later runs go right behind the sorted stream, as in pd_runs_create: what counts is how many runs there ARE, not how many were reserved)
+    r->ctx = c; r->lo = x.lo(); r->hi = x.hi(); r->own_lo = true; r->n_s = (uint32_t)x.n_s; r->n_o = (uint32_t)x.n_o; r->n = r->n_s + r->n_o; r->o_base = r->n_s;      // (the later runs go right behind the sorted stream, as in pd_runs_create: what counts is how many runs there ARE, not how many were reserved)
     r->b1 = x.b1; r->o1 = x.b1 + x.nbw; r->td = (TileDesc *)((uint8_t *)x.b1 + c8_desc_offset(x.nbw)); r->bshift = x.bshift;
     const pd_iv *oth = x.oth(); const size_t no1 = (size_t)x.n_o;
     uint32_t *tmp = nullptr, *words = nullptr, *d_base = nullptr;
@@ -1083,7 +1088,7 @@ int end_compact(pd_ctx *c, const std::vector<RunSeg> &segs, uint32_t span)
     }
     if ((nf && hipMalloc(&c->run_first, (size_t)nf * sizeof(pd_iv)) != hipSuccess) || (no && hipMalloc(&c->run_other, (size_t)no * sizeof(pd_iv)) != hipSuccess)) {
         c8_drop(c); return fail(c, PD_ENOMEM, "pd_decode_end: run array allocation failed"); }
-    if (nf) launch_r8_to_iv(c->stream, x.r8(), nf, tab_of(c), c->run_first);
+    if (nf) launch_r8_to_iv(c->stream, x.lo(), x.hi(), nf, tab_of(c), c->run_first);
     if (no) HIPOK(c, hipMemcpyAsync(c->run_other, x.oth(), (size_t)no * sizeof(pd_iv), hipMemcpyDeviceToDevice, c->stream));
     HIPOK(c, hipGetLastError());
     HIPOK(c, hipStreamSynchronize(c->stream));

@@ -44,18 +44,27 @@ struct CheckWords {           // context-wide, read back at pd_scan / pd_synchro
 #define PD_HALF 4096          /* granularity of the "written since reset" flags */
 
 // A whole sample in the engine's COMPACT form (pd_runs_create; what the GPU decoder leaves for the whole-contig modes): 8 bytes per run —
-// the low 32 bits of its FLAT begin (cell index in the context's buffer; the begin is already clamped to [0, len] of its contig) and its
-// clamped length (0: a run without cells) — in TWO streams, each grouped by bucket of (8192 >> bshift) cells of the flat cell space:
-//   r8[0 ..) / b1        the file's sorted stream (every read's first run) in file order, exactly as the decoder's emit kernel wrote it;
-//                        bucket k's runs are r8[b1[k] .. b1[k + 1])
-//   r8[o_base ..) / o1   the other runs (later runs of reads with deletions / skips), counting-sorted by bucket:
-//                        r8[o_base + o1[k] .. o_base + o1[k + 1]), any order inside
+// the low 32 bits b of its FLAT begin (cell index in the context's buffer; the begin is already clamped to [0, len] of its contig) and its
+// clamped length len (0: a run without cells) — kept as TWO PLANES of 32-bit words with the same index, a lossless split of the 32 + 32 bits:
+//   lo[i] = (b & 0xFFFF) | (len << 16)            the low halves: all the direct kernels read (see k_direct_c8)
+//   hi[i] = (b >> 16)    | (len & 0xFFFF0000)     the high halves: only for who needs the whole run (k_c8_expand, k_r8_to_iv)
+// (one allocation, lo first), each in TWO streams, grouped by bucket of (8192 >> bshift) cells of the flat cell space:
+//   [0 ..) / b1        the file's sorted stream (every read's first run) in file order, exactly as the decoder's emit kernel wrote it;
+//                      bucket k's runs are [b1[k] .. b1[k + 1])
+//   [o_base ..) / o1   the other runs (later runs of reads with deletions / skips), counting-sorted by bucket:
+//                      [o_base + o1[k] .. o_base + o1[k + 1]), any order inside
 // (both streams in ONE array, so that a kernel walking a tile's candidates of both selects a 32-bit index, not a pointer)
-// Contig slots start on tile boundaries, so a tile's own runs are those of its 1 << bshift buckets and all belong to the tile's contig
-// (which is why 32 bits of the begin are enough: a consumer only ever needs a begin relative to the tile it is working on); no run is
-// longer than a bucket, so the only other runs that can reach into tile t are those of the bucket right before it.
-struct Run8 { uint32_t b; uint32_t len; };
-struct C8Sample { const Run8 *r8; const uint32_t *b1, *o1; uint32_t o_base, bshift; };
+// Contig slots start on tile boundaries, so a tile's own runs are those of its 1 << bshift buckets and all belong to the tile's contig; no
+// run of a sample the direct kernels take is longer than a bucket (at most 8192 cells), so the only other runs that can reach into tile t are
+// those of the bucket right before it — every candidate of a tile begins less than 2^16 cells from the tile's first cell and is shorter than
+// 2^16 cells, which is why 16 + 16 bits are all a direct kernel needs.
+struct Run8 { uint32_t b; uint32_t len; };                       // a whole run, as the planes hold it between them
+static inline __host__ __device__ uint32_t c8_lo(uint32_t b, uint32_t len) { return (b & 0xFFFFu) | (len << 16); }
+static inline __host__ __device__ uint32_t c8_hi(uint32_t b, uint32_t len) { return (b >> 16) | (len & 0xFFFF0000u); }
+static inline __host__ __device__ Run8 c8_join(uint32_t lo, uint32_t hi) { return Run8{(lo & 0xFFFFu) | (hi << 16), (lo >> 16) | (hi & 0xFFFF0000u)}; }
+struct C8Sample { const uint32_t *lo, *hi; const uint32_t *b1, *o1; uint32_t o_base, bshift; };
+// a batch of n compact runs on its way (the decoder's segments): lo plane, then the hi plane on a 16-byte boundary
+static inline size_t c8_plane_words(size_t n) { return (n + 3) & ~(size_t)3; }
 // What k_direct_c8 needs to know about a tile before it can fetch the tile's runs, worked out once when the sample is finished (its inputs —
 // b1, o1, the context's contig layout, bshift — are fixed for the sample's life): the candidates' ranges in the two streams ([slo, shi) of
 // b1's numbering, [olo, ohi) of o1's; a contig's first tile does not look back), the tile's first cell inside its contig and the contig's
@@ -90,17 +99,19 @@ void launch_direct_tiles(hipStream_t st, const PendSet &ps, ContigTab tab, const
                          uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un);
 // compact samples: the passes that make one (words: [0] not sorted / invalid contig, [1] runs longer than a bucket), the reverse
 // (12-byte runs, bucket by bucket), and the direct kernels that read them
-void launch_c8_from_sorted(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, Run8 *out, uint32_t *b1 /* pre-set to 0xFF */, uint32_t *words);
+void launch_c8_from_sorted(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *lo, uint32_t *hi, uint32_t *b1 /* pre-set to 0xFF */, uint32_t *words);
 void launch_c8_hist(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *hist, uint32_t *words);
 void launch_excl_scan_u32(hipStream_t st, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *block_sums /* n / 1024 + 2 words */);
 void launch_c8_fill_starts(hipStream_t st, uint32_t *b1, uint32_t n_buckets, uint32_t n_runs, uint32_t *tmp /* n_buckets / 1024 + 2 words */);
 void launch_c8_marks_to_index(hipStream_t st, const unsigned long long *marks, uint32_t n_buckets, const uint32_t *base, uint32_t *b1);
-void launch_c8_place_other(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, const uint32_t *o1, uint32_t *cursor, Run8 *out);
+void launch_c8_place_other(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, const uint32_t *o1, uint32_t *cursor, uint32_t *lo, uint32_t *hi /* both at o_base */);
 void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc);
 void launch_c8_expand(hipStream_t st, C8Sample cs, const uint32_t *tile_contig, const uint64_t *contig_off, uint32_t n_tiles, pd_iv *out);
-void launch_r8_to_iv(hipStream_t st, const Run8 *r8, uint64_t n, ContigTab tab, pd_iv *out);
+void launch_r8_to_iv(hipStream_t st, const uint32_t *lo, const uint32_t *hi, uint64_t n, ContigTab tab, pd_iv *out);
 void launch_copy_words(hipStream_t st, void *dst, const void *src, uint64_t n_words);      // device-to-device, 4-byte words (both pointers 4-byte aligned)
-// (k_direct_c8 itself reads cs.r8, cs.o_base and desc only; tab, tile_contig and the bucket starts in cs serve the int-window pass launched
+// ... and the two planes of n compact runs in ONE launch
+void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, const uint32_t *src_lo, const uint32_t *src_hi, uint64_t n);
+// (k_direct_c8 itself reads cs.lo, cs.o_base and desc only; tab, tile_contig and the bucket starts in cs serve the int-window pass launched
 // behind it for the pile-up tiles)
 void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
                       uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un);

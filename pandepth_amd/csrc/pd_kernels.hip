@@ -1094,7 +1094,7 @@ __global__ __launch_bounds__(WG) void k_direct_tiles_heavy(const PendSet ps, uin
                                                      const uint64_t *win_off, uint32_t *n_long,
                                                      const uint32_t *heavy_list, const uint32_t *heavy_count,
                                                      const DirectExport ex,          // ex.img != null: export instead of statistics
-                                                     const C8Sample cs)              // cs.r8 != null: a compact sample (then ps is empty)
+                                                     const C8Sample cs)              // cs.lo != null: a compact sample (then ps is empty)
 {
     const uint32_t w = wa.w, min_dep = wa.min_dep;
     TilePart *const part = wa.part;
@@ -1163,20 +1163,20 @@ __global__ __launch_bounds__(WG) void k_direct_tiles_heavy(const PendSet ps, uin
                 }
             }
         }
-        if (cs.r8) {                                              // a compact sample: the tile's own buckets and the one before them, in both streams
+        if (cs.lo) {                                              // a compact sample: the tile's own buckets and the one before them, in both streams (16-bit arithmetic: k_direct_c8)
             const uint32_t k0 = (uint32_t)t << cs.bshift, kl = rel < 0 ? k0 - 1 : k0;           // (a contig's first tile has nothing before it)
             const uint32_t a32 = (uint32_t)a;
             for (int strm = 0; strm < 2; ++strm) {
                 const uint32_t *bs = strm ? cs.o1 : cs.b1;
-                const Run8 *r8 = strm ? cs.r8 + cs.o_base : cs.r8;
+                const uint32_t *rl = strm ? cs.lo + cs.o_base : cs.lo;
                 const uint32_t lo = bs[kl], hi = bs[k0 + (1u << cs.bshift)];
                 for (uint32_t i = lo + threadIdx.x; i < hi; i += WG) {
-                    const Run8 r = r8[i];
-                    if (!r.len) continue;
-                    const int64_t sb = (int64_t)(int32_t)(r.b - a32), se = sb + (int64_t)r.len;   // tile-relative (the begins are flat, mod 2^32)
-                    if (sb >= 0 && sb < ST) atomicAdd(&win[sb], 1);
-                    if (se >= 0 && se < ST) atomicAdd(&win[se], -1);
-                    if (sb < 0 && se >= 0) ++carry;
+                    const uint32_t r = rl[i];
+                    if (!(r >> 16)) continue;
+                    const uint32_t sb = (r - a32) & 0xFFFFu, se = sb + (r >> 16), se16 = se & 0xFFFFu;   // tile-relative mod 2^16: a run of the bucket before begins at 2^16 - bucket or later
+                    if (sb < (uint32_t)ST) atomicAdd(&win[sb], 1);
+                    if (se16 < (uint32_t)ST) atomicAdd(&win[se16], -1);
+                    if (se >= 0x10000u) ++carry;
                 }
             }
         }
@@ -1322,11 +1322,11 @@ __device__ __forceinline__ uint64_t c8_flat(const pd_iv v, const ContigTab tab, 
 }
 
 // The sorted stream from 12-byte runs (pd_runs_create; the decoder's emit kernel, pd_bamwalk.h, does the same while it writes its runs):
-// every run becomes 8 bytes — the low 32 bits of its flat begin, its clamped length —, its order is CHECKED against its predecessor
+// every run becomes 8 bytes — the low 32 bits of its flat begin, its clamped length, split over the two planes (C8Sample) —, its order is CHECKED against its predecessor
 // (words[0]: a contig id out of range, or a run that begins before the one in front of it), runs longer than a bucket are counted
 // (words[1]: such a sample is not used in this form), and the first run of every bucket leaves its index in b1[bucket] (pre-set to
 // 0xFFFFFFFF; the buckets nobody begins in are filled by launch_c8_fill_starts).
-__global__ __launch_bounds__(WG) void k_c8_from_sorted(const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, Run8 *out, uint32_t *b1, uint32_t *words)
+__global__ __launch_bounds__(WG) void k_c8_from_sorted(const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *lo, uint32_t *hi, uint32_t *b1, uint32_t *words)
 {
     const uint64_t i64 = (uint64_t)blockIdx.x * WG + threadIdx.x;
     const uint32_t i = i64 < n ? (uint32_t)i64 : n - 1;
@@ -1339,7 +1339,7 @@ __global__ __launch_bounds__(WG) void k_c8_from_sorted(const pd_iv *iv, uint32_t
     if (i64 >= n) return;
     if (!valid || (i > 0 && (!pvalid || gb < prev))) atomicOr(&words[0], 1u);
     if (len > (1u << cshift)) atomicAdd(&words[1], 1u);
-    out[i] = Run8{(uint32_t)gb, len};
+    lo[i] = c8_lo((uint32_t)gb, len); hi[i] = c8_hi((uint32_t)gb, len);
     if (valid && (i == 0 || !pvalid || (prev >> cshift) != (gb >> cshift))) atomicMin(&b1[gb >> cshift], i);
 }
 
@@ -1508,7 +1508,7 @@ __global__ __launch_bounds__(WG) void k_c8_marks_to_index(const unsigned long lo
 // the other streams' runs to their buckets: o1 = exclusive prefix sum of the histogram; the runs of a group of equal neighbours take
 // consecutive places from ONE atomic on the bucket's cursor
 __global__ __launch_bounds__(WG) void k_c8_place_other(const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, const uint32_t *o1,
-                                                       uint32_t *cursor, Run8 *out)
+                                                       uint32_t *cursor, uint32_t *lo, uint32_t *hi)
 {
     const uint32_t cshift = 13u - bshift;
     const int lane = threadIdx.x & 63;
@@ -1521,7 +1521,7 @@ __global__ __launch_bounds__(WG) void k_c8_place_other(const pd_iv *iv, uint32_t
         uint32_t at = 0;
         if (hl == lane && key != 0xFFFFFFFFu) at = o1[key] + atomicAdd(&cursor[key], sz);
         at = (uint32_t)__shfl((int)at, hl);
-        if (key != 0xFFFFFFFFu) out[at + (uint32_t)(lane - hl)] = Run8{(uint32_t)gb, len};
+        if (key != 0xFFFFFFFFu) { const uint32_t j = at + (uint32_t)(lane - hl); lo[j] = c8_lo((uint32_t)gb, len); hi[j] = c8_hi((uint32_t)gb, len); }
     }
 }
 
@@ -1535,12 +1535,12 @@ __global__ __launch_bounds__(WG) void k_c8_expand(const C8Sample cs, const uint3
         const int32_t ctg = (int32_t)tile_contig[t];
         const uint32_t a32 = (uint32_t)((uint64_t)t * TILE), c32 = (uint32_t)contig_off[ctg];
         for (uint32_t i = cs.b1[k0] + threadIdx.x; i < cs.b1[k0 + nbk]; i += WG) {
-            const Run8 r = cs.r8[i];
+            const Run8 r = c8_join(cs.lo[i], cs.hi[i]);
             const uint32_t kb = k0 + ((r.b - a32) >> cshift), beg = r.b - c32;
             out[i + cs.o1[kb]] = pd_iv{ctg, (int32_t)beg, (int32_t)(beg + r.len)};
         }
         for (uint32_t j = cs.o1[k0] + threadIdx.x; j < cs.o1[k0 + nbk]; j += WG) {
-            const Run8 r = cs.r8[cs.o_base + j];
+            const Run8 r = c8_join(cs.lo[cs.o_base + j], cs.hi[cs.o_base + j]);
             const uint32_t kb = k0 + ((r.b - a32) >> cshift), beg = r.b - c32;
             out[j + cs.b1[kb + 1]] = pd_iv{ctg, (int32_t)beg, (int32_t)(beg + r.len)};
         }
@@ -1550,17 +1550,31 @@ __global__ __launch_bounds__(WG) void k_c8_expand(const C8Sample cs, const uint3
 // A batch's runs on their way to their places (a few MB, twice per decode batch): the runtime's device-to-device copy is a blit kernel that
 // took 0.15 ms per call among the decode kernels (13 % of the decode phase's kernel time, profiles/r05_decode_timeline.txt); this one moves
 // 4-byte words with every lane on its own 16 bytes where source and destination allow it.
-__global__ __launch_bounds__(256) void k_copy_words(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, uint64_t n)
+__device__ __forceinline__ void copy_words(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, uint64_t n)
 {
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    if ((((uintptr_t)dst | (uintptr_t)src) & 15) == 0) {
-        const uint64_t n4 = n / 4;
-        uint4 *d4 = reinterpret_cast<uint4 *>(dst); const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-        for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) d4[i] = s4[i];
-        for (uint64_t i = n4 * 4 + (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) dst[i] = src[i];
-        return;
+    const uint64_t stride = (uint64_t)gridDim.x * 256, gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    // up to three words bring the destination to a 16-byte boundary (a plane of 4-byte runs starts anywhere); from there 16-byte stores, and
+    // 16-byte loads where the source is on such a boundary too
+    uint64_t head = ((0 - (uintptr_t)dst) >> 2) & 3; if (head > n) head = n;
+    if (gid < head) dst[gid] = src[gid];
+    dst += head; src += head; n -= head;
+    const uint64_t n4 = n / 4;
+    uint4 *d4 = reinterpret_cast<uint4 *>(dst);
+    if (((uintptr_t)src & 15) == 0) {
+        const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
+        for (uint64_t i = gid; i < n4; i += stride) d4[i] = s4[i];
+    } else {
+        for (uint64_t i = gid; i < n4; i += stride) d4[i] = make_uint4(src[4 * i], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]);
     }
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) dst[i] = src[i];
+    for (uint64_t i = n4 * 4 + gid; i < n; i += stride) dst[i] = src[i];
+}
+__global__ __launch_bounds__(256) void k_copy_words(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, uint64_t n) { copy_words(dst, src, n); }
+// the two planes of n compact runs (C8Sample) in one launch
+__global__ __launch_bounds__(256) void k_copy_planes(uint32_t *__restrict__ dst_lo, uint32_t *__restrict__ dst_hi, const uint32_t *__restrict__ src_lo,
+                                                     const uint32_t *__restrict__ src_hi, uint64_t n)
+{
+    copy_words(dst_lo, src_lo, n);
+    copy_words(dst_hi, src_hi, n);
 }
 
 // The per-tile descriptors of a finished compact sample (TileDesc in pd_kernels.h): one thread per tile reads the bucket starts around the
@@ -1583,34 +1597,38 @@ __global__ __launch_bounds__(WG) void k_c8_tile_desc(const C8Sample cs, const Co
 
 // a sorted stream of compact runs whose sample turned out not to be usable as one (the file's order does not hold after all): back to
 // 12-byte runs; the contig of a flat begin by bisection over the slots (genomes below 2^32 cells only: the caller has made sure)
-__global__ __launch_bounds__(WG) void k_r8_to_iv(const Run8 *r8, uint64_t n, ContigTab tab, pd_iv *out)
+__global__ __launch_bounds__(WG) void k_r8_to_iv(const uint32_t *lo, const uint32_t *hi, uint64_t n, ContigTab tab, pd_iv *out)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * WG) {
-        const Run8 r = r8[i];
-        int lo = 0, hi = tab.n - 1;                               // last contig whose slot starts at or before r.b
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab.off[mid] <= (uint64_t)r.b) lo = mid; else hi = mid - 1; }
-        const uint32_t beg = r.b - (uint32_t)tab.off[lo];
-        out[i] = pd_iv{lo, (int32_t)beg, (int32_t)(beg + r.len)};
+        const Run8 r = c8_join(lo[i], hi[i]);
+        int a = 0, z = tab.n - 1;                               // last contig whose slot starts at or before r.b
+        while (a < z) { const int mid = (a + z + 1) >> 1; if (tab.off[mid] <= (uint64_t)r.b) a = mid; else z = mid - 1; }
+        const uint32_t beg = r.b - (uint32_t)tab.off[a];
+        out[i] = pd_iv{a, (int32_t)beg, (int32_t)(beg + r.len)};
     }
 }
 
 // k_direct_c8 — the wide-window direct kernel on a compact sample: exact bounds, nothing to test but where the two
-// events of a run fall.  Per run (13 vector instructions; k_direct_wide3: 26, on 12-byte runs with a contig compare and clamps):
-//   sb = b - p0 (mod 2^32; b = the low 32 bits of the run's flat begin, p0 those of the tile's first cell): < TILE exactly for the tile's
-//   own runs;  se = sb + len: < TILE when the end lies in the tile;  se < len exactly when the run begins before the tile and reaches
-//   its first cell or further (the carry-in).
+// events of a run fall.  It reads the LO plane only — 4 bytes per run, r = (b & 0xFFFF) | (len << 16) —: every candidate of a tile begins in
+// the tile or in the one bucket before it and is no longer than a bucket (at most 8192 cells), so with p0 the tile's first flat cell
+//   sb = (r - p0) & 0xFFFF: < TILE exactly for the tile's own runs (a run of the bucket before lands in [2^16 - bucket, 2^16));
+//   se = sb + (r >> 16):    its low 16 bits are < TILE exactly when the end lies in the tile;  se >= 2^16 exactly when the run begins
+//   before the tile and reaches its first cell or further (the carry-in)
+// — the same three answers as b - p0, + len and the carry of the full 32 + 32 bits, on half the bytes (k_direct_wide3: 26 vector instructions
+// per run, on 12-byte runs with a contig compare and clamps).
 // A run without cells adds and subtracts at the same cell.  The tile's candidates are its own buckets and the one before them, in
 // BOTH streams of the sample (the file's sorted first runs as the decoder wrote them, and the later runs counting-sorted by bucket):
 // one loop over the two ranges laid end to end.  Same window arithmetic and prefix sum as k_direct_wide3; the statistics of an interior tile
 // take a packed minimum and a packed sum per word (exact loops for the waves that hold a cell below the threshold, and for edge tiles); tiles
 // with more than 32 000 candidates go to the int-window kernel through the same list.
-// V4 (round 6, JOIN only, UN8 even): the full chunks of the sorted stream are fetched 16 bytes per lane — two runs per load, a kilobyte per wave and
-// instruction instead of 512 bytes; which thread works on which run changes, nothing else (the window's updates commute).
-template <int WPE, int UN8, bool EXPORT, bool JOIN = false, bool V4 = false>
+// LW (JOIN only, a divisor of UN8): runs per lane and load in the full chunks of the sorted stream — 1, 2 (8-byte loads) or 4 (16-byte loads; the
+// stream's words are 4-byte aligned, the loads are not); which thread works on which run changes, nothing else (the window's updates commute).
+template <int WPE, int UN8, bool EXPORT, bool JOIN = false, int LW = 1>
 __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const TileDesc *__restrict__ desc, uint32_t n_tiles,
                                                      uint32_t wrap_mask, const DirectWide args, uint32_t *__restrict__ heavy_list,
                                                      uint32_t *__restrict__ heavy_count, const DirectExport ex)
 {
+    static_assert(LW == 1 || (JOIN && (LW == 2 || LW == 4) && UN8 % LW == 0), "wide loads: JOIN form, LW runs per load");
     const uint32_t w = args.w, min_dep = args.min_dep; TilePart *const part = args.part;
     constexpr uint32_t ST = TILE, HT = TILE / 2;
     constexpr int ROWS = (int)(HT / (WG * 4));
@@ -1633,7 +1651,7 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
         const uint32_t olo = cur.olo, no = cur.ohi - olo;         // ... and in the other stream
         const uint32_t cand = ns + no;
         const uint32_t clen = cur.clen;
-        const uint32_t p0 = (uint32_t)a;                          // the runs' begins are flat (mod 2^32), like this
+        const uint32_t p0 = (uint32_t)a & 0xFFFFu;                // the low 16 bits of the tile's first flat cell, like the runs' begins in the lo plane
         const uint32_t pc = cur.pc;                               // the tile's first cell inside its contig
         if (cand > 32000u) {                                      // workgroup-uniform: the int-window kernel does this tile (no LDS touched: no barrier)
             if (threadIdx.x == 0) heavy_list[atomicAdd(heavy_count, 1u)] = (uint32_t)t;
@@ -1646,61 +1664,67 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
             // ONE sequence of chunks: those of the sorted stream's candidates, then those of the other stream's — which stream a chunk
             // belongs to is a scalar decision (base index, position, end), so the double-buffered loop runs through both without a restart
             constexpr uint32_t C = UN8 * WG;
-            const Run8 *__restrict__ const p = cs.r8;
+            const uint32_t *__restrict__ const p = cs.lo;
             // JOIN: the sorted stream's full chunks, then its remainder and the other stream's runs as ONE sequence (a lane picks its array by
             // its index there) — four chunks for the typical tile's 2 730 + 300 candidates instead of four + one
             const uint32_t c1 = JOIN ? ns / C : (ns + C - 1) / C;
             const uint32_t rem = JOIN ? ns - c1 * C : 0u, tail = rem + no;
             const uint32_t nq = c1 + ((JOIN ? tail : no) + C - 1) / C;
             const uint32_t o_at = cs.o_base + olo;
-            auto load8 = [&](uint2 (&dst)[UN8], const uint32_t q) {
+            // slot k of a lane is run slot(k) of its chunk
+            auto slot = [&](const int k) -> uint32_t { return (uint32_t)LW * (threadIdx.x + (uint32_t)(k / LW) * WG) + (uint32_t)(k % LW); };
+            auto load8 = [&](uint32_t (&dst)[UN8], const uint32_t q) {
                 const bool second = q >= c1;
                 if constexpr (JOIN) {
                     if (!second) {
-                        if constexpr (V4) {
+                        const uint32_t *const pq = p + (s_at + q * C);
+                        if constexpr (LW == 4) {
+#pragma unroll
+                            for (int k4 = 0; k4 < UN8 / 4; ++k4) {
+                                const uint4 u = *reinterpret_cast<const uint4 *>(pq + slot(4 * k4));
+                                dst[4 * k4] = u.x; dst[4 * k4 + 1] = u.y; dst[4 * k4 + 2] = u.z; dst[4 * k4 + 3] = u.w;
+                            }
+                        } else if constexpr (LW == 2) {
 #pragma unroll
                             for (int k2 = 0; k2 < UN8 / 2; ++k2) {
-                                const uint4 u = *reinterpret_cast<const uint4 *>(p + (s_at + q * C + 2u * (threadIdx.x + k2 * WG)));
-                                dst[2 * k2] = make_uint2(u.x, u.y); dst[2 * k2 + 1] = make_uint2(u.z, u.w);
+                                const uint2 u = *reinterpret_cast<const uint2 *>(pq + slot(2 * k2));
+                                dst[2 * k2] = u.x; dst[2 * k2 + 1] = u.y;
                             }
                         } else {
 #pragma unroll
-                        for (int k = 0; k < UN8; ++k) dst[k] = *reinterpret_cast<const uint2 *>(p + (s_at + q * C + threadIdx.x + k * WG));
+                            for (int k = 0; k < UN8; ++k) dst[k] = pq[slot(k)];
                         }
                     } else {
                         const uint32_t i = (q - c1) * C, s_rem = s_at + c1 * C, o_rem = o_at - rem, last = tail - 1u;
 #pragma unroll
                         for (int k = 0; k < UN8; ++k) {
-                            uint32_t j = i + (V4 ? 2u * (threadIdx.x + (k >> 1) * WG) + (k & 1) : threadIdx.x + k * WG); j = j < last ? j : last;
-                            dst[k] = *reinterpret_cast<const uint2 *>(p + ((j < rem ? s_rem : o_rem) + j));
+                            uint32_t j = i + slot(k); j = j < last ? j : last;
+                            dst[k] = p[(j < rem ? s_rem : o_rem) + j];
                         }
                     }
                     return;
                 }
                 const uint32_t at = second ? o_at : s_at, i = (second ? q - c1 : q) * C, last = (second ? no : ns) - 1u;
 #pragma unroll
-                for (int k = 0; k < UN8; ++k) { const uint32_t j = i + threadIdx.x + k * WG; dst[k] = *reinterpret_cast<const uint2 *>(p + (at + (j < last ? j : last))); }
+                for (int k = 0; k < UN8; ++k) { const uint32_t j = i + threadIdx.x + k * WG; dst[k] = p[at + (j < last ? j : last)]; }
             };
-            auto ev8 = [&](const uint32_t b, const uint32_t len) {
-                const uint32_t sb = b - p0, se = sb + len;
-                const unsigned long long m_c = __builtin_amdgcn_ballot_w64(se < len);
+            auto ev8 = [&](const uint32_t r) {
+                const uint32_t sb = (r - p0) & 0xFFFFu, se = sb + (r >> 16), se16 = se & 0xFFFFu;
+                const unsigned long long m_c = __builtin_amdgcn_ballot_w64(se >= 0x10000u);
                 if (sb < ST) atomicAdd(&win[sb & (HT - 1u)], 1u + (sb >> 12) * 0xFFFFu);
-                if (se < ST) atomicSub(&win[se & (HT - 1u)], 1u + (se >> 12) * 0xFFFFu);
+                if (se16 < ST) atomicSub(&win[se16 & (HT - 1u)], 1u + (se16 >> 12) * 0xFFFFu);
                 carry_s += __builtin_popcountll(m_c);
             };
-            auto work8 = [&](const uint2 (&c)[UN8], const uint32_t q) {
+            auto work8 = [&](const uint32_t (&c)[UN8], const uint32_t q) {
                 const bool second = q >= c1;
                 const uint32_t left = JOIN ? (second ? tail - (q - c1) * C : C) : (second ? no : ns) - (second ? q - c1 : q) * C;
                 if (left >= C) {
 #pragma unroll
-                    for (int k = 0; k < UN8; ++k) ev8(c[k].x, c[k].y);
+                    for (int k = 0; k < UN8; ++k) ev8(c[k]);
                 } else {                                          // a stream's tail chunk: slots past the end become runs outside the tile
-                    const int nu = V4 ? 2 * (int)((left + 2 * WG - 1) / (2 * WG)) : (int)((left + WG - 1) / WG);   // uniform, 1 .. UN8
+                    const int nu = LW * (int)((left + LW * WG - 1) / (LW * WG));   // uniform, 1 .. UN8
 #pragma unroll
-                    for (int k = 0; k < UN8; ++k) if (k < nu) {
-                        const bool in = (V4 ? 2u * (threadIdx.x + (k >> 1) * WG) + (k & 1) : threadIdx.x + k * WG) < left;
-                        ev8(in ? c[k].x : p0 + ST, in ? c[k].y : 0u);
-                    }
+                    for (int k = 0; k < UN8; ++k) if (k < nu) ev8(slot(k) < left ? c[k] : (p0 + ST) & 0xFFFFu);
                 }
             };
             auto clear_window = [&]() {                           // ... and the next tile's descriptor: behind the run loads, so that the wait in front of the barrier covers both
@@ -1711,7 +1735,7 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
             };
             if (!nq) clear_window();                              // (workgroup-uniform: every thread meets one of the two barriers)
             else {
-                uint2 A[UN8], B[UN8];
+                uint32_t A[UN8], B[UN8];
                 uint32_t q = 0;
                 load8(A, q);                                      // the first chunk is on its way before the window is cleared: nothing it needs is in LDS
                 clear_window();
@@ -3037,10 +3061,10 @@ void launch_direct_tiles(hipStream_t st, const PendSet &ps, ContigTab tab, const
 
 static unsigned grid_1k(uint64_t n) { return (unsigned)((n + 1023) / 1024 ? (n + 1023) / 1024 : 1); }
 
-void launch_c8_from_sorted(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, Run8 *out, uint32_t *b1, uint32_t *words)
+void launch_c8_from_sorted(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *lo, uint32_t *hi, uint32_t *b1, uint32_t *words)
 {
     if (!n) return;
-    hipLaunchKernelGGL(k_c8_from_sorted, dim3((unsigned)(((uint64_t)n + WG - 1) / WG)), dim3(WG), 0, st, iv, n, tab, bshift, out, b1, words);
+    hipLaunchKernelGGL(k_c8_from_sorted, dim3((unsigned)(((uint64_t)n + WG - 1) / WG)), dim3(WG), 0, st, iv, n, tab, bshift, lo, hi, b1, words);
 }
 
 void launch_c8_hist(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *hist, uint32_t *words)
@@ -3076,11 +3100,11 @@ void launch_c8_marks_to_index(hipStream_t st, const unsigned long long *marks, u
     hipLaunchKernelGGL(k_c8_marks_to_index, dim3((unsigned)(((uint64_t)n_buckets + WG - 1) / WG)), dim3(WG), 0, st, marks, n_buckets, base, b1);
 }
 
-void launch_c8_place_other(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, const uint32_t *o1, uint32_t *cursor, Run8 *out)
+void launch_c8_place_other(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, const uint32_t *o1, uint32_t *cursor, uint32_t *lo, uint32_t *hi)
 {
     if (!n) return;
     const uint64_t g = ((uint64_t)n + WG - 1) / WG;
-    hipLaunchKernelGGL(k_c8_place_other, dim3((unsigned)(g > 65536 ? 65536 : g)), dim3(WG), 0, st, iv, n, tab, bshift, o1, cursor, out);
+    hipLaunchKernelGGL(k_c8_place_other, dim3((unsigned)(g > 65536 ? 65536 : g)), dim3(WG), 0, st, iv, n, tab, bshift, o1, cursor, lo, hi);
 }
 
 void launch_c8_expand(hipStream_t st, C8Sample cs, const uint32_t *tile_contig, const uint64_t *contig_off, uint32_t n_tiles, pd_iv *out)
@@ -3095,16 +3119,23 @@ void launch_copy_words(hipStream_t st, void *dst, const void *src, uint64_t n_wo
     hipLaunchKernelGGL(k_copy_words, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, st, (uint32_t *)dst, (const uint32_t *)src, n_words);
 }
 
+void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, const uint32_t *src_lo, const uint32_t *src_hi, uint64_t n)
+{
+    if (!n) return;
+    const uint64_t g = (n / 4 + 255) / 256 + 1;
+    hipLaunchKernelGGL(k_copy_planes, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, st, dst_lo, dst_hi, src_lo, src_hi, n);
+}
+
 void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc)
 {
     if (n_tiles) hipLaunchKernelGGL(k_c8_tile_desc, dim3((n_tiles + WG - 1) / WG), dim3(WG), 0, st, cs, tab, tile_contig, n_tiles, desc);
 }
 
-void launch_r8_to_iv(hipStream_t st, const Run8 *r8, uint64_t n, ContigTab tab, pd_iv *out)
+void launch_r8_to_iv(hipStream_t st, const uint32_t *lo, const uint32_t *hi, uint64_t n, ContigTab tab, pd_iv *out)
 {
     if (!n) return;
     const uint64_t g = (n + WG - 1) / WG;
-    hipLaunchKernelGGL(k_r8_to_iv, dim3((unsigned)(g > 65536 ? 65536 : g)), dim3(WG), 0, st, r8, n, tab, out);
+    hipLaunchKernelGGL(k_r8_to_iv, dim3((unsigned)(g > 65536 ? 65536 : g)), dim3(WG), 0, st, lo, hi, n, tab, out);
 }
 
 void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
@@ -3130,18 +3161,29 @@ void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigT
     // <8, 1> 2.42, <5, 2> 2.70 — k_direct_wide3 on the same sample as 12-byte streams: 3.11
     case 704: PD_C8(7, 4); break;
     // the joined tail (JOIN): 1000 + the numbers above
-    case 1803: hipLaunchKernelGGL((k_direct_c8<8, 3, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 1703: hipLaunchKernelGGL((k_direct_c8<7, 3, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 1704: hipLaunchKernelGGL((k_direct_c8<7, 4, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 1802: hipLaunchKernelGGL((k_direct_c8<8, 2, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    // 5000 +: 16-byte loads (two runs per lane and load) for the sorted stream's full chunks
-    case 5704: hipLaunchKernelGGL((k_direct_c8<7, 4, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 5702: hipLaunchKernelGGL((k_direct_c8<7, 2, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 5802: hipLaunchKernelGGL((k_direct_c8<8, 2, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
-    case 5706: hipLaunchKernelGGL((k_direct_c8<7, 6, false, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
+#define PD_C8J(WPE_, UN8_, LW_) hipLaunchKernelGGL((k_direct_c8<WPE_, UN8_, false, true, LW_>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{})
+    case 1803: PD_C8J(8, 3, 1); break;
+    case 1703: PD_C8J(7, 3, 1); break;
+    case 1704: PD_C8J(7, 4, 1); break;
+    case 1802: PD_C8J(8, 2, 1); break;
+    case 1708: PD_C8J(7, 8, 1); break;
+    // 5000 +: 8-byte loads (two runs per lane and load) for the sorted stream's full chunks
+    case 5704: PD_C8J(7, 4, 2); break;
+    case 5702: PD_C8J(7, 2, 2); break;
+    case 5802: PD_C8J(8, 2, 2); break;
+    case 5706: PD_C8J(7, 6, 2); break;
+    case 5708: PD_C8J(7, 8, 2); break;
+    case 5608: PD_C8J(6, 8, 2); break;
+    // 9000 +: 16-byte loads (four runs per lane and load)
+    case 9704: PD_C8J(7, 4, 4); break;
+    case 9708: PD_C8J(7, 8, 4); break;
+    case 9608: PD_C8J(6, 8, 4); break;
     // round 4, two streams (ms by the context's events, which also bracket the pile-up and finish launches): <8, 3> 2.35; joined tail: <8, 3> 2.33, <8, 2> 2.07, <7, 3> 2.07, <7, 4> 2.04
-    default: hipLaunchKernelGGL((k_direct_c8<7, 4, false, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); break;
+    // round 9, 4-byte runs (lo plane), the same events on the bench sample: <7, 4> 1.390, <6, 8> with 8-byte loads 1.384, <8, 4> plain 1.390, <7, 8> 1.392, <7, 4> with 8- / 16-byte
+    // loads 1.416 / 1.407, <6, 8> with 16-byte loads 1.438, <7, 8> with 8- / 16-byte loads 1.605 / 1.811 (spills) — loads in flight no longer decide (profiles/r09_runs_planes_ab.txt)
+    default: PD_C8J(7, 4, 1); break;
     }
+#undef PD_C8J
 #undef PD_C8
     WinArgs wa; wa.w = w; wa.min_dep = min_dep; wa.inv_w = 1.0f / (float)w; wa.cover = nullptr; wa.sum = nullptr; wa.part = part;
     PendSet none{}; none.nb = 0; none.lmax = 0;
