@@ -199,6 +199,16 @@ int pd_depth_quantiles(pd_ctx *ctx, const pd_region *segs, size_t n_segs, const 
 /* the same for the windows of pd_window_layout(w) (row = window win_off[t] + k), without a region list crossing the link */
 int pd_window_quantiles(pd_ctx *ctx, uint32_t w, const uint32_t *pct, uint32_t n_pct, uint32_t *q);
 
+/* Cells at or above given depths, of many rows at once, counted on the device in one pass over the cells.  After pd_scan.  Rows,
+ * segments and their errors are those of pd_depth_quantiles.  thr: 1..16 strictly ascending values, else PD_EINVAL.
+ * cells[i] = cells of row i (may be NULL); counts[i * n_thr + j] = the number of cells of row i whose value is >= thr[j] (uint64: a
+ * multiset row can hold more than 2^32 cells); a row without cells gives zeros.  Only the results cross the link; device scratch
+ * stays below 256 MiB whatever the number of rows (rows are served in batches).  The context is left as it was found. */
+int pd_depth_thresholds(pd_ctx *ctx, const pd_region *segs, size_t n_segs, const uint64_t *row_off, size_t n_rows,
+                        const uint32_t *thr, uint32_t n_thr, uint64_t *cells, uint64_t *counts);
+/* the same for the windows of pd_window_layout(w) (row = window win_off[t] + k), without a region list crossing the link */
+int pd_window_thresholds(pd_ctx *ctx, uint32_t w, const uint32_t *thr, uint32_t n_thr, uint32_t *counts);
+
 /* Replaces the per-site read loop PD:4278-4281: copies depth cells [beg, beg+n) of contig tid
  * to the host.  Requires pd_scan first. */
 int pd_read_depth(pd_ctx *ctx, int32_t tid, uint32_t beg, size_t n, uint32_t *out);
@@ -389,7 +399,7 @@ int pd_synchronize(pd_ctx *ctx);
  * ("reset", "fill", "scatter_index", "scatter_tiles", "scatter_finish", "scatter_atomic", "tile_carry",
  * "scan", "scan_reduce_windows", "reduce_intervals", "reduce_windows", "direct_tiles", "direct_export",
  * "export_i4", "export_i8", "import_i8", "slice_sweep", "gather_windows", "accumulate_from",
- * "quantile_narrow", "quantile_block", "quantile_pieces", "quantile_pick");
+ * "quantile_narrow", "quantile_block", "quantile_pieces", "quantile_pick", "threshold_narrow", "threshold_pieces");
  * pd_profile(ctx, 0/1) switches it (and clears the accumulators).
  * Names that begin with "decode_" are counters of the last decode session (counted whether or not profiling is on, cleared by
  * pd_decode_begin; *ms is 0): which way pd_decode_end went — "decode_end_compact" (the compact session's sample), "decode_end_c8_fallback"

@@ -23,7 +23,10 @@ extern "C" {
  * + the tables / the members read in place: all measured slower), "decode_warm" (1: the session's first slots made ready by a helper thread).
  * Quantiles: "quantile_wave_max" (0..2048, default 512: rows of up to that many cells are selected by a group of lanes from LDS),
  * "quantile_split_cells" (default 262144: rows of up to that many cells are one workgroup's LDS histogram; longer rows are cut into pieces
- * over many workgroups).  0 / 0 sends every row through the pieces, 0 / 2^32-1 every row through one workgroup. */
+ * over many workgroups).  0 / 0 sends every row through the pieces, 0 / 2^32-1 every row through one workgroup.
+ * Thresholds: "threshold_wave_max" (below 2^32, default 65536: rows of up to that many cells are counted by a group of lanes with one
+ * writer per row; longer rows are cut into pieces of 16384 cells, a wave each, that add into the row).  0 sends every row with cells
+ * through the pieces, 2^32-1 every row through the lanes. */
 int pd_set_param(pd_ctx *ctx, const char *name, uint64_t value);
 
 /* ---- GPU-side BAM decode, the one-call synchronous form (round 1's entry point, kept on top of

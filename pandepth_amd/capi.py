@@ -107,6 +107,8 @@ def load():
         "pd_depth_levels": (I, [P, ctypes.c_int32, ctypes.c_uint32, SZ, P, ctypes.c_uint32, P, SZ, ctypes.POINTER(SZ)]),
         "pd_depth_quantiles": (I, [P, P, SZ, P, SZ, P, ctypes.c_uint32, P, P]),
         "pd_window_quantiles": (I, [P, ctypes.c_uint32, P, ctypes.c_uint32, P]),
+        "pd_depth_thresholds": (I, [P, P, SZ, P, SZ, P, ctypes.c_uint32, P, P]),
+        "pd_window_thresholds": (I, [P, ctypes.c_uint32, P, ctypes.c_uint32, P]),
         "pd_read_depth": (I, [P, ctypes.c_int32, ctypes.c_uint32, SZ, P]),
         "pd_format_sites": (I, [P, ctypes.c_int32, ctypes.c_uint32, SZ, ctypes.c_char_p, SZ, P, SZ, ctypes.POINTER(SZ)]),
         "pd_deflate_parse": (I, [P, P, SZ, P, ctypes.c_uint32, P, SZ, P]),
@@ -169,7 +171,7 @@ def load():
 
 EXPORTS = ["pd_abi_version", "pd_create", "pd_destroy", "pd_strerror", "pd_reset", "pd_push_intervals",
            "pd_push_intervals_device", "pd_runs_create", "pd_runs_destroy", "pd_push_runs", "pd_stage_acquire", "pd_stage_submit", "pd_set_param", "pd_keep_deferred", "pd_scan",
-           "pd_reduce_intervals", "pd_window_layout", "pd_scan_reduce_windows", "pd_reduce_windows", "pd_scan_depth_histogram", "pd_depth_histogram", "pd_depth_levels", "pd_depth_quantiles", "pd_window_quantiles",
+           "pd_reduce_intervals", "pd_window_layout", "pd_scan_reduce_windows", "pd_reduce_windows", "pd_scan_depth_histogram", "pd_depth_histogram", "pd_depth_levels", "pd_depth_quantiles", "pd_window_quantiles", "pd_depth_thresholds", "pd_window_thresholds",
            "pd_read_depth", "pd_format_sites", "pd_deflate_parse", "pd_host_register", "pd_host_unregister", "pd_text_open", "pd_text_close", "pd_text_append_sites", "pd_text_parse", "pd_text_read", "pd_text_release", "pd_text_append_window_rows", "pd_text_append_bytes", "pd_device_buffer", "pd_device_count", "pd_accumulate_from", "pd_device_layout", "pd_export_i8", "pd_import_i8", "pd_export_i4",
            "pd_slice_sweep_i4", "pd_gather_windows", "pd_push_bgzf_units", "pd_decode_begin", "pd_decode_acquire", "pd_decode_submit", "pd_decode_queue", "pd_decode_collect", "pd_decode_end", "pd_decode_abort", "pd_comm_unique_id", "pd_comm_init", "pd_comm_init_all", "pd_comm_init_local", "pd_comm_preinit", "pd_comm_prepare", "pd_comm_destroy",
            "pd_comm_strerror", "pd_sliced_window_sum", "pd_sliced_interval_sum", "pd_sliced_sum_start", "pd_sliced_sum_finish", "pd_x_bgzf_inflate", "pd_stream", "pd_synchronize", "pd_profile",
@@ -474,6 +476,30 @@ class Engine:
         pcb = pc if npc else np.zeros(1, dtype=np.uint32)
         self._ck(self.L.pd_window_quantiles(self.h, int(w), _ptr(pcb), npc, _ptr(q)))
         return off, q[:n]
+
+    def depth_thresholds(self, segs, row_off, thr):
+        """pd_depth_thresholds after scan: rows as in depth_quantiles; returns (cells uint64 (n_rows,), counts uint64
+        (n_rows, len(thr))), counts[i, j] = the number of cells of row i that are >= thr[j] (zeros for a row without cells)."""
+        sg = np.ascontiguousarray(segs, dtype=np.int32).reshape(-1, 3)
+        ro = np.ascontiguousarray(row_off, dtype=np.uint64)
+        th = np.ascontiguousarray(thr, dtype=np.uint32)
+        n_rows, nt = int(ro.size) - 1, int(th.size)
+        cells = np.zeros(max(n_rows, 1), dtype=np.uint64)
+        counts = np.zeros((max(n_rows, 1), max(nt, 1)), dtype=np.uint64)
+        thb = th if nt else np.zeros(1, dtype=np.uint32)
+        self._ck(self.L.pd_depth_thresholds(self.h, _ptr(sg) if sg.shape[0] else None, sg.shape[0], _ptr(ro), n_rows, _ptr(thb), nt, _ptr(cells), _ptr(counts)))
+        return cells[:n_rows], counts[:n_rows]
+
+    def window_thresholds(self, w, thr):
+        """pd_window_thresholds after scan: (win_off, counts uint32 (n_windows, len(thr))) for the windows of window_layout(w)."""
+        off = self.window_layout(w)
+        n = int(off[-1])
+        th = np.ascontiguousarray(thr, dtype=np.uint32)
+        nt = int(th.size)
+        counts = np.zeros((max(n, 1), max(nt, 1)), dtype=np.uint32)
+        thb = th if nt else np.zeros(1, dtype=np.uint32)
+        self._ck(self.L.pd_window_thresholds(self.h, int(w), _ptr(thb), nt, _ptr(counts)))
+        return off, counts[:n]
 
     def read_depth(self, tid, beg=0, n=None):
         if n is None:

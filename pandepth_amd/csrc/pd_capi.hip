@@ -685,6 +685,7 @@ int pd_set_param(pd_ctx *c, const char *name, uint64_t value)
     if (!strcmp(name, "decode_max_redo")) { c->dec_max_redo = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "hist_variant")) { if (value > 3) return fail(c, PD_EINVAL, "hist_variant must be in [0, 3]"); c->hist_variant = (int)value; return PD_OK; }
     if (!strcmp(name, "quantile_wave_max")) { if (value > 2048) return fail(c, PD_EINVAL, "quantile_wave_max must be in [0, 2048]"); c->q_wave_max = (uint32_t)value; return PD_OK; }
+    if (!strcmp(name, "threshold_wave_max")) { if (value > 0xFFFFFFFFull) return fail(c, PD_EINVAL, "threshold_wave_max must be below 2^32"); c->t_wave_max = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "quantile_split_cells")) { if (value > 0xFFFFFFFFull) return fail(c, PD_EINVAL, "quantile_split_cells must be below 2^32"); c->q_split = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "decode_near_span")) { c->dec_near_span = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
     return fail(c, PD_EINVAL, std::string("unknown parameter ") + name);
@@ -1366,6 +1367,84 @@ inline int quant_add_pieces(pd_ctx *c, std::vector<Piece> &pieces, uint64_t star
     }
     return PD_OK;
 }
+
+// What pd_depth_quantiles and pd_depth_thresholds share: the checks of a row list, the clipping of a segment to its contig, and
+// the batches in which the rows go up (at most 2^20 rows and 2^21 segments; a row alone always fits).
+constexpr size_t ROW_BATCH = (size_t)1 << 20;
+
+int rows_check(pd_ctx *c, const char *fn, const pd_region *segs, size_t n_segs, const uint64_t *row_off, size_t n_rows)
+{
+    const std::string f(fn);
+    if (row_off[0] != 0 || row_off[n_rows] != n_segs) return fail(c, PD_EINVAL, f + ": row_off must run from 0 to n_segs");
+    for (size_t i = 0; i < n_rows; ++i) {
+        if (row_off[i + 1] < row_off[i] || row_off[i + 1] > n_segs) return fail(c, PD_EINVAL, f + ": row_off must not decrease");
+        if (row_off[i + 1] - row_off[i] > Q_SEG_BATCH) return fail(c, PD_EINVAL, f + ": at most 2^21 segments per row");
+    }
+    for (size_t i = 0; i < n_segs; ++i)
+        if (segs[i].tid < 0 || segs[i].tid >= c->n_contigs) return fail(c, PD_EINVAL, f + ": contig id out of range");
+    return PD_OK;
+}
+
+inline void seg_clip(const pd_ctx *c, const pd_region &r, uint64_t *start, uint64_t *count)
+{
+    int64_t b = (int64_t)r.first - 1, e = r.second;
+    if (b < 0) b = 0;
+    if (e > (int64_t)c->len[(size_t)r.tid]) e = (int64_t)c->len[(size_t)r.tid];
+    *start = c->off[(size_t)r.tid] + (uint64_t)b; *count = e > b ? (uint64_t)(e - b) : 0;
+}
+
+// the batch at hand, on the host (rows [r0, r1): their clipped segments, the segment offsets, the rows of every launch shape by
+// their number in the batch, the largest row of shape 0) and its copies in the scratch
+struct RowBatches {
+    Piece *d_seg; uint64_t *d_off; uint32_t *d_list[3];
+    std::vector<Piece> hseg; std::vector<uint64_t> hoff; std::vector<uint32_t> list[3];
+    size_t r0 = 0, r1 = 0; uint32_t cap = 0;
+    static size_t b_seg(size_t n_segs) { return q_al(std::min<size_t>(Q_SEG_BATCH, n_segs) * sizeof(Piece)); }
+    static size_t b_off(size_t n_rows) { return q_al((std::min(ROW_BATCH, n_rows) + 1) * 8); }
+    static size_t b_list(size_t n_rows) { return q_al(std::min(ROW_BATCH, n_rows) * 4); }
+    static size_t bytes(size_t n_rows, size_t n_segs) { return b_seg(n_segs) + b_off(n_rows) + 3 * b_list(n_rows); }
+    unsigned char *carve(unsigned char *s, size_t n_rows, size_t n_segs)
+    {
+        d_seg = (Piece *)s; s += b_seg(n_segs);
+        d_off = (uint64_t *)s; s += b_off(n_rows);
+        for (int k = 0; k < 3; ++k) { d_list[k] = (uint32_t *)s; s += b_list(n_rows); }
+        return s;
+    }
+};
+
+// regime(cells of a row) = its launch shape, 0 .. 2; serve(R) launches over the batch in B and brings its results back
+template <class Regime, class Serve>
+int rows_serve(pd_ctx *c, const pd_region *segs, const uint64_t *row_off, size_t n_rows, const uint64_t *cells, RowBatches &B, Regime regime, Serve serve)
+{
+    for (size_t r0 = 0; r0 < n_rows;) {
+        size_t r1 = r0;
+        while (r1 < n_rows && r1 - r0 < ROW_BATCH && row_off[r1 + 1] - row_off[r0] <= Q_SEG_BATCH) ++r1;     // (a row alone always fits)
+        B.r0 = r0; B.r1 = r1; B.cap = 0;
+        B.hseg.clear(); B.hoff.clear(); for (auto &l : B.list) l.clear();
+        for (size_t i = r0; i < r1; ++i) {
+            B.hoff.push_back(B.hseg.size());
+            for (uint64_t k = row_off[i]; k < row_off[i + 1]; ++k) {
+                uint64_t st, cn; seg_clip(c, segs[k], &st, &cn);
+                Piece pc; pc.start = st; pc.count = (uint32_t)cn; pc.region = 0;
+                B.hseg.push_back(pc);
+            }
+            const uint64_t C = cells[i];
+            const int rg = regime(C);
+            if (rg == 0) B.cap = std::max(B.cap, (uint32_t)C);
+            B.list[rg].push_back((uint32_t)(i - r0));
+        }
+        B.hoff.push_back(B.hseg.size());
+        if (!B.hseg.empty()) HIPOK(c, hipMemcpyAsync(B.d_seg, B.hseg.data(), B.hseg.size() * sizeof(Piece), hipMemcpyHostToDevice, c->stream));
+        HIPOK(c, hipMemcpyAsync(B.d_off, B.hoff.data(), B.hoff.size() * 8, hipMemcpyHostToDevice, c->stream));
+        for (int k = 0; k < 3; ++k)
+            if (!B.list[k].empty()) HIPOK(c, hipMemcpyAsync(B.d_list[k], B.list[k].data(), B.list[k].size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(c, hipStreamSynchronize(c->stream));          // the host arrays are refilled by the next batch
+        const pdk::QRows R{B.d_seg, B.d_off, nullptr, c->d_off, c->d_len, 0, 0, c->n_contigs};
+        if (int rc = serve(R)) return rc;
+        r0 = r1;
+    }
+    return PD_OK;
+}
 } // namespace
 
 extern "C" {
@@ -1433,96 +1512,207 @@ int pd_depth_quantiles(pd_ctx *c, const pd_region *segs, size_t n_segs, const ui
     if (int rs = need_state(c, 1, "pd_depth_quantiles")) return rs;
     pdk::QPct P;
     if (int rc = quant_pct(c, pct, n_pct, "pd_depth_quantiles", &P)) return rc;
-    if (row_off[0] != 0 || row_off[n_rows] != n_segs) return fail(c, PD_EINVAL, "pd_depth_quantiles: row_off must run from 0 to n_segs");
-    for (size_t i = 0; i < n_rows; ++i) {
-        if (row_off[i + 1] < row_off[i] || row_off[i + 1] > n_segs) return fail(c, PD_EINVAL, "pd_depth_quantiles: row_off must not decrease");
-        if (row_off[i + 1] - row_off[i] > Q_SEG_BATCH) return fail(c, PD_EINVAL, "pd_depth_quantiles: at most 2^21 segments per row");
-    }
-    for (size_t i = 0; i < n_segs; ++i)
-        if (segs[i].tid < 0 || segs[i].tid >= c->n_contigs) return fail(c, PD_EINVAL, "pd_depth_quantiles: contig id out of range");
+    if (int rc = rows_check(c, "pd_depth_quantiles", segs, n_segs, row_off, n_rows)) return rc;
     if (n_rows == 0) return PD_OK;
     HIPOK(c, hipSetDevice(c->device));
-    auto clip = [&](const pd_region &r, uint64_t *start, uint64_t *count) {
-        int64_t b = (int64_t)r.first - 1, e = r.second;
-        if (b < 0) b = 0;
-        if (e > (int64_t)c->len[(size_t)r.tid]) e = (int64_t)c->len[(size_t)r.tid];
-        *start = c->off[(size_t)r.tid] + (uint64_t)b; *count = e > b ? (uint64_t)(e - b) : 0;
-    };
     std::vector<uint64_t> own_cells;
     if (!cells) { own_cells.resize(n_rows); cells = own_cells.data(); }
     size_t n_wide = 0; uint64_t wide_pieces = 0;
     for (size_t i = 0; i < n_rows; ++i) {
         uint64_t C = 0, np = 0;
-        for (uint64_t k = row_off[i]; k < row_off[i + 1]; ++k) { uint64_t st, cn; clip(segs[k], &st, &cn); C += cn; np += (cn + Q_PIECE - 1) / Q_PIECE; }
+        for (uint64_t k = row_off[i]; k < row_off[i + 1]; ++k) { uint64_t st, cn; seg_clip(c, segs[k], &st, &cn); C += cn; np += (cn + Q_PIECE - 1) / Q_PIECE; }
         cells[i] = C;
         if (C > c->q_wave_max && C > c->q_split) { ++n_wide; wide_pieces += np; }
     }
-    const size_t BR = (size_t)1 << 20, nbmax = std::min(BR, n_rows), sgmax = std::min<size_t>(Q_SEG_BATCH, n_segs), nwmax = std::min<size_t>(Q_WIDE_ROWS, n_wide);
-    const size_t b_seg = q_al(sgmax * sizeof(Piece)), b_off = q_al((nbmax + 1) * 8), b_list = q_al(nbmax * 4), b_q = q_al(nbmax * n_pct * 4);
+    RowBatches B;
+    const size_t nbmax = std::min(ROW_BATCH, n_rows), nwmax = std::min<size_t>(Q_WIDE_ROWS, n_wide);
+    const size_t b_rows = RowBatches::bytes(n_rows, n_segs), b_q = q_al(nbmax * n_pct * 4);
     const size_t b_hist = q_al(nwmax * 4096 * 8), b_pc = q_al((size_t)std::min<uint64_t>(Q_PIECE_CHUNK, wide_pieces) * sizeof(Piece));
-    if (int rc = ensure_scratch(c, b_seg + b_off + 3 * b_list + b_q + b_hist + b_pc + 256)) return rc;
-    unsigned char *s = (unsigned char *)c->scratch;
-    Piece *d_seg = (Piece *)s; s += b_seg;
-    uint64_t *d_off = (uint64_t *)s; s += b_off;
-    uint32_t *d_list[3]; for (int k = 0; k < 3; ++k) { d_list[k] = (uint32_t *)s; s += b_list; }
+    if (int rc = ensure_scratch(c, b_rows + b_q + b_hist + b_pc + 256)) return rc;
+    unsigned char *s = B.carve((unsigned char *)c->scratch, n_rows, n_segs);
     uint32_t *d_q = (uint32_t *)s; s += b_q;
     unsigned long long *d_hist = (unsigned long long *)s; s += b_hist;
     Piece *d_pc = (Piece *)s;
-    std::vector<Piece> hseg, pieces;
-    std::vector<uint64_t> hoff;
-    std::vector<uint32_t> list[3];
-    for (size_t r0 = 0; r0 < n_rows;) {
-        size_t r1 = r0;
-        while (r1 < n_rows && r1 - r0 < BR && row_off[r1 + 1] - row_off[r0] <= Q_SEG_BATCH) ++r1;     // (a row alone always fits)
-        const uint32_t nb = (uint32_t)(r1 - r0);
-        hseg.clear(); hoff.clear(); for (auto &l : list) l.clear();
-        uint32_t cap = 0;
-        for (size_t i = r0; i < r1; ++i) {
-            hoff.push_back(hseg.size());
-            for (uint64_t k = row_off[i]; k < row_off[i + 1]; ++k) {
-                uint64_t st, cn; clip(segs[k], &st, &cn);
-                Piece pc; pc.start = st; pc.count = (uint32_t)cn; pc.region = 0;
-                hseg.push_back(pc);
+    std::vector<Piece> pieces;
+    return rows_serve(c, segs, row_off, n_rows, cells, B,
+        [&](uint64_t C) { return C <= c->q_wave_max ? 0 : C <= c->q_split ? 1 : 2; },
+        [&](const pdk::QRows &R) -> int {
+            const std::vector<uint32_t> *list = B.list;
+            if (!list[0].empty()) {
+                ProfScope ps(c, "quantile_narrow");
+                if (pdk::launch_quant_narrow(c->stream, c->buf, R, B.d_list[0], (uint32_t)list[0].size(), B.cap, 6, P, d_q)) return fail(c, PD_EHIP, "quantile kernel: cannot reserve LDS");
             }
-            const uint64_t C = cells[i];
-            const int regime = C <= c->q_wave_max ? 0 : C <= c->q_split ? 1 : 2;
-            if (regime == 0) cap = std::max(cap, (uint32_t)C);
-            list[regime].push_back((uint32_t)(i - r0));
-        }
-        hoff.push_back(hseg.size());
-        if (!hseg.empty()) HIPOK(c, hipMemcpyAsync(d_seg, hseg.data(), hseg.size() * sizeof(Piece), hipMemcpyHostToDevice, c->stream));
-        HIPOK(c, hipMemcpyAsync(d_off, hoff.data(), hoff.size() * 8, hipMemcpyHostToDevice, c->stream));
-        for (int k = 0; k < 3; ++k)
-            if (!list[k].empty()) HIPOK(c, hipMemcpyAsync(d_list[k], list[k].data(), list[k].size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(c, hipStreamSynchronize(c->stream));          // the host arrays are refilled by the next batch
-        pdk::QRows R{d_seg, d_off, nullptr, c->d_off, c->d_len, 0, 0, c->n_contigs};
-        if (!list[0].empty()) {
-            ProfScope ps(c, "quantile_narrow");
-            if (pdk::launch_quant_narrow(c->stream, c->buf, R, d_list[0], (uint32_t)list[0].size(), cap, 6, P, d_q)) return fail(c, PD_EHIP, "quantile kernel: cannot reserve LDS");
-        }
-        if (!list[1].empty()) {
-            ProfScope ps(c, "quantile_block");
-            pdk::launch_quant_block(c->stream, c->buf, R, d_list[1], (uint32_t)list[1].size(), P, d_q, nullptr);
-        }
-        for (size_t w0 = 0; w0 < list[2].size(); w0 += Q_WIDE_ROWS) {
-            const uint32_t nwr = (uint32_t)std::min<size_t>(Q_WIDE_ROWS, list[2].size() - w0);
-            HIPOK(c, hipMemsetAsync(d_hist, 0, (size_t)nwr * 4096 * 8, c->stream));
-            for (uint32_t k = 0; k < nwr; ++k) {
-                const uint32_t lr = list[2][w0 + k];
-                for (uint64_t j = hoff[lr]; j < hoff[lr + 1]; ++j)
-                    if (int rc = quant_add_pieces(c, pieces, hseg[j].start, hseg[j].count, k, d_pc, d_hist)) return rc;
+            if (!list[1].empty()) {
+                ProfScope ps(c, "quantile_block");
+                pdk::launch_quant_block(c->stream, c->buf, R, B.d_list[1], (uint32_t)list[1].size(), P, d_q, nullptr);
             }
-            if (int rc = quant_flush_pieces(c, pieces, d_pc, d_hist)) return rc;
-            ProfScope ps(c, "quantile_pick");
-            pdk::launch_quant_block(c->stream, c->buf, R, d_list[2] + w0, nwr, P, d_q, d_hist);
-        }
-        HIPOK(c, hipGetLastError());
-        HIPOK(c, hipMemcpyAsync(q + r0 * n_pct, d_q, (size_t)nb * n_pct * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(c, hipStreamSynchronize(c->stream));
-        r0 = r1;
+            for (size_t w0 = 0; w0 < list[2].size(); w0 += Q_WIDE_ROWS) {
+                const uint32_t nwr = (uint32_t)std::min<size_t>(Q_WIDE_ROWS, list[2].size() - w0);
+                HIPOK(c, hipMemsetAsync(d_hist, 0, (size_t)nwr * 4096 * 8, c->stream));
+                for (uint32_t k = 0; k < nwr; ++k) {
+                    const uint32_t lr = list[2][w0 + k];
+                    for (uint64_t j = B.hoff[lr]; j < B.hoff[lr + 1]; ++j)
+                        if (int rc = quant_add_pieces(c, pieces, B.hseg[j].start, B.hseg[j].count, k, d_pc, d_hist)) return rc;
+                }
+                if (int rc = quant_flush_pieces(c, pieces, d_pc, d_hist)) return rc;
+                ProfScope ps(c, "quantile_pick");
+                pdk::launch_quant_block(c->stream, c->buf, R, B.d_list[2] + w0, nwr, P, d_q, d_hist);
+            }
+            HIPOK(c, hipGetLastError());
+            HIPOK(c, hipMemcpyAsync(q + B.r0 * n_pct, d_q, (size_t)(B.r1 - B.r0) * n_pct * 4, hipMemcpyDeviceToHost, c->stream));
+            HIPOK(c, hipStreamSynchronize(c->stream));
+            return PD_OK;
+        });
+}
+
+} // extern "C"
+
+// ---- depth thresholds ----
+// The quantiles' rows and batches with two launch shapes: a row of up to "threshold_wave_max" cells is counted by a group of
+// lanes, a longer one is cut into pieces that add into the batch's zeroed result rows.
+namespace {
+int thr_set(pd_ctx *c, const uint32_t *thr, uint32_t n_thr, const char *fn, pdk::ThrSet *T)
+{
+    if (!thr || n_thr < 1 || n_thr > 16) return fail(c, PD_EINVAL, std::string(fn) + ": 1 to 16 thresholds");
+    T->n = n_thr;
+    for (uint32_t j = 0; j < 16; ++j) T->t[j] = 0xFFFFFFFFu;
+    for (uint32_t j = 0; j < n_thr; ++j) {
+        if (j && thr[j] <= thr[j - 1]) return fail(c, PD_EINVAL, std::string(fn) + ": thresholds must be strictly ascending");
+        T->t[j] = thr[j];
     }
     return PD_OK;
 }
+
+// the pieces collected so far, added into `out` (Piece.region = the row's slot in it)
+template <typename OutT>
+int thr_flush_pieces(pd_ctx *c, std::vector<Piece> &pieces, Piece *d_pieces, const pdk::ThrSet &T, OutT *out)
+{
+    if (pieces.empty()) return PD_OK;
+    HIPOK(c, hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(Piece), hipMemcpyHostToDevice, c->stream));
+    HIPOK(c, hipStreamSynchronize(c->stream));          // pieces is refilled by the caller
+    {
+        ProfScope ps(c, "threshold_pieces");
+        pdk::launch_thr_pieces(c->stream, c->buf, d_pieces, (uint32_t)pieces.size(), T, out, (unsigned)c->n_cu * 8);
+    }
+    HIPOK(c, hipGetLastError());
+    pieces.clear();
+    return PD_OK;
+}
+template <typename OutT>
+int thr_add_pieces(pd_ctx *c, std::vector<Piece> &pieces, uint64_t start, uint64_t count, uint32_t slot, Piece *d_pieces, const pdk::ThrSet &T, OutT *out)
+{
+    for (uint64_t p = 0; p < count; p += Q_PIECE) {
+        Piece pc; pc.start = start + p; pc.count = (uint32_t)std::min<uint64_t>(Q_PIECE, count - p); pc.region = slot;
+        pieces.push_back(pc);
+        if (pieces.size() == Q_PIECE_CHUNK) if (int rc = thr_flush_pieces(c, pieces, d_pieces, T, out)) return rc;
+    }
+    return PD_OK;
+}
+} // namespace
+
+extern "C" {
+
+int pd_window_thresholds(pd_ctx *c, uint32_t w, const uint32_t *thr, uint32_t n_thr, uint32_t *counts)
+{
+    if (!c || !counts || w == 0) return PD_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int rs = need_state(c, 1, "pd_window_thresholds")) return rs;
+    pdk::ThrSet T;
+    if (int rc = thr_set(c, thr, n_thr, "pd_window_thresholds", &T)) return rc;
+    std::vector<uint64_t> wo((size_t)c->n_contigs + 1);
+    pd_window_layout(c, w, wo.data());
+    const uint64_t nw = wo[c->n_contigs];
+    if (nw == 0) return PD_OK;
+    HIPOK(c, hipSetDevice(c->device));
+    uint32_t maxlen = 0;
+    for (uint32_t l : c->len) maxlen = std::max(maxlen, l);
+    const uint32_t weff = std::min(w, maxlen);
+    const bool wide = weff > c->t_wave_max;
+    const uint64_t BR = std::min<uint64_t>((uint64_t)1 << 22, ((uint64_t)1 << 24) / n_thr), nbmax = std::min(BR, nw);
+    const size_t b_wo = q_al(wo.size() * 8), b_cnt = q_al((size_t)nbmax * n_thr * 4), b_pc = wide ? Q_PIECE_CHUNK * sizeof(Piece) : 0;
+    if (int rc = ensure_scratch(c, b_wo + b_cnt + b_pc + 256)) return rc;
+    unsigned char *s = (unsigned char *)c->scratch;
+    uint64_t *d_wo = (uint64_t *)s; uint32_t *d_cnt = (uint32_t *)(s + b_wo); Piece *d_pc = (Piece *)(s + b_wo + b_cnt);
+    HIPOK(c, hipMemcpyAsync(d_wo, wo.data(), wo.size() * 8, hipMemcpyHostToDevice, c->stream));
+    std::vector<Piece> pieces;
+    int32_t t = 0;
+    for (uint64_t row0 = 0; row0 < nw; row0 += BR) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(BR, nw - row0);
+        if (!wide) {
+            const pdk::QRows R{nullptr, nullptr, d_wo, c->d_off, c->d_len, row0, w, c->n_contigs};
+            uint32_t gshift = 3; while (gshift < 6 && (8u << gshift) < weff) ++gshift;      // a lane takes 8 cells before the group grows
+            const uint32_t rpg = std::min(16u, std::max(1u, 8192u / weff));                  // rows a group takes one after the other
+            ProfScope ps(c, "threshold_narrow");
+            pdk::launch_thr_narrow(c->stream, c->buf, R, nullptr, nb, gshift, rpg, T, d_cnt);
+        } else {
+            HIPOK(c, hipMemsetAsync(d_cnt, 0, (size_t)nb * n_thr * 4, c->stream));
+            for (uint64_t g = row0; g < row0 + nb; ++g) {
+                while (wo[(size_t)t + 1] <= g) ++t;
+                const uint64_t b = (g - wo[(size_t)t]) * w, e = std::min<uint64_t>(b + w, c->len[(size_t)t]);
+                if (int rc = thr_add_pieces(c, pieces, c->off[(size_t)t] + b, e - b, (uint32_t)(g - row0), d_pc, T, d_cnt)) return rc;
+            }
+            if (int rc = thr_flush_pieces(c, pieces, d_pc, T, d_cnt)) return rc;
+        }
+        HIPOK(c, hipGetLastError());
+        HIPOK(c, hipMemcpyAsync(counts + row0 * n_thr, d_cnt, (size_t)nb * n_thr * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(c, hipStreamSynchronize(c->stream));
+    }
+    return PD_OK;
+}
+
+int pd_depth_thresholds(pd_ctx *c, const pd_region *segs, size_t n_segs, const uint64_t *row_off, size_t n_rows,
+                        const uint32_t *thr, uint32_t n_thr, uint64_t *cells, uint64_t *counts)
+{
+    if (!c || (n_segs && !segs) || !row_off || (n_rows && !counts)) return PD_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int rs = need_state(c, 1, "pd_depth_thresholds")) return rs;
+    pdk::ThrSet T;
+    if (int rc = thr_set(c, thr, n_thr, "pd_depth_thresholds", &T)) return rc;
+    if (int rc = rows_check(c, "pd_depth_thresholds", segs, n_segs, row_off, n_rows)) return rc;
+    if (n_rows == 0) return PD_OK;
+    HIPOK(c, hipSetDevice(c->device));
+    std::vector<uint64_t> own_cells;
+    if (!cells) { own_cells.resize(n_rows); cells = own_cells.data(); }
+    uint64_t wide_pieces = 0;
+    for (size_t i = 0; i < n_rows; ++i) {
+        uint64_t C = 0, np = 0;
+        for (uint64_t k = row_off[i]; k < row_off[i + 1]; ++k) { uint64_t st, cn; seg_clip(c, segs[k], &st, &cn); C += cn; np += (cn + Q_PIECE - 1) / Q_PIECE; }
+        cells[i] = C;
+        if (C > c->t_wave_max) wide_pieces += np;
+    }
+    RowBatches B;
+    const size_t b_rows = RowBatches::bytes(n_rows, n_segs), b_cnt = q_al(std::min(ROW_BATCH, n_rows) * n_thr * 8);
+    const size_t b_pc = q_al((size_t)std::min<uint64_t>(Q_PIECE_CHUNK, wide_pieces) * sizeof(Piece));
+    if (int rc = ensure_scratch(c, b_rows + b_cnt + b_pc + 256)) return rc;
+    unsigned char *s = B.carve((unsigned char *)c->scratch, n_rows, n_segs);
+    unsigned long long *d_cnt = (unsigned long long *)s; s += b_cnt;
+    Piece *d_pc = (Piece *)s;
+    std::vector<Piece> pieces;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counts are copied as they are");
+    return rows_serve(c, segs, row_off, n_rows, cells, B,
+        [&](uint64_t C) { return C <= c->t_wave_max ? 0 : 1; },
+        [&](const pdk::QRows &R) -> int {
+            const size_t nb = B.r1 - B.r0;
+            if (!B.list[1].empty()) HIPOK(c, hipMemsetAsync(d_cnt, 0, nb * n_thr * 8, c->stream));       // (the narrow rows are written, not added to)
+            if (!B.list[0].empty()) {
+                uint32_t gshift = 3; while (gshift < 6 && (8u << gshift) < B.cap) ++gshift;
+                ProfScope ps(c, "threshold_narrow");
+                pdk::launch_thr_narrow(c->stream, c->buf, R, B.d_list[0], (uint32_t)B.list[0].size(), gshift, 1, T, d_cnt);
+            }
+            for (uint32_t lr : B.list[1])
+                for (uint64_t j = B.hoff[lr]; j < B.hoff[lr + 1]; ++j)
+                    if (int rc = thr_add_pieces(c, pieces, B.hseg[j].start, B.hseg[j].count, lr, d_pc, T, d_cnt)) return rc;
+            if (int rc = thr_flush_pieces(c, pieces, d_pc, T, d_cnt)) return rc;
+            HIPOK(c, hipGetLastError());
+            HIPOK(c, hipMemcpyAsync(counts + B.r0 * n_thr, d_cnt, nb * n_thr * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPOK(c, hipStreamSynchronize(c->stream));
+            return PD_OK;
+        });
+}
+
+} // extern "C"
+
+extern "C" {
 
 int pd_device_buffer(pd_ctx *c, void **dev_ptr, uint64_t *n_words, uint64_t *contig_off)
 {

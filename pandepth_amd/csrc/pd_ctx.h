@@ -125,6 +125,7 @@ struct pd_ctx {
     std::atomic<uint64_t> dec_n_fast{0}, dec_n_slow{0}, dec_n_redo{0};   // batches finished without / with the host's chain check; segments the device walked again
     uint32_t direct_sample = 256;                                 // index stride of the direct path (runs)
     uint32_t q_wave_max = 512, q_split = 262144;                  // "quantile_wave_max" / "quantile_split_cells": the cell counts up to which a quantile row takes the narrow / the workgroup kernel
+    uint32_t t_wave_max = 65536;                                  // "threshold_wave_max": the cell count up to which a threshold row is counted by a group of lanes, not in pieces
     int hist_variant = 1;                                         // "hist_variant": the histogram kernels' LDS form (launch_sweep_hist): 1 = one copy per workgroup, folded (measured best)
     int direct_un = 0;                                           // 0 = the default form of the wide direct kernel (launch_direct_tiles)
     bool all_valid_host = false;

@@ -188,6 +188,17 @@ int launch_quant_narrow(hipStream_t st, const int *depth, const QRows &R, const 
 void launch_quant_block(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, const QPct &P, uint32_t *q,
                         const unsigned long long *ghist);
 
+// depth thresholds (pd_depth_thresholds / pd_window_thresholds): out[r * T.n + j] = the cells of row r that are >= T.t[j]; rows as
+// above.  T.t[T.n ..) is 2^32-1.  out is uint64 for segment rows, uint32 for windows.
+//   launch_thr_narrow : a group of 1 << gshift lanes (3 .. 6) takes `rpg` consecutive rows of the launch, one writer per row (rows of
+//                       less than 2^32 cells)
+//   launch_thr_pieces : Piece.region = the row's slot in `out`, which the caller has zeroed; a wave per piece, T.n atomics per piece
+struct ThrSet { uint32_t n; uint32_t t[16]; };
+void launch_thr_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t gshift, uint32_t rpg, const ThrSet &T, uint32_t *out);
+void launch_thr_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t gshift, uint32_t rpg, const ThrSet &T, unsigned long long *out);
+void launch_thr_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, const ThrSet &T, uint32_t *out, unsigned grid);
+void launch_thr_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, const ThrSet &T, unsigned long long *out, unsigned grid);
+
 // GPU-side BAM decode (pd_bgzf.hip)
 void launch_bgzf_inflate(hipStream_t st, const uint8_t *comp, const pd_bgzf_block *blk, uint32_t n_blk, uint8_t *out,
                          int *status, void *scratch);

@@ -3557,16 +3557,27 @@ void launch_levels(hipStream_t st, const uint32_t *src, uint32_t first_cell, uin
 // ------------------------------------------------------------------------------------------
 struct QSel { unsigned long long below[16], total, dbelow; uint32_t bin[16], dbin; };
 
+// window g of pd_window_layout: the last contig whose first window is <= g, and the window's cells in it
+__device__ __forceinline__ int q_win_contig(const QRows &R, uint64_t g)
+{
+    int lo = 0, hi = R.n_contigs - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (R.win_off[mid] <= g) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+__device__ __forceinline__ void q_win_cells(const QRows &R, uint64_t g, int t, uint64_t *ws, uint32_t *wc)
+{
+    const uint64_t b = (g - R.win_off[t]) * R.w, clen = R.contig_len[t];
+    *ws = R.contig_off[t] + b;
+    *wc = b >= clen ? 0u : (uint32_t)(clen - b < (uint64_t)R.w ? clen - b : (uint64_t)R.w);
+}
+
 // the cells of row r: segments [s0, s0 + ns) of R.segs, or (window mode) the one stretch (ws, wc)
 __device__ __forceinline__ void q_row_begin(const QRows &R, uint64_t r, uint64_t *s0, uint32_t *ns, uint64_t *ws, uint32_t *wc)
 {
     if (R.segs) { *s0 = R.seg_off[r]; *ns = (uint32_t)(R.seg_off[r + 1] - *s0); *ws = 0; *wc = 0; return; }
     const uint64_t g = R.row0 + r;
-    int lo = 0, hi = R.n_contigs - 1;                            // the last contig whose first window is <= g
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (R.win_off[mid] <= g) lo = mid; else hi = mid - 1; }
-    const uint64_t b = (g - R.win_off[lo]) * R.w, clen = R.contig_len[lo];
-    *s0 = 0; *ns = 1; *ws = R.contig_off[lo] + b;
-    *wc = b >= clen ? 0u : (uint32_t)(clen - b < (uint64_t)R.w ? clen - b : (uint64_t)R.w);
+    *s0 = 0; *ns = 1;
+    q_win_cells(R, g, q_win_contig(R, g), ws, wc);
 }
 __device__ __forceinline__ void q_seg(const QRows &R, uint64_t s0, uint32_t i, uint64_t ws, uint32_t wc, uint64_t *start, uint32_t *count)
 {
@@ -3757,6 +3768,154 @@ void launch_quant_block(hipStream_t st, const int *depth, const QRows &R, const 
     if (ghist) hipLaunchKernelGGL((k_quant_block<unsigned long long, true>), dim3(n), dim3(WG), 0, st, d, R, list, P, q, ghist);
     else hipLaunchKernelGGL((k_quant_block<uint32_t, false>), dim3(n), dim3(WG), 0, st, d, R, list, P, q, ghist);
 }
+
+// ------------------------------------------------------------------------------------------
+// depth thresholds (pd_depth_thresholds / pd_window_thresholds): for every row (QRows, as the quantiles have them) the number of
+// cells >= T.t[j], j < T.n.  A cell is read once; a lane keeps NT counters in registers (NT = 1, 4 or 16, the thresholds padded
+// with 2^32-1 and the padding's counters never written), the thresholds sit in scalar registers.  A stretch of cells is read by
+// thr_span: scalar head to the first 16-byte boundary, 16-byte loads (four in flight per lane), scalar tail.  Two launch shapes:
+//   k_thr_narrow   a GROUP of 8 .. 64 lanes per row, many rows per wave, `rpg` consecutive rows per group one after the other (a
+//                  window's contig is found by bisection for the group's first row and by stepping for the rest); the group's
+//                  counters are summed with __shfl_xor and the row has one writer (no atomics, the result need not be zeroed)
+//   k_thr_pieces   rows cut into pieces of at most 16384 cells (Piece.region = the row's slot); a WAVE per piece, every wave of
+//                  `grid` workgroups takes a run of consecutive pieces; at the end of a row's pieces the wave's counters are summed
+//                  with __shfl_xor and added to the zeroed result row with T.n atomics
+// ------------------------------------------------------------------------------------------
+template <int NT>
+__device__ __forceinline__ void thr_count(uint32_t v, const ThrSet &T, uint32_t (&cnt)[NT])
+{
+#pragma unroll
+    for (int j = 0; j < NT; ++j) cnt[j] += v >= T.t[j] ? 1u : 0u;
+}
+template <int NT>
+__device__ __forceinline__ void thr_count4(const uint4 x, const ThrSet &T, uint32_t (&cnt)[NT])
+{
+    thr_count<NT>(x.x, T, cnt); thr_count<NT>(x.y, T, cnt); thr_count<NT>(x.z, T, cnt); thr_count<NT>(x.w, T, cnt);
+}
+
+// cells d[0 .. count) by lanes gl = 0 .. G - 1 (G >= 4); d is a cell of the depth array, whose base is 16-byte aligned
+template <int NT>
+__device__ __forceinline__ void thr_span(const uint32_t *d, uint32_t count, uint32_t gl, uint32_t G, const ThrSet &T, uint32_t (&cnt)[NT])
+{
+    uint32_t head = (4u - (uint32_t)((reinterpret_cast<uintptr_t>(d) >> 2) & 3u)) & 3u;     // cells before the first 16-byte boundary
+    if (head > count) head = count;
+    const uint32_t n4 = (count - head) >> 2, tail0 = head + (n4 << 2);
+    if (gl < head) thr_count<NT>(d[gl], T, cnt);
+    const uint4 *d4 = reinterpret_cast<const uint4 *>(d + head);
+    for (uint32_t k0 = 0; k0 < n4; k0 += 4 * G) {               // the same trips for every lane of the group; a lane past the end reads d4[0] and skips the count
+        const uint32_t k = k0 + gl;
+        const bool ok0 = k < n4, ok1 = k + G < n4, ok2 = k + 2 * G < n4, ok3 = k + 3 * G < n4;
+        const uint4 x0 = d4[ok0 ? k : 0u], x1 = d4[ok1 ? k + G : 0u], x2 = d4[ok2 ? k + 2 * G : 0u], x3 = d4[ok3 ? k + 3 * G : 0u];
+        if (ok0) thr_count4<NT>(x0, T, cnt);
+        if (ok1) thr_count4<NT>(x1, T, cnt);
+        if (ok2) thr_count4<NT>(x2, T, cnt);
+        if (ok3) thr_count4<NT>(x3, T, cnt);
+    }
+    if (tail0 + gl < count) thr_count<NT>(d[tail0 + gl], T, cnt);                           // (fewer than 4 cells)
+}
+
+template <int NT, typename OutT>
+__global__ __launch_bounds__(WG) void k_thr_narrow(const uint32_t *depth, const QRows R, const uint32_t *list, uint32_t n, uint32_t gshift,
+                                                   uint32_t rpg, const ThrSet T, OutT *out)
+{
+    const uint32_t G = 1u << gshift, gl = threadIdx.x & (G - 1);
+    const uint64_t slot0 = ((uint64_t)blockIdx.x * (WG >> gshift) + (threadIdx.x >> gshift)) * rpg;
+    int t = -1;                                                  // window mode: the contig of the row before
+    for (uint32_t i = 0; i < rpg; ++i) {
+        const uint64_t slot = slot0 + i;
+        if (slot >= n) break;                                    // (whole groups leave; nothing below synchronises the workgroup)
+        const uint64_t r = list ? list[slot] : slot;
+        uint32_t cnt[NT];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) cnt[j] = 0;
+        if (R.segs) {
+            const uint64_t s0 = R.seg_off[r], s1 = R.seg_off[r + 1];
+            for (uint64_t s = s0; s < s1; ++s) { const Piece pc = R.segs[s]; thr_span<NT>(depth + pc.start, pc.count, gl, G, T, cnt); }
+        } else {
+            const uint64_t g = R.row0 + r;
+            if (t < 0) t = q_win_contig(R, g);
+            else while (R.win_off[t + 1] <= g) ++t;              // (g is below win_off[n_contigs]: t stays a contig)
+            uint64_t ws; uint32_t wc;
+            q_win_cells(R, g, t, &ws, &wc);
+            thr_span<NT>(depth + ws, wc, gl, G, T, cnt);
+        }
+        OutT *o = out + r * T.n;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            int x = (int)cnt[j];                                 // (constant distances: the first steps are DPP moves)
+            if (G > 32) x += __shfl_xor(x, 32);
+            if (G > 16) x += __shfl_xor(x, 16);
+            if (G > 8) x += __shfl_xor(x, 8);
+            x += __shfl_xor(x, 4); x += __shfl_xor(x, 2); x += __shfl_xor(x, 1);
+            if ((uint32_t)j < T.n && gl == (uint32_t)j % G) o[j] = (OutT)x;
+        }
+    }
+}
+
+template <int NT, typename OutT>
+__device__ __forceinline__ void thr_add_row(uint32_t (&cnt)[NT], uint32_t lane, const ThrSet &T, OutT *o)
+{
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const uint32_t x = (uint32_t)wave_sum((int)cnt[j]);
+        if ((uint32_t)j < T.n && lane == (uint32_t)j && x) atomicAdd(&o[j], (OutT)x);
+        cnt[j] = 0;
+    }
+}
+
+// wave k of the grid takes pieces [k * ppw, (k + 1) * ppw): consecutive pieces of one row are added to it once
+template <int NT, typename OutT>
+__global__ __launch_bounds__(WG) void k_thr_pieces(const uint32_t *depth, const Piece *pieces, uint32_t n_pieces, uint32_t ppw, const ThrSet T, OutT *out)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t p0 = ((uint64_t)blockIdx.x * (WG / 64) + (threadIdx.x >> 6)) * ppw;
+    if (p0 >= n_pieces) return;
+    const uint32_t p1 = (uint32_t)(p0 + ppw < n_pieces ? p0 + ppw : n_pieces);
+    uint32_t cnt[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) cnt[j] = 0;
+    uint32_t cur = pieces[p0].region;
+    for (uint32_t pi = (uint32_t)p0; pi < p1; ++pi) {
+        const Piece pc = pieces[pi];
+        if (pc.region != cur) { thr_add_row<NT>(cnt, lane, T, out + (size_t)cur * T.n); cur = pc.region; }
+        thr_span<NT>(depth + pc.start, pc.count, lane, 64u, T, cnt);
+    }
+    thr_add_row<NT>(cnt, lane, T, out + (size_t)cur * T.n);
+}
+
+template <typename OutT>
+static void thr_narrow_any(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t gshift, uint32_t rpg, const ThrSet &T, OutT *out)
+{
+    if (!n) return;
+    if (rpg < 1) rpg = 1;
+    const uint32_t rpb = ((uint32_t)WG >> gshift) * rpg;         // rows per workgroup
+    const dim3 grid((n + rpb - 1) / rpb);
+    const uint32_t *d = reinterpret_cast<const uint32_t *>(depth);
+    if (T.n == 1) hipLaunchKernelGGL((k_thr_narrow<1, OutT>), grid, dim3(WG), 0, st, d, R, list, n, gshift, rpg, T, out);
+    else if (T.n <= 4) hipLaunchKernelGGL((k_thr_narrow<4, OutT>), grid, dim3(WG), 0, st, d, R, list, n, gshift, rpg, T, out);
+    else hipLaunchKernelGGL((k_thr_narrow<16, OutT>), grid, dim3(WG), 0, st, d, R, list, n, gshift, rpg, T, out);
+}
+template <typename OutT>
+static void thr_pieces_any(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, const ThrSet &T, OutT *out, unsigned grid)
+{
+    if (!n_pieces) return;
+    if (grid < 1) grid = 1;
+    const uint32_t waves = grid * (WG / 64), ppw = (n_pieces + waves - 1) / waves;           // pieces per wave
+    const dim3 g((n_pieces + ppw * (WG / 64) - 1) / (ppw * (WG / 64)));
+    const uint32_t *d = reinterpret_cast<const uint32_t *>(depth);
+    if (T.n == 1) hipLaunchKernelGGL((k_thr_pieces<1, OutT>), g, dim3(WG), 0, st, d, pieces, n_pieces, ppw, T, out);
+    else if (T.n <= 4) hipLaunchKernelGGL((k_thr_pieces<4, OutT>), g, dim3(WG), 0, st, d, pieces, n_pieces, ppw, T, out);
+    else hipLaunchKernelGGL((k_thr_pieces<16, OutT>), g, dim3(WG), 0, st, d, pieces, n_pieces, ppw, T, out);
+}
+
+void launch_thr_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t gshift, uint32_t rpg, const ThrSet &T, uint32_t *out)
+{ thr_narrow_any(st, depth, R, list, n, gshift, rpg, T, out); }
+void launch_thr_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t gshift, uint32_t rpg, const ThrSet &T, unsigned long long *out)
+{ thr_narrow_any(st, depth, R, list, n, gshift, rpg, T, out); }
+void launch_thr_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, const ThrSet &T, uint32_t *out, unsigned grid)
+{ thr_pieces_any(st, depth, pieces, n_pieces, T, out, grid); }
+void launch_thr_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, const ThrSet &T, unsigned long long *out, unsigned grid)
+{ thr_pieces_any(st, depth, pieces, n_pieces, T, out, grid); }
 
 } // namespace pdk
 

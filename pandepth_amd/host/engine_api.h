@@ -79,6 +79,9 @@ typedef struct pd_engine_api {
     /* optional (NULL = the host reads the depth back and selects with std::nth_element): the -quantile file, see pd_depth_quantiles */
     int (*depth_quantiles)(pd_ctx *, const pd_region *, size_t, const uint64_t *, size_t, const uint32_t *, uint32_t, uint64_t *, uint32_t *);
     int (*window_quantiles)(pd_ctx *, uint32_t, const uint32_t *, uint32_t, uint32_t *);
+    /* optional (NULL = the host reads the depth back and counts): the -thresholds file, see pd_depth_thresholds */
+    int (*depth_thresholds)(pd_ctx *, const pd_region *, size_t, const uint64_t *, size_t, const uint32_t *, uint32_t, uint64_t *, uint64_t *);
+    int (*window_thresholds)(pd_ctx *, uint32_t, const uint32_t *, uint32_t, uint32_t *);
 } pd_engine_api;
 
 /* Runs one `pandepth` invocation (argv as given to main) on the engine behind `api`. */

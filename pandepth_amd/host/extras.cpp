@@ -1,4 +1,4 @@
-// extras.cpp — the outputs the reference does not have: -dist, -levels and -quantile.  Each is made after the main table is
+// extras.cpp — the outputs the reference does not have: -dist, -levels, -quantile and -thresholds.  Each is made after the main table is
 // written and the per-site job started, so that their path and timing stay as they are; each is one entry of EXTRAS, which the
 // finish step of every table family and the exit for a PAF without targets (pipeline.cpp) walk in order.
 #include <string.h>
@@ -18,6 +18,18 @@ std::string quantile_header(const Run &r)
     if (!r.synthetic) h += r.o.mode == 3 ? "\tRegionID" : "\tGeneID";
     h += "\tCells";
     for (uint32_t p : r.o.quantile) { h += "\tQ"; h += std::to_string(p); }
+    h += '\n';
+    return h;
+}
+
+// -thresholds' table: -quantile's identity columns and Cells, then one column per threshold
+std::string thresholds_header(const Run &r)
+{
+    std::string h = "#Chr";
+    if (r.o.mode != 0) h += "\tStart\tEnd";
+    if (!r.synthetic) h += r.o.mode == 3 ? "\tRegionID" : "\tGeneID";
+    h += "\tCells";
+    for (uint32_t t : r.o.thresholds) { h += "\tGE"; h += std::to_string(t); }
     h += '\n';
     return h;
 }
@@ -376,12 +388,96 @@ bool write_quantile(Run &r)
     return true;
 }
 
+// -thresholds on engines without the entry points: a contig's cells are read back once, its rows counted on the threads
+bool host_thresholds(Run &r, const QPlan &q, std::vector<uint64_t> *cells, std::vector<uint64_t> *cnt)
+{
+    const std::vector<uint32_t> &thr = r.o.thresholds;
+    const uint32_t nt = (uint32_t)thr.size();
+    const size_t n_rows = q.rows.size();
+    const int nw = host_workers(r.o.threads);
+    std::vector<uint32_t> d;
+    for (size_t r0 = 0, r1; r0 < n_rows; r0 = r1) {
+        const int32_t t = q.rows[r0].tid;
+        for (r1 = r0; r1 < n_rows && q.rows[r1].tid == t;) ++r1;
+        const uint64_t len = r.hdr.lens[(size_t)t];
+        d.resize(len);
+        if (!r.read_cells(t, 0, len, d.data())) return false;
+        parallel_for(r1 - r0, nw, [&](size_t item, int) {
+            const size_t i = r0 + item;
+            uint64_t C = 0, *row = &(*cnt)[i * nt];
+            for (uint64_t s = q.roff[i]; s < q.roff[i + 1]; ++s) {
+                const int64_t b = std::max<int64_t>((int64_t)q.segs[s].first - 1, 0), e = std::min<int64_t>(q.segs[s].second, (int64_t)len);
+                if (b >= e) continue;
+                C += (uint64_t)(e - b);
+                for (int64_t p = b; p < e; ++p)                          // class = the thresholds <= the cell; suffix sums below
+                    if (const size_t k = (size_t)(std::upper_bound(thr.begin(), thr.end(), d[(size_t)p]) - thr.begin())) ++row[k - 1];
+            }
+            for (uint32_t j = nt; j-- > 1;) row[j - 1] += row[j];
+            (*cells)[i] = C;
+        });
+    }
+    return true;
+}
+
+// -thresholds SPEC: for every row of the main table, in the table's row order, the number of the row's cells whose value is at
+// or above each depth of SPEC, in <prefix>.thresholds.stat.gz.  The rows and their cells are -quantile's (quantile_rows); a row
+// without cells prints zeros.  Counted on the engine in one pass over the cells (pd_window_thresholds / pd_depth_thresholds:
+// only the results come back) or, without those members, on the host threads.
+bool write_thresholds(Run &r)
+{
+    const pd_engine_api *api = r.api;
+    Engine &eng = *r.eng;
+    const Options &o = r.o;
+    if (!r.need_scan()) return false;
+    const std::vector<uint32_t> &thr = o.thresholds;
+    const uint32_t nt = (uint32_t)thr.size();
+    const bool dev = api->depth_thresholds && api->window_thresholds && !(tune("thresholds_device") && tune("thresholds_device")[0] == '0');
+    if (dev && api->set_param)
+        if (const char *e = tune("threshold_wave_max")) (void)api->set_param(eng.ctx, "threshold_wave_max", (uint64_t)strtoull(e, nullptr, 10));
+    const bool by_window = dev && (o.mode == 5 || o.mode == 6);
+    QPlan q;
+    quantile_rows(r, by_window, &q);
+    std::vector<uint32_t> wcnt;                  // by_window: the windows' counts, at qi
+    std::vector<uint64_t> cnt;                   // else the rows'
+    if (by_window) {
+        wcnt.resize((size_t)std::max<uint64_t>(1, q.woff.back() * nt));
+        if (!eng.ck(api->window_thresholds(eng.ctx, (uint32_t)o.win, thr.data(), nt, wcnt.data()), "pd_window_thresholds")) return false;
+    } else {
+        const size_t n_rows = q.rows.size();
+        std::vector<uint64_t> cells(n_rows ? n_rows : 1);
+        cnt.assign(n_rows ? n_rows * nt : 1, 0);
+        if (dev) {
+            if (!eng.ck(api->depth_thresholds(eng.ctx, q.segs.data(), q.segs.size(), q.roff.data(), n_rows, thr.data(), nt, cells.data(), cnt.data()), "pd_depth_thresholds")) return false;
+        } else if (!host_thresholds(r, q, &cells, &cnt)) return false;
+        for (size_t i = 0; i < n_rows; ++i) q.rows[i].cells = cells[i];
+    }
+    GzWriter W;
+    W.set_threads(o.threads);
+    const std::string path = r.prefix + ".thresholds.stat.gz";
+    if (!W.open(path)) { eng.fail("cannot open " + path); return false; }
+    std::string out = thresholds_header(r);
+    for (const QRow &row : q.rows) {
+        out += r.hdr.names[(size_t)row.tid];
+        if (o.mode != 0) { out += '\t'; append_i64(&out, row.start); out += '\t'; append_i64(&out, row.end); }
+        if (row.id) { out += '\t'; out += *row.id; }
+        out += '\t'; append_u64(&out, row.cells);
+        for (uint32_t j = 0; j < nt; ++j) { out += '\t'; append_u64(&out, by_window ? wcnt[row.qi * nt + j] : cnt[row.qi * nt + j]); }
+        out += '\n';
+        if (out.size() > (1u << 22)) { W.write(out); out.clear(); }
+    }
+    W.write(out);
+    if (!W.close()) { ::remove(path.c_str()); eng.fail("cannot write " + path); return false; }
+    r.tm.mark("depth thresholds");
+    return true;
+}
+
 } // namespace
 
 const Extra EXTRAS[] = {
     {".dist.stat.gz", [](const Options &o) { return o.dist != 0; }, [](const Run &) { return std::string(DIST_HEADER); }, write_dist},
     {".levels.bed.gz", [](const Options &o) { return o.levels; }, [](const Run &) { return std::string(); }, write_levels},
     {".quantile.stat.gz", [](const Options &o) { return !o.quantile.empty(); }, quantile_header, write_quantile},
+    {".thresholds.stat.gz", [](const Options &o) { return !o.thresholds.empty(); }, thresholds_header, write_thresholds},
 };
 const size_t N_EXTRAS = sizeof(EXTRAS) / sizeof(EXTRAS[0]);
 

@@ -218,6 +218,20 @@ int parse_options(int argc, char **argv, Options *o)
             }
             if (!good) { o->quantile.clear(); std::cerr << "Error: -quantile should be 1 to 16 ascending percentages between 0 and 100, such as 25,50,75" << std::endl; return 0; }
         }
+        else if (flag == "thresholds") {                                         // not in the reference: the .thresholds.stat.gz counts (README)
+            if (!arg(&v)) return 0;
+            bool good = !v.empty();
+            o->thresholds.clear();
+            uint64_t x = 0; size_t digits = 0;
+            for (size_t k = 0; good && k <= v.size(); ++k) {
+                if (k < v.size() && v[k] >= '0' && v[k] <= '9') { x = x * 10 + (uint64_t)(v[k] - '0'); if (++digits > 10) good = false; continue; }
+                if ((k < v.size() && v[k] != ',') || digits == 0 || x >= (1ull << 31) || o->thresholds.size() == 16 ||
+                    (!o->thresholds.empty() && x <= o->thresholds.back())) { good = false; break; }
+                o->thresholds.push_back((uint32_t)x);
+                x = 0; digits = 0;
+            }
+            if (!good) { o->thresholds.clear(); std::cerr << "Error: -thresholds should be 1 to 16 ascending depths, such as 1,10,20,30" << std::endl; return 0; }
+        }
         else if (flag == "help" || flag == "h") { print_help(); return 0; }
         else { std::cerr << "Error UnKnow argument -" << flag << std::endl; return 0; }
     }

@@ -32,6 +32,7 @@ struct Options {
     bool levels = false;                 // -levels SPEC (not in the reference): <out>.levels.bed.gz, runs of equal depth ('exact': levels_edges empty) or depth class
     std::vector<uint32_t> levels_edges;  // the classes' lower edges, strictly ascending, at most 64
     std::vector<uint32_t> quantile;      // -quantile SPEC (not in the reference): <out>.quantile.stat.gz, per-row depth percentiles; 1..16 values in 0..100, strictly ascending
+    std::vector<uint32_t> thresholds;    // -thresholds SPEC (not in the reference): <out>.thresholds.stat.gz, per-row counts of cells at or above each depth; 1..16 values below 2^31, strictly ascending
 };
 
 // Returns the number of input files (0 => nothing to do / message already printed), like
@@ -56,6 +57,8 @@ void print_help();
 //   levels_chunk=N (cells per pd_depth_levels call of the -levels writer; default 2^24)
 //   quantile_wave_max=N  quantile_split_cells=N (pd_set_param keys of the -quantile kernels: the row sizes at which the launch shape changes, see pandepth_amd_dev.h)
 //   quantile_device=0 (the -quantile rows selected on the host threads from cells read back, as an engine without the entry points does)
+//   threshold_wave_max=N (pd_set_param key of the -thresholds kernels: the row size above which a row is counted in pieces, see pandepth_amd_dev.h)
+//   thresholds_device=0 (the -thresholds rows counted on the host threads from cells read back, as an engine without the entry points does)
 //   environment: PANDEPTH_DEVTRACE=1 (a [devtrace] line per batch: host-clock times of its stage events; first batches: what pd_decode_queue's own time went to)
 // -X is not part of the reference's command line (which answers an unknown flag with "Error UnKnow argument"): it is accepted only in this
 // spelling, is not listed by -h, and a PANDEPTH_* variable of the earlier rounds that is still set gets a note on stderr.
