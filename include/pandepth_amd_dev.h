@@ -14,7 +14,9 @@ extern "C" {
 /* Tuning knobs (never change results): "lmax" (owner-tile look-back in cells, also the bucket width of compact samples; longer
  * runs take the overflow path), "sample" / "direct_sample" (sparse-index stride in runs), "grid_tiles" (persistent grid of the
  * tile kernels), "scatter_tile" (4096 | 8192), "accumulate_packed" (pd_accumulate_from's transport, default 1), "direct_un"
- * (which compiled variant of the direct kernels runs), "decode_crc" (0: the device decoder skips the members' CRC-32 — kernel
+ * (which compiled variant of the direct kernels runs), "direct_cover" (default 1: the default variant of the compact sample's direct
+ * kernel settles the tiles its runs cover without a window; 0: every tile through the window), "direct_cover_min" (default 2048: tiles
+ * with fewer candidates are not tried), "decode_crc" (0: the device decoder skips the members' CRC-32 — kernel
  * timing only), "decode_near_span" (split of the decoder's later-run stream), "inflate_waves" (one-wave inflate workgroups per CU and
  * launch, 1..23: what the kernel's 7 KB of LDS a wave allow; default 20), "lz_group" (consecutive chunks per workgroup of pd_deflate_parse's LDS parse, 0..16; 0: every chunk reads its
  * text from memory), "lz_slots" (2 | 4 parse calls in flight).  Round 6, the decode pipeline: "decode_h2d_fifo" (default 1: the batches' host-to-device copies

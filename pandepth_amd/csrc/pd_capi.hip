@@ -667,6 +667,8 @@ int pd_set_param(pd_ctx *c, const char *name, uint64_t value)
     if (!strcmp(name, "grid_tiles")) { if (value > (1u << 20)) return fail(c, PD_EINVAL, "grid_tiles out of range"); c->grid_tiles = (unsigned)value; return PD_OK; }
     if (!strcmp(name, "accumulate_packed")) { c->accumulate_packed = value != 0; return PD_OK; }
     if (!strcmp(name, "direct_un")) { c->direct_un = (int)value; return PD_OK; }
+    if (!strcmp(name, "direct_cover")) { c->direct_cover = value != 0; return PD_OK; }
+    if (!strcmp(name, "direct_cover_min")) { c->direct_cover_min = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "direct_sample")) { if (value < 1 || value > 65536) return fail(c, PD_EINVAL, "direct_sample must be in [1, 65536]"); c->direct_sample = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "decode_crc")) { c->dec_crc = value != 0; return PD_OK; }
     if (!strcmp(name, "sweep_i4_fast")) { pdk::set_sweep_i4_fast(value != 0); return PD_OK; }
@@ -1010,7 +1012,8 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
     if (grid > c->n_tiles) grid = (unsigned)c->n_tiles;
     { ProfScope sc(c, "direct_tiles");
       if (c8) launch_direct_c8(c->stream, c->pend[0].cr->view(), c->pend[0].cr->td, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part,
-                               c->direct_words + 16, c->direct_words + 2, grid, c->direct_un);
+                               c->direct_words + 16, c->direct_words + 2, grid, c->direct_un,
+                               c->direct_cover && all >= (uint64_t)c->direct_cover_min * c->n_tiles /* a thin sample: the form without the pass (launch_direct_c8) */, c->direct_cover_min);
       else launch_direct_tiles(c->stream, ps, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, d_wo,
                                d_cov, d_sum, c->direct_words, c->direct_words + 1, c->direct_words + 16, c->direct_words + 2, grid, c->direct_un); }
     if (w >= PD_TILE) {
@@ -1019,11 +1022,12 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
         launch_window_gather(c->stream, d_part, tm, c->n_contigs, w, nw, d_cov, d_sum);
     }
     HIPOK(c, hipGetLastError());
-    uint32_t words[12] = {0};
-    HIPOK(c, hipMemcpyAsync(words, c->direct_words, 48, hipMemcpyDeviceToHost, c->stream));
+    uint32_t words[13] = {0};                            // [12]: heavy_count[PD_HEAVY_SETTLED]
+    HIPOK(c, hipMemcpyAsync(words, c->direct_words, sizeof words, hipMemcpyDeviceToHost, c->stream));
     HIPOK(c, hipMemcpyAsync(sum, d_sum, b_sum, hipMemcpyDeviceToHost, c->stream));
     HIPOK(c, hipMemcpyAsync(cover, d_cov, (size_t)nw * 4, hipMemcpyDeviceToHost, c->stream));
     HIPOK(c, hipStreamSynchronize(c->stream));
+    c->direct_settled = words[2 + pdk::PD_HEAVY_SETTLED];
     if (words[1]) {                                      // not applicable: batches stay pending
         if (getenv("PANDEPTH_TIMING")) fprintf(stderr, "[timing]   direct window path declined: begins owned %llu of %llu runs, runs with cells %u vs ends owned %u (difference), index error bits 0x%x, "
                             "long runs %u: the arrays are materialised\n", (unsigned long long)words[3] | ((unsigned long long)words[4] << 32),
@@ -1042,6 +1046,7 @@ int pd_scan_reduce_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, unsigned wra
     std::lock_guard<std::mutex> lk(c->mu);
     if (int rs = need_state(c, 0, "pd_scan_reduce_windows")) return rs;
     HIPOK(c, hipSetDevice(c->device));
+    c->direct_settled = 0;
     if (c->direct_windows && c->pristine && !c->pend.empty() && w >= 64 && c->stile == PD_TILE) {
         const uint32_t m = (wrap_bits == 0 || wrap_bits == 32) ? 0xFFFFFFFFu : ((1u << wrap_bits) - 1u);
         bool done = false;
@@ -2453,6 +2458,7 @@ int pd_profile_get(pd_ctx *c, const char *name, double *ms, uint64_t *launches)
             {"decode_end_pending", pd_ctx::DN_END_PEND}, {"decode_guess_units", pd_ctx::DN_GUESS}};
         uint64_t v = 0; bool hit = false;
         for (auto &d : dn) if (!strcmp(name, d.name)) { v = c->dec_n[d.k].load(); hit = true; }
+        if (!strcmp(name, "direct_cover_settled")) { v = c->direct_settled; hit = true; }     // tiles of the last direct window call that k_direct_c8 settled without a window
         if (!strcmp(name, "decode_chain_device")) { v = c->dec_n_fast.load(); hit = true; }
         if (!strcmp(name, "decode_chain_host")) { v = c->dec_n_slow.load(); hit = true; }
         if (!strcmp(name, "decode_segments_redone")) { v = c->dec_n_redo.load(); hit = true; }

@@ -1,0 +1,91 @@
+// pd_cover_rule.h — when is a tile of the direct depth pass COVERED by its candidates, decided from the runs alone (no per-cell depth)?
+//
+// k_direct_c8's cover pass (pd_kernels.hip) and tests/harness/cover_rule_check.cpp (against a per-cell union, on the CPU) share this code.
+//
+// The candidates of a tile are lo words r = (b & 0xFFFF) | (len << 16) (pd_kernels.h) and p0 is the low 16 bits of the tile's first flat
+// cell.  In the kernel's own 16-bit arithmetic sb = (r - p0) & 0xFFFF is < tile for the tile's own runs and lies in [2^16 - bucket, 2^16)
+// for the runs of the bucket before it, which stand for NEGATIVE begins: begin = (int16)sb, end = begin + (r >> 16), both tile-relative.
+//
+// The rule: sweep the runs in the order they are stored, reach = 0; a run with begin > reach is a GAP, any other run makes
+// reach = max(reach, end).  With no gap and reach >= tile at the end, every cell of [0, tile) lies in some run — by induction [0, reach) is
+// covered after every run, whatever the order of the runs, so a stream that is not sorted after all can only make the rule decline.  On a
+// stream sorted by begin the rule is exact.  A run without cells is swept like any other: its end equals its begin, so it never
+// extends the reach past a cell that is not covered, and where it begins beyond the reach the next run with cells begins there too.
+//
+// A sweep may be cut into SEGMENTS of consecutive runs (the kernel: one per wave).  A segment judges its gaps by its own running maximum,
+// which starts at its first begin; combine() then asks of every segment, in order, that its first begin is within the reach of those before
+// it.  That declines some covered tiles (a run reached only by an earlier segment's maximum), never the reverse.
+// The sum of the lengths clipped to the tile (the tile's TotalDepth when nothing wraps) and the number of runs that begin before the tile
+// and reach its first cell (the window path's carry-in) need no order at all.  The cover pass itself needs no carry — a settled tile's depths
+// are never formed — and does not compute one (it passes 0); seg_add keeps it so that the CPU check can hold the 16-bit carry test against the cells.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define PD_COVER_HD __host__ __device__
+#else
+#define PD_COVER_HD
+#endif
+
+namespace pdcover {
+
+constexpr int NONE = -32768;                    // below every begin and end of a candidate (a look-back begin is >= -8192)
+
+struct Seg {                                    // the summary of consecutive runs of one stream
+    int first;                                  // the first run's begin (NONE: no run)
+    int maxend;                                 // the largest end (NONE: no run)
+    int gap;                                    // != 0: a run began in the tile, beyond the running maximum of the runs before it in this segment
+    uint32_t sum;                               // lengths clipped to [0, tile)
+    uint32_t carry;                             // runs with begin < 0 <= end
+};
+struct Tile { bool covered; uint32_t sum, carry; };
+
+PD_COVER_HD inline Seg seg_none() { return Seg{NONE, NONE, 0, 0u, 0u}; }
+PD_COVER_HD inline int run_begin(uint32_t r, uint32_t p0) { return (int)(int16_t)(uint16_t)(r - p0); }
+PD_COVER_HD inline int run_end(uint32_t r, int begin) { return begin + (int)(r >> 16); }
+// |[b, e) ∩ [0, tile)|, for b < tile and b <= e
+PD_COVER_HD inline uint32_t run_clipped(int b, int e, int tile)
+{
+    const int hi = e < 0 ? 0 : (e > tile ? tile : e), lo = b < 0 ? 0 : b;
+    return (uint32_t)(hi - lo);
+}
+// a run that changes no summary it is swept into (the kernel pads a wave's last chunk with it)
+PD_COVER_HD inline uint32_t run_neutral(uint32_t p0) { return (p0 + 0x8000u) & 0xFFFFu; }
+
+PD_COVER_HD inline void seg_add(Seg &s, uint32_t r, uint32_t p0, int tile)
+{
+    const int b = run_begin(r, p0), e = run_end(r, b);
+    if (b == NONE) return;                      // run_neutral
+    if (s.first == NONE) { s.first = b; s.maxend = b; }
+    if (b > s.maxend && b > 0) s.gap = 1;       // (nothing before cell 0 has to be covered)
+    if (e > s.maxend) s.maxend = e;
+    s.sum += run_clipped(b, e, tile);
+    s.carry += (b < 0 && e >= 0) ? 1u : 0u;     // == ((r - p0) & 0xFFFF) + (r >> 16) >= 2^16 for a run no longer than a bucket
+}
+
+PD_COVER_HD inline Seg seg_sweep(const uint32_t *lo, uint32_t n, uint32_t p0, int tile)
+{
+    Seg s = seg_none();
+    for (uint32_t i = 0; i < n; ++i) seg_add(s, lo[i], p0, tile);
+    return s;
+}
+
+// The tile's answer from the summaries of the sorted stream's segments, in order, and of the other stream's, in any order.  The other
+// stream gives its sums only: what it covers is ignored, so a gap that only one of its runs closes declines the tile.
+PD_COVER_HD inline Tile combine(const Seg *sorted, int n_sorted, const Seg *other, int n_other, int tile)
+{
+    Tile t{true, 0u, 0u};
+    int reach = 0;
+    for (int k = 0; k < n_sorted; ++k) {
+        const Seg &s = sorted[k];
+        t.sum += s.sum; t.carry += s.carry;
+        if (s.first == NONE) continue;
+        if (s.gap || s.first > reach) t.covered = false;
+        if (s.maxend > reach) reach = s.maxend;
+    }
+    if (reach < tile) t.covered = false;
+    for (int k = 0; k < n_other; ++k) { t.sum += other[k].sum; t.carry += other[k].carry; }
+    return t;
+}
+
+} // namespace pdcover

@@ -102,7 +102,7 @@ struct pd_ctx {
     bool direct_windows = false;                                  // pd_keep_deferred: a whole deferred sample stays deferred, the direct kernels may read it
     bool pristine = true;                                         // nothing materialised in the arrays since the last reset
     bool sums_stale = false;                                      // the tile sums hold what a direct export wrote while the sample is still deferred
-    uint32_t *direct_words = nullptr;                             // [n_long, fail, heavy_count, pad | heavy tile list]
+    uint32_t *direct_words = nullptr;                             // [n_long, fail, heavy_count, diagnostics ..., [12] tiles settled by the cover pass | heavy tile list at +16]
     bool dec_crc = true;                                          // the decoder checks every member's CRC-32 ("decode_crc")
     unsigned lz_group = 16;                                       // chunks per workgroup of the LDS parse ("lz_group", up to 16; 0: every chunk parses with its text in memory).  Round 5's default: sixteen
                                                                   // chunks of 8 + 2 KiB share a CU's LDS (158 KB: 32 KiB of history + their text), 16 waves per CU — 8.6 ms against 11.8 for the 60 MB call of
@@ -128,6 +128,9 @@ struct pd_ctx {
     uint32_t t_wave_max = 65536;                                  // "threshold_wave_max": the cell count up to which a threshold row is counted by a group of lanes, not in pieces
     int hist_variant = 1;                                         // "hist_variant": the histogram kernels' LDS form (launch_sweep_hist): 1 = one copy per workgroup, folded (measured best)
     int direct_un = 0;                                           // 0 = the default form of the wide direct kernel (launch_direct_tiles)
+    bool direct_cover = true;                                    // k_direct_c8's default form settles covered tiles from the runs (false: the window path for every tile)
+    uint32_t direct_cover_min = 2048;                            // ... of tiles with at least this many candidates (launch_direct_c8)
+    uint64_t direct_settled = 0;                                 // tiles the cover pass settled in the last direct_windows call
     bool all_valid_host = false;
     std::vector<Pending> pend;
     // ---- device decode (pd_decode_*): a few batch slots, each with its own stream and buffers ----

@@ -113,8 +113,11 @@ void launch_copy_words(hipStream_t st, void *dst, const void *src, uint64_t n_wo
 void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, const uint32_t *src_lo, const uint32_t *src_hi, uint64_t n);
 // (k_direct_c8 itself reads cs.lo, cs.o_base and desc only; tab, tile_contig and the bucket starts in cs serve the int-window pass launched
 // behind it for the pile-up tiles)
+// cover (with un = 0 only): the default form with the cover pass in front of the window path (pd_cover_rule.h); the tiles it settles are
+// added to heavy_count[PD_HEAVY_SETTLED]; tiles with fewer than cover_min candidates are not tried
+constexpr int PD_HEAVY_SETTLED = 10;
 void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
-                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un);
+                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min);
 void launch_direct_c8_export(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, void *img, pd_exc *exc,
                              uint32_t cap, uint32_t *count, int *sums, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles);
 void launch_direct_export(hipStream_t st, const PendSet &ps, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles,

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pd_kernels.h"
+#include "pd_cover_rule.h"
 
 namespace pdk {
 
@@ -66,6 +67,22 @@ __device__ __forceinline__ int wave_incl_scan(int x)
     x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2,3
     return x;
 }
+
+// the same for a running maximum of signed values (a lane without a source takes INT_MIN, the maximum's identity)
+__device__ __forceinline__ int wave_incl_scan_max(int x)
+{
+    constexpr int ID = (int)0x80000000u;
+    auto mx = [](int a, int b) { return a > b ? a : b; };
+    x = mx(x, __builtin_amdgcn_update_dpp(ID, x, 0x111, 0xf, 0xf, false));   // row_shr:1
+    x = mx(x, __builtin_amdgcn_update_dpp(ID, x, 0x112, 0xf, 0xf, false));   // row_shr:2
+    x = mx(x, __builtin_amdgcn_update_dpp(ID, x, 0x114, 0xf, 0xf, false));   // row_shr:4
+    x = mx(x, __builtin_amdgcn_update_dpp(ID, x, 0x118, 0xf, 0xf, false));   // row_shr:8
+    x = mx(x, __builtin_amdgcn_update_dpp(ID, x, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1,3
+    x = mx(x, __builtin_amdgcn_update_dpp(ID, x, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2,3
+    return x;
+}
+// lane i takes lane i - 1's value, lane 0 takes `first` (wave_shr:1)
+__device__ __forceinline__ int wave_shift_up(int x, int first) { return __builtin_amdgcn_update_dpp(first, x, 0x138, 0xf, 0xf, false); }
 
 // ------------------------------------------------------------------------------------------
 // fill: 16 B/lane stores, grid-stride
@@ -446,7 +463,7 @@ __device__ __forceinline__ void direct_candidate(const pd_iv v, int32_t ctg, uin
     c.carry += (mine && nonempty && bb < p0 && x >= p0) ? 1 : 0;  // covers the cell just before the tile
 }
 
-struct DirectWide { static constexpr bool narrow = false, exporting = false; uint32_t w, min_dep; TilePart *part; };
+struct DirectWide { static constexpr bool narrow = false, exporting = false; uint32_t w, min_dep; TilePart *part; uint32_t cover_min = 0; /* k_direct_c8's cover pass: tiles with fewer candidates are left to the window */ };
 struct DirectNarrow { static constexpr bool narrow = true, exporting = false; WinArgs wa; const uint64_t *win_off; };
 struct DirectExport {                  // the multi-GPU sum's 4-bit image straight from the tile windows (pd_export_i4)
     static constexpr bool narrow = false, exporting = true;
@@ -1623,12 +1640,18 @@ __global__ __launch_bounds__(WG) void k_r8_to_iv(const uint32_t *lo, const uint3
 // with more than 32 000 candidates go to the int-window kernel through the same list.
 // LW (JOIN only, a divisor of UN8): runs per lane and load in the full chunks of the sorted stream — 1, 2 (8-byte loads) or 4 (16-byte loads; the
 // stream's words are 4-byte aligned, the loads are not); which thread works on which run changes, nothing else (the window's updates commute).
-template <int WPE, int UN8, bool EXPORT, bool JOIN = false, int LW = 1>
+// COVER (statistics form only): the cover pass in front of the window path — see it below.  Its gate is a score per workgroup: a declined tile adds
+// COVER_DECLINE, a settled one takes 1 off (not below 0); at COVER_CLOSE the workgroup leaves the pass out for COVER_SKIP tiles, tries one, and goes on
+// so while the score stays there.  Four declined tiles in a row close it; so does, in the long run, any mix in which fewer than two tiles in three
+// settle (a declined tile costs a sweep on top of its window, about twice what a settled one saves: launch_direct_c8).
+constexpr uint32_t COVER_DECLINE = 2, COVER_CLOSE = 8, COVER_SKIP = 15;
+template <int WPE, int UN8, bool EXPORT, bool JOIN = false, int LW = 1, bool COVER = false>
 __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const TileDesc *__restrict__ desc, uint32_t n_tiles,
                                                      uint32_t wrap_mask, const DirectWide args, uint32_t *__restrict__ heavy_list,
                                                      uint32_t *__restrict__ heavy_count, const DirectExport ex)
 {
     static_assert(LW == 1 || (JOIN && (LW == 2 || LW == 4) && UN8 % LW == 0), "wide loads: JOIN form, LW runs per load");
+    static_assert(!(COVER && EXPORT), "the cover pass settles statistics, the export form needs every cell");
     const uint32_t w = args.w, min_dep = args.min_dep; TilePart *const part = args.part;
     constexpr uint32_t ST = TILE, HT = TILE / 2;
     constexpr int ROWS = (int)(HT / (WG * 4));
@@ -1637,6 +1660,8 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
     __shared__ int wtot[4];
     __shared__ unsigned long long red_s[4][2];
     __shared__ int red_c[4][2];
+    __shared__ uint4 s_cov[2][4];                                 // COVER: the four waves' summaries, two sets in turn
+    uint32_t cov_flip = 0, cov_miss = 0, cov_skip = 0, cov_settled = 0;   // COVER, workgroup-uniform
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // a tile's bounds, its place in its contig and the contig's length are ONE record of the sample's descriptor table (TileDesc), read
     // through a pointer nothing is stored through: scalar loads, issued a tile ahead behind the first run loads, so that no tile waits
@@ -1657,6 +1682,100 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
             if (threadIdx.x == 0) heavy_list[atomicAdd(heavy_count, 1u)] = (uint32_t)t;
             if (t_next < n_tiles) nxt = desc[t_next];
             continue;
+        }
+        if constexpr (COVER) {
+            // ---- the cover pass: an interior tile whose depths cannot wrap, asked for min_dep <= 1, needs no window when its runs cover it ----
+            // (pd_cover_rule.h.)  TotalDepth is the sum of the candidates' lengths clipped to the tile, CoveredSite is all of the tile's cells
+            // when the sorted stream's runs leave no gap (always, for min_dep = 0).  Workgroup-uniform, from the descriptor and the arguments:
+            // inside the contig, inside one window, no depth above the candidate count, and enough candidates for the sweep to be the cheaper way
+            // (cover_min, see launch_direct_c8).  A tile the pass cannot settle takes the window
+            // path below from its top, so the result never depends on it; a workgroup whose tiles mostly decline skips the pass
+            // and tries it again on every (COVER_SKIP + 1)-th tile (the gate above).
+            bool eligible = false;
+            if (cov_skip) --cov_skip;
+            else if (min_dep <= 1u && cand <= wrap_mask && cand >= args.cover_min && pc < clen && clen - pc >= ST)
+                eligible = ((uint64_t)(pc / w) + 1u) * (uint64_t)w - pc >= (uint64_t)ST;
+            if (eligible) {
+                if (t_next < n_tiles) nxt = desc[t_next];
+                uint32_t ln = (uint32_t)lane;                      // made opaque here: what the pass derives from the lane is computed in the pass, not kept
+                asm volatile("" : "+v"(ln));                      // in registers across the window path (72 VGPRs hold both only this way)
+                const uint32_t *__restrict__ const p = cs.lo;
+                const bool any_gap_ends = min_dep != 0u;          // min_dep = 0 counts every cell: only the sum is needed, never stop early
+                const uint32_t wvu = (uint32_t)__builtin_amdgcn_readfirstlane(wv);
+                // this wave's quarter of the sorted candidates, in order, and its quarter of the other stream's
+                const uint32_t qs = (ns + 3u) >> 2, s_lo = wvu * qs < ns ? wvu * qs : ns, n_w = ns - s_lo < qs ? ns - s_lo : qs;
+                const uint32_t qo = (no + 3u) >> 2, o_lo = wvu * qo < no ? wvu * qo : no, n_o = no - o_lo < qo ? no - o_lo : qo;
+                const uint32_t *const ps = p + (s_at + s_lo), *const po = p + (cs.o_base + olo + o_lo);
+                const uint32_t n_full = n_w >> 8, n_rem = n_w & 255u;
+                const uint32_t neutral = pdcover::run_neutral(p0);
+                // loads first: the quarter's last, partial chunk (four consecutive runs per lane; past the end: a run that changes nothing),
+                // the first 64 runs of the other stream, the first full chunk
+                uint32_t tl[4] = {neutral, neutral, neutral, neutral}, o0 = neutral;
+                if (n_rem) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) { const uint32_t j = ln * 4u + (uint32_t)k; if (j < n_rem) tl[k] = ps[n_full * 256u + j]; }
+                }
+                if (ln < n_o) o0 = po[ln];
+                uint4 cur4 = make_uint4(neutral, neutral, neutral, neutral);
+                if (n_full) cur4 = *reinterpret_cast<const uint4 *>(ps + ln * 4u);
+                int first = pdcover::NONE, reach = pdcover::NONE;   // wave-uniform: the quarter's first begin, its running maximum
+                bool gap = false;
+                uint32_t sum = 0;                                 // this lane's clipped lengths
+                auto sweep4 = [&](const uint32_t r0, const uint32_t r1, const uint32_t r2, const uint32_t r3) {
+                    const int b0 = pdcover::run_begin(r0, p0), b1 = pdcover::run_begin(r1, p0), b2 = pdcover::run_begin(r2, p0), b3 = pdcover::run_begin(r3, p0);
+                    const int e0 = pdcover::run_end(r0, b0), e1 = pdcover::run_end(r1, b1), e2 = pdcover::run_end(r2, b2), e3 = pdcover::run_end(r3, b3);
+                    sum += pdcover::run_clipped(b0, e0, (int)ST) + pdcover::run_clipped(b1, e1, (int)ST) + pdcover::run_clipped(b2, e2, (int)ST) + pdcover::run_clipped(b3, e3, (int)ST);
+                    if (first == pdcover::NONE) {                 // (lane 0's first run is a real one: the chunk is not empty)
+                        first = __builtin_amdgcn_readfirstlane(b0);
+                        reach = first > 0 ? first : 0;            // nothing before cell 0 has to be covered
+                    }
+                    const int m0 = e0, m1 = m0 > e1 ? m0 : e1, m2 = m1 > e2 ? m1 : e2, m3 = m2 > e3 ? m2 : e3;
+                    const int incl = wave_incl_scan_max(m3);
+                    const int before = wave_shift_up(incl, pdcover::NONE);      // the largest end of the lanes before this one
+                    const int P = before > reach ? before : reach;
+                    const int P0 = P > m0 ? P : m0, P1 = P > m1 ? P : m1, P2 = P > m2 ? P : m2;
+                    const unsigned long long g = __builtin_amdgcn_ballot_w64(b0 > P) | __builtin_amdgcn_ballot_w64(b1 > P0) | __builtin_amdgcn_ballot_w64(b2 > P1) |
+                                                 __builtin_amdgcn_ballot_w64(b3 > P2);          // four compares, joined on the scalar side
+                    if (g != 0ull) gap = true;
+                    const int top = __builtin_amdgcn_readlane(incl, 63);
+                    reach = top > reach ? top : reach;
+                };
+#pragma unroll 1
+                for (uint32_t q = 0; q < n_full; ++q) {
+                    const uint4 u = cur4;
+                    if (q + 1 < n_full) cur4 = *reinterpret_cast<const uint4 *>(ps + (q + 1) * 256u + ln * 4u);
+                    sweep4(u.x, u.y, u.z, u.w);
+                    if (gap && any_gap_ends) break;
+                }
+                if (!(gap && any_gap_ends)) {
+                    if (n_rem) sweep4(tl[0], tl[1], tl[2], tl[3]);
+                    {   // the other stream: what it covers is ignored, its lengths count
+                        const int b = pdcover::run_begin(o0, p0);
+                        sum += pdcover::run_clipped(b, pdcover::run_end(o0, b), (int)ST);
+                    }
+                    for (uint32_t j = ln + 64u; j < n_o; j += 64u) {
+                        const uint32_t r = po[j];
+                        const int b = pdcover::run_begin(r, p0);
+                        sum += pdcover::run_clipped(b, pdcover::run_end(r, b), (int)ST);
+                    }
+                }
+                const uint32_t wsum = (uint32_t)wave_total((int)sum);
+                uint4 *const slot = &s_cov[cov_flip][0];
+                if (ln == 0u) slot[wvu] = make_uint4((uint32_t)first, (uint32_t)reach, gap ? 1u : 0u, wsum);
+                __syncthreads();                                  // (the slots alternate: the next pass writes the other four while a late wave still reads these)
+                pdcover::Seg seg[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { const uint4 u = slot[k]; seg[k] = pdcover::Seg{(int)u.x, (int)u.y, (int)u.z, u.w, 0u}; }
+                cov_flip ^= 1u;
+                const pdcover::Tile tile = pdcover::combine(seg, 4, nullptr, 0, (int)ST);
+                if (tile.covered || !any_gap_ends) {
+                    if (threadIdx.x == 0) { TilePart tp; tp.c0 = ST; tp.c1 = 0u; tp.s0 = tile.sum; tp.s1 = 0ull; part[t] = tp; }
+                    ++cov_settled; cov_miss -= cov_miss ? 1u : 0u;
+                    continue;
+                }
+                cov_miss += COVER_DECLINE;
+                if (cov_miss >= COVER_CLOSE) { cov_miss = COVER_CLOSE; cov_skip = COVER_SKIP; }
+            }
         }
         uint4 *w4 = reinterpret_cast<uint4 *>(win);
         int carry_s = 0;
@@ -1870,6 +1989,9 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
             tp.s1 = red_s[0][1] + red_s[1][1] + red_s[2][1] + red_s[3][1];
             part[t] = tp;
         }
+    }
+    if constexpr (COVER) {                                        // how many tiles the pass settled: one addition per workgroup, for the tests
+        if (threadIdx.x == 0 && cov_settled) atomicAdd(heavy_count + PD_HEAVY_SETTLED, cov_settled);
     }
 }
 
@@ -3139,9 +3261,18 @@ void launch_r8_to_iv(hipStream_t st, const uint32_t *lo, const uint32_t *hi, uin
 }
 
 void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
-                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un)
+                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min)
 {
-    const DirectWide dw{w, min_dep, part};
+    // cover_min ("direct_cover_min", default 2048 candidates per tile): a tile visit costs the cover pass more than the window path before its first run
+    // (measured on the bench genome, ms per launch with / without the pass tried on every tile: 1e9 records, 3 224 candidates per tile: 1.10 / 1.38; 3e8,
+    // 970 per tile, 98 % of the tiles settled: 0.82 / 0.74; 1e8, 322 per tile, 6 % settled: 1.14 / 0.85 — the lines cross near 1 450 candidates), so thinner
+    // tiles keep the window.  The cover form's window path is itself 0.04 - 0.06 ms per launch behind the parent form's on those samples (17 SGPRs kept in
+    // VGPR lanes), so the CALLER passes cover = false for a sample whose mean is below cover_min candidates per tile: it then runs the form without the pass.
+    // The gate (COVER_DECLINE = 2, COVER_CLOSE = 8, COVER_SKIP = 15) is per workgroup and acts only where a workgroup walks many tiles ("grid_tiles"): with
+    // the default grid a workgroup walks five or six tiles, the gate closes after four of them, and a dense sample with gaps pays a sweep on top of the window
+    // for most of its tiles — measured 1.480 -> 1.949 ms where every tile has gaps, 1.440 -> 1.624 where every other has (profiles/r10_direct_cover_ab.txt,
+    // section 6).  Such a sample is better off with "direct_cover" 0 until the tallies are shared between workgroups.
+    const DirectWide dw{w, min_dep, part, cover_min};
     // "direct_un" for a compact sample: 100 x waves-per-SIMD target + loads in flight per thread (0 = default)
 #define PD_C8(WPE_, UN8_) hipLaunchKernelGGL((k_direct_c8<WPE_, UN8_, false>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{})
     switch (un) {
@@ -3181,7 +3312,10 @@ void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigT
     // round 4, two streams (ms by the context's events, which also bracket the pile-up and finish launches): <8, 3> 2.35; joined tail: <8, 3> 2.33, <8, 2> 2.07, <7, 3> 2.07, <7, 4> 2.04
     // round 9, 4-byte runs (lo plane), the same events on the bench sample: <7, 4> 1.390, <6, 8> with 8-byte loads 1.384, <8, 4> plain 1.390, <7, 8> 1.392, <7, 4> with 8- / 16-byte
     // loads 1.416 / 1.407, <6, 8> with 16-byte loads 1.438, <7, 8> with 8- / 16-byte loads 1.605 / 1.811 (spills) — loads in flight no longer decide (profiles/r09_runs_planes_ab.txt)
-    default: PD_C8J(7, 4, 1); break;
+    default:
+        if (cover) hipLaunchKernelGGL((k_direct_c8<7, 4, false, true, 1, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{});
+        else PD_C8J(7, 4, 1);
+        break;
     }
 #undef PD_C8J
 #undef PD_C8

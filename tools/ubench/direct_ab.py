@@ -12,6 +12,14 @@ names, lens = synth.genome_c2()
 eng = pda.Engine(lens.astype(np.uint32), device=0)
 R = int(float(os.environ.get("R", "1e9")))
 first, other = synth.gen_runs_torch(lens, R, dev, seed=42)
+# GAPS=all: no run begins in the first 400 of every 5000 cells, so every tile keeps its candidates and has a gap of 250 cells or more; GAPS=half: only in
+# every other tile (a dense sample WITH gaps: what the cover pass's gate is for)
+if os.environ.get("GAPS"):
+    def keep(iv):
+        hole = (iv[:, 1] % 5000) < 400
+        if os.environ["GAPS"] == "half": hole &= (iv[:, 1] // 8192) % 2 == 0
+        return iv[~hole].contiguous()
+    first, other = keep(first), keep(other)
 torch.cuda.synchronize()
 eng.keep_deferred(True)
 runs8 = eng.runs_create(first.data_ptr(), int(first.shape[0]), other.data_ptr(), int(other.shape[0]))   # the sample in the compact form (variants "c<un>")
@@ -37,7 +45,13 @@ for vs in variants:
     if compact: vs = vs[1:]
     v = int(vs.split("@")[0].split("/")[0])
     eng.set_param("grid_tiles", int(vs.split("@")[1]) if "@" in vs else 0)
-    opts = vs.split("/")[1:]                                  # /s64 = direct_sample 64, /l160 = lmax 160
+    opts = vs.split("/")[1:]                                  # /s64 = direct_sample 64, /l160 = lmax 160, /k0 = direct_cover 0 (k_direct_c8 without the cover pass), /m0 = direct_cover_min 0
+    cover = next((int(o[1:]) for o in opts if o[0] == "k"), 1)
+    try:
+        eng.set_param("direct_cover", cover)
+        eng.set_param("direct_cover_min", next((int(o[1:]) for o in opts if o[0] == "m"), 2048))
+    except Exception:                                         # (a library from before the knob, chosen with PANDEPTH_AMD_LIB: its kernel IS the /k0 form,
+        if cover: raise                                       #  so only /k0 may be asked of it)
     eng.set_param("direct_sample", next((int(o[1:]) for o in opts if o[0] == "s"), 256))
     eng.set_param("lmax", next((int(o[1:]) for o in opts if o[0] == "l"), 512))
     eng.set_param("direct_un", v)
@@ -63,7 +77,7 @@ for vs in variants:
     ms, n = eng.profile_get("direct_tiles")
     ims, inn = eng.profile_get("scatter_index")
     eng.profile(False)
-    print("variant %s%5d %s grid %s: direct_tiles %.3f ms/launch (%d), index %.3f ms/step, step wall %.3f ms, tables %s" % ("compact " if compact else "", v, "/".join(opts), vs.split("@")[1] if "@" in vs else "auto", ms / max(n, 1), n, ims / N, dt, "equal" if ok else "DIFFERENT"), flush=True)
+    print("variant %s%5d %s grid %s: direct_tiles %.3f ms/launch (%d), index %.3f ms/step, step wall %.3f ms, tables %s, tiles settled by the cover pass %d" % ("compact " if compact else "", v, "/".join(opts), vs.split("@")[1] if "@" in vs else "auto", ms / max(n, 1), n, ims / N, dt, "equal" if ok else "DIFFERENT", eng.profile_get("direct_cover_settled")[1] if cover else 0), flush=True)
     if os.environ.get("EXPORT", "1") == "1":
         # the export instantiation (pd_export_i4 on the deferred sample: what a rank of the multi-GPU sum runs)
         scatter(); eng.export_i4(img.data_ptr(), exc.data_ptr(), 1 << 18, cnt.data_ptr()); eng.synchronize()
