@@ -451,6 +451,14 @@ typedef struct pd_decode_cfg {
                                     /* flags: PD_DECODE_COMPACT — the caller will ask for whole-contig statistics                */
                                     /* (pd_scan_reduce_windows, w >= 8192): pd_decode_end leaves a sorted file's runs as ONE        */
                                     /* compact sample (pd_runs) instead of 12-byte arrays                                          */
+                                    /* PD_DECODE_DELETIONS — deletions count as covered (the executable's -del): a kept read adds 1   */
+                                    /* to every cell inside an M/=/X/D operation, and the walk emits ONE run per group — a maximal    */
+                                    /* sequence of M/=/X/D operations with no N between them (I/S/H/P do not split it, an N of any     */
+                                    /* length does).  The group no N comes before is the read's first run and begins at pos; a read  */
+                                    /* without N is that one run.  Read selection, the region test's endpos, clipping and everything   */
+                                    /* after the runs are as without the flag; pd_decode_result::n_first / n_other count groups.       */
+                                    /* (Long reads become runs longer than a bucket: a PD_DECODE_COMPACT session counts them and the   */
+                                    /* compact sample takes them by its long-run path, as it does any such run.)                       */
     uint64_t n_batches;             /* 0 = unknown.  Otherwise the caller promises to submit exactly this many batches, once each, with */
                                     /* pd_decode_batch::order = 0 .. n_batches - 1 in file order (a batch with nothing to decode is still   */
                                     /* submitted, empty; orders need not ARRIVE in order, but a thread must hold its buffer — pd_decode_-   */
@@ -460,6 +468,7 @@ typedef struct pd_decode_cfg {
                                     /* sorts the later runs of multi-run reads (about a tenth of all runs) by bucket.                       */
 } pd_decode_cfg;
 #define PD_DECODE_COMPACT 1u
+#define PD_DECODE_DELETIONS 2u
 typedef struct pd_decode_unit { uint64_t start, stop, avail; uint32_t first_block, n_blocks, flags, pad; } pd_decode_unit;
 typedef struct pd_decode_batch {
     void *host_buf; size_t n_bytes;                              /* from pd_decode_acquire: whole BGZF members           */

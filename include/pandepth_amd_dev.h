@@ -17,7 +17,8 @@ extern "C" {
  * (which compiled variant of the direct kernels runs), "direct_cover" (default 1: the default variant of the compact sample's direct
  * kernel settles the tiles its runs cover without a window; 0: every tile through the window), "direct_cover_min" (default 2048: tiles
  * with fewer candidates are not tried), "decode_crc" (0: the device decoder skips the members' CRC-32 — kernel
- * timing only), "decode_near_span" (split of the decoder's later-run stream), "inflate_waves" (one-wave inflate workgroups per CU and
+ * timing only), "decode_near_span" (split of the decoder's later-run stream), "decode_deletions" (0 | 1: this one DOES change results — pd_push_bgzf_units,
+ * whose signature is fixed, opens its session with PD_DECODE_DELETIONS while it is 1; sessions opened with pd_decode_begin say so in their own flags and ignore it), "inflate_waves" (one-wave inflate workgroups per CU and
  * launch, 1..23: what the kernel's 7 KB of LDS a wave allow; default 20), "lz_group" (consecutive chunks per workgroup of pd_deflate_parse's LDS parse, 0..16; 0: every chunk reads its
  * text from memory), "lz_slots" (2 | 4 parse calls in flight).  Round 6, the decode pipeline: "decode_h2d_fifo" (default 1: the batches' host-to-device copies
  * first come, first served on the context's main stream, one copy per batch; 0: on the batch's own stream), "decode_h2d_lanes" (1 | 2 copies on the link at a

@@ -20,6 +20,7 @@ def PD_PUSH_DISORDER(cells):
 PD_TILE = 8192
 PD_UNIT_GUESS = 1
 PD_DECODE_COMPACT = 1
+PD_DECODE_DELETIONS = 2
 PD_NONE = 0xFFFFFFFFFFFFFFFF                     # pd_decode_result::first_start / next_start: no such record
 
 
@@ -563,9 +564,11 @@ class Engine:
         self._ck(self.L.pd_gather_windows(self.h, ctypes.c_void_p(int(partials_ptr)), int(w), _ptr(cover), _ptr(tot)))
         return off, cover[:n], tot[:n]
 
-    def push_bgzf_units(self, blob, blocks, units, inflated_bytes, flag_mask=1796, min_mapq=-1):
+    def push_bgzf_units(self, blob, blocks, units, inflated_bytes, flag_mask=1796, min_mapq=-1, count_deletions=False):
         """blocks: (n,4) uint64-compatible rows {in_off, out_off, in_len, out_len}; units: rows
-        {start, stop, avail, first_block, n_blocks}.  Returns (unit_status int32 array, n_records)."""
+        {start, stop, avail, first_block, n_blocks}.  Returns (unit_status int32 array, n_records).
+        count_deletions: deletions count as covered (PD_DECODE_DELETIONS).  The C entry takes it from the parameter "decode_deletions",
+        which every call here sets to this argument's value: the argument alone decides, whatever set_param left there."""
         blob = np.frombuffer(blob, dtype=np.uint8)
         bd = np.zeros(len(blocks), dtype=np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4")]))
         for k, name in enumerate(("in_off", "out_off", "in_len", "out_len")):
@@ -576,6 +579,7 @@ class Engine:
             ud[name] = [u[k] for u in units]
         st = np.zeros(max(1, len(units)), dtype=np.int32)
         nrec = ctypes.c_uint64()
+        self.set_param("decode_deletions", 1 if count_deletions else 0)
         self._ck(self.L.pd_push_bgzf_units(self.h, _ptr(blob), blob.size, _ptr(bd), len(blocks), _ptr(ud), len(units),
                                            int(inflated_bytes), int(flag_mask), int(min_mapq), _ptr(st), ctypes.byref(nrec)))
         return st[:len(units)], int(nrec.value)
@@ -614,7 +618,10 @@ class DecodeSession:
         self.held = []                       # buffers acquired and not yet handed to submit / queue
 
     def begin(self, flag_mask=1796, min_mapq=-1, contig_on=None, span_off=None, spans=None, sorted=1, bytes_hint=0, batch_bytes=0,
-              batches_in_flight=0, flags=0, n_batches=0):
+              batches_in_flight=0, flags=0, n_batches=0, count_deletions=False):
+        """count_deletions adds PD_DECODE_DELETIONS to `flags`: deletions count as covered, one run per group of M/=/X/D operations"""
+        if count_deletions:
+            flags = int(flags) | PD_DECODE_DELETIONS
         cfg = pd_decode_cfg()
         cfg.flag_mask, cfg.min_mapq, cfg.sorted = int(flag_mask), int(min_mapq), int(sorted)
         cfg.bytes_hint, cfg.batch_bytes, cfg.batches_in_flight, cfg.flags, cfg.n_batches = int(bytes_hint), int(batch_bytes), int(batches_in_flight), int(flags), int(n_batches)

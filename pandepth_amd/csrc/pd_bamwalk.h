@@ -18,6 +18,14 @@
 // dense arrays: the first run of every read in file order (position sorted for a coordinate-sorted BAM), the other runs
 // behind them in the same order.
 //
+// Two counting rules, chosen when the kernels are compiled (the template parameter DEL of everything from walk_segment /
+// emit_segment down; Cfg::count_del says which instance a launch takes):
+//   * DEL = false, the reference's rule (PD:438-460): one run per M/=/X operation, D and N only move the cursor;
+//   * DEL = true, `-del`: deletions count as covered.  A GROUP is a maximal sequence of M/=/X/D operations with no N between
+//     them (I/S/H/P inside do not split it, an N of any length, 0 included, does); every group is ONE run from the cursor at its
+//     first operation to the cursor behind its last.  The group no N comes before is the record's first run (it begins at
+//     pos); every later group is an "other" run.  A read without N is one run.
+//
 // The same source compiles for gfx950 and for the host (tests/harness/bamwalk_check.cpp compares it with the host reader).
 #ifndef PD_BAMWALK_H_
 #define PD_BAMWALK_H_
@@ -66,6 +74,7 @@ struct Cfg {                              // wave-uniform
     uint32_t flag_mask; int32_t min_mapq;
     const uint32_t *span_off; const int32_t *spans;                            // -g / -b: (begin0, end) per contig, sorted; or null
     uint32_t near_span;
+    uint32_t count_del = 0;               // PD_DECODE_DELETIONS: the launch takes the DEL = true kernels (the walk itself reads the template parameter)
     C8Out c8;
 };
 
@@ -167,10 +176,27 @@ PW_FN Rec open_record(const Cfg &c, uint64_t p, uint32_t bs)
     return x;
 }
 
-// M/=/X runs of one kept record; emit(first?, beg, end).  Returns the reference end position.
-template <class F> PW_FN int32_t walk_cigar(const Rec &x, F emit)
+// M/=/X runs (DEL: the groups) of one kept record; emit(first?, beg, end).  Returns the reference end position.
+template <bool DEL = false, class F> PW_FN int32_t walk_cigar(const Rec &x, F emit)
 {
     int32_t cur = x.pos;
+    if (DEL) {
+        bool open = false, first = true;                                  // a group is open (it began at gbeg); no N so far
+        int32_t gbeg = 0;
+        for (uint32_t i = 0; i < x.n_cig; ++i) {
+            const uint32_t cg = rd32(x.cig + 4 * i), op = cg & 0xf;
+            const int32_t nxt = (int32_t)((uint32_t)cur + (cg >> 4));      // (the same spelled-out wrap as below)
+            if (op == 0 || op == 7 || op == 8 || op == 2) {
+                if (!open) { open = true; gbeg = cur; }
+                cur = nxt;
+            } else if (op == 3) {
+                if (open) { emit(first, gbeg, cur); open = false; }
+                first = false; cur = nxt;
+            }
+        }
+        if (open) emit(first, gbeg, cur);
+        return cur;
+    }
     bool first_done = false, moved = false;
     for (uint32_t i = 0; i < x.n_cig; ++i) {
         const uint32_t cg = rd32(x.cig + 4 * i), op = cg & 0xf;
@@ -235,7 +261,7 @@ PW_FN void first_run(const Cfg &c, LaneWalk &w, int32_t tid, int32_t beg, int32_
 // stands (p, guard, w: its state, so that the walk can be taken up again).  Returns true when it has stopped AT a record whose CIGAR
 // the wave is to walk (`pend` says which; nothing of that record has been counted yet but ++n_rec) — the caller adds the record's
 // runs and calls again with p = pend.next_p — and false when the lane is through (w.e = where its chain ends).
-template <bool EMIT>
+template <bool EMIT, bool DEL>
 PW_FN bool walk_lane(const Cfg &c, uint64_t &p, uint64_t b, uint32_t &guard, LaneWalk &w, Pending &pend, pd_iv *first, pd_iv *other, pd_iv *far, uint64_t of, uint64_t oo, uint64_t ofar)
 {
     for (; p < b && guard < SUB / 36 + 2; ++guard) {
@@ -263,7 +289,7 @@ PW_FN bool walk_lane(const Cfg &c, uint64_t &p, uint64_t b, uint32_t &guard, Lan
             }
             if (take) {
                 uint32_t nf = 0, no = 0, nfar = 0, span = 0;
-                walk_cigar(x, [&](bool is_first, int32_t beg, int32_t end) {
+                walk_cigar<DEL>(x, [&](bool is_first, int32_t beg, int32_t end) {
                     if (is_first) { first_run<EMIT>(c, w, x.tid, beg, end, first, of); nf = 1; return; }
                     const uint32_t d = (uint32_t)beg - (uint32_t)x.pos;
                     if (d > span) span = d;
@@ -285,9 +311,94 @@ PW_FN bool walk_lane(const Cfg &c, uint64_t &p, uint64_t b, uint32_t &guard, Lan
 // lane that owns the record writes it, with the keys and marks of its stream), every other run is written (emit) at
 // other[obase + its rank] and counted; span = the largest distance of such a run's begin from the record's position.
 struct CoopOut { uint32_t has_first; int32_t fbeg, fend; uint32_t n_other, span; int32_t endpos; };
+
+// The same for the groups of the DEL rule.  Per step of 64 operations: rm = the M/=/X/D operations, gm = the N.  A group ends at the
+// run operation whose next run-or-gap operation is an N — that lane writes it (or it is the record's first run: no N before it;
+// where the N is the first such operation of a later step, the group is closed there from the carried scalars) —,
+// and begins at the first run operation behind the last N before that lane, whose cursor the lane fetches with one shuffle of the
+// prefix sums; a group that is open when a step ends is carried on in two scalars (open, gbeg) and the record's last one is closed
+// behind the loop.  Everything but the lanes' own bit arithmetic and stores is wave-uniform.
 template <class W>
+PW_FN CoopOut coop_groups(const Cfg &c, uint64_t cig_off, uint32_t n, int32_t tid, int32_t pos, pd_iv *other, uint64_t obase, bool emit)
+{
+    typedef typename W::template Var<uint32_t> U;
+    CoopOut r; r.has_first = 0; r.fbeg = r.fend = 0; r.n_other = 0; r.span = 0;
+    uint32_t cur0 = (uint32_t)pos, gbeg = 0;
+    bool open = false, cut = false;                                       // a group is open across the step boundary; an N has been passed
+    const auto close_carried = [&]() {                                    // the open group ends where the cursor stands (wave-uniform; the store is lane 0's alone)
+        if (!cut) { r.has_first = 1; r.fbeg = pos; r.fend = (int32_t)cur0; }
+        else {
+            const uint32_t d = gbeg - (uint32_t)pos;
+            if (d > r.span) r.span = d;
+            if (emit) W::each([&](int l) { if (l == 0) other[obase + r.n_other] = pd_iv{tid, (int32_t)gbeg, (int32_t)cur0}; });
+            ++r.n_other;
+        }
+        open = false;
+    };
+    for (uint32_t k0 = 0; k0 < n; k0 += 64) {
+        U adv, isrun, isgap, len;
+        W::each([&](int l) {
+            const uint32_t i = k0 + (uint32_t)l;
+            const uint32_t cg = i < n ? rd32(c.buf + cig_off + 4ull * i) : 0xFu;         // (15: no operation)
+            const uint32_t op = cg & 0xf;
+            len[l] = cg >> 4;
+            isrun[l] = (op == 0 || op == 7 || op == 8 || op == 2) ? 1u : 0u;
+            isgap[l] = op == 3 ? 1u : 0u;
+            adv[l] = (isrun[l] | isgap[l]) ? len[l] : 0u;
+        });
+        uint32_t tot = 0;
+        const U ea = W::excl_scan(adv, &tot);                                              // (wraps like the reference's int cursor)
+        const uint64_t rm = W::ballot_ne(isrun, 0u), gm = W::ballot_ne(isgap, 0u), am = rm | gm;
+        if (open && gm && !(rm & ((1ull << ctz64(gm)) - 1))) close_carried();              // its last operation was in an earlier step: an N comes first here
+        if (rm) {
+            U src, closes;                                                                 // src: the lane whose cursor is the group's begin (64: gbeg)
+            W::each([&](int l) {
+                src[l] = (uint32_t)l; closes[l] = 0;
+                if (!((rm >> l) & 1)) return;
+                const uint64_t nx = l == 63 ? 0ull : am & (~0ull << (l + 1));
+                if (!nx || !((gm >> ctz64(nx)) & 1)) return;                               // the group goes on behind this operation
+                closes[l] = 1;
+                const uint64_t gb = gm & ((1ull << l) - 1);                                // the N before it in this step (the last one is below lane 63)
+                src[l] = gb ? (uint32_t)ctz64(rm & (~0ull << (64 - __builtin_clzll(gb)))) : open ? 64u : (uint32_t)ctz64(rm);
+            });
+            const uint64_t em = W::ballot_ne(closes, 0u);
+            const U sb = W::shfl(ea, src);
+            int fl = -1;                                                                   // the record's first run closes here
+            if (em && !cut && !(gm & ((1ull << ctz64(em)) - 1))) fl = ctz64(em);
+            const uint64_t om = fl >= 0 ? em & ~(1ull << fl) : em;
+            U dd;
+            W::each([&](int l) {
+                dd[l] = 0;
+                if (!((om >> l) & 1)) return;
+                const uint32_t beg = src[l] == 64u ? gbeg : cur0 + sb[l], d = beg - (uint32_t)pos;
+                dd[l] = d;
+                if (emit) other[obase + r.n_other + W::prefix_count(om, l)] = pd_iv{tid, (int32_t)beg, (int32_t)(cur0 + ea[l] + len[l])};
+            });
+            if (om) { const uint32_t mx = W::reduce_max(dd); if (mx > r.span) r.span = mx; }
+            if (fl >= 0) { r.has_first = 1; r.fbeg = pos; r.fend = (int32_t)(cur0 + W::bcast(ea, fl) + W::bcast(len, fl)); }
+            r.n_other += (uint32_t)__builtin_popcountll(om);
+        }
+        if (am) {                                                                          // what the step leaves open
+            const int last = 63 - __builtin_clzll(am);
+            if ((gm >> last) & 1) open = false;
+            else {
+                if (gm) gbeg = cur0 + W::bcast(ea, ctz64(rm & (~0ull << (64 - __builtin_clzll(gm)))));
+                else if (!open) gbeg = cur0 + W::bcast(ea, ctz64(rm));
+                open = true;
+            }
+            if (gm) cut = true;
+        }
+        cur0 += tot;
+    }
+    if (open) close_carried();
+    r.endpos = (int32_t)cur0;
+    return r;
+}
+
+template <class W, bool DEL>
 PW_FN CoopOut coop_cigar(const Cfg &c, uint64_t cig_off, uint32_t n, int32_t tid, int32_t pos, pd_iv *other, uint64_t obase, bool emit)
 {
+    if (DEL) return coop_groups<W>(c, cig_off, n, tid, pos, other, obase, emit);
     typedef typename W::template Var<uint32_t> U;
     CoopOut r; r.has_first = 0; r.fbeg = r.fend = 0; r.n_other = 0; r.span = 0;
     uint32_t cur0 = (uint32_t)pos;
@@ -336,7 +447,7 @@ PW_FN CoopOut coop_cigar(const Cfg &c, uint64_t cig_off, uint32_t n, int32_t tid
 // Every lane's walk of its stretch, to the end: the lanes walk on their own until each is through or stands at a record for the
 // wave; those records are walked by the wave one after the other, their runs added to their lanes' counts (or written behind the runs
 // the lane has written so far), and the lanes go on.  active[l] = 0: the lane has nothing to walk.
-template <class W, bool EMIT>
+template <class W, bool EMIT, bool DEL>
 PW_FN void run_lanes(const Cfg &c, typename W::template Var<uint32_t> &active, typename W::template Var<uint64_t> &p, const typename W::template Var<uint64_t> &b,
                      typename W::template Var<LaneWalk> &lw, pd_iv *first, pd_iv *other, pd_iv *far, const typename W::template Var<uint64_t> &of,
                      const typename W::template Var<uint64_t> &oo, const typename W::template Var<uint64_t> &ofar)
@@ -351,7 +462,7 @@ PW_FN void run_lanes(const Cfg &c, typename W::template Var<uint32_t> &active, t
             if (!active[l]) return;
             Pending pd; pd.cig_off = 0; pd.next_p = 0; pd.n_cig = 0; pd.tid = 0; pd.pos = 0;
             uint64_t pp = p[l]; uint32_t g = guard[l];
-            const bool stop = walk_lane<EMIT>(c, pp, b[l], g, lw[l], pd, first, other, far, of[l], oo[l], ofar[l]);
+            const bool stop = walk_lane<EMIT, DEL>(c, pp, b[l], g, lw[l], pd, first, other, far, of[l], oo[l], ofar[l]);
             p[l] = pp; guard[l] = g;
             pending[l] = stop ? 1u : 0u;
             if (stop) { pcig[l] = pd.cig_off; pnext[l] = pd.next_p; pn[l] = pd.n_cig; ptid[l] = (uint32_t)pd.tid; ppos[l] = (uint32_t)pd.pos; pob[l] = oo[l] + lw[l].n_other; }
@@ -366,7 +477,7 @@ PW_FN void run_lanes(const Cfg &c, typename W::template Var<uint32_t> &active, t
             const uint32_t n = W::bcast(pn, j);
             const int32_t tid = (int32_t)W::bcast(ptid, j), pos = (int32_t)W::bcast(ppos, j);
             // -g / -b sessions: the read counts only when it meets a target span, which takes its end — a pass that only counts, first
-            CoopOut r = coop_cigar<W>(c, cig_off, n, tid, pos, other, obase, EMIT && !c.spans);
+            CoopOut r = coop_cigar<W, DEL>(c, cig_off, n, tid, pos, other, obase, EMIT && !c.spans);
             U tk;
             W::each([&](int l) {
                 tk[l] = 0;
@@ -376,7 +487,7 @@ PW_FN void run_lanes(const Cfg &c, typename W::template Var<uint32_t> &active, t
                 tk[l] = take ? 1u : 0u;
             });
             const bool take = W::ballot_ne(tk, 0u) != 0;
-            if (take && EMIT && c.spans) r = coop_cigar<W>(c, cig_off, n, tid, pos, other, obase, true);
+            if (take && EMIT && c.spans) r = coop_cigar<W, DEL>(c, cig_off, n, tid, pos, other, obase, true);
             W::each([&](int l) {
                 if (l != j) return;
                 LaneWalk &w = lw[l];
@@ -394,7 +505,7 @@ PW_FN void run_lanes(const Cfg &c, typename W::template Var<uint32_t> &active, t
 // pass 1: one wave, one segment.  lanes[64] receives every lane's start and counts for pass 2.  `hint_in` (or null: the
 // segment's own) is the first record start to walk from — the chain kernel passes a corrected start in a register, so that
 // no lane has to read what another lane of the wave has just stored.
-template <class W>
+template <class W, bool DEL = false>
 PW_FN WalkOut walk_segment(const Cfg &cfg, Seg &sg, LaneOut *lanes, const uint64_t *hint_in = nullptr)
 {
     Cfg c = cfg; c.avail = sg.avail;
@@ -461,7 +572,7 @@ PW_FN WalkOut walk_segment(const Cfg &cfg, Seg &sg, LaneOut *lanes, const uint64
         });
         U walked;
         W::each([&](int l) { walked[l] = active[l]; });
-        run_lanes<W, false>(c, active, wp, b, lw, nullptr, nullptr, nullptr, zero64, zero64, zero64);
+        run_lanes<W, false, DEL>(c, active, wp, b, lw, nullptr, nullptr, nullptr, zero64, zero64, zero64);
         W::each([&](int l) {
             if (!walked[l]) return;
             const LaneWalk &w = lw[l];
@@ -502,7 +613,7 @@ PW_FN WalkOut walk_segment(const Cfg &cfg, Seg &sg, LaneOut *lanes, const uint64
 }
 
 // pass 2: the same lanes write their runs; sg.base_first / base_other say where the segment's runs go
-template <class W>
+template <class W, bool DEL = false>
 PW_FN void emit_segment(const Cfg &cfg, const Seg &sg, const LaneOut *lanes, pd_iv *first, pd_iv *other, pd_iv *far, SegOut *seg_out = nullptr)
 {
     Cfg c = cfg; c.avail = sg.avail;
@@ -532,7 +643,7 @@ PW_FN void emit_segment(const Cfg &cfg, const Seg &sg, const LaneOut *lanes, pd_
     });
     U walked;
     W::each([&](int l) { walked[l] = active[l]; });
-    run_lanes<W, true>(c, active, wp, bb, lw, first, other, far, of, oo, ofr);
+    run_lanes<W, true, DEL>(c, active, wp, bb, lw, first, other, far, of, oo, ofr);
     W::each([&](int l) {
         if (!walked[l]) return;
         const LaneWalk &w = lw[l];

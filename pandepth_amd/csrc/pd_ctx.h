@@ -173,6 +173,7 @@ struct pd_ctx {
     std::thread dec_warm;                                         // pd_decode_begin's helper: the first slots' page-locked buffers, streams and hardware queues, one after the other, beside the caller
     void *dec_warm_word = nullptr;
     uint32_t dec_near_span = 0xFFFFFFFFu;                         // "decode_near_span": split the later runs into two streams (off)
+    bool dec_deletions = false;                                   // "decode_deletions": pd_push_bgzf_units opens its session with PD_DECODE_DELETIONS
     pd_decode_cfg dec_cfg{}; uint8_t *d_contig_on = nullptr; uint32_t *d_span_off = nullptr; int32_t *d_spans = nullptr;
     std::vector<RunSeg> run_segs;
     pd_iv *run_first = nullptr, *run_other = nullptr, *run_far = nullptr;   // the concatenated sample (owned until the next reset)

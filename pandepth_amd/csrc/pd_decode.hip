@@ -554,6 +554,7 @@ int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t 
     cfg.buf = d_inf; cfg.avail = bt->inflated_bytes; cfg.n_ref = c->n_contigs; cfg.contig_len = c->d_len; cfg.contig_on = c->d_contig_on;
     cfg.flag_mask = c->dec_cfg.flag_mask; cfg.min_mapq = c->dec_cfg.min_mapq; cfg.span_off = c->d_span_off; cfg.spans = c->d_spans;
     cfg.near_span = c8 ? 0xFFFFFFFFu : c->dec_near_span;                   // (a compact session has one stream of later runs)
+    cfg.count_del = c->dec_cfg.flags & PD_DECODE_DELETIONS ? 1u : 0u;      // (`-del`: every launch of this batch takes the kernels of the group rule)
     cfg.c8 = pdb2::C8Out{};
     launch_bgzf_inflate_wave(st, members, (const pd_bgzf_block *)(d_tab + J.o.blk), bt->n_blocks, d_inf, (int *)sl.d[DS_ST], sl.d_tok, n_wg, c->dec_crc,
                              (uint32_t *)(d_tab + J.o.next), false);
@@ -1164,7 +1165,13 @@ int pd_decode_end(pd_ctx *c)
         for (pd_iv **q : {&c->run_first, &c->run_other, &c->run_far}) if (*q) { (void)hipFree(*q); *q = nullptr; }
         runs_free(c->dec_runs); c->dec_runs = nullptr;
     }
-    return c->c8.on ? end_compact(c, segs, span) : end_concat(c, segs, nf, no, nfar, span);
+    const int rc = c->c8.on ? end_compact(c, segs, span) : end_concat(c, segs, nf, no, nfar, span);
+    if (getenv("PANDEPTH_TIMING"))                                   // (which way the sample was made: the counters pd_profile_get reports as decode_end_*)
+        fprintf(stderr, "[timing]   pd_decode_end: runs of the batches %llu first, %llu later; decode_end_compact %llu, decode_end_c8_fallback %llu, decode_end_runs_make %llu, "
+                        "decode_end_scatter %llu, decode_end_unsorted %llu, decode_end_pending %llu\n", (unsigned long long)nf, (unsigned long long)(no + nfar),
+                (unsigned long long)c->dec_n[pd_ctx::DN_END_COMPACT], (unsigned long long)c->dec_n[pd_ctx::DN_END_C8_FALLBACK], (unsigned long long)c->dec_n[pd_ctx::DN_END_RUNS_MAKE],
+                (unsigned long long)c->dec_n[pd_ctx::DN_END_SCATTER], (unsigned long long)c->dec_n[pd_ctx::DN_END_UNSORTED], (unsigned long long)c->dec_n[pd_ctx::DN_END_PEND]);
+    return rc;
 }
 
 int pd_decode_abort(pd_ctx *c)
@@ -1187,6 +1194,7 @@ int pd_push_bgzf_units(pd_ctx *c, const void *blob, size_t n_bytes, const pd_bgz
     if (n_records) *n_records = 0;
     if (n_units == 0 || n_blocks == 0) return PD_OK;
     pd_decode_cfg cfg{}; cfg.flag_mask = flag_mask; cfg.min_mapq = min_mapq; cfg.sorted = 1;
+    if (c->dec_deletions) cfg.flags |= PD_DECODE_DELETIONS;               // (pd_set_param "decode_deletions": this entry's signature has no room for flags)
     int rc = pd_decode_begin(c, &cfg);
     if (rc) return rc;
     // the session this call opens is closed on every path out of it (its batch is taken out of the list below, so the

@@ -232,6 +232,7 @@ int parse_options(int argc, char **argv, Options *o)
             }
             if (!good) { o->thresholds.clear(); std::cerr << "Error: -thresholds should be 1 to 16 ascending depths, such as 1,10,20,30" << std::endl; return 0; }
         }
+        else if (flag == "del") o->count_del = true;                             // not in the reference: deletions count as covered (README)
         else if (flag == "help" || flag == "h") { print_help(); return 0; }
         else { std::cerr << "Error UnKnow argument -" << flag << std::endl; return 0; }
     }

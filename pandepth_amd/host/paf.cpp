@@ -182,9 +182,21 @@ struct LineParser {
             }
             ++n_records;
             int32_t cur = s;
-            for (const Op &x : ops) {
-                if (x.c == 'M' || x.c == '=' || x.c == 'X') { out->emit(tid, cur, cur + x.n); cur += x.n; }
-                else if (x.c == 'D' || x.c == 'N') cur += x.n;
+            if (o.count_del) {
+                // -del: D counts as covered; one run per group of M/=/X/D operations that no N splits (pipeline.cpp: emit_runs)
+                // (the cursor's wrap on corrupt lengths spelled out in unsigned arithmetic, as emit_runs does)
+                bool open = false; int32_t gbeg = 0;
+                for (const Op &x : ops) {
+                    const int32_t nxt = (int32_t)((uint32_t)cur + (uint32_t)x.n);
+                    if (x.c == 'M' || x.c == '=' || x.c == 'X' || x.c == 'D') { if (!open) { open = true; gbeg = cur; } cur = nxt; }
+                    else if (x.c == 'N') { if (open) { out->emit(tid, gbeg, cur); open = false; } cur = nxt; }
+                }
+                if (open) out->emit(tid, gbeg, cur);
+            } else {
+                for (const Op &x : ops) {
+                    if (x.c == 'M' || x.c == '=' || x.c == 'X') { out->emit(tid, cur, cur + x.n); cur += x.n; }
+                    else if (x.c == 'D' || x.c == 'N') cur += x.n;
+                }
             }
         } else {
             ++n_records;

@@ -93,9 +93,22 @@ private:
 };
 
 // PD:438-460: CIGAR walk with an int32 cursor; one run per M/=/X operation, D/N advance only.
-inline void emit_runs(const AlnRec &r, RunSink *sink)
+// count_del (-del): D counts as covered, and the walk emits one run per GROUP — a maximal sequence of M/=/X/D operations with no N
+// between them (I/S/H/P do not split it; an N of any length, 0 included, does; a group of length 0 is still a run, as 0M is).
+inline void emit_runs(const AlnRec &r, RunSink *sink, bool count_del)
 {
     int32_t cur = r.pos;
+    if (count_del) {
+        bool open = false; int32_t gbeg = 0;
+        for (uint32_t i = 0; i < r.n_cigar; ++i) {
+            const uint32_t op = r.cigar[i] & 0xf;
+            const int32_t nxt = (int32_t)((uint32_t)cur + (r.cigar[i] >> 4));  // (the same spelled-out wrap as below)
+            if (op == 0 || op == 7 || op == 8 || op == 2) { if (!open) { open = true; gbeg = cur; } cur = nxt; }
+            else if (op == 3) { if (open) { sink->emit(r.tid, gbeg, cur); open = false; } cur = nxt; }
+        }
+        if (open) sink->emit(r.tid, gbeg, cur);
+        return;
+    }
     for (uint32_t i = 0; i < r.n_cigar; ++i) {
         const uint32_t op = r.cigar[i] & 0xf;
         const int32_t len = (int32_t)(r.cigar[i] >> 4);
@@ -152,7 +165,7 @@ bool index_exists(const std::string &p) { return file_exists(p + ".bai") || file
 // ---- readers ---------------------------------------------------------------------------------
 // records that START in [begin, stop) of an open BAM, through the host decoder
 bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter &flt, const struct SpanIndex &spans,
-                  RunSink *sink, uint64_t *n_rec, std::string *err);
+                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del);
 
 struct DevRange;
 int read_bam_device(const std::string &path, const Options &o, const AlnHeader &main_hdr, const SpanIndex &spans, const RegionModel &rm,
@@ -187,7 +200,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
             });
         while ((k = probe.next(&r)) == 1) {
             ++n;
-            if (flt.pass(r) && spans.hit(r)) emit_runs(r, &sink);
+            if (flt.pass(r) && spans.hit(r)) emit_runs(r, &sink, o.count_del);
         }
         if (k < 0) { eng->fail(probe.error() + " (" + path + ")"); return false; }
         if (getenv("PANDEPTH_TIMING"))
@@ -250,7 +263,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
             if (t >= n_tasks || !eng->ok()) break;
             for (size_t w = tasks[t].first; w < tasks[t].second; ++w) {
                 std::string e3;
-                if (!decode_range(rd, work[w].first, work[w].second, flt, spans, &sink, &my_rec, &e3)) { eng->fail(e3 + " (" + path + ")"); return; }
+                if (!decode_range(rd, work[w].first, work[w].second, flt, spans, &sink, &my_rec, &e3, o.count_del)) { eng->fail(e3 + " (" + path + ")"); return; }
             }
         }
     };
@@ -267,7 +280,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
 }
 
 bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter &flt, const SpanIndex &spans,
-                  RunSink *sink, uint64_t *n_rec, std::string *err)
+                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del)
 {
     if (!rd.seek(begin)) { *err = "seek failed"; return false; }
     AlnRec r;
@@ -279,7 +292,7 @@ bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter
         ++*n_rec;
         if (!flt.pass(r)) continue;
         if (!spans.hit(r)) continue;
-        emit_runs(r, sink);
+        emit_runs(r, sink, count_del);
     }
     return true;
 }
@@ -385,6 +398,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
     // whole-contig statistics over windows of >= 8192 cells (mode 0's 10 Mb bins, -w >= 8192) read the sample once, in the
     // engine's compact form; every other mode needs the arrays and keeps 12-byte runs
     if (spans.synthetic && !o.site_out && (o.mode == 0 || (o.mode == 5 && o.win >= 8192))) cfg.flags |= PD_DECODE_COMPACT;
+    if (o.count_del) cfg.flags |= PD_DECODE_DELETIONS;
     { uint64_t b = 0; for (auto &v : batches) for (auto &r : v) b += ((r.vend == UINT64_MAX ? F : (r.vend >> 16)) - (r.vbeg >> 16)) + 65536; cfg.bytes_hint = std::min(b, 2 * F); }
     if (!spans.synthetic) {
         soff.assign(on.size() + 1, 0);
@@ -701,7 +715,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
                 const size_t i = nb.fetch_add(1);
                 if (i >= backlog.size() || !eng->ok()) break;
                 uint64_t nr = 0;
-                if (!decode_range(rd, backlog[i].first, backlog[i].second, flt, spans, &sink, &nr, &e2)) { eng->fail(e2 + " (" + path + ")"); break; }
+                if (!decode_range(rd, backlog[i].first, backlog[i].second, flt, spans, &sink, &nr, &e2, o.count_del)) { eng->fail(e2 + " (" + path + ")"); break; }
                 n_host += nr;
             }
         };
@@ -747,7 +761,7 @@ bool read_sorted_stream(AlnReader *rd, const Options &o, const AlnHeader &main_h
                 if (all) break;                      // this read is NOT counted (PD:4641-4644)
             }
         }
-        emit_runs(r, &sink);                         // counted even when the cursor just ran off the end
+        emit_runs(r, &sink, o.count_del);            // counted even when the cursor just ran off the end
     }
     if (k < 0) eng->fail(rd->error());
     return eng->ok();
@@ -763,7 +777,7 @@ bool read_all(AlnReader *rd, const Options &o, const AlnHeader &main_hdr, const 
     while ((k = rd->next(&r)) > 0) {
         if (!flt.pass(r)) continue;
         if (!rm.has(r.tid)) continue;                // depth on contigs without targets is never reported
-        emit_runs(r, &sink);
+        emit_runs(r, &sink, o.count_del);
     }
     if (k < 0) eng->fail(rd->error());
     return eng->ok();
