@@ -219,10 +219,9 @@ int ensure_scratch(pd_ctx *c, size_t bytes)
 int do_reset(pd_ctx *c)
 {
     ProfScope ps(c, "reset");
-    HIPOK(c, hipMemsetAsync(c->hstate, 0, c->n_half, c->stream));
-    HIPOK(c, hipMemsetAsync(c->sums, 0, (c->n_words - c->n_cells) * 4, c->stream));
-    HIPOK(c, hipMemsetAsync(c->chk, 0, sizeof(CheckWords), c->stream));
-    HIPOK(c, hipMemsetAsync(c->desc, 0, sizeof(BatchDesc) * PD_MAXPEND, c->stream));
+    launch_reset_spans(c->stream, ResetSpans{{c->hstate, c->sums, c->chk, c->desc},
+                                             {(size_t)c->n_half, (size_t)(c->n_words - c->n_cells) * 4, sizeof(CheckWords), sizeof(BatchDesc) * PD_MAXPEND}});
+    HIPOK(c, hipGetLastError());
     c->all_valid_host = false;
     c->pristine = true;
     c->sums_stale = false;
@@ -590,9 +589,10 @@ int pd_destroy(pd_ctx *c)
     for (void *p : {(void *)c->carry, (void *)c->bsum, (void *)c->d_off, (void *)c->d_len, (void *)c->d_tile_contig, (void *)c->ub_a[0], (void *)c->ub_a[1], (void *)c->ub_a[2],
                     (void *)c->ub_a[3], (void *)c->cand_lo[0], (void *)c->cand_lo[1], (void *)c->cand_lo[2], (void *)c->cand_lo[3], (void *)c->hstate, (void *)c->slice_flags,
                     (void *)c->direct_words, (void *)c->desc, (void *)c->chk}) pdguard::drop(p);            // (parts of the slab)
-    void *ptrs[] = {c->buf, c->slab, c->ovf, c->scratch, c->wk};
+    void *ptrs[] = {c->buf, c->slab, c->ovf, c->scratch, c->wk, c->d_woff};
     t1 = dec_now_us();
     for (void *p : ptrs) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->woff_host, (void *)c->wk_pin}) if (p) (void)hipHostFree(p);
     t2 = dec_now_us();
     for (auto &sl : c->dec) {
         if (sl.st) (void)hipStreamSynchronize(sl.st);
@@ -733,7 +733,7 @@ void runs_finish(pd_ctx *c, pd_runs *r, const pd_iv *const *others, const size_t
     for (int k = 0; k < n_arr; ++k) launch_c8_hist(st, others[k], (uint32_t)n_others[k], tab, r->bshift, hist, words);
     launch_excl_scan_u32(st, hist, r->o1, nb + 1, bs);
     for (int k = 0; k < n_arr; ++k) launch_c8_place_other(st, others[k], (uint32_t)n_others[k], tab, r->bshift, r->o1, cursor, r->lo + r->o_base, r->hi + r->o_base);
-    launch_c8_tile_desc(st, r->view(), tab, c->d_tile_contig, (uint32_t)c->n_tiles, r->td);       // both streams' bucket starts are final
+    launch_c8_tile_desc(st, r->view(), tab, c->d_tile_contig, (uint32_t)c->n_tiles, r->td, words + 2);       // both streams' bucket starts are final; words[2]: the pile-up tiles
 }
 
 // caller holds c->mu and has set the device.  `sorted` must be sorted by (tid, beg) — checked; the `others` may be in any order.
@@ -762,7 +762,7 @@ int runs_make(pd_ctx *c, const pd_iv *sorted, size_t n_sorted, const pd_iv *cons
     }
     r->hi = r->lo + n;                                            // one allocation: lo | hi, n words each
     r->o1 = r->b1 + nbw; r->td = (TileDesc *)((uint8_t *)r->b1 + c8_desc_offset(nbw));
-    uint32_t h[2] = {0, 0};
+    uint32_t h[3] = {0, 0, 0};
     hipStream_t st = c->stream;
     hipError_t e = hipMemsetAsync(words, 0, 16, st);
     if (e == hipSuccess) e = hipMemsetAsync(r->b1, 0xFF, nbw * 4, st);
@@ -773,12 +773,13 @@ int runs_make(pd_ctx *c, const pd_iv *sorted, size_t n_sorted, const pd_iv *cons
         runs_finish(c, r, others, n_others, n_arr, tmp, words);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(h, words, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h, words, sizeof h, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipFree(tmp); (void)hipFree(words);
     if (e != hipSuccess) { runs_free(r); return fail(c, PD_EHIP, std::string("pd_runs_create: ") + hipGetErrorString(e)); }
     if (h[0]) { runs_free(r); return fail(c, PD_EINVAL, "pd_runs_create: the first batch is not sorted by (tid, beg), or a contig id is out of range"); }
     r->n_long = h[1];
+    r->n_heavy = h[2];
     *out = r;
     return PD_OK;
 }
@@ -909,6 +910,9 @@ int pd_window_layout(const pd_ctx *c, uint32_t w, uint64_t *win_off)
     return PD_OK;
 }
 
+// c->wk of a window call: [sums, 8 B per window | covers, 4 B per window, padded to 16 B | WK_WORDS bytes: the direct path's status words], so
+// that all a call hands back is one contiguous range
+constexpr size_t WK_WORDS = 64;
 static int win_keep_fit(pd_ctx *c, size_t bytes)
 {
     c->wk_valid = false;
@@ -920,27 +924,48 @@ static int win_keep_fit(pd_ctx *c, size_t bytes)
     return PD_OK;
 }
 
+// The device's copy of the window offsets `wo` of width w.  The offsets follow from the contig table, which is fixed at pd_create, and w, so the copy
+// is kept from call to call and uploaded only for another width — queued, from the context's page-locked copy: the call's final sync covers it.
+// (Until round 11 every window call uploaded a local vector and synchronised the stream before it queued anything else: in the traced bench step, 48 us
+// from the reset's last fill to the direct kernel's start, 29 us without the copy and the sync — profiles/r11_direct_call_ab.txt, sections 0 and 4.)
+static int win_offsets(pd_ctx *c, uint32_t w, const std::vector<uint64_t> &wo, const uint64_t **d_wo)
+{
+    const size_t b_off = wo.size() * 8;
+    if (!c->d_woff) {
+        if (hipMalloc(&c->d_woff, b_off) != hipSuccess) { (void)hipGetLastError(); c->d_woff = nullptr; return fail(c, PD_ENOMEM, "window offsets: device allocation failed"); }
+        if (hipHostMalloc((void **)&c->woff_host, b_off, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipFree(c->d_woff); c->d_woff = nullptr; c->woff_host = nullptr;
+            return fail(c, PD_ENOMEM, "window offsets: page-locked allocation failed");
+        }
+    }
+    if (c->woff_w != w) {
+        c->woff_w = 0;                                   // (every call that used woff_host has synchronised the stream behind its upload)
+        memcpy(c->woff_host, wo.data(), b_off);
+        HIPOK(c, hipMemcpyAsync(c->d_woff, c->woff_host, b_off, hipMemcpyHostToDevice, c->stream));
+        c->woff_w = w;
+    }
+    *d_wo = c->d_woff;
+    return PD_OK;
+}
+
 static int windows_common(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask, bool from_depth,
                           uint32_t *cover, uint64_t *sum)
 {
     std::vector<uint64_t> wo((size_t)c->n_contigs + 1);
     pd_window_layout(c, w, wo.data());
     const uint64_t nw = wo[c->n_contigs];
-    const size_t b_off = ((size_t)c->n_contigs + 1) * 8;
     const size_t b_sum = (size_t)nw * 8, b_cov = ((size_t)nw * 4 + 15) / 16 * 16;
     const size_t b_part = (size_t)c->n_tiles * sizeof(TilePart);      // wide windows: every tile's shares; narrow ones: the shares of the windows across tile boundaries
-    const size_t b_offr = (b_off + 15) / 16 * 16;
-    int rc = ensure_scratch(c, b_offr + b_part + 64);
+    int rc = ensure_scratch(c, b_part + 64);
     if (rc) return rc;
-    rc = win_keep_fit(c, b_sum + b_cov + 64);
+    rc = win_keep_fit(c, b_sum + b_cov + WK_WORDS);
     if (rc) return rc;
-    unsigned char *s = (unsigned char *)c->scratch;
-    uint64_t *d_wo = (uint64_t *)s;
+    const uint64_t *d_wo = nullptr;
+    rc = win_offsets(c, w, wo, &d_wo);
+    if (rc) return rc;
     unsigned long long *d_sum = (unsigned long long *)c->wk;
     uint32_t *d_cov = (uint32_t *)(c->wk + b_sum);
-    TilePart *d_part = (TilePart *)(s + b_offr);
-    HIPOK(c, hipMemcpyAsync(d_wo, wo.data(), b_off, hipMemcpyHostToDevice, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));          // wo is a local
+    TilePart *d_part = (TilePart *)c->scratch;
     if (w < PD_TILE) HIPOK(c, hipMemsetAsync(d_sum, 0, b_sum + b_cov, c->stream));   // windows nobody writes stay zero
     if (!from_depth) { ProfScope ps(c, "tile_carry"); launch_tile_carry(c->stream, c->sums, c->bsum, c->carry, (uint32_t)c->n_tiles); }
     {
@@ -969,23 +994,29 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
     std::vector<uint64_t> wo((size_t)c->n_contigs + 1);
     pd_window_layout(c, w, wo.data());
     const uint64_t nw = wo[c->n_contigs];
-    const size_t b_off = ((size_t)c->n_contigs + 1) * 8;
-    const size_t b_sum = (size_t)nw * 8, b_cov = ((size_t)nw * 4 + 15) / 16 * 16;
+    const size_t b_sum = (size_t)nw * 8, b_cov = ((size_t)nw * 4 + 15) / 16 * 16, b_all = b_sum + b_cov + WK_WORDS;
     const size_t b_part = (size_t)c->n_tiles * sizeof(TilePart);
-    const size_t b_offr = (b_off + 15) / 16 * 16;
-    int rc = ensure_scratch(c, b_offr + b_part + 64);
+    int rc = ensure_scratch(c, b_part + 64);
     if (rc) return rc;
-    rc = win_keep_fit(c, b_sum + b_cov + 64);
+    rc = win_keep_fit(c, b_all);
     if (rc) return rc;
-    unsigned char *s = (unsigned char *)c->scratch;
-    uint64_t *d_wo = (uint64_t *)s;
+    const uint64_t *d_wo = nullptr;
+    rc = win_offsets(c, w, wo, &d_wo);
+    if (rc) return rc;
     unsigned long long *d_sum = (unsigned long long *)c->wk;
     uint32_t *d_cov = (uint32_t *)(c->wk + b_sum);
-    TilePart *d_part = (TilePart *)(s + b_offr);
-    HIPOK(c, hipMemcpyAsync(d_wo, wo.data(), b_off, hipMemcpyHostToDevice, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));          // wo is a local
-    HIPOK(c, hipMemsetAsync(c->direct_words, 0, 64, c->stream));
-    if (w < PD_TILE) HIPOK(c, hipMemsetAsync(d_sum, 0, b_sum + b_cov, c->stream));   // edge windows are accumulated
+    uint32_t *d_words = (uint32_t *)(c->wk + b_sum + b_cov);      // [n_long, fail, heavy_count, diagnostics ..., [12] tiles settled by the cover pass]; the heavy tile list: c->direct_words + 16
+    TilePart *d_part = (TilePart *)c->scratch;
+    // Up to WK_PIN_BYTES the call's results come back in one copy through the context's page-locked buffer (three copies into the caller's pageable arrays
+    // were three staged round trips: 53 us from the gather's end to the last copy's, 10 us with the one copy — profiles/r11_direct_call_ab.txt, sections 0
+    // and 4); a larger result goes straight to the caller's arrays, so that no call pins memory in proportion to its output.
+    const bool pinned = b_all <= pd_ctx::WK_PIN_BYTES;
+    if (pinned && !c->wk_pin && hipHostMalloc((void **)&c->wk_pin, pd_ctx::WK_PIN_BYTES, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError(); c->wk_pin = nullptr;
+        return fail(c, PD_ENOMEM, "window statistics: page-locked allocation failed");
+    }
+    if (w < PD_TILE) HIPOK(c, hipMemsetAsync(d_sum, 0, b_all, c->stream));   // edge windows are accumulated; the status words with them
+    else HIPOK(c, hipMemsetAsync(d_words, 0, WK_WORDS, c->stream));
     const uint32_t n_stiles = (uint32_t)c->n_tiles;
     PendSet ps{};
     ps.nb = (int)c->pend.size(); ps.lmax = c->lmax;
@@ -1012,11 +1043,19 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
     }
     if (grid > c->n_tiles) grid = (unsigned)c->n_tiles;
     { ProfScope sc(c, "direct_tiles");
-      if (c8) launch_direct_c8(c->stream, c->pend[0].cr->view(), c->pend[0].cr->td, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part,
-                               c->direct_words + 16, c->direct_words + 2, grid, c->direct_un,
-                               c->direct_cover && all >= (uint64_t)c->direct_cover_min * c->n_tiles /* a thin sample: the form without the pass (launch_direct_c8) */, c->direct_cover_min);
+      if (c8) {
+          const pd_runs *cr = c->pend[0].cr;
+          launch_direct_c8(c->stream, cr->view(), cr->td, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, c->direct_words + 16, d_words + 2, grid, c->direct_un,
+                           c->direct_cover && all >= (uint64_t)c->direct_cover_min * c->n_tiles /* a thin sample: the form without the pass (launch_direct_c8) */, c->direct_cover_min);
+          // The int-window pass for the pile-up tiles k_direct_c8 lists, launched only for a sample that has some: the sample knows from its making
+          // (pd_runs::n_heavy, counted by k_c8_tile_desc from the records k_direct_c8 reads), so no round trip decides.  The bench's 1e9-record sample HAS
+          // pile-up tiles: the pass's 0.099 ms per call there are its work; on the empty lists of the 1e8- and 3e8-record samples a launch took 0.004 ms, and
+          // deciding by the count that comes back with the results (a second gather, copy and sync) gained a 1e9-record step 0.024 ms where this form gains
+          // 0.069 (profiles/r11_direct_call_ab.txt, sections 2 and 3).
+          if (cr->n_heavy) launch_direct_c8_heavy(c->stream, cr->view(), tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, c->direct_words + 16, d_words + 2);
+      }
       else launch_direct_tiles(c->stream, ps, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, d_wo,
-                               d_cov, d_sum, c->direct_words, c->direct_words + 1, c->direct_words + 16, c->direct_words + 2, grid, c->direct_un); }
+                               d_cov, d_sum, d_words, d_words + 1, c->direct_words + 16, d_words + 2, grid, c->direct_un); }
     if (w >= PD_TILE) {
         ProfScope sc(c, "gather_windows");
         TileMap tm{c->d_tile_contig, c->d_off, c->d_len, d_wo};
@@ -1024,10 +1063,16 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
     }
     HIPOK(c, hipGetLastError());
     uint32_t words[13] = {0};                            // [12]: heavy_count[PD_HEAVY_SETTLED]
-    HIPOK(c, hipMemcpyAsync(words, c->direct_words, sizeof words, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(c, hipMemcpyAsync(sum, d_sum, b_sum, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(c, hipMemcpyAsync(cover, d_cov, (size_t)nw * 4, hipMemcpyDeviceToHost, c->stream));
+    if (pinned) HIPOK(c, hipMemcpyAsync(c->wk_pin, c->wk, b_all, hipMemcpyDeviceToHost, c->stream));
+    else {
+        HIPOK(c, hipMemcpyAsync(words, d_words, sizeof words, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(c, hipMemcpyAsync(sum, d_sum, b_sum, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(c, hipMemcpyAsync(cover, d_cov, (size_t)nw * 4, hipMemcpyDeviceToHost, c->stream));
+    }
     HIPOK(c, hipStreamSynchronize(c->stream));
+    if (pinned) memcpy(words, c->wk_pin + b_sum + b_cov, sizeof words);
+    if (c8 && words[2] != c->pend[0].cr->n_heavy)       // (k_direct_c8's own count of the tiles it listed: the same candidates, the same threshold)
+        return fail(c, PD_ESTATE, "direct windows: the kernel listed " + std::to_string(words[2]) + " pile-up tiles, the sample was made with " + std::to_string(c->pend[0].cr->n_heavy));
     c->direct_settled = words[2 + pdk::PD_HEAVY_SETTLED];
     if (words[1]) {                                      // not applicable: batches stay pending
         if (getenv("PANDEPTH_TIMING")) fprintf(stderr, "[timing]   direct window path declined: begins owned %llu of %llu runs, runs with cells %u vs ends owned %u (difference), index error bits 0x%x, "
@@ -1035,6 +1080,7 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
                     (unsigned long long)words[5] | ((unsigned long long)words[6] << 32), words[7], words[8], words[9], words[10]);
         return PD_OK;
     }
+    if (pinned) { memcpy(sum, c->wk_pin, b_sum); memcpy(cover, c->wk_pin + b_sum, (size_t)nw * 4); }
     // the call READ the sample: it stays deferred (like pd_export_i4's direct form), every other call still works on it
     *done = true;
     c->wk_w = w; c->wk_nw = nw; c->wk_woff = wo; c->wk_valid = true;

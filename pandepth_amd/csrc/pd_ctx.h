@@ -76,6 +76,7 @@ struct pd_runs {
     TileDesc *td = nullptr;                                      // per tile: what k_direct_c8 reads before the tile's runs (made by runs_finish)
     uint32_t bshift = 4;                                         // 16 buckets of 512 cells per tile
     uint32_t n_long = 0;                                         // runs longer than a bucket: the direct kernels cannot use the sample
+    uint32_t n_heavy = 0;                                        // pile-up tiles (more than PD_C8_HEAVY_CAND candidates): k_direct_c8 leaves them to the int-window pass
     pd_iv *iv12 = nullptr;                                       // the expanded copy, made on first need
     bool own_lo = true;                                          // the planes are this object's allocation (false: they live in the decode session's arena)
     C8Sample view() const { return C8Sample{lo, hi, b1, o1, o_base, bshift}; }
@@ -103,6 +104,7 @@ struct pd_ctx {
     bool pristine = true;                                         // nothing materialised in the arrays since the last reset
     bool sums_stale = false;                                      // the tile sums hold what a direct export wrote while the sample is still deferred
     uint32_t *direct_words = nullptr;                             // [n_long, fail, heavy_count, diagnostics ..., [12] tiles settled by the cover pass | heavy tile list at +16]
+                                                                  // (the status words of a direct WINDOW call lie behind its results in wk, so that one copy brings both back; the export's are here)
     bool dec_crc = true;                                          // the decoder checks every member's CRC-32 ("decode_crc")
     unsigned lz_group = 16;                                       // chunks per workgroup of the LDS parse ("lz_group", up to 16; 0: every chunk parses with its text in memory).  Round 5's default: sixteen
                                                                   // chunks of 8 + 2 KiB share a CU's LDS (158 KB: 32 KiB of history + their text), 16 waves per CU — 8.6 ms against 11.8 for the 60 MB call of
@@ -233,6 +235,13 @@ struct pd_ctx {
     bool lz_mix = false;                                          // "lz_mix": see lz_run
     // the statistics of the last window call stay on the device (pd_text_append_window_rows formats the table's rows from them)
     unsigned char *wk = nullptr; size_t wk_bytes = 0; uint32_t wk_w = 0; uint64_t wk_nw = 0; bool wk_valid = false; std::vector<uint64_t> wk_woff;
+    // the window offsets of width woff_w on the device: an allocation of their own (c->scratch is every other call's too), uploaded only when a call
+    // asks for another width, from woff_host — page-locked and the context's, so that no sync has to guard the upload's source (win_offsets)
+    uint64_t *d_woff = nullptr, *woff_host = nullptr; uint32_t woff_w = 0;
+    // the direct path's results (sums | covers | status words, contiguous in wk) come back in ONE copy into this page-locked buffer of WK_PIN_BYTES,
+    // made by the first call that needs it; larger results go straight to the caller's arrays
+    static constexpr size_t WK_PIN_BYTES = (size_t)1 << 20;
+    unsigned char *wk_pin = nullptr;
     bool prof = false;
     std::vector<ProfRec> prof_pending;
     std::vector<hipEvent_t> ev_pool;

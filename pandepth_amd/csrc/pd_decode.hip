@@ -1025,7 +1025,7 @@ int compact_to_sample(pd_ctx *c, uint64_t n_long)
         (void)hipGetLastError(); for (void *q : {(void *)tmp, (void *)words, (void *)d_base, (void *)marks}) if (q) (void)hipFree(q); runs_free(r);
         return fail(c, PD_ENOMEM, "pd_decode_end: allocation failed");
     }
-    uint32_t h[2] = {0, 0};
+    uint32_t h[3] = {0, 0, 0};
     hipError_t e = hipMemsetAsync(words, 0, 16, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_base, base_s.data(), base_s.size() * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
@@ -1035,11 +1035,12 @@ int compact_to_sample(pd_ctx *c, uint64_t n_long)
         runs_finish(c, r, o, non, no1 ? 1 : 0, tmp, words);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(h, words, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h, words, sizeof h, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(tmp); (void)hipFree(words); (void)hipFree(d_base); (void)hipFree(marks);
     if (e != hipSuccess) { runs_free(r); return fail(c, PD_EHIP, std::string("pd_decode_end: ") + hipGetErrorString(e)); }
     r->n_long = (uint32_t)std::min<uint64_t>(n_long + h[1], 0xFFFFFFFFull);
+    r->n_heavy = h[2];
     install_sample(c, r, pd_ctx::DN_END_COMPACT);
     return PD_OK;
 }

@@ -86,6 +86,8 @@ struct Piece { uint64_t start; uint32_t count; uint32_t region; };
 struct TilePart { uint32_t c0, c1; unsigned long long s0, s1; };   // a tile's share of windows k0, k0+1
 
 void launch_fill(hipStream_t st, void *p, size_t bytes);
+struct ResetSpans { static constexpr int N = 4; void *p[N]; size_t bytes[N]; };      // what pd_reset zeroes, in one launch
+void launch_reset_spans(hipStream_t st, const ResetSpans &rs);
 void launch_scatter_atomic(hipStream_t st, const pd_iv *iv, size_t n, ContigTab tab, int *diff, int *sums);
 void launch_scatter_index(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t lmax,
                           uint32_t disorder, uint32_t sample, uint32_t *ub_a, uint32_t *cand_lo,
@@ -105,19 +107,25 @@ void launch_excl_scan_u32(hipStream_t st, const uint32_t *in, uint32_t *out, uin
 void launch_c8_fill_starts(hipStream_t st, uint32_t *b1, uint32_t n_buckets, uint32_t n_runs, uint32_t *tmp /* n_buckets / 1024 + 2 words */);
 void launch_c8_marks_to_index(hipStream_t st, const unsigned long long *marks, uint32_t n_buckets, const uint32_t *base, uint32_t *b1);
 void launch_c8_place_other(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, const uint32_t *o1, uint32_t *cursor, uint32_t *lo, uint32_t *hi /* both at o_base */);
-void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc);
+// (*n_heavy += the tiles with more than PD_C8_HEAVY_CAND candidates: the pile-up tiles k_direct_c8 leaves to the int-window pass — it counts the same
+// candidates from the same record, so the sample knows from its making whether that pass has anything to do)
+constexpr uint32_t PD_C8_HEAVY_CAND = 32000u;
+void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc, uint32_t *n_heavy);
 void launch_c8_expand(hipStream_t st, C8Sample cs, const uint32_t *tile_contig, const uint64_t *contig_off, uint32_t n_tiles, pd_iv *out);
 void launch_r8_to_iv(hipStream_t st, const uint32_t *lo, const uint32_t *hi, uint64_t n, ContigTab tab, pd_iv *out);
 void launch_copy_words(hipStream_t st, void *dst, const void *src, uint64_t n_words);      // device-to-device, 4-byte words (both pointers 4-byte aligned)
 // ... and the two planes of n compact runs in ONE launch
 void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, const uint32_t *src_lo, const uint32_t *src_hi, uint64_t n);
-// (k_direct_c8 itself reads cs.lo, cs.o_base and desc only; tab, tile_contig and the bucket starts in cs serve the int-window pass launched
-// behind it for the pile-up tiles)
+// (k_direct_c8 itself reads cs.lo, cs.o_base and desc only)
 // cover (with un = 0 only): the default form with the cover pass in front of the window path (pd_cover_rule.h); the tiles it settles are
 // added to heavy_count[PD_HEAVY_SETTLED]; tiles with fewer than cover_min candidates are not tried
 constexpr int PD_HEAVY_SETTLED = 10;
-void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
+void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
                       uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min);
+// ... and the int-window pass for the pile-up tiles k_direct_c8 put on heavy_list (it reads tab, tile_contig and the bucket starts in cs).  Its own launcher:
+// the caller launches it only for a sample that has pile-up tiles (pd_runs::n_heavy, counted by k_c8_tile_desc).
+void launch_direct_c8_heavy(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w, uint32_t min_dep,
+                            TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count);
 void launch_direct_c8_export(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, void *img, pd_exc *exc,
                              uint32_t cap, uint32_t *count, int *sums, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles);
 void launch_direct_export(hipStream_t st, const PendSet &ps, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles,

@@ -95,6 +95,25 @@ __global__ __launch_bounds__(WG) void k_fill(int4 *p, size_t n16)
     for (; i < n16; i += st) p[i] = z;
 }
 
+// pd_reset's four spans zeroed by ONE launch (four hipMemsetAsync calls were six fill kernels, 34 us of the traced bench step from the first one's
+// start to the last one's end; this kernel: 3 us — profiles/r11_direct_call_ab.txt): 16-byte stores where the span begins on a 16-byte boundary,
+// bytes for its tail (or for all of it)
+__global__ __launch_bounds__(WG) void k_reset_spans(const ResetSpans rs)
+{
+    const size_t i0 = blockIdx.x * (size_t)WG + threadIdx.x;
+    const size_t st = (size_t)gridDim.x * WG;
+    const int4 z = make_int4(0, 0, 0, 0);
+#pragma unroll
+    for (int k = 0; k < ResetSpans::N; ++k) {
+        unsigned char *p = static_cast<unsigned char *>(rs.p[k]);
+        const size_t n = rs.bytes[k];
+        const size_t n16 = (reinterpret_cast<uintptr_t>(p) & 15) ? 0 : n / 16;
+        int4 *q = reinterpret_cast<int4 *>(p);
+        for (size_t i = i0; i < n16; i += st) q[i] = z;
+        for (size_t i = n16 * 16 + i0; i < n; i += st) p[i] = 0;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // scatter, unsorted fallback: two device atomics per run (+ tile-sum atomics only when the
 // run crosses a tile boundary; inside one tile +1 and -1 cancel in the tile sum)
@@ -1596,7 +1615,7 @@ __global__ __launch_bounds__(256) void k_copy_planes(uint32_t *__restrict__ dst_
 
 // The per-tile descriptors of a finished compact sample (TileDesc in pd_kernels.h): one thread per tile reads the bucket starts around the
 // tile in both streams and the tile's contig, so that k_direct_c8 finds them in one record instead of a chain of dependent loads.
-__global__ __launch_bounds__(WG) void k_c8_tile_desc(const C8Sample cs, const ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc)
+__global__ __launch_bounds__(WG) void k_c8_tile_desc(const C8Sample cs, const ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc, uint32_t *n_heavy)
 {
     const uint32_t t = blockIdx.x * WG + threadIdx.x;
     if (t >= n_tiles) return;
@@ -1610,6 +1629,8 @@ __global__ __launch_bounds__(WG) void k_c8_tile_desc(const C8Sample cs, const Co
     d.olo = cs.o1[lo]; d.ohi = cs.o1[k0 + nbk];
     d.spare0 = d.spare1 = 0;
     desc[t] = d;
+    // a pile-up tile: k_direct_c8 will count the same candidates from this record and leave the tile to the int-window pass
+    if ((d.shi - d.slo) + (d.ohi - d.olo) > PD_C8_HEAVY_CAND) atomicAdd(n_heavy, 1u);
 }
 
 // a sorted stream of compact runs whose sample turned out not to be usable as one (the file's order does not hold after all): back to
@@ -3113,6 +3134,14 @@ void launch_fill(hipStream_t st, void *p, size_t bytes)
     hipLaunchKernelGGL(k_fill, dim3((unsigned)g), dim3(WG), 0, st, (int4 *)p, n16);
 }
 
+void launch_reset_spans(hipStream_t st, const ResetSpans &rs)
+{
+    size_t most = 0;
+    for (int k = 0; k < ResetSpans::N; ++k) if (rs.bytes[k] > most) most = rs.bytes[k];
+    size_t g = (most / 16 + WG - 1) / WG; if (g > 2048) g = 2048; if (g == 0) g = 1;
+    hipLaunchKernelGGL(k_reset_spans, dim3((unsigned)g), dim3(WG), 0, st, rs);
+}
+
 void launch_scatter_atomic(hipStream_t st, const pd_iv *iv, size_t n, ContigTab tab, int *diff, int *sums)
 {
     size_t g = (n + WG - 1) / WG; if (g > 8192) g = 8192; if (g == 0) return;
@@ -3248,9 +3277,9 @@ void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, cons
     hipLaunchKernelGGL(k_copy_planes, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, st, dst_lo, dst_hi, src_lo, src_hi, n);
 }
 
-void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc)
+void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc, uint32_t *n_heavy)
 {
-    if (n_tiles) hipLaunchKernelGGL(k_c8_tile_desc, dim3((n_tiles + WG - 1) / WG), dim3(WG), 0, st, cs, tab, tile_contig, n_tiles, desc);
+    if (n_tiles) hipLaunchKernelGGL(k_c8_tile_desc, dim3((n_tiles + WG - 1) / WG), dim3(WG), 0, st, cs, tab, tile_contig, n_tiles, desc, n_heavy);
 }
 
 void launch_r8_to_iv(hipStream_t st, const uint32_t *lo, const uint32_t *hi, uint64_t n, ContigTab tab, pd_iv *out)
@@ -3260,7 +3289,7 @@ void launch_r8_to_iv(hipStream_t st, const uint32_t *lo, const uint32_t *hi, uin
     hipLaunchKernelGGL(k_r8_to_iv, dim3((unsigned)(g > 65536 ? 65536 : g)), dim3(WG), 0, st, lo, hi, n, tab, out);
 }
 
-void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
+void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
                       uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min)
 {
     // cover_min ("direct_cover_min", default 2048 candidates per tile): a tile visit costs the cover pass more than the window path before its first run
@@ -3319,6 +3348,11 @@ void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigT
     }
 #undef PD_C8J
 #undef PD_C8
+}
+
+void launch_direct_c8_heavy(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w, uint32_t min_dep,
+                            TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count)
+{
     WinArgs wa; wa.w = w; wa.min_dep = min_dep; wa.inv_w = 1.0f / (float)w; wa.cover = nullptr; wa.sum = nullptr; wa.part = part;
     PendSet none{}; none.nb = 0; none.lmax = 0;
     hipLaunchKernelGGL(k_direct_tiles_heavy, dim3(128), dim3(WG), 0, st, none, n_tiles, tab, tile_contig, wrap_mask, wa, (const uint64_t *)nullptr,
