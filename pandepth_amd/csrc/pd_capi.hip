@@ -1049,10 +1049,10 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
                            c->direct_cover && all >= (uint64_t)c->direct_cover_min * c->n_tiles /* a thin sample: the form without the pass (launch_direct_c8) */, c->direct_cover_min);
           // The int-window pass for the pile-up tiles k_direct_c8 lists, launched only for a sample that has some: the sample knows from its making
           // (pd_runs::n_heavy, counted by k_c8_tile_desc from the records k_direct_c8 reads), so no round trip decides.  The bench's 1e9-record sample HAS
-          // pile-up tiles: the pass's 0.099 ms per call there are its work; on the empty lists of the 1e8- and 3e8-record samples a launch took 0.004 ms, and
+          // pile-up tiles (12): the pass's 0.028 ms per call there (k_c8_heavy; 0.099 as the compact branch of k_direct_tiles_heavy, profiles/r12_pileup_gather_ab.txt) are its work; on the empty lists of the 1e8- and 3e8-record samples a launch took 0.004 ms, and
           // deciding by the count that comes back with the results (a second gather, copy and sync) gained a 1e9-record step 0.024 ms where this form gains
           // 0.069 (profiles/r11_direct_call_ab.txt, sections 2 and 3).
-          if (cr->n_heavy) launch_direct_c8_heavy(c->stream, cr->view(), tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, c->direct_words + 16, d_words + 2);
+          if (cr->n_heavy) launch_direct_c8_heavy(c->stream, cr->view(), tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, c->direct_words + 16, d_words + 2, cr->n_heavy);
       }
       else launch_direct_tiles(c->stream, ps, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, d_wo,
                                d_cov, d_sum, d_words, d_words + 1, c->direct_words + 16, d_words + 2, grid, c->direct_un); }
@@ -1074,6 +1074,7 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
     if (c8 && words[2] != c->pend[0].cr->n_heavy)       // (k_direct_c8's own count of the tiles it listed: the same candidates, the same threshold)
         return fail(c, PD_ESTATE, "direct windows: the kernel listed " + std::to_string(words[2]) + " pile-up tiles, the sample was made with " + std::to_string(c->pend[0].cr->n_heavy));
     c->direct_settled = words[2 + pdk::PD_HEAVY_SETTLED];
+    c->direct_pileup = c8 ? words[2] : 0;
     if (words[1]) {                                      // not applicable: batches stay pending
         if (getenv("PANDEPTH_TIMING")) fprintf(stderr, "[timing]   direct window path declined: begins owned %llu of %llu runs, runs with cells %u vs ends owned %u (difference), index error bits 0x%x, "
                             "long runs %u: the arrays are materialised\n", (unsigned long long)words[3] | ((unsigned long long)words[4] << 32),
@@ -1093,7 +1094,7 @@ int pd_scan_reduce_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, unsigned wra
     std::lock_guard<std::mutex> lk(c->mu);
     if (int rs = need_state(c, 0, "pd_scan_reduce_windows")) return rs;
     HIPOK(c, hipSetDevice(c->device));
-    c->direct_settled = 0;
+    c->direct_settled = 0; c->direct_pileup = 0;
     if (c->direct_windows && c->pristine && !c->pend.empty() && w >= 64 && c->stile == PD_TILE) {
         const uint32_t m = (wrap_bits == 0 || wrap_bits == 32) ? 0xFFFFFFFFu : ((1u << wrap_bits) - 1u);
         bool done = false;
@@ -1960,7 +1961,7 @@ static int direct_export(pd_ctx *c, void *dev_i4, pd_exc *dev_exc, uint32_t exc_
     if (grid > c->n_tiles) grid = (unsigned)c->n_tiles;
     { ProfScope sc(c, "direct_export");
       if (c8) launch_direct_c8_export(c->stream, c->pend[0].cr->view(), c->pend[0].cr->td, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, dev_i4, dev_exc, exc_cap,
-                                      dev_count, c->sums, c->direct_words + 16, c->direct_words + 2, grid);
+                                      dev_count, c->sums, c->direct_words + 16, c->direct_words + 2, grid, c->pend[0].cr->n_heavy);
       else launch_direct_export(c->stream, ps, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, dev_i4, dev_exc, exc_cap, dev_count,
                                 c->sums, c->direct_words, c->direct_words + 1, c->direct_words + 16, c->direct_words + 2, grid); }
     HIPOK(c, hipGetLastError());
@@ -2506,6 +2507,7 @@ int pd_profile_get(pd_ctx *c, const char *name, double *ms, uint64_t *launches)
         uint64_t v = 0; bool hit = false;
         for (auto &d : dn) if (!strcmp(name, d.name)) { v = c->dec_n[d.k].load(); hit = true; }
         if (!strcmp(name, "direct_cover_settled")) { v = c->direct_settled; hit = true; }     // tiles of the last direct window call that k_direct_c8 settled without a window
+        if (!strcmp(name, "direct_pileup_tiles")) { v = c->direct_pileup; hit = true; }       // ... and the tiles it left to the pile-up pass (k_c8_heavy)
         if (!strcmp(name, "decode_chain_device")) { v = c->dec_n_fast.load(); hit = true; }
         if (!strcmp(name, "decode_chain_host")) { v = c->dec_n_slow.load(); hit = true; }
         if (!strcmp(name, "decode_segments_redone")) { v = c->dec_n_redo.load(); hit = true; }

@@ -133,6 +133,7 @@ struct pd_ctx {
     bool direct_cover = true;                                    // k_direct_c8's default form settles covered tiles from the runs (false: the window path for every tile)
     uint32_t direct_cover_min = 2048;                            // ... of tiles with at least this many candidates (launch_direct_c8)
     uint64_t direct_settled = 0;                                 // tiles the cover pass settled in the last direct_windows call
+    uint64_t direct_pileup = 0;                                  // pile-up tiles k_direct_c8 listed in the last direct_windows call (the int-window pass did them)
     bool all_valid_host = false;
     std::vector<Pending> pend;
     // ---- device decode (pd_decode_*): a few batch slots, each with its own stream and buffers ----

@@ -122,12 +122,12 @@ void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, cons
 constexpr int PD_HEAVY_SETTLED = 10;
 void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
                       uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min);
-// ... and the int-window pass for the pile-up tiles k_direct_c8 put on heavy_list (it reads tab, tile_contig and the bucket starts in cs).  Its own launcher:
-// the caller launches it only for a sample that has pile-up tiles (pd_runs::n_heavy, counted by k_c8_tile_desc).
+// ... and the int-window pass for the pile-up tiles k_direct_c8 put on heavy_list: k_c8_heavy (it reads tab, tile_contig and the bucket starts in cs), a workgroup per
+// listed tile up to 1024.  Its own launcher: the caller launches it only for a sample that has pile-up tiles (pd_runs::n_heavy, counted by k_c8_tile_desc).
 void launch_direct_c8_heavy(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w, uint32_t min_dep,
-                            TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count);
+                            TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, uint32_t n_heavy /* pd_runs::n_heavy: the grid */);
 void launch_direct_c8_export(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, void *img, pd_exc *exc,
-                             uint32_t cap, uint32_t *count, int *sums, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles);
+                             uint32_t cap, uint32_t *count, int *sums, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, uint32_t n_heavy);
 void launch_direct_export(hipStream_t st, const PendSet &ps, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles,
                           void *img, pd_exc *exc, uint32_t cap, uint32_t *count, int *sums, uint32_t *n_long, uint32_t *fail,
                           uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles);

@@ -22,6 +22,7 @@
 #include <stdint.h>
 #include "pd_kernels.h"
 #include "pd_cover_rule.h"
+#include "pd_pile_rule.h"
 
 namespace pdk {
 
@@ -1125,24 +1126,144 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_wide3(const PendSet ps, uint
     }
 }
 
+// The int-window pass of the pile-up tiles — k_direct_tiles_heavy on 12-byte runs, k_c8_heavy on a compact sample — keeps a tile's window as
+// 8192 ints in LDS; the two kernels differ only in how the candidates reach it and share what follows.
+struct HeavyLds {
+    alignas(16) int win[TILE];
+    unsigned long long acc[TILE / 64 + 2];
+    unsigned long long red_s[16][2];                             // (per wave: up to 16 of them)
+    int red_c[16][2];
+    int wtot[16];
+    int s_carry;
+};
+
+template <int NT = WG>
+__device__ __forceinline__ void heavy_tile_clear(HeavyLds &L)
+{
+    int4 *w4 = reinterpret_cast<int4 *>(L.win);
+    for (int j = threadIdx.x; j < TILE / 4; j += NT) w4[j] = make_int4(0, 0, 0, 0);
+    if (threadIdx.x == 0) L.s_carry = 0;
+}
+
+// Tile t's window is complete but for this thread's share `carry` of the runs that cover the cell before the tile: export it (ex.img != null,
+// workgroup-uniform) or take the prefix sum and the tile's shares of its windows.  Ends behind a barrier: the window may be cleared again.
+// NT: the workgroup's threads (256: k_direct_tiles_heavy, with narrow windows too; 1024: k_c8_heavy, whose windows are never narrower than a tile).
+template <int NT = WG>
+__device__ __forceinline__ void heavy_tile_finish(HeavyLds &L, int carry, const uint64_t t, const int32_t ctg, const uint32_t clen, const ContigTab tab,
+                                                  const uint32_t wrap_mask, const WinArgs &wa, const uint64_t *win_off, const DirectExport &ex)
+{
+    constexpr int ST = TILE;
+    constexpr int NW = NT / 64;                                   // waves
+    constexpr int ROWS = TILE / (NT * 4);                        // 8, or 2
+    static_assert(NW <= 16 && ROWS >= 1 && ROWS * NT * 4 == TILE, "the window is split evenly over at most 16 waves");
+    const uint32_t w = wa.w, min_dep = wa.min_dep;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint64_t a = t * ST;
+    int4 *w4 = reinterpret_cast<int4 *>(L.win);
+    carry = wave_sum(carry);
+    if (lane == 0 && carry != 0) atomicAdd(&L.s_carry, carry);
+    __syncthreads();
+    if (ex.img) {                                                 // workgroup-uniform: the window leaves as nibbles (k_export_i4's layout)
+        const uint64_t cw = a + (uint64_t)wv * (ROWS * 256);
+        unsigned short *o = ex.img + cw / 4 + lane;
+        int tsum = 0;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const int4 q = w4[wv * (ROWS * 64) + r * 64 + lane];
+            int x[4] = {q.x, q.y, q.z, q.w};
+            unsigned wb = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                tsum += x[k];
+                if (x[k] > 7 || x[k] < -8) {
+                    const uint32_t slot = atomicAdd(ex.count, 1u);
+                    if (slot < ex.cap) { ex.exc[slot].cell = cw + (uint64_t)(r * 256 + lane * 4 + k); ex.exc[slot].value = x[k]; ex.exc[slot].pad = 0; }
+                    x[k] = 0;
+                }
+                wb |= (unsigned)((x[k] + 8) & 0xf) << (4 * k);
+            }
+            o[r * 64] = (unsigned short)wb;
+        }
+        tsum = wave_sum(tsum);
+        if (lane == 0) L.wtot[wv] = tsum;
+        __syncthreads();
+        if (threadIdx.x == 0) { int ts = 0; for (int k = 0; k < NW; ++k) ts += L.wtot[k]; ex.sums[t] = ts; }
+        __syncthreads();
+        return;
+    }
+    // ---- prefix sum of the window, straight from LDS (k_sweep's layout) ----
+    int4 v[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) v[r] = w4[wv * (ROWS * 64) + r * 64 + lane];
+    int tot[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        v[r].y += v[r].x; v[r].z += v[r].y; v[r].w += v[r].z;
+        tot[r] = v[r].w;
+    }
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) tot[r] = wave_incl_scan(tot[r]);
+    int run = 0;
+    int excl[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        excl[r] = run + tot[r] - v[r].w;
+        run += __builtin_amdgcn_readlane(tot[r], 63);
+    }
+    if (lane == 0) L.wtot[wv] = run;
+    __syncthreads();
+    int base = L.s_carry;
+    for (int k = 0; k < wv; ++k) base += L.wtot[k];
+    if constexpr (NT == WG) {
+        if (w < (uint32_t)ST) {                                   // narrow windows: LDS accumulators (uniform branch)
+            const uint32_t p0 = (uint32_t)(a - tab.off[ctg]);
+            if (p0 < clen) direct_small_windows<ROWS>(v, excl, base, wrap_mask, p0, clen, wa, win_off[ctg], L.acc, wa.part + t);
+            __syncthreads();
+            return;
+        }
+    }
+    // ---- the tile's share of windows k0 and k0 + 1 ----
+    const uint64_t local0 = a - tab.off[ctg];
+    int c0 = 0, c1 = 0; unsigned long long s0 = 0, s1 = 0;
+    if (local0 < clen) {
+        const uint64_t k0 = local0 / w;
+        const uint64_t nb = (k0 + 1) * (uint64_t)w - local0;     // tile-local start of window k0+1
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const int bsum = base + excl[r];
+            const uint32_t pos = (uint32_t)(wv * (ROWS * 256) + r * 256 + lane * 4);
+            const uint32_t d[4] = {(uint32_t)(v[r].x + bsum) & wrap_mask, (uint32_t)(v[r].y + bsum) & wrap_mask,
+                                   (uint32_t)(v[r].z + bsum) & wrap_mask, (uint32_t)(v[r].w + bsum) & wrap_mask};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const bool ok = local0 + pos + q < clen && d[q] >= min_dep;
+                if (ok) { if (pos + q < nb) { ++c0; s0 += d[q]; } else { ++c1; s1 += d[q]; } }
+            }
+        }
+    }
+    c0 = wave_sum(c0); c1 = wave_sum(c1);
+#pragma unroll
+    for (int o = 32; o; o >>= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); }
+    if (lane == 0) { L.red_c[wv][0] = c0; L.red_c[wv][1] = c1; L.red_s[wv][0] = s0; L.red_s[wv][1] = s1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        TilePart tp; tp.c0 = tp.c1 = 0u; tp.s0 = tp.s1 = 0ull;
+        for (int k = 0; k < NW; ++k) { tp.c0 += (uint32_t)L.red_c[k][0]; tp.c1 += (uint32_t)L.red_c[k][1]; tp.s0 += L.red_s[k][0]; tp.s1 += L.red_s[k][1]; }
+        wa.part[t] = tp;
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(WG) void k_direct_tiles_heavy(const PendSet ps, uint32_t n_tiles, ContigTab tab,
                                                      const uint32_t *tile_contig, uint32_t wrap_mask, const WinArgs wa,
                                                      const uint64_t *win_off, uint32_t *n_long,
                                                      const uint32_t *heavy_list, const uint32_t *heavy_count,
-                                                     const DirectExport ex,          // ex.img != null: export instead of statistics
-                                                     const C8Sample cs)              // cs.lo != null: a compact sample (then ps is empty)
+                                                     const DirectExport ex)          // ex.img != null: export instead of statistics
 {
-    const uint32_t w = wa.w, min_dep = wa.min_dep;
-    TilePart *const part = wa.part;
-    __shared__ unsigned long long acc[TILE / 64 + 2];
     constexpr int ST = TILE;
-    constexpr int ROWS = TILE / (WG * 4);                        // 8
-    __shared__ __attribute__((aligned(16))) int win[ST];
-    __shared__ int s_carry;
-    __shared__ int wtot[4];
-    __shared__ unsigned long long red_s[4][2];
-    __shared__ int red_c[4][2];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __shared__ HeavyLds L;
+    int *const win = L.win;
+    const int lane = threadIdx.x & 63;
     uint32_t tf[PD_MAXPEND], na[PD_MAXPEND];
     uint32_t n_beg[PD_MAXPEND], n_has[PD_MAXPEND], n_end[PD_MAXPEND];
     uint32_t longs = 0;
@@ -1156,9 +1277,7 @@ __global__ __launch_bounds__(WG) void k_direct_tiles_heavy(const PendSet ps, uin
     for (uint32_t hi_ = blockIdx.x; hi_ < n_heavy; hi_ += gridDim.x) {
         const uint64_t t = heavy_list[hi_];
         const uint64_t a = t * ST;
-        int4 *w4 = reinterpret_cast<int4 *>(win);
-        for (int j = threadIdx.x; j < ST / 4; j += WG) w4[j] = make_int4(0, 0, 0, 0);
-        if (threadIdx.x == 0) s_carry = 0;
+        heavy_tile_clear(L);
         const int32_t ctg = (int32_t)tile_contig[t];
         const uint32_t clen = tab.len[ctg];
         const int64_t rel = (int64_t)(tab.off[ctg] - a);          // slot start relative to the tile (<= 0)
@@ -1199,116 +1318,7 @@ __global__ __launch_bounds__(WG) void k_direct_tiles_heavy(const PendSet ps, uin
                 }
             }
         }
-        if (cs.lo) {                                              // a compact sample: the tile's own buckets and the one before them, in both streams (16-bit arithmetic: k_direct_c8)
-            const uint32_t k0 = (uint32_t)t << cs.bshift, kl = rel < 0 ? k0 - 1 : k0;           // (a contig's first tile has nothing before it)
-            const uint32_t a32 = (uint32_t)a;
-            for (int strm = 0; strm < 2; ++strm) {
-                const uint32_t *bs = strm ? cs.o1 : cs.b1;
-                const uint32_t *rl = strm ? cs.lo + cs.o_base : cs.lo;
-                const uint32_t lo = bs[kl], hi = bs[k0 + (1u << cs.bshift)];
-                for (uint32_t i = lo + threadIdx.x; i < hi; i += WG) {
-                    const uint32_t r = rl[i];
-                    if (!(r >> 16)) continue;
-                    const uint32_t sb = (r - a32) & 0xFFFFu, se = sb + (r >> 16), se16 = se & 0xFFFFu;   // tile-relative mod 2^16: a run of the bucket before begins at 2^16 - bucket or later
-                    if (sb < (uint32_t)ST) atomicAdd(&win[sb], 1);
-                    if (se16 < (uint32_t)ST) atomicAdd(&win[se16], -1);
-                    if (se >= 0x10000u) ++carry;
-                }
-            }
-        }
-        carry = wave_sum(carry);
-        if (lane == 0 && carry != 0) atomicAdd(&s_carry, carry);
-        __syncthreads();
-        if (ex.img) {                                             // workgroup-uniform: the window leaves as nibbles (k_export_i4's layout)
-            const uint64_t cw = a + (uint64_t)wv * (ROWS * 256);
-            unsigned short *o = ex.img + cw / 4 + lane;
-            int tsum = 0;
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const int4 q = w4[wv * (ROWS * 64) + r * 64 + lane];
-                int x[4] = {q.x, q.y, q.z, q.w};
-                unsigned wb = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    tsum += x[k];
-                    if (x[k] > 7 || x[k] < -8) {
-                        const uint32_t slot = atomicAdd(ex.count, 1u);
-                        if (slot < ex.cap) { ex.exc[slot].cell = cw + (uint64_t)(r * 256 + lane * 4 + k); ex.exc[slot].value = x[k]; ex.exc[slot].pad = 0; }
-                        x[k] = 0;
-                    }
-                    wb |= (unsigned)((x[k] + 8) & 0xf) << (4 * k);
-                }
-                o[r * 64] = (unsigned short)wb;
-            }
-            tsum = wave_sum(tsum);
-            if (lane == 0) wtot[wv] = tsum;
-            __syncthreads();
-            if (threadIdx.x == 0) ex.sums[t] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-            __syncthreads();
-            continue;
-        }
-        // ---- prefix sum of the window, straight from LDS (k_sweep's layout) ----
-        int4 v[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) v[r] = w4[wv * (ROWS * 64) + r * 64 + lane];
-        int tot[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            v[r].y += v[r].x; v[r].z += v[r].y; v[r].w += v[r].z;
-            tot[r] = v[r].w;
-        }
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) tot[r] = wave_incl_scan(tot[r]);
-        int run = 0;
-        int excl[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            excl[r] = run + tot[r] - v[r].w;
-            run += __builtin_amdgcn_readlane(tot[r], 63);
-        }
-        if (lane == 0) wtot[wv] = run;
-        __syncthreads();
-        int base = s_carry;
-        for (int k = 0; k < wv; ++k) base += wtot[k];
-        if (w < (uint32_t)ST) {                                   // narrow windows: LDS accumulators (uniform branch)
-            const uint32_t p0 = (uint32_t)(a - tab.off[ctg]);
-            if (p0 < clen) direct_small_windows<ROWS>(v, excl, base, wrap_mask, p0, clen, wa, win_off[ctg], acc, wa.part + t);
-            __syncthreads();
-            continue;
-        }
-        // ---- the tile's share of windows k0 and k0 + 1 ----
-        const uint64_t local0 = a - tab.off[ctg];
-        int c0 = 0, c1 = 0; unsigned long long s0 = 0, s1 = 0;
-        if (local0 < clen) {
-            const uint64_t k0 = local0 / w;
-            const uint64_t nb = (k0 + 1) * (uint64_t)w - local0;     // tile-local start of window k0+1
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const int bsum = base + excl[r];
-                const uint32_t pos = (uint32_t)(wv * (ROWS * 256) + r * 256 + lane * 4);
-                const uint32_t d[4] = {(uint32_t)(v[r].x + bsum) & wrap_mask, (uint32_t)(v[r].y + bsum) & wrap_mask,
-                                       (uint32_t)(v[r].z + bsum) & wrap_mask, (uint32_t)(v[r].w + bsum) & wrap_mask};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const bool ok = local0 + pos + q < clen && d[q] >= min_dep;
-                    if (ok) { if (pos + q < nb) { ++c0; s0 += d[q]; } else { ++c1; s1 += d[q]; } }
-                }
-            }
-        }
-        c0 = wave_sum(c0); c1 = wave_sum(c1);
-#pragma unroll
-        for (int o = 32; o; o >>= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); }
-        if (lane == 0) { red_c[wv][0] = c0; red_c[wv][1] = c1; red_s[wv][0] = s0; red_s[wv][1] = s1; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            TilePart tp;
-            tp.c0 = (uint32_t)(red_c[0][0] + red_c[1][0] + red_c[2][0] + red_c[3][0]);
-            tp.c1 = (uint32_t)(red_c[0][1] + red_c[1][1] + red_c[2][1] + red_c[3][1]);
-            tp.s0 = red_s[0][0] + red_s[1][0] + red_s[2][0] + red_s[3][0];
-            tp.s1 = red_s[0][1] + red_s[1][1] + red_s[2][1] + red_s[3][1];
-            part[t] = tp;
-        }
-        __syncthreads();
+        heavy_tile_finish(L, carry, t, ctg, clen, tab, wrap_mask, wa, win_off, ex);
     }
     // the same accounting as k_scatter_tiles: every begin and every end must have found its owner tile
     __shared__ unsigned s_cnt[PD_MAXPEND][3];
@@ -1339,6 +1349,93 @@ __global__ __launch_bounds__(WG) void k_direct_tiles_heavy(const PendSet ps, uin
         }
     }
     if (threadIdx.x == 0 && s_long) atomicAdd(n_long, s_long);
+}
+
+// k_c8_heavy — the pile-up pass of a compact sample: the tiles k_direct_c8 put on heavy_list (more than PD_C8_HEAVY_CAND candidates: tens of
+// thousands of reads that begin on one cell), one workgroup per tile, the window as ints in LDS (HeavyLds).  A tile's candidates are those of
+// k_direct_c8 — its own buckets and the one before them, in both streams, 16-bit arithmetic on the lo plane (pdpile::events) — and reach the window so:
+//   * chunks of UN * WG consecutive runs, the sorted stream's and then the other stream's as ONE sequence of chunks, lane after lane (slot k of a
+//     thread is run threadIdx.x + k * WG of its chunk); a chunk's UN loads per thread are issued before the chunk in front of it is worked on
+//     (two register buffers in turn, as in k_direct_c8).  Indices are clamped to the stream's last run and the slots past it become a run
+//     without cells, which takes no part;
+//   * for every slot, neighbouring lanes that name the same begin cell add ONCE (pd_pile_rule.h): the first lane of such a group adds the group's
+//     size, the others do nothing — a pile's 64 begins in a wave are one LDS atomic, not 64 to one word in turn; the same, grouped on their own,
+//     for the end cells (equal where the pile's reads have one length).  Integer additions commute: the window is the one a run-by-run walk leaves;
+//   * the carry-in (runs of the bucket before that reach the tile's first cell) is counted with a ballot per slot.
+// A tile's cost stays linear in its candidates: one workgroup walks them all.
+template <bool EXPORT, int UN, int NT>
+__global__ __launch_bounds__(NT) void k_c8_heavy(const C8Sample cs, uint32_t n_tiles, ContigTab tab, const uint32_t *tile_contig, uint32_t wrap_mask,
+                                                  const WinArgs wa, const uint32_t *heavy_list, const uint32_t *heavy_count, const DirectExport ex)
+{
+    constexpr uint32_t ST = TILE, C = UN * NT;
+    __shared__ HeavyLds L;
+    int *const win = L.win;
+    const int lane = threadIdx.x & 63;
+    const uint32_t *__restrict__ const p = cs.lo;
+    const uint32_t n_heavy = *heavy_count < n_tiles ? *heavy_count : n_tiles;
+    for (uint32_t hi_ = blockIdx.x; hi_ < n_heavy; hi_ += gridDim.x) {
+        const uint64_t t = heavy_list[hi_];
+        const uint64_t a = t * ST;
+        const int32_t ctg = (int32_t)tile_contig[t];
+        const uint32_t clen = tab.len[ctg];
+        const uint32_t k0 = (uint32_t)t << cs.bshift, kl = tab.off[ctg] < a ? k0 - 1 : k0;   // (a contig's first tile has nothing before it)
+        const uint32_t kh = k0 + (1u << cs.bshift);
+        const uint32_t s_at = cs.b1[kl], ns = cs.b1[kh] - s_at;   // the tile's candidates in the sorted stream
+        const uint32_t olo = cs.o1[kl], no = cs.o1[kh] - olo;     // ... and in the other stream
+        const uint32_t o_at = cs.o_base + olo;
+        const uint32_t p0 = (uint32_t)a & 0xFFFFu;
+        const uint32_t none = (p0 + ST) & 0xFFFFu;                // a run without cells
+        const uint32_t c1 = (ns + C - 1) / C, nq = c1 + (no + C - 1) / C;
+        int carry_s = 0;                                          // wave-uniform
+        auto load = [&](uint32_t (&dst)[UN], const uint32_t q) {
+            const bool second = q >= c1;
+            const uint32_t at = second ? o_at : s_at, i = (second ? q - c1 : q) * C + threadIdx.x, last = (second ? no : ns) - 1u;
+#pragma unroll
+            for (int k = 0; k < UN; ++k) { const uint32_t j = i + (uint32_t)k * NT; dst[k] = p[at + (j < last ? j : last)]; }
+        };
+        // the wave's lanes with `valid` add sign to win[v], neighbours that name one cell as one addition (pd_pile_rule.h)
+        auto add_grouped = [&](const uint32_t v, const bool valid, const unsigned long long m_valid, const int sign) {
+            if (!m_valid) return;                                 // wave-uniform
+            const uint32_t key = pdpile::lane_key(v, valid);
+            const bool head = pdpile::is_head(key, (uint32_t)wave_shift_up((int)key, (int)pdpile::NO_LANE));
+            const unsigned long long m_h = __builtin_amdgcn_ballot_w64(head);
+            if (head) atomicAdd(&win[v], sign * (int)pdpile::multiplicity(m_h, m_valid, lane));
+        };
+        auto work = [&](const uint32_t (&c)[UN], const uint32_t q) {
+            const bool second = q >= c1;
+            const uint32_t i = (second ? q - c1 : q) * C + threadIdx.x, n = second ? no : ns;
+            const uint32_t left = n - (second ? q - c1 : q) * C;  // >= 1
+            const int nu = left >= C ? UN : (int)((left + NT - 1) / NT);      // workgroup-uniform, 1 .. UN: the slots that hold a run at all
+#pragma unroll
+            for (int k = 0; k < UN; ++k) {
+                if (k >= nu) continue;
+                const uint32_t r = i + (uint32_t)k * NT < n ? c[k] : none;
+                const pdpile::Events e = pdpile::events(r, p0);
+                const bool vb = e.has && e.sb < ST, ve = e.has && e.se16 < ST;
+                const unsigned long long m_vb = __builtin_amdgcn_ballot_w64(vb), m_ve = __builtin_amdgcn_ballot_w64(ve);
+                carry_s += __builtin_popcountll(__builtin_amdgcn_ballot_w64(e.carry && e.has));
+                add_grouped(e.sb, vb, m_vb, 1);
+                add_grouped(e.se16, ve, m_ve, -1);
+            }
+        };
+        uint32_t A[UN], B[UN];
+        if (nq) load(A, 0);                                       // the first chunk is on its way before the window is cleared
+        heavy_tile_clear<NT>(L);
+        __syncthreads();
+        if (nq) {
+            uint32_t q = 0;
+#pragma unroll 1
+            for (;;) {                                            // two buffers: B is in flight while A is worked on
+                if (q + 1 < nq) load(B, q + 1);
+                work(A, q);
+                if (++q >= nq) break;
+                if (q + 1 < nq) load(A, q + 1);
+                work(B, q);
+                if (++q >= nq) break;
+            }
+        }
+        heavy_tile_finish<NT>(L, lane == 0 ? carry_s : 0, t, ctg, clen, tab, wrap_mask, wa, nullptr, EXPORT ? ex : DirectExport{});
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2322,32 +2419,62 @@ __global__ __launch_bounds__(WG) void k_window_edges(const TilePart *part, const
     sum[tmap.win_off[ctg] + k] = a.s1 + b.s0;
 }
 
-// w >= TILE: one wave per window adds up the partials of the tiles it spans (plain loads/stores).
-__global__ __launch_bounds__(WG) void k_window_gather(const TilePart *part, const TileMap tmap, int32_t n_contigs,
+// w >= TILE: the partials of the tiles a window spans, added up with plain loads and stores.  WAVES = 1: a wave per window, four windows per
+// workgroup (windows of up to a few hundred tiles: with w = 8192 there are as many windows as tiles); WAVES = 4: a workgroup per window and a
+// cross-wave add (the 10 Mb bins' ~1 220 tiles: 792 waves left most of the device idle).  A lane keeps GU TilePart loads in flight: indices
+// past the window's last tile are clamped to it and count nothing.  A tile's share of THIS window is its first pair when the tile begins at or
+// behind the window's first cell k * w, its second pair when it begins before it — only the window's first tile can.
+template <int WAVES>
+__global__ __launch_bounds__(WG) void k_window_gather(const TilePart *__restrict__ part, const TileMap tmap, int32_t n_contigs,
                                                       uint32_t w, uint64_t n_windows, uint32_t *cover,
                                                       unsigned long long *sum)
 {
-    const uint64_t g = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (g >= n_windows) return;
-    const int lane = threadIdx.x & 63;
-    int lo = 0, hi = n_contigs;                                  // contig c with win_off[c] <= g < win_off[c+1]
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tmap.win_off[mid] <= g) lo = mid; else hi = mid; }
+    static_assert(WAVES == 1 || WAVES == 4, "a wave or the workgroup per window");
+    constexpr int GU = 5;                                         // (256 lanes x 5 take a 10 Mb bin's 1 222 tiles in one trip, 64 x 5 any window of the wave form)
+    constexpr uint32_t NL = WAVES * 64;                          // lanes per window
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint64_t g = WAVES == 1 ? (uint64_t)blockIdx.x * 4 + wv : (uint64_t)blockIdx.x;
+    if (g >= n_windows) return;                                  // (wave-uniform; WAVES = 4: workgroup-uniform)
+    int lo = 0, hi = n_contigs;                                  // the last contig c with win_off[c] <= g: 64 probes a round (two dependent loads for 4 096 contigs, not twelve)
+    while (hi - lo > 1) {
+        const int step = (hi - lo + 63) >> 6, probe = lo + lane * step;
+        const int le = __builtin_popcountll(__builtin_amdgcn_ballot_w64(probe < hi && tmap.win_off[probe] <= g));     // >= 1: lane 0 probes lo
+        lo += (le - 1) * step;
+        hi = hi < lo + step ? hi : lo + step;
+    }
     const uint64_t k = g - tmap.win_off[lo];
     const uint64_t coff = tmap.contig_off[lo];
     const uint64_t clen = tmap.contig_len[lo];
     const uint64_t b = k * w;
     uint64_t e = b + w; if (e > clen) e = clen;
     const uint64_t t0 = (coff + b) / TILE, t1 = (coff + e - 1) / TILE;
+    const uint64_t tb = (coff + b + TILE - 1) / TILE;             // the first tile that begins inside the window: t0 or t0 + 1
     uint32_t c = 0; unsigned long long s = 0;
-    for (uint64_t t = t0 + lane; t <= t1; t += 64) {
-        const TilePart tp = part[t];
-        const uint64_t k0 = (t * TILE - coff) / w;
-        if (k0 == k) { c += tp.c0; s += tp.s0; } else { c += tp.c1; s += tp.s1; }
+    for (uint64_t base = t0 + (WAVES == 1 ? (uint32_t)lane : threadIdx.x); base <= t1; base += (uint64_t)NL * GU) {
+        TilePart tp[GU];
+#pragma unroll
+        for (int u = 0; u < GU; ++u) { const uint64_t t = base + (uint64_t)u * NL; tp[u] = part[t <= t1 ? t : t1]; }
+#pragma unroll
+        for (int u = 0; u < GU; ++u) {
+            const uint64_t t = base + (uint64_t)u * NL;
+            const bool second = t < tb;
+            const uint32_t ci = second ? tp[u].c1 : tp[u].c0;
+            const unsigned long long si = second ? tp[u].s1 : tp[u].s0;
+            if (t <= t1) { c += ci; s += si; }
+        }
     }
     c = (uint32_t)wave_sum((int)c);
 #pragma unroll
     for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) { cover[g] = c; sum[g] = s; }
+    if (WAVES == 1) {
+        if (lane == 0) { cover[g] = c; sum[g] = s; }
+        return;
+    }
+    __shared__ uint32_t red_c[4];
+    __shared__ unsigned long long red_s[4];
+    if (lane == 0) { red_c[wv] = c; red_s[wv] = s; }
+    __syncthreads();
+    if (threadIdx.x == 0) { cover[g] = red_c[0] + red_c[1] + red_c[2] + red_c[3]; sum[g] = red_s[0] + red_s[1] + red_s[2] + red_s[3]; }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3120,8 +3247,11 @@ void launch_window_gather(hipStream_t st, const TilePart *part, TileMap tm, int3
                           uint64_t n_windows, uint32_t *cover, unsigned long long *sum)
 {
     if (!n_windows) return;
-    hipLaunchKernelGGL(k_window_gather, dim3((unsigned)((n_windows + 3) / 4)), dim3(WG), 0, st, part, tm, n_contigs,
-                       w, n_windows, cover, sum);
+    // a workgroup per window once a window's tiles give each of its 256 lanes one (w >= 256 tiles), a wave per window below that
+    if (w / (uint32_t)TILE >= (uint32_t)WG)
+        hipLaunchKernelGGL(k_window_gather<4>, dim3((unsigned)n_windows), dim3(WG), 0, st, part, tm, n_contigs, w, n_windows, cover, sum);
+    else
+        hipLaunchKernelGGL(k_window_gather<1>, dim3((unsigned)((n_windows + 3) / 4)), dim3(WG), 0, st, part, tm, n_contigs, w, n_windows, cover, sum);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3203,7 +3333,7 @@ void launch_direct_tiles(hipStream_t st, const PendSet &ps, ContigTab tab, const
     }
 #undef PD_DIRECT
     hipLaunchKernelGGL(k_direct_tiles_heavy, dim3(128), dim3(WG), 0, st, ps, n_tiles, tab, tile_contig, wrap_mask, wa, win_off,
-                       n_long, (const uint32_t *)heavy_list, (const uint32_t *)heavy_count, DirectExport{}, C8Sample{});
+                       n_long, (const uint32_t *)heavy_list, (const uint32_t *)heavy_count, DirectExport{});
     if (w < (uint32_t)TILE && n_tiles > 1)
         hipLaunchKernelGGL(k_window_edges, dim3((n_tiles + WG - 1) / WG), dim3(WG), 0, st, (const TilePart *)part, TileMap{tile_contig, tab.off, tab.len, win_off},
                            n_tiles, w, cover, sum);
@@ -3350,25 +3480,31 @@ void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_
 #undef PD_C8
 }
 
+// k_c8_heavy's form, by measurement on the bench's 12 pile-up tiles of 32 025 - 48 063 candidates (profiles/r12_pileup_gather_ab.txt): 1024 threads with 8 loads each
+constexpr int HEAVY_UN = 8, HEAVY_NT = 1024;
+
 void launch_direct_c8_heavy(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w, uint32_t min_dep,
-                            TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count)
+                            TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, uint32_t n_heavy)
 {
+    if (!n_heavy) return;
     WinArgs wa; wa.w = w; wa.min_dep = min_dep; wa.inv_w = 1.0f / (float)w; wa.cover = nullptr; wa.sum = nullptr; wa.part = part;
-    PendSet none{}; none.nb = 0; none.lmax = 0;
-    hipLaunchKernelGGL(k_direct_tiles_heavy, dim3(128), dim3(WG), 0, st, none, n_tiles, tab, tile_contig, wrap_mask, wa, (const uint64_t *)nullptr,
-                       heavy_count + 1 /* n_long: unused here */, (const uint32_t *)heavy_list, (const uint32_t *)heavy_count, DirectExport{}, cs);
+    // a workgroup per listed tile (the sample's own count), so that no list is walked by a fixed few workgroups in turns
+    const unsigned grid = n_heavy < 1024u ? n_heavy : 1024u;
+    hipLaunchKernelGGL((k_c8_heavy<false, HEAVY_UN, HEAVY_NT>), dim3(grid), dim3(HEAVY_NT), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, wa, (const uint32_t *)heavy_list,
+                       (const uint32_t *)heavy_count, DirectExport{});
 }
 
 void launch_direct_c8_export(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, void *img, pd_exc *exc,
-                             uint32_t cap, uint32_t *count, int *sums, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles)
+                             uint32_t cap, uint32_t *count, int *sums, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, uint32_t n_heavy)
 {
     const DirectExport de{(unsigned short *)img, exc, cap, count, sums};
     hipLaunchKernelGGL((k_direct_c8<7, 4, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, 0xFFFFFFFFu,
                        DirectWide{(uint32_t)TILE, 1u, nullptr}, heavy_list, heavy_count, de);
     WinArgs wa; wa.w = (uint32_t)TILE; wa.min_dep = 1; wa.inv_w = 0.f; wa.cover = nullptr; wa.sum = nullptr; wa.part = nullptr;
-    PendSet none{}; none.nb = 0; none.lmax = 0;
-    hipLaunchKernelGGL(k_direct_tiles_heavy, dim3(128), dim3(WG), 0, st, none, n_tiles, tab, tile_contig, 0xFFFFFFFFu, wa, (const uint64_t *)nullptr,
-                       heavy_count + 1, (const uint32_t *)heavy_list, (const uint32_t *)heavy_count, de, cs);
+    // (launched for a sample without pile-up tiles too, one workgroup then: this call has no check of the list's length behind it)
+    const unsigned grid = n_heavy < 1024u ? (n_heavy ? n_heavy : 1u) : 1024u;
+    hipLaunchKernelGGL((k_c8_heavy<true, HEAVY_UN, HEAVY_NT>), dim3(grid), dim3(HEAVY_NT), 0, st, cs, n_tiles, tab, tile_contig, 0xFFFFFFFFu, wa, (const uint32_t *)heavy_list,
+                       (const uint32_t *)heavy_count, de);
 }
 
 void launch_direct_export(hipStream_t st, const PendSet &ps, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles,
@@ -3383,7 +3519,7 @@ void launch_direct_export(hipStream_t st, const PendSet &ps, ContigTab tab, cons
     // tiles with more than 32 000 candidates: the int-window kernel exports them
     WinArgs wa; wa.w = (uint32_t)TILE; wa.min_dep = 1; wa.inv_w = 0.f; wa.cover = nullptr; wa.sum = nullptr; wa.part = nullptr;
     hipLaunchKernelGGL(k_direct_tiles_heavy, dim3(128), dim3(WG), 0, st, ps, n_tiles, tab, tile_contig, 0xFFFFFFFFu, wa,
-                       (const uint64_t *)nullptr, n_long, (const uint32_t *)heavy_list, (const uint32_t *)heavy_count, de, C8Sample{});
+                       (const uint64_t *)nullptr, n_long, (const uint32_t *)heavy_list, (const uint32_t *)heavy_count, de);
     hipLaunchKernelGGL(k_finish_direct, dim3(1), dim3(1), 0, st, ps, n_long, fail);
 }
 
@@ -3448,9 +3584,7 @@ int launch_sweep_windows(hipStream_t st, int *buf, const int *carry, uint32_t n_
         if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL((k_sweep<false, true, false>), dim3(n_tiles), dim3(WG), lds, st, buf, carry, wrap_mask, tm, wa, hstate, 0u);
     }
-    if (w >= (uint32_t)TILE && n_windows)
-        hipLaunchKernelGGL(k_window_gather, dim3((unsigned)((n_windows + 3) / 4)), dim3(WG), 0, st, part, tm, n_contigs,
-                           w, n_windows, cover, sum);
+    if (w >= (uint32_t)TILE) launch_window_gather(st, part, tm, n_contigs, w, n_windows, cover, sum);
     if (w < (uint32_t)TILE && n_tiles > 1)
         hipLaunchKernelGGL(k_window_edges, dim3((n_tiles + WG - 1) / WG), dim3(WG), 0, st, (const TilePart *)part, tm, n_tiles, w, cover, sum);
     return 0;

@@ -11,7 +11,7 @@ import sys
 
 
 def short(name):
-    for k in ("k_direct_c8", "k_direct_tiles_heavy", "k_window_gather", "k_reset_spans", "fillBuffer", "copyBuffer"):
+    for k in ("k_direct_c8", "k_direct_tiles_heavy", "k_c8_heavy", "k_window_gather", "k_reset_spans", "fillBuffer", "copyBuffer"):
         if k in name:
             return k
     return name.split("(")[0][:40]
