@@ -1045,8 +1045,15 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
     { ProfScope sc(c, "direct_tiles");
       if (c8) {
           const pd_runs *cr = c->pend[0].cr;
-          launch_direct_c8(c->stream, cr->view(), cr->td, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, c->direct_words + 16, d_words + 2, grid, c->direct_un,
-                           c->direct_cover && all >= (uint64_t)c->direct_cover_min * c->n_tiles /* a thin sample: the form without the pass (launch_direct_c8) */, c->direct_cover_min);
+          const bool cover = c->direct_cover && all >= (uint64_t)c->direct_cover_min * c->n_tiles;   // a thin sample: the form without the pass (launch_direct_c8)
+          // The cover form walks GROUPS of four tiles and a settled group costs a workgroup little more than its start, so its default grid is 64 workgroups
+          // per CU, not one per 256 runs: on the bench sample (91 623 groups; ms per launch with the pile-up pass) 65 536 workgroups 0.985, one per group
+          // 1.352, 32 768: 0.798, 16 384: 0.806, 7 168: 0.797 (profiles/r13_cover_wave_ab.txt).  "grid_tiles" still overrides it.
+          if (cover && !c->grid_tiles && !c->direct_un) {
+              const uint64_t groups = ((uint64_t)c->n_tiles + 3) / 4, g = (uint64_t)c->n_cu * 64;
+              grid = (unsigned)(g < groups ? g : groups);
+          }
+          launch_direct_c8(c->stream, cr->view(), cr->td, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, c->direct_words + 16, d_words + 2, grid, c->direct_un, cover, c->direct_cover_min);
           // The int-window pass for the pile-up tiles k_direct_c8 lists, launched only for a sample that has some: the sample knows from its making
           // (pd_runs::n_heavy, counted by k_c8_tile_desc from the records k_direct_c8 reads), so no round trip decides.  The bench's 1e9-record sample HAS
           // pile-up tiles (12): the pass's 0.028 ms per call there (k_c8_heavy; 0.099 as the compact branch of k_direct_tiles_heavy, profiles/r12_pileup_gather_ab.txt) are its work; on the empty lists of the 1e8- and 3e8-record samples a launch took 0.004 ms, and

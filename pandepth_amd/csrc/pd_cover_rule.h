@@ -12,7 +12,8 @@
 // stream sorted by begin the rule is exact.  A run without cells is swept like any other: its end equals its begin, so it never
 // extends the reach past a cell that is not covered, and where it begins beyond the reach the next run with cells begins there too.
 //
-// A sweep may be cut into SEGMENTS of consecutive runs (the kernel: one per wave).  A segment judges its gaps by its own running maximum,
+// The kernel sweeps a tile's sorted candidates as ONE segment (a wave per tile), so for it the rule is exact.
+// A sweep may also be cut into SEGMENTS of consecutive runs (the CPU check does, 1 - 4 of them).  A segment judges its gaps by its own running maximum,
 // which starts at its first begin; combine() then asks of every segment, in order, that its first begin is within the reach of those before
 // it.  That declines some covered tiles (a run reached only by an earlier segment's maximum), never the reverse.
 // The sum of the lengths clipped to the tile (the tile's TotalDepth when nothing wraps) and the number of runs that begin before the tile
@@ -49,7 +50,7 @@ PD_COVER_HD inline uint32_t run_clipped(int b, int e, int tile)
     const int hi = e < 0 ? 0 : (e > tile ? tile : e), lo = b < 0 ? 0 : b;
     return (uint32_t)(hi - lo);
 }
-// a run that changes no summary it is swept into (the kernel pads a wave's last chunk with it)
+// a run that changes no summary it is swept into (the kernel puts it in the places of a partial chunk that hold no run of the lane's own)
 PD_COVER_HD inline uint32_t run_neutral(uint32_t p0) { return (p0 + 0x8000u) & 0xFFFFu; }
 
 PD_COVER_HD inline void seg_add(Seg &s, uint32_t r, uint32_t p0, int tile)

@@ -1758,10 +1758,13 @@ __global__ __launch_bounds__(WG) void k_r8_to_iv(const uint32_t *lo, const uint3
 // with more than 32 000 candidates go to the int-window kernel through the same list.
 // LW (JOIN only, a divisor of UN8): runs per lane and load in the full chunks of the sorted stream — 1, 2 (8-byte loads) or 4 (16-byte loads; the
 // stream's words are 4-byte aligned, the loads are not); which thread works on which run changes, nothing else (the window's updates commute).
-// COVER (statistics form only): the cover pass in front of the window path — see it below.  Its gate is a score per workgroup: a declined tile adds
+// COVER (statistics form only): the cover pass in front of the window path — see it below.  The form walks GROUPS of four consecutive tiles (group
+// blockIdx.x + k * gridDim.x): each wave sweeps ONE tile of the group by itself, one barrier follows, and the tiles the pass did not settle take
+// the window path, all four waves together, in tile order.  Its gate is a score per workgroup, played over the tiles in their order: a declined tile adds
 // COVER_DECLINE, a settled one takes 1 off (not below 0); at COVER_CLOSE the workgroup leaves the pass out for COVER_SKIP tiles, tries one, and goes on
 // so while the score stays there.  Four declined tiles in a row close it; so does, in the long run, any mix in which fewer than two tiles in three
-// settle (a declined tile costs a sweep on top of its window, about twice what a settled one saves: launch_direct_c8).
+// settle (a declined tile costs a sweep on top of its window: launch_direct_c8).  A workgroup that walks consecutive tiles settles exactly the tiles it
+// would settle taking them one by one: a tile swept in a group in which an earlier tile's decline closed the gate is not counted and takes the window.
 constexpr uint32_t COVER_DECLINE = 2, COVER_CLOSE = 8, COVER_SKIP = 15;
 template <int WPE, int UN8, bool EXPORT, bool JOIN = false, int LW = 1, bool COVER = false>
 __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const TileDesc *__restrict__ desc, uint32_t n_tiles,
@@ -1778,122 +1781,205 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
     __shared__ int wtot[4];
     __shared__ unsigned long long red_s[4][2];
     __shared__ int red_c[4][2];
-    __shared__ uint4 s_cov[2][4];                                 // COVER: the four waves' summaries, two sets in turn
+    __shared__ __attribute__((aligned(16))) uint32_t s_cov[2][4];  // COVER: the outcome of each wave's tile (COV_*), two sets in turn
     uint32_t cov_flip = 0, cov_miss = 0, cov_skip = 0, cov_settled = 0;   // COVER, workgroup-uniform
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    // COVER: a step of the walk is a GROUP of four consecutive tiles, one per wave in the cover pass, and the window path for those the pass left
+    constexpr uint32_t GT = COVER ? 4u : 1u;
+    constexpr uint32_t COV_NONE = 0u /* no tile here, or a pile-up tile */, COV_WINDOW = 1u /* not swept */, COV_DECLINED = 2u, COV_SETTLED = 3u;
+    const uint32_t wvu = COVER ? (uint32_t)__builtin_amdgcn_readfirstlane(wv) : 0u;
+    const uint32_t n_steps = COVER ? (n_tiles >> 2) + ((n_tiles & 3u) ? 1u : 0u) : n_tiles;
     // a tile's bounds, its place in its contig and the contig's length are ONE record of the sample's descriptor table (TileDesc), read
     // through a pointer nothing is stored through: scalar loads, issued a tile ahead behind the first run loads, so that no tile waits
     // for metadata and nothing at the top of a tile depends on another load's result but the run loads themselves
+    // (COVER: a wave reads the record of ITS tile of the next group; the window path reads a tile's record when it is needed.)
     TileDesc nxt = TileDesc{};
-    if (blockIdx.x < n_tiles) nxt = desc[blockIdx.x];
-    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    if constexpr (COVER) { if (blockIdx.x < n_steps && blockIdx.x * 4u + wvu < n_tiles) nxt = desc[blockIdx.x * 4u + wvu]; }   // (32-bit: a group's number is below 2^30)
+    else if (blockIdx.x < n_tiles) nxt = desc[blockIdx.x];
+    for (uint64_t it = blockIdx.x; it < n_steps; it += gridDim.x) {
+      uint32_t todo = 1u;                                         // workgroup-uniform: bit k: tile it * GT + k takes the window path
+      if constexpr (COVER) {
+        // ---- the cover pass: an interior tile whose depths cannot wrap, asked for min_dep <= 1, needs no window when its runs cover it ----
+        // (pd_cover_rule.h, ONE segment: reach = 0, a run that begins beyond the reach is a gap, covered when no gap was met and the reach ends at
+        // TILE or further — exact on the sorted stream.)  TotalDepth is the sum of the candidates' lengths clipped to the tile, CoveredSite is all of
+        // the tile's cells when the sorted stream's runs leave no gap (always, for min_dep = 0).  Phase 1: wave k sweeps tile 4 * it + k by itself —
+        // no LDS window, no barrier, nothing shared with the other waves — when the tile is eligible (from the descriptor and the arguments: inside
+        // the contig, inside one window, no depth above the candidate count, enough candidates for the sweep to be the cheaper way: cover_min, see
+        // launch_direct_c8) and the gate may be open when the walk reaches it (cov_skip at the group's start <= k).  It lists a pile-up tile and
+        // leaves its outcome in s_cov.  Phase 2, behind ONE barrier: every thread reads the four outcomes and plays the gate over them in tile order
+        // — so what follows is workgroup-uniform, and the same whatever each wave met: a swept tile the gate had closed on by then (an earlier tile
+        // of the group declined) counts as not tried; a tile settled and tried is written by its wave's first lane; every other tile of the group
+        // takes the window path below, all four waves together, from its top, so the result never depends on the pass.
+        const uint32_t tw = (uint32_t)it * 4u + wvu;              // this wave's tile
+        const TileDesc mine = nxt;
+        const uint32_t g_next = (uint32_t)it + gridDim.x;
+        if (g_next < n_steps && g_next * 4u + wvu < n_tiles) nxt = desc[g_next * 4u + wvu];
+        uint32_t outcome = COV_NONE, wsum = 0;                    // wave-uniform
+        if (tw < n_tiles) {
+            const uint32_t ns = mine.shi - mine.slo, no = mine.ohi - mine.olo, cand = ns + no;
+            const uint32_t p0 = (tw * ST) & 0xFFFFu, pc = mine.pc, clen = mine.clen;
+            uint32_t ln = (uint32_t)lane;                          // made opaque here: what the pass derives from the lane is computed in the pass, not kept
+            asm volatile("" : "+v"(ln));                          // in registers across the window path
+            ln &= 63u;                                            // (its range known again: the loads' offsets fit 32 bits, so they need no address pairs)
+            if (cand > 32000u) {                                  // the int-window kernel does this tile
+                if (ln == 0u) heavy_list[atomicAdd(heavy_count, 1u)] = tw;
+            } else {
+                outcome = COV_WINDOW;
+                bool eligible = false;
+                if (cov_skip <= wvu && min_dep <= 1u && cand <= wrap_mask && cand >= args.cover_min && pc < clen && clen - pc >= ST)
+                    eligible = ((uint64_t)(pc / w) + 1u) * (uint64_t)w - pc >= (uint64_t)ST;
+                // (a stream of the tile that ends inside the first eight words of the sample's array — fewer than eight runs in all up to there — has
+                // no eight words to load: the window path does such a tile)
+                if ((ns && mine.shi < 8u) || (no && cs.o_base + mine.ohi < 8u)) eligible = false;
+                if (eligible) {
+                    // The tile's candidates as ONE sequence of chunks of CW = 512 runs, eight consecutive runs per lane: the sorted stream's full chunks,
+                    // its last, partial chunk, then the other stream's (their order does not matter: what they cover is ignored, their lengths count).
+                    // EVERY chunk is loaded the same way — two 16-byte loads per lane (the words are 4-byte aligned, the loads are not), no branch around
+                    // them — so that the wait in front of a chunk's work counts exactly the loads issued behind it: two chunks are in flight behind the
+                    // one worked on (three register buffers in turn, no copies).  One wave streams the tile's 12 KB by itself, and a CU's 28 waves
+                    // must keep HBM's latency covered.  In a partial chunk of cnt runs a lane's eight words begin at run min(8 * lane, cnt - 8) — still
+                    // inside the sample's array, not before its first word — and work() replaces what is not this lane's (runs before 8 * lane: the
+                    // lane before has them; everything, for a lane behind the end) by a run that changes nothing.  Behind the last chunk the loads go on,
+                    // all lanes to one place.
+                    constexpr uint32_t CW = 512u;
+                    const bool any_gap_ends = min_dep != 0u;      // min_dep = 0 counts every cell: only the sum is needed, never stop early
+                    const uint32_t n_full = ns / CW, n_rem = ns % CW, c_s = n_full + (n_rem ? 1u : 0u), nq = c_s + (no + CW - 1u) / CW;
+                    const uint32_t neutral = pdcover::run_neutral(p0);
+                    const uint32_t o_at = cs.o_base + mine.olo;
+                    // chunk q (wave-uniform): its first run's index in the array, its runs, and how far before it the loads may reach (8 words, or to the array's first)
+                    auto chunk_at = [&](const uint32_t q) -> uint32_t { return q < c_s ? mine.slo + q * CW : o_at + (q - c_s) * CW; };
+                    auto chunk_cnt = [&](const uint32_t q) -> uint32_t {
+                        if (q < n_full) return CW;
+                        if (q < c_s) return n_rem;
+                        const uint32_t left = no - (q - c_s) * CW;
+                        return left < CW ? left : CW;
+                    };
+                    // the lane's first word, counted from `back` words before the chunk
+                    auto lane_rel = [&](const uint32_t cnt, const uint32_t back) -> uint32_t {
+                        const int off = (int)(ln * 8u) < (int)cnt - 8 ? (int)(ln * 8u) : (int)cnt - 8;
+                        const int rel = off + (int)back;
+                        return (uint32_t)(rel > 0 ? rel : 0) & 1023u;   // (at most 512: said so that the loads take a 32-bit offset, not an address pair)
+                    };
+                    auto load = [&](uint32_t (&x)[8], const uint32_t q) {
+                        const uint32_t qq = q < nq ? q : nq - 1u;
+                        uint32_t cnt = chunk_cnt(qq);
+                        if (q >= nq && cnt > 8u) cnt = 8u;        // behind the last chunk: one place for all lanes
+                        const uint32_t at = chunk_at(qq), back = at < 8u ? at : 8u;
+                        const uint32_t *const cb = cs.lo + (at - back);
+                        const uint32_t rel = lane_rel(cnt, back);
+                        const uint4 u0 = *reinterpret_cast<const uint4 *>(cb + rel), u1 = *reinterpret_cast<const uint4 *>(cb + (rel + 4u));
+                        x[0] = u0.x; x[1] = u0.y; x[2] = u0.z; x[3] = u0.w; x[4] = u1.x; x[5] = u1.y; x[6] = u1.z; x[7] = u1.w;
+                    };
+                    int reach = 0;                                // wave-uniform: [0, reach) is covered by the runs swept so far
+                    bool gap = false;
+                    uint32_t sum = 0;                             // this lane's clipped lengths
+                    auto work = [&](uint32_t (&x)[8], const uint32_t q) {
+                        if (q >= n_full) {                        // a partial chunk (wave-uniform): keep this lane's own runs
+                            const uint32_t cnt = chunk_cnt(q), at = chunk_at(q), back = at < 8u ? at : 8u;
+                            const int mine0 = (int)(ln * 8u), got0 = (int)lane_rel(cnt, back) - (int)back;   // word 0 should be run mine0, and is run got0 <= mine0
+                            const int skip = mine0 < (int)cnt ? mine0 - got0 : 8;
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) x[k] = k >= skip ? x[k] : neutral;
+                        }
+                        int b[8], e[8];
+                        uint32_t neg = 0;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) { b[k] = pdcover::run_begin(x[k], p0); e[k] = pdcover::run_end(x[k], b[k]); neg |= (uint32_t)b[k]; }
+                        if (q < c_s) {                            // the sorted stream: the rule
+                            int m = e[0];
+#pragma unroll
+                            for (int k = 1; k < 8; ++k) m = m > e[k] ? m : e[k];
+                            const int incl = wave_incl_scan_max(m);
+                            const int before = wave_shift_up(incl, pdcover::NONE);      // the largest end of the lanes before this one
+                            int P = before > reach ? before : reach;
+                            unsigned long long g = 0ull;
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) { g |= __builtin_amdgcn_ballot_w64(b[k] > P); P = P > e[k] ? P : e[k]; }   // eight compares, joined on the scalar side
+                            if (g != 0ull) gap = true;
+                            const int top = __builtin_amdgcn_readlane(incl, 63);
+                            reach = top > reach ? top : reach;
+                            // clipping only where it is needed (wave-uniform): no run of the chunk begins before the tile, none ends behind it
+                            if (top <= (int)ST && __builtin_amdgcn_ballot_w64((int)neg < 0) == 0ull) {
+#pragma unroll
+                                for (int k = 0; k < 8; ++k) sum += x[k] >> 16;
+                                return;
+                            }
+                        }
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) sum += pdcover::run_clipped(b[k], e[k], (int)ST);
+                    };
+                    if (nq) {
+                        uint32_t A[8], B[8], C[8];
+                        uint32_t q = 0;
+                        load(A, 0u);
+                        load(B, 1u);
+#pragma unroll 1
+                        for (;;) {                                // a gap ends the sweep (the tile is declined, its sum is not used)
+                            load(C, q + 2u);
+                            work(A, q);
+                            if (++q >= nq || (gap && any_gap_ends)) break;
+                            load(A, q + 2u);
+                            work(B, q);
+                            if (++q >= nq || (gap && any_gap_ends)) break;
+                            load(B, q + 2u);
+                            work(C, q);
+                            if (++q >= nq || (gap && any_gap_ends)) break;
+                        }
+                        // nothing of this tile stays in flight: the next sweep's waits then count its own loads only (left pending, the loads issued
+                        // last make the compiler wait for ALL loads at the loop's top, every third chunk: measured)
+                        __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0)
+                    }
+                    wsum = (uint32_t)wave_total((int)sum);
+                    outcome = ((!gap && reach >= (int)ST) || !any_gap_ends) ? COV_SETTLED : COV_DECLINED;
+                }
+            }
+            if (ln == 0u) s_cov[cov_flip][wvu] = outcome;
+        } else if (lane == 0) s_cov[cov_flip][wvu] = COV_NONE;
+        __syncthreads();                                          // (the sets alternate: the next group's waves write the other four while a late wave still reads these)
+        const uint4 oc4 = *reinterpret_cast<const uint4 *>(&s_cov[cov_flip][0]);
+        const uint32_t oc[4] = {(uint32_t)__builtin_amdgcn_readfirstlane((int)oc4.x), (uint32_t)__builtin_amdgcn_readfirstlane((int)oc4.y),
+                                (uint32_t)__builtin_amdgcn_readfirstlane((int)oc4.z), (uint32_t)__builtin_amdgcn_readfirstlane((int)oc4.w)};
+        cov_flip ^= 1u;
+        todo = 0u;
+        bool write_mine = false;                                  // wave-uniform
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {                       // the gate, tile by tile as one workgroup walking them in order would play it
+            if (oc[k] == COV_NONE) continue;
+            if (cov_skip) { --cov_skip; todo |= 1u << k; }        // closed: not tried, whatever its wave found
+            else if (oc[k] == COV_SETTLED) { ++cov_settled; cov_miss -= cov_miss ? 1u : 0u; if (k == wvu) write_mine = true; }
+            else {
+                todo |= 1u << k;
+                if (oc[k] == COV_DECLINED) { cov_miss += COVER_DECLINE; if (cov_miss >= COVER_CLOSE) { cov_miss = COVER_CLOSE; cov_skip = COVER_SKIP; } }
+            }
+        }
+        if (write_mine && lane == 0) {
+            uint32_t all = ST;
+            asm volatile("" : "+v"(all));                         // (set here: as a constant it is kept in a register pair from the kernel's top, and spilled)
+            TilePart tp; tp.c0 = all; tp.c1 = 0u; tp.s0 = wsum; tp.s1 = 0ull; part[tw] = tp;
+        }
+      }
+#pragma unroll 1
+      for (uint32_t kt = 0; kt < GT; ++kt) {
+        if (COVER && !((todo >> kt) & 1u)) continue;
+        // COVER: what the window path derives from the thread's number is formed here again for every tile that takes it, not kept in registers
+        // across the cover pass (72 VGPRs hold both only this way: the pass needs its three buffers)
+        uint32_t tix = threadIdx.x;
+        if constexpr (COVER) { asm volatile("" : "+v"(tix)); tix &= (uint32_t)WG - 1u; }
+        const int lane = (int)(tix & 63u), wv = (int)(tix >> 6);
+        const uint64_t t = it * GT + kt;
         const uint64_t a = t * ST;
-        const TileDesc cur = nxt;
-        const uint64_t t_next = t + gridDim.x;
+        const TileDesc cur = COVER ? desc[t] : nxt;
+        const uint64_t t_next = COVER ? ~0ull : t + gridDim.x;    // (COVER: nxt is not the window path's)
         const uint32_t ns = cur.shi - cur.slo, s_at = cur.slo;    // the tile's candidates in the sorted stream
         const uint32_t olo = cur.olo, no = cur.ohi - olo;         // ... and in the other stream
         const uint32_t cand = ns + no;
         const uint32_t clen = cur.clen;
         const uint32_t p0 = (uint32_t)a & 0xFFFFu;                // the low 16 bits of the tile's first flat cell, like the runs' begins in the lo plane
         const uint32_t pc = cur.pc;                               // the tile's first cell inside its contig
-        if (cand > 32000u) {                                      // workgroup-uniform: the int-window kernel does this tile (no LDS touched: no barrier)
-            if (threadIdx.x == 0) heavy_list[atomicAdd(heavy_count, 1u)] = (uint32_t)t;
+        if (!COVER && cand > 32000u) {                            // workgroup-uniform: the int-window kernel does this tile (no LDS touched: no barrier)
+            if (tix == 0) heavy_list[atomicAdd(heavy_count, 1u)] = (uint32_t)t;
             if (t_next < n_tiles) nxt = desc[t_next];
             continue;
-        }
-        if constexpr (COVER) {
-            // ---- the cover pass: an interior tile whose depths cannot wrap, asked for min_dep <= 1, needs no window when its runs cover it ----
-            // (pd_cover_rule.h.)  TotalDepth is the sum of the candidates' lengths clipped to the tile, CoveredSite is all of the tile's cells
-            // when the sorted stream's runs leave no gap (always, for min_dep = 0).  Workgroup-uniform, from the descriptor and the arguments:
-            // inside the contig, inside one window, no depth above the candidate count, and enough candidates for the sweep to be the cheaper way
-            // (cover_min, see launch_direct_c8).  A tile the pass cannot settle takes the window
-            // path below from its top, so the result never depends on it; a workgroup whose tiles mostly decline skips the pass
-            // and tries it again on every (COVER_SKIP + 1)-th tile (the gate above).
-            bool eligible = false;
-            if (cov_skip) --cov_skip;
-            else if (min_dep <= 1u && cand <= wrap_mask && cand >= args.cover_min && pc < clen && clen - pc >= ST)
-                eligible = ((uint64_t)(pc / w) + 1u) * (uint64_t)w - pc >= (uint64_t)ST;
-            if (eligible) {
-                if (t_next < n_tiles) nxt = desc[t_next];
-                uint32_t ln = (uint32_t)lane;                      // made opaque here: what the pass derives from the lane is computed in the pass, not kept
-                asm volatile("" : "+v"(ln));                      // in registers across the window path (72 VGPRs hold both only this way)
-                const uint32_t *__restrict__ const p = cs.lo;
-                const bool any_gap_ends = min_dep != 0u;          // min_dep = 0 counts every cell: only the sum is needed, never stop early
-                const uint32_t wvu = (uint32_t)__builtin_amdgcn_readfirstlane(wv);
-                // this wave's quarter of the sorted candidates, in order, and its quarter of the other stream's
-                const uint32_t qs = (ns + 3u) >> 2, s_lo = wvu * qs < ns ? wvu * qs : ns, n_w = ns - s_lo < qs ? ns - s_lo : qs;
-                const uint32_t qo = (no + 3u) >> 2, o_lo = wvu * qo < no ? wvu * qo : no, n_o = no - o_lo < qo ? no - o_lo : qo;
-                const uint32_t *const ps = p + (s_at + s_lo), *const po = p + (cs.o_base + olo + o_lo);
-                const uint32_t n_full = n_w >> 8, n_rem = n_w & 255u;
-                const uint32_t neutral = pdcover::run_neutral(p0);
-                // loads first: the quarter's last, partial chunk (four consecutive runs per lane; past the end: a run that changes nothing),
-                // the first 64 runs of the other stream, the first full chunk
-                uint32_t tl[4] = {neutral, neutral, neutral, neutral}, o0 = neutral;
-                if (n_rem) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) { const uint32_t j = ln * 4u + (uint32_t)k; if (j < n_rem) tl[k] = ps[n_full * 256u + j]; }
-                }
-                if (ln < n_o) o0 = po[ln];
-                uint4 cur4 = make_uint4(neutral, neutral, neutral, neutral);
-                if (n_full) cur4 = *reinterpret_cast<const uint4 *>(ps + ln * 4u);
-                int first = pdcover::NONE, reach = pdcover::NONE;   // wave-uniform: the quarter's first begin, its running maximum
-                bool gap = false;
-                uint32_t sum = 0;                                 // this lane's clipped lengths
-                auto sweep4 = [&](const uint32_t r0, const uint32_t r1, const uint32_t r2, const uint32_t r3) {
-                    const int b0 = pdcover::run_begin(r0, p0), b1 = pdcover::run_begin(r1, p0), b2 = pdcover::run_begin(r2, p0), b3 = pdcover::run_begin(r3, p0);
-                    const int e0 = pdcover::run_end(r0, b0), e1 = pdcover::run_end(r1, b1), e2 = pdcover::run_end(r2, b2), e3 = pdcover::run_end(r3, b3);
-                    sum += pdcover::run_clipped(b0, e0, (int)ST) + pdcover::run_clipped(b1, e1, (int)ST) + pdcover::run_clipped(b2, e2, (int)ST) + pdcover::run_clipped(b3, e3, (int)ST);
-                    if (first == pdcover::NONE) {                 // (lane 0's first run is a real one: the chunk is not empty)
-                        first = __builtin_amdgcn_readfirstlane(b0);
-                        reach = first > 0 ? first : 0;            // nothing before cell 0 has to be covered
-                    }
-                    const int m0 = e0, m1 = m0 > e1 ? m0 : e1, m2 = m1 > e2 ? m1 : e2, m3 = m2 > e3 ? m2 : e3;
-                    const int incl = wave_incl_scan_max(m3);
-                    const int before = wave_shift_up(incl, pdcover::NONE);      // the largest end of the lanes before this one
-                    const int P = before > reach ? before : reach;
-                    const int P0 = P > m0 ? P : m0, P1 = P > m1 ? P : m1, P2 = P > m2 ? P : m2;
-                    const unsigned long long g = __builtin_amdgcn_ballot_w64(b0 > P) | __builtin_amdgcn_ballot_w64(b1 > P0) | __builtin_amdgcn_ballot_w64(b2 > P1) |
-                                                 __builtin_amdgcn_ballot_w64(b3 > P2);          // four compares, joined on the scalar side
-                    if (g != 0ull) gap = true;
-                    const int top = __builtin_amdgcn_readlane(incl, 63);
-                    reach = top > reach ? top : reach;
-                };
-#pragma unroll 1
-                for (uint32_t q = 0; q < n_full; ++q) {
-                    const uint4 u = cur4;
-                    if (q + 1 < n_full) cur4 = *reinterpret_cast<const uint4 *>(ps + (q + 1) * 256u + ln * 4u);
-                    sweep4(u.x, u.y, u.z, u.w);
-                    if (gap && any_gap_ends) break;
-                }
-                if (!(gap && any_gap_ends)) {
-                    if (n_rem) sweep4(tl[0], tl[1], tl[2], tl[3]);
-                    {   // the other stream: what it covers is ignored, its lengths count
-                        const int b = pdcover::run_begin(o0, p0);
-                        sum += pdcover::run_clipped(b, pdcover::run_end(o0, b), (int)ST);
-                    }
-                    for (uint32_t j = ln + 64u; j < n_o; j += 64u) {
-                        const uint32_t r = po[j];
-                        const int b = pdcover::run_begin(r, p0);
-                        sum += pdcover::run_clipped(b, pdcover::run_end(r, b), (int)ST);
-                    }
-                }
-                const uint32_t wsum = (uint32_t)wave_total((int)sum);
-                uint4 *const slot = &s_cov[cov_flip][0];
-                if (ln == 0u) slot[wvu] = make_uint4((uint32_t)first, (uint32_t)reach, gap ? 1u : 0u, wsum);
-                __syncthreads();                                  // (the slots alternate: the next pass writes the other four while a late wave still reads these)
-                pdcover::Seg seg[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { const uint4 u = slot[k]; seg[k] = pdcover::Seg{(int)u.x, (int)u.y, (int)u.z, u.w, 0u}; }
-                cov_flip ^= 1u;
-                const pdcover::Tile tile = pdcover::combine(seg, 4, nullptr, 0, (int)ST);
-                if (tile.covered || !any_gap_ends) {
-                    if (threadIdx.x == 0) { TilePart tp; tp.c0 = ST; tp.c1 = 0u; tp.s0 = tile.sum; tp.s1 = 0ull; part[t] = tp; }
-                    ++cov_settled; cov_miss -= cov_miss ? 1u : 0u;
-                    continue;
-                }
-                cov_miss += COVER_DECLINE;
-                if (cov_miss >= COVER_CLOSE) { cov_miss = COVER_CLOSE; cov_skip = COVER_SKIP; }
-            }
         }
         uint4 *w4 = reinterpret_cast<uint4 *>(win);
         int carry_s = 0;
@@ -1909,7 +1995,7 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
             const uint32_t nq = c1 + ((JOIN ? tail : no) + C - 1) / C;
             const uint32_t o_at = cs.o_base + olo;
             // slot k of a lane is run slot(k) of its chunk
-            auto slot = [&](const int k) -> uint32_t { return (uint32_t)LW * (threadIdx.x + (uint32_t)(k / LW) * WG) + (uint32_t)(k % LW); };
+            auto slot = [&](const int k) -> uint32_t { return (uint32_t)LW * (tix + (uint32_t)(k / LW) * WG) + (uint32_t)(k % LW); };
             auto load8 = [&](uint32_t (&dst)[UN8], const uint32_t q) {
                 const bool second = q >= c1;
                 if constexpr (JOIN) {
@@ -1943,7 +2029,7 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
                 }
                 const uint32_t at = second ? o_at : s_at, i = (second ? q - c1 : q) * C, last = (second ? no : ns) - 1u;
 #pragma unroll
-                for (int k = 0; k < UN8; ++k) { const uint32_t j = i + threadIdx.x + k * WG; dst[k] = p[at + (j < last ? j : last)]; }
+                for (int k = 0; k < UN8; ++k) { const uint32_t j = i + tix + k * WG; dst[k] = p[at + (j < last ? j : last)]; }
             };
             auto ev8 = [&](const uint32_t r) {
                 const uint32_t sb = (r - p0) & 0xFFFFu, se = sb + (r >> 16), se16 = se & 0xFFFFu;
@@ -1965,8 +2051,8 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
                 }
             };
             auto clear_window = [&]() {                           // ... and the next tile's descriptor: behind the run loads, so that the wait in front of the barrier covers both
-                for (uint32_t j = threadIdx.x; j < HT / 4; j += WG) w4[j] = make_uint4(0u, 0u, 0u, 0u);
-                if (threadIdx.x == 0) s_carry = 0;
+                for (uint32_t j = tix; j < HT / 4; j += WG) w4[j] = make_uint4(0u, 0u, 0u, 0u);
+                if (tix == 0) s_carry = 0;
                 if (t_next < n_tiles) nxt = desc[t_next];
                 __syncthreads();
             };
@@ -2099,7 +2185,7 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
         }
         if (lane == 0) { red_c[wv][0] = c0; red_c[wv][1] = c1; red_s[wv][0] = s0; red_s[wv][1] = s1; }
         __syncthreads();
-        if (threadIdx.x == 0) {
+        if (tix == 0) {
             TilePart tp;
             tp.c0 = (uint32_t)(red_c[0][0] + red_c[1][0] + red_c[2][0] + red_c[3][0]);
             tp.c1 = (uint32_t)(red_c[0][1] + red_c[1][1] + red_c[2][1] + red_c[3][1]);
@@ -2107,6 +2193,7 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
             tp.s1 = red_s[0][1] + red_s[1][1] + red_s[2][1] + red_s[3][1];
             part[t] = tp;
         }
+      }
     }
     if constexpr (COVER) {                                        // how many tiles the pass settled: one addition per workgroup, for the tests
         if (threadIdx.x == 0 && cov_settled) atomicAdd(heavy_count + PD_HEAVY_SETTLED, cov_settled);
@@ -3427,10 +3514,13 @@ void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_
     // 970 per tile, 98 % of the tiles settled: 0.82 / 0.74; 1e8, 322 per tile, 6 % settled: 1.14 / 0.85 — the lines cross near 1 450 candidates), so thinner
     // tiles keep the window.  The cover form's window path is itself 0.04 - 0.06 ms per launch behind the parent form's on those samples (17 SGPRs kept in
     // VGPR lanes), so the CALLER passes cover = false for a sample whose mean is below cover_min candidates per tile: it then runs the form without the pass.
-    // The gate (COVER_DECLINE = 2, COVER_CLOSE = 8, COVER_SKIP = 15) is per workgroup and acts only where a workgroup walks many tiles ("grid_tiles"): with
-    // the default grid a workgroup walks five or six tiles, the gate closes after four of them, and a dense sample with gaps pays a sweep on top of the window
-    // for most of its tiles — measured 1.480 -> 1.949 ms where every tile has gaps, 1.440 -> 1.624 where every other has (profiles/r10_direct_cover_ab.txt,
-    // section 6).  Such a sample is better off with "direct_cover" 0 until the tallies are shared between workgroups.
+    // (Those figures are of the quarter-per-wave pass, four waves to a tile.  The pass now gives a tile to ONE wave and a workgroup walks groups of four
+    // tiles, profiles/r13_cover_wave_ab.txt; the thresholds were not measured again and stand.)
+    // The gate (COVER_DECLINE = 2, COVER_CLOSE = 8, COVER_SKIP = 15) is per workgroup and acts only where a workgroup walks many tiles ("grid_tiles"): the
+    // caller's default grid for this form is 64 workgroups per CU, so on the bench genome a workgroup walks five or six GROUPS, 22 tiles, and the gate closes
+    // after the first of them where every tile has gaps.  With the quarter-per-wave pass and a workgroup per five or six tiles such a sample paid a sweep on
+    // top of the window for most of its tiles — 1.480 -> 1.949 ms where every tile has gaps, 1.440 -> 1.624 where every other has
+    // (profiles/r10_direct_cover_ab.txt, section 6); what it pays now: r13, section 5.  "direct_cover" 0 remains the way out.
     const DirectWide dw{w, min_dep, part, cover_min};
     // "direct_un" for a compact sample: 100 x waves-per-SIMD target + loads in flight per thread (0 = default)
 #define PD_C8(WPE_, UN8_) hipLaunchKernelGGL((k_direct_c8<WPE_, UN8_, false>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{})
