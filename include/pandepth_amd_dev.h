@@ -64,6 +64,13 @@ int pd_push_bgzf_units(pd_ctx *ctx, const void *blob, size_t n_bytes, const pd_b
 int pd_x_bgzf_inflate(int device, const void *host_bgzf, size_t n_bytes, void *host_out, size_t out_cap,
                       size_t *out_len, int variant, int reps, double *kernel_ms, uint32_t *n_blocks);
 
+/* ---- a compact sample's pile-up tiles (tests) ----------------------------------------------------
+ * The tiles with more candidates than the direct kernel's window takes are listed when the sample is made (pd_runs_create, or a
+ * PD_DECODE_COMPACT session's pd_decode_end), and the direct window call's pile-up pass works from that list.  *n = how many there
+ * are; the first min(cap, *n) tile numbers (8192-cell tiles of the context's buffer, contig slots included), in no particular
+ * order, go to `tiles`.  runs = NULL: the sample the context's last decode session left. */
+int pd_runs_pileup_tiles(pd_ctx *ctx, const pd_runs *runs, uint32_t *tiles, uint32_t cap, uint32_t *n);
+
 /* ---- guarded device allocations (a debugging aid for the library's own kernels) -----------------
  * With PANDEPTH_GUARD=1 in the environment every device buffer the library allocates is surrounded by two 256-byte canaries (the
  * one behind it starting exactly at the buffer's last byte + 1).  pd_guard_check waits for the device, compares every live

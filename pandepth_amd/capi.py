@@ -176,7 +176,7 @@ EXPORTS = ["pd_abi_version", "pd_create", "pd_destroy", "pd_strerror", "pd_reset
            "pd_read_depth", "pd_format_sites", "pd_deflate_parse", "pd_host_register", "pd_host_unregister", "pd_text_open", "pd_text_close", "pd_text_append_sites", "pd_text_parse", "pd_text_read", "pd_text_release", "pd_text_append_window_rows", "pd_text_append_bytes", "pd_device_buffer", "pd_device_count", "pd_accumulate_from", "pd_device_layout", "pd_export_i8", "pd_import_i8", "pd_export_i4",
            "pd_slice_sweep_i4", "pd_gather_windows", "pd_push_bgzf_units", "pd_decode_begin", "pd_decode_acquire", "pd_decode_submit", "pd_decode_queue", "pd_decode_collect", "pd_decode_end", "pd_decode_abort", "pd_comm_unique_id", "pd_comm_init", "pd_comm_init_all", "pd_comm_init_local", "pd_comm_preinit", "pd_comm_prepare", "pd_comm_destroy",
            "pd_comm_strerror", "pd_sliced_window_sum", "pd_sliced_interval_sum", "pd_sliced_sum_start", "pd_sliced_sum_finish", "pd_x_bgzf_inflate", "pd_stream", "pd_synchronize", "pd_profile",
-           "pd_profile_get", "pd_guard_check", "pd_guard_selftest"]
+           "pd_profile_get", "pd_guard_check", "pd_guard_selftest", "pd_runs_pileup_tiles"]
 
 
 def _ptr(a):
@@ -368,6 +368,18 @@ class Engine:
 
     def push_runs(self, runs, flags=PD_PUSH_MORE):
         self._ck(self.L.pd_push_runs(self.h, runs, int(flags)))
+
+    def runs_pileup_tiles(self, runs=None):
+        """The pile-up tiles a compact sample listed at its making, sorted (runs=None: the decode session's sample).
+        (Its signature is set here, not in load(): a tuning library from before the entry point still loads.)"""
+        f = self.L.pd_runs_pileup_tiles
+        f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        n = ctypes.c_uint32(0)
+        self._ck(f(self.h, runs, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            self._ck(f(self.h, runs, _ptr(out), n.value, ctypes.byref(n)))
+        return np.sort(out)
 
     def deflate_parse(self, text, chunks):
         """zlib's level-6 LZ77 parse of the chunks [(start, end, origin), ...] of `text` (bytes / uint8 array) on the device:

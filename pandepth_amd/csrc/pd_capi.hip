@@ -218,6 +218,8 @@ int ensure_scratch(pd_ctx *c, size_t bytes)
 // them without reading, the sweep reads them as zeros) and zero the tile sums.  No 12 GB fill.
 int do_reset(pd_ctx *c)
 {
+    // (Skipping the launch while nobody has written the four spans since the last reset — every step of the direct path on a compact sample — was built and
+    // taken out again: the launch hides behind the host's turn-around, the traced cycle and the step did not move.  profiles/r14_direct_step_ab.txt.)
     ProfScope ps(c, "reset");
     launch_reset_spans(c->stream, ResetSpans{{c->hstate, c->sums, c->chk, c->desc},
                                              {(size_t)c->n_half, (size_t)(c->n_words - c->n_cells) * 4, sizeof(CheckWords), sizeof(BatchDesc) * PD_MAXPEND}});
@@ -514,6 +516,9 @@ int pd_create(int device, int32_t n_contigs, const uint32_t *contig_len, pd_ctx 
         pd_destroy(c); return fail(nullptr, e_ == hipErrorOutOfMemory ? PD_ENOMEM : PD_EHIP, m_); } } while (0)
 
     CREATE_OK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    CREATE_OK(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
+    CREATE_OK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    CREATE_OK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     // (the copy stream of the host staging path is made by its first user: a queue costs ~15 ms, and the device-decode path
     // of the executable never stages runs from the host)
     tm_mark("streams");
@@ -577,6 +582,7 @@ int pd_destroy(pd_ctx *c)
     const uint64_t t0 = dec_now_us(); uint64_t t1 = t0, t2 = t0, t3 = t0;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     for (size_t i = 0; i < c->stage.size(); ++i) {
         if (c->stage[i].host) (void)hipHostFree(c->stage[i].host);
@@ -611,6 +617,8 @@ int pd_destroy(pd_ctx *c)
     t3 = dec_now_us();
     for (auto &w : c->lz) { std::lock_guard<std::mutex> g(w.mu); w.release(); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
+    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
+    for (hipEvent_t e : {c->ev_fork, c->ev_join}) if (e) (void)hipEventDestroy(e);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->dec_copy_st2) (void)hipStreamDestroy(c->dec_copy_st2);
     if (c->dec_warm_word) (void)hipFree(c->dec_warm_word);
@@ -733,7 +741,7 @@ void runs_finish(pd_ctx *c, pd_runs *r, const pd_iv *const *others, const size_t
     for (int k = 0; k < n_arr; ++k) launch_c8_hist(st, others[k], (uint32_t)n_others[k], tab, r->bshift, hist, words);
     launch_excl_scan_u32(st, hist, r->o1, nb + 1, bs);
     for (int k = 0; k < n_arr; ++k) launch_c8_place_other(st, others[k], (uint32_t)n_others[k], tab, r->bshift, r->o1, cursor, r->lo + r->o_base, r->hi + r->o_base);
-    launch_c8_tile_desc(st, r->view(), tab, c->d_tile_contig, (uint32_t)c->n_tiles, r->td, words + 2);       // both streams' bucket starts are final; words[2]: the pile-up tiles
+    launch_c8_tile_desc(st, r->view(), tab, c->d_tile_contig, (uint32_t)c->n_tiles, r->td, words + 2, r->heavy_tiles);       // both streams' bucket starts are final; words[2]: the pile-up tiles, listed in r->heavy_tiles
 }
 
 // caller holds c->mu and has set the device.  `sorted` must be sorted by (tid, beg) — checked; the `others` may be in any order.
@@ -761,7 +769,7 @@ int runs_make(pd_ctx *c, const pd_iv *sorted, size_t n_sorted, const pd_iv *cons
         return fail(c, PD_ENOMEM, "pd_runs_create: allocation failed");
     }
     r->hi = r->lo + n;                                            // one allocation: lo | hi, n words each
-    r->o1 = r->b1 + nbw; r->td = (TileDesc *)((uint8_t *)r->b1 + c8_desc_offset(nbw));
+    r->o1 = r->b1 + nbw; r->td = (TileDesc *)((uint8_t *)r->b1 + c8_desc_offset(nbw)); r->heavy_tiles = (uint32_t *)((uint8_t *)r->b1 + c8_heavy_offset(nbw, c->n_tiles));
     uint32_t h[3] = {0, 0, 0};
     hipStream_t st = c->stream;
     hipError_t e = hipMemsetAsync(words, 0, 16, st);
@@ -806,6 +814,22 @@ int pd_runs_destroy(pd_runs *r)
     for (auto &p : c->pend) if (p.cr == r) return fail(c, PD_ESTATE, "pd_runs_destroy: the sample is still deferred on its context (pd_reset first)");
     (void)hipStreamSynchronize(c->stream);
     runs_free(r);
+    return PD_OK;
+}
+
+int pd_runs_pileup_tiles(pd_ctx *c, const pd_runs *r, uint32_t *tiles, uint32_t cap, uint32_t *n)
+{
+    if (!c || !n || (cap && !tiles) || (r && r->ctx != c)) return PD_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!r) r = c->dec_runs;
+    if (!r) return fail(c, PD_ESTATE, "pd_runs_pileup_tiles: the context holds no compact sample of a decode session");
+    HIPOK(c, hipSetDevice(c->device));
+    *n = r->n_heavy;
+    const uint32_t m = r->n_heavy < cap ? r->n_heavy : cap;
+    if (m) {
+        HIPOK(c, hipMemcpyAsync(tiles, r->heavy_tiles, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(c, hipStreamSynchronize(c->stream));
+    }
     return PD_OK;
 }
 
@@ -913,9 +937,11 @@ int pd_window_layout(const pd_ctx *c, uint32_t w, uint64_t *win_off)
 // c->wk of a window call: [sums, 8 B per window | covers, 4 B per window, padded to 16 B | WK_WORDS bytes: the direct path's status words], so
 // that all a call hands back is one contiguous range
 constexpr size_t WK_WORDS = 64;
+static_assert(WK_WORDS == PD_STATUS_WORDS * 4, "the gather zeroes a whole set of status words");
 static int win_keep_fit(pd_ctx *c, size_t bytes)
 {
     c->wk_valid = false;
+    c->wk_words_ok = false;                              // whoever calls writes c->wk: the direct call's status words are no longer known to be zero (direct_windows)
     if (bytes <= c->wk_bytes) return PD_OK;
     if (c->wk) { HIPOK(c, hipStreamSynchronize(c->stream)); HIPOK(c, hipFree(c->wk)); c->wk = nullptr; c->wk_bytes = 0; }
     const size_t want = bytes + bytes / 8 + 4096;
@@ -994,29 +1020,45 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
     std::vector<uint64_t> wo((size_t)c->n_contigs + 1);
     pd_window_layout(c, w, wo.data());
     const uint64_t nw = wo[c->n_contigs];
-    const size_t b_sum = (size_t)nw * 8, b_cov = ((size_t)nw * 4 + 15) / 16 * 16, b_all = b_sum + b_cov + WK_WORDS;
+    const size_t b_sum = (size_t)nw * 8, b_cov = ((size_t)nw * 4 + 15) / 16 * 16, b_res = b_sum + b_cov, b_all = b_res + WK_WORDS;
     const size_t b_part = (size_t)c->n_tiles * sizeof(TilePart);
     int rc = ensure_scratch(c, b_part + 64);
     if (rc) return rc;
-    rc = win_keep_fit(c, b_all);
+    // Wide windows have TWO sets of status words behind the results, used in turn: the gather of one call zeroes the set the next call counts into, so
+    // that no call fills its own (a 64-byte fill was 2.5 us of every step and a boundary of its own in the stream).  The sets are known to be as a gather
+    // left them only while nothing else has been at c->wk since (win_keep_fit: every user calls it) and the results end where they did; any other
+    // call — the first, another width, one behind a call that failed, returned early or took another path — fills both.
+    const bool gathered = w >= PD_TILE && nw > 0;
+    const bool words_kept = gathered && c->wk_words_ok && c->wk_words_at == b_res;
+    rc = win_keep_fit(c, b_all + WK_WORDS);
     if (rc) return rc;
     const uint64_t *d_wo = nullptr;
     rc = win_offsets(c, w, wo, &d_wo);
     if (rc) return rc;
+    const unsigned turn = words_kept ? c->wk_turn : 0;
     unsigned long long *d_sum = (unsigned long long *)c->wk;
     uint32_t *d_cov = (uint32_t *)(c->wk + b_sum);
-    uint32_t *d_words = (uint32_t *)(c->wk + b_sum + b_cov);      // [n_long, fail, heavy_count, diagnostics ..., [12] tiles settled by the cover pass]; the heavy tile list: c->direct_words + 16
+    uint32_t *d_words = (uint32_t *)(c->wk + b_res + turn * WK_WORDS);      // [n_long, fail, heavy_count, diagnostics ..., [12] tiles settled by the cover pass]; the heavy tile list: c->direct_words + 16
+    uint32_t *d_words_next = (uint32_t *)(c->wk + b_res + (turn ^ 1u) * WK_WORDS);
     TilePart *d_part = (TilePart *)c->scratch;
     // Up to WK_PIN_BYTES the call's results come back in one copy through the context's page-locked buffer (three copies into the caller's pageable arrays
     // were three staged round trips: 53 us from the gather's end to the last copy's, 10 us with the one copy — profiles/r11_direct_call_ab.txt, sections 0
     // and 4); a larger result goes straight to the caller's arrays, so that no call pins memory in proportion to its output.
-    const bool pinned = b_all <= pd_ctx::WK_PIN_BYTES;
-    if (pinned && !c->wk_pin && hipHostMalloc((void **)&c->wk_pin, pd_ctx::WK_PIN_BYTES, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError(); c->wk_pin = nullptr;
-        return fail(c, PD_ENOMEM, "window statistics: page-locked allocation failed");
+    // Where a gather ends the call it stores every window to that buffer itself, through the buffer's device address, and one of its lanes copies the status
+    // words there: no copy is queued at all, and the call's sync is what makes the stores visible to the host.  c->wk still gets the windows
+    // (pd_text_append_window_rows formats from it).  Narrow windows (no gather) keep the one copy.
+    const bool pinned = b_all <= pd_ctx::WK_PIN_BYTES, pin_stores = pinned && gathered;
+    if (pinned && !c->wk_pin) {
+        if (hipHostMalloc((void **)&c->wk_pin, pd_ctx::WK_PIN_BYTES, hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer((void **)&c->wk_pin_dev, c->wk_pin, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            if (c->wk_pin) (void)hipHostFree(c->wk_pin);
+            c->wk_pin = c->wk_pin_dev = nullptr;
+            return fail(c, PD_ENOMEM, "window statistics: page-locked allocation failed");
+        }
     }
     if (w < PD_TILE) HIPOK(c, hipMemsetAsync(d_sum, 0, b_all, c->stream));   // edge windows are accumulated; the status words with them
-    else HIPOK(c, hipMemsetAsync(d_words, 0, WK_WORDS, c->stream));
+    else if (!words_kept) HIPOK(c, hipMemsetAsync(c->wk + b_res, 0, 2 * WK_WORDS, c->stream));
     const uint32_t n_stiles = (uint32_t)c->n_tiles;
     PendSet ps{};
     ps.nb = (int)c->pend.size(); ps.lmax = c->lmax;
@@ -1053,31 +1095,49 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
               const uint64_t groups = ((uint64_t)c->n_tiles + 3) / 4, g = (uint64_t)c->n_cu * 64;
               grid = (unsigned)(g < groups ? g : groups);
           }
+          // The pile-up pass runs BESIDE k_direct_c8 on the context's side stream: its list and count are the sample's (k_c8_tile_desc), it writes the
+          // TileParts of exactly the tiles k_direct_c8 skips, and neither touches what the other reads.  Fork: an event in front of k_direct_c8 (the pass
+          // must not overtake what is queued before the call: the fills above, an upload of the offsets, the sample's making); join: main waits for the
+          // pass before the section's end event, so "direct_tiles" still times both, and before the gather.  Every exit from here on is behind the join.
+          if (cr->n_heavy) HIPOK(c, hipEventRecord(c->ev_fork, c->stream));
           launch_direct_c8(c->stream, cr->view(), cr->td, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, c->direct_words + 16, d_words + 2, grid, c->direct_un, cover, c->direct_cover_min);
           // The int-window pass for the pile-up tiles k_direct_c8 lists, launched only for a sample that has some: the sample knows from its making
           // (pd_runs::n_heavy, counted by k_c8_tile_desc from the records k_direct_c8 reads), so no round trip decides.  The bench's 1e9-record sample HAS
           // pile-up tiles (12): the pass's 0.028 ms per call there (k_c8_heavy; 0.099 as the compact branch of k_direct_tiles_heavy, profiles/r12_pileup_gather_ab.txt) are its work; on the empty lists of the 1e8- and 3e8-record samples a launch took 0.004 ms, and
           // deciding by the count that comes back with the results (a second gather, copy and sync) gained a 1e9-record step 0.024 ms where this form gains
           // 0.069 (profiles/r11_direct_call_ab.txt, sections 2 and 3).
-          if (cr->n_heavy) launch_direct_c8_heavy(c->stream, cr->view(), tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, c->direct_words + 16, d_words + 2, cr->n_heavy);
+          if (cr->n_heavy) {
+              hipError_t e = hipStreamWaitEvent(c->side_stream, c->ev_fork, 0);
+              if (e == hipSuccess) {
+                  launch_direct_c8_heavy(c->side_stream, cr->view(), tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, cr->heavy_tiles, cr->n_heavy);
+                  e = hipEventRecord(c->ev_join, c->side_stream);
+                  if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_join, 0);
+                  // (the pass may be in the side stream without main waiting for it: wait here, so that whoever syncs main afterwards is behind it)
+                  if (e != hipSuccess) (void)hipStreamSynchronize(c->side_stream);
+              }
+              if (e != hipSuccess) return fail(c, PD_EHIP, std::string("direct windows: the pile-up pass's stream: ") + hipGetErrorString(e));
+          }
       }
       else launch_direct_tiles(c->stream, ps, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, d_wo,
                                d_cov, d_sum, d_words, d_words + 1, c->direct_words + 16, d_words + 2, grid, c->direct_un); }
     if (w >= PD_TILE) {
         ProfScope sc(c, "gather_windows");
         TileMap tm{c->d_tile_contig, c->d_off, c->d_len, d_wo};
-        launch_window_gather(c->stream, d_part, tm, c->n_contigs, w, nw, d_cov, d_sum);
+        GatherCall gc{gathered ? d_words_next : nullptr, d_words, nullptr, nullptr, nullptr};
+        if (pin_stores) { gc.pin_sum = (unsigned long long *)c->wk_pin_dev; gc.pin_cover = (uint32_t *)(c->wk_pin_dev + b_sum); gc.pin_words = (uint32_t *)(c->wk_pin_dev + b_res); }
+        launch_window_gather(c->stream, d_part, tm, c->n_contigs, w, nw, d_cov, d_sum, gc);
     }
     HIPOK(c, hipGetLastError());
-    uint32_t words[13] = {0};                            // [12]: heavy_count[PD_HEAVY_SETTLED]
-    if (pinned) HIPOK(c, hipMemcpyAsync(c->wk_pin, c->wk, b_all, hipMemcpyDeviceToHost, c->stream));
+    if (gathered) { c->wk_words_ok = true; c->wk_words_at = b_res; c->wk_turn = turn ^ 1u; }      // (the gather is in the stream: the other set is zero for whoever comes behind it)
+    uint32_t words[PD_STATUS_READ] = {0};                // [12]: heavy_count[PD_HEAVY_SETTLED]
+    if (pinned) { if (!pin_stores) HIPOK(c, hipMemcpyAsync(c->wk_pin, c->wk, b_all, hipMemcpyDeviceToHost, c->stream)); }
     else {
         HIPOK(c, hipMemcpyAsync(words, d_words, sizeof words, hipMemcpyDeviceToHost, c->stream));
         HIPOK(c, hipMemcpyAsync(sum, d_sum, b_sum, hipMemcpyDeviceToHost, c->stream));
         HIPOK(c, hipMemcpyAsync(cover, d_cov, (size_t)nw * 4, hipMemcpyDeviceToHost, c->stream));
     }
     HIPOK(c, hipStreamSynchronize(c->stream));
-    if (pinned) memcpy(words, c->wk_pin + b_sum + b_cov, sizeof words);
+    if (pinned) memcpy(words, c->wk_pin + b_res, sizeof words);
     if (c8 && words[2] != c->pend[0].cr->n_heavy)       // (k_direct_c8's own count of the tiles it listed: the same candidates, the same threshold)
         return fail(c, PD_ESTATE, "direct windows: the kernel listed " + std::to_string(words[2]) + " pile-up tiles, the sample was made with " + std::to_string(c->pend[0].cr->n_heavy));
     c->direct_settled = words[2 + pdk::PD_HEAVY_SETTLED];

@@ -77,6 +77,7 @@ struct pd_runs {
     uint32_t bshift = 4;                                         // 16 buckets of 512 cells per tile
     uint32_t n_long = 0;                                         // runs longer than a bucket: the direct kernels cannot use the sample
     uint32_t n_heavy = 0;                                        // pile-up tiles (more than PD_C8_HEAVY_CAND candidates): k_direct_c8 leaves them to the int-window pass
+    uint32_t *heavy_tiles = nullptr;                             // ... and their numbers, n_heavy of them in no particular order (behind td in the index allocation; k_c8_tile_desc)
     pd_iv *iv12 = nullptr;                                       // the expanded copy, made on first need
     bool own_lo = true;                                          // the planes are this object's allocation (false: they live in the decode session's arena)
     C8Sample view() const { return C8Sample{lo, hi, b1, o1, o_base, bshift}; }
@@ -87,6 +88,10 @@ static inline size_t slice_flag_bytes(uint64_t n_tiles) { return (size_t)((n_til
 struct pd_ctx {
     int device = 0;
     hipStream_t stream = nullptr, copy_stream = nullptr;
+    // the direct window call's pile-up pass runs on a stream of its own beside k_direct_c8 (not copy_stream, whose users must not be reordered): it waits
+    // for ev_fork, recorded on `stream` in front of that kernel, and `stream` waits for ev_join, recorded behind the pass, before the gather.  Both are made
+    // with the context.  Whoever frees or reuses what the pass reads (the sample, c->scratch) syncs `stream`, which is behind the join on every path.
+    hipStream_t side_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int32_t n_contigs = 0;
     std::vector<uint32_t> len;
     std::vector<uint64_t> off;                       // first cell of each slot
@@ -239,10 +244,13 @@ struct pd_ctx {
     // the window offsets of width woff_w on the device: an allocation of their own (c->scratch is every other call's too), uploaded only when a call
     // asks for another width, from woff_host — page-locked and the context's, so that no sync has to guard the upload's source (win_offsets)
     uint64_t *d_woff = nullptr, *woff_host = nullptr; uint32_t woff_w = 0;
+    // the direct call's two sets of status words behind its results in wk (direct_windows): the last call's gather left set wk_turn zeroed for the next call,
+    // wk_words_at bytes into wk; not ok: nobody knows what the sets hold, the next call fills both
+    bool wk_words_ok = false; size_t wk_words_at = 0; unsigned wk_turn = 0;
     // the direct path's results (sums | covers | status words, contiguous in wk) come back in ONE copy into this page-locked buffer of WK_PIN_BYTES,
     // made by the first call that needs it; larger results go straight to the caller's arrays
     static constexpr size_t WK_PIN_BYTES = (size_t)1 << 20;
-    unsigned char *wk_pin = nullptr;
+    unsigned char *wk_pin = nullptr, *wk_pin_dev = nullptr;      // (wk_pin_dev: its device address, what k_window_gather stores through)
     bool prof = false;
     std::vector<ProfRec> prof_pending;
     std::vector<hipEvent_t> ev_pool;

@@ -1013,7 +1013,7 @@ int compact_to_sample(pd_ctx *c, uint64_t n_long)
     pd_ctx::C8Dec &x = c->c8;
     pd_runs *r = new pd_runs;
     r->ctx = c; r->lo = x.lo(); r->hi = x.hi(); r->own_lo = true; r->n_s = (uint32_t)x.n_s; r->n_o = (uint32_t)x.n_o; r->n = r->n_s + r->n_o; r->o_base = r->n_s;      // (the later runs go right behind the sorted stream, as in pd_runs_create: what counts is how many runs there ARE, not how many were reserved)
-    r->b1 = x.b1; r->o1 = x.b1 + x.nbw; r->td = (TileDesc *)((uint8_t *)x.b1 + c8_desc_offset(x.nbw)); r->bshift = x.bshift;
+    r->b1 = x.b1; r->o1 = x.b1 + x.nbw; r->td = (TileDesc *)((uint8_t *)x.b1 + c8_desc_offset(x.nbw)); r->heavy_tiles = (uint32_t *)((uint8_t *)x.b1 + c8_heavy_offset(x.nbw, c->n_tiles)); r->bshift = x.bshift;
     const pd_iv *oth = x.oth(); const size_t no1 = (size_t)x.n_o;
     uint32_t *tmp = nullptr, *words = nullptr, *d_base = nullptr;
     const size_t nbw = x.nbw;

@@ -70,9 +70,11 @@ static inline size_t c8_plane_words(size_t n) { return (n + 3) & ~(size_t)3; }
 // b1's numbering, [olo, ohi) of o1's; a contig's first tile does not look back), the tile's first cell inside its contig and the contig's
 // length.  One 32-byte record per tile, read through a pointer of its own, so that the kernel's loop gets it with scalar loads.
 struct alignas(32) TileDesc { uint32_t slo, shi, olo, ohi, pc, clen, spare0, spare1; };
-// a compact sample's index arrays are ONE allocation: b1 | o1 (nbw words each) | pad to 32 bytes | TileDesc x n_tiles
+// a compact sample's index arrays are ONE allocation: b1 | o1 (nbw words each) | pad to 32 bytes | TileDesc x n_tiles | the pile-up tiles' numbers,
+// room for n_tiles words (pd_runs::heavy_tiles: k_c8_tile_desc lists the tiles it counts, in no particular order)
 static inline size_t c8_desc_offset(size_t nbw) { return (2 * nbw * 4 + 31) / 32 * 32; }
-static inline size_t c8_index_bytes(size_t nbw, uint64_t n_tiles) { return c8_desc_offset(nbw) + (size_t)n_tiles * sizeof(TileDesc); }
+static inline size_t c8_heavy_offset(size_t nbw, uint64_t n_tiles) { return c8_desc_offset(nbw) + (size_t)n_tiles * sizeof(TileDesc); }
+static inline size_t c8_index_bytes(size_t nbw, uint64_t n_tiles) { return c8_heavy_offset(nbw, n_tiles) + (size_t)n_tiles * 4; }
 
 struct PendBatch {            // one sorted batch of a tile pass (device pointers)
     const pd_iv *iv;
@@ -108,9 +110,10 @@ void launch_c8_fill_starts(hipStream_t st, uint32_t *b1, uint32_t n_buckets, uin
 void launch_c8_marks_to_index(hipStream_t st, const unsigned long long *marks, uint32_t n_buckets, const uint32_t *base, uint32_t *b1);
 void launch_c8_place_other(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, const uint32_t *o1, uint32_t *cursor, uint32_t *lo, uint32_t *hi /* both at o_base */);
 // (*n_heavy += the tiles with more than PD_C8_HEAVY_CAND candidates: the pile-up tiles k_direct_c8 leaves to the int-window pass — it counts the same
-// candidates from the same record, so the sample knows from its making whether that pass has anything to do)
+// candidates from the same record, so the sample knows from its making whether that pass has anything to do; heavy_tiles[the count before the
+// addition] = the tile: the pass's work list, known before k_direct_c8 has run)
 constexpr uint32_t PD_C8_HEAVY_CAND = 32000u;
-void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc, uint32_t *n_heavy);
+void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc, uint32_t *n_heavy, uint32_t *heavy_tiles);
 void launch_c8_expand(hipStream_t st, C8Sample cs, const uint32_t *tile_contig, const uint64_t *contig_off, uint32_t n_tiles, pd_iv *out);
 void launch_r8_to_iv(hipStream_t st, const uint32_t *lo, const uint32_t *hi, uint64_t n, ContigTab tab, pd_iv *out);
 void launch_copy_words(hipStream_t st, void *dst, const void *src, uint64_t n_words);      // device-to-device, 4-byte words (both pointers 4-byte aligned)
@@ -122,10 +125,11 @@ void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, cons
 constexpr int PD_HEAVY_SETTLED = 10;
 void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
                       uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min);
-// ... and the int-window pass for the pile-up tiles k_direct_c8 put on heavy_list: k_c8_heavy (it reads tab, tile_contig and the bucket starts in cs), a workgroup per
-// listed tile up to 1024.  Its own launcher: the caller launches it only for a sample that has pile-up tiles (pd_runs::n_heavy, counted by k_c8_tile_desc).
+// ... and the int-window pass for the pile-up tiles k_direct_c8 leaves: k_c8_heavy (it reads tab, tile_contig and the bucket starts in cs), a workgroup per
+// listed tile up to 1024.  Its own launcher: the caller launches it only for a sample that has pile-up tiles, with the SAMPLE's list and count
+// (pd_runs::heavy_tiles / n_heavy, made by k_c8_tile_desc) — nothing of it waits for k_direct_c8, whose TileParts are other tiles', so the two may run side by side.
 void launch_direct_c8_heavy(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w, uint32_t min_dep,
-                            TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, uint32_t n_heavy /* pd_runs::n_heavy: the grid */);
+                            TilePart *part, const uint32_t *heavy_tiles, uint32_t n_heavy);
 void launch_direct_c8_export(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, void *img, pd_exc *exc,
                              uint32_t cap, uint32_t *count, int *sums, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, uint32_t n_heavy);
 void launch_direct_export(hipStream_t st, const PendSet &ps, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles,
@@ -160,8 +164,14 @@ void launch_sweep_i4(hipStream_t st, const void *parts, uint32_t n_parts, uint64
 int launch_sweep_windows_slice(hipStream_t st, int *depth_slice, uint32_t tile_first, uint32_t tile_count, TileMap tm, uint32_t w, uint32_t min_dep,
                                uint32_t *cover, unsigned long long *sum, TilePart *part);
 void launch_window_edges(hipStream_t st, const TilePart *part, TileMap tm, uint32_t n_tiles, uint32_t w, uint32_t *cover, unsigned long long *sum);
+// What the direct window call has the gather do besides adding up the windows (all null: nothing).  One lane of the first workgroup zeroes
+// the PD_STATUS_WORDS status words the NEXT call will use (next_words: that call's kernels are behind this one in the stream) and copies this
+// call's PD_STATUS_READ words, final when the gather starts, to the host's buffer; every window's cover and sum are stored to the page-locked
+// buffer as well (pin_cover / pin_sum / pin_words: its device address).
+constexpr int PD_STATUS_WORDS = 16, PD_STATUS_READ = 13;
+struct GatherCall { uint32_t *next_words; const uint32_t *words; uint32_t *pin_words; uint32_t *pin_cover; unsigned long long *pin_sum; };
 void launch_window_gather(hipStream_t st, const TilePart *part, TileMap tm, int32_t n_contigs, uint32_t w,
-                          uint64_t n_windows, uint32_t *cover, unsigned long long *sum);
+                          uint64_t n_windows, uint32_t *cover, unsigned long long *sum, const GatherCall &gc = GatherCall{});
 void launch_reduce_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces,
                           uint32_t min_dep, int *cover, unsigned long long *sum);
 

@@ -1365,14 +1365,17 @@ __global__ __launch_bounds__(WG) void k_direct_tiles_heavy(const PendSet ps, uin
 // A tile's cost stays linear in its candidates: one workgroup walks them all.
 template <bool EXPORT, int UN, int NT>
 __global__ __launch_bounds__(NT) void k_c8_heavy(const C8Sample cs, uint32_t n_tiles, ContigTab tab, const uint32_t *tile_contig, uint32_t wrap_mask,
-                                                  const WinArgs wa, const uint32_t *heavy_list, const uint32_t *heavy_count, const DirectExport ex)
+                                                  const WinArgs wa, const uint32_t *heavy_list, const uint32_t *heavy_count, uint32_t n_list, const DirectExport ex)
 {
     constexpr uint32_t ST = TILE, C = UN * NT;
     __shared__ HeavyLds L;
     int *const win = L.win;
     const int lane = threadIdx.x & 63;
     const uint32_t *__restrict__ const p = cs.lo;
-    const uint32_t n_heavy = *heavy_count < n_tiles ? *heavy_count : n_tiles;
+    // the export form walks what k_direct_c8 listed in front of it (heavy_count: the call's); the statistics form the SAMPLE's list, n_list tiles
+    // by value (heavy_count unused), so that it depends on nothing k_direct_c8 writes
+    const uint32_t listed = EXPORT ? *heavy_count : n_list;
+    const uint32_t n_heavy = listed < n_tiles ? listed : n_tiles;
     for (uint32_t hi_ = blockIdx.x; hi_ < n_heavy; hi_ += gridDim.x) {
         const uint64_t t = heavy_list[hi_];
         const uint64_t a = t * ST;
@@ -1712,7 +1715,8 @@ __global__ __launch_bounds__(256) void k_copy_planes(uint32_t *__restrict__ dst_
 
 // The per-tile descriptors of a finished compact sample (TileDesc in pd_kernels.h): one thread per tile reads the bucket starts around the
 // tile in both streams and the tile's contig, so that k_direct_c8 finds them in one record instead of a chain of dependent loads.
-__global__ __launch_bounds__(WG) void k_c8_tile_desc(const C8Sample cs, const ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc, uint32_t *n_heavy)
+__global__ __launch_bounds__(WG) void k_c8_tile_desc(const C8Sample cs, const ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc, uint32_t *n_heavy,
+                                                     uint32_t *heavy_tiles)
 {
     const uint32_t t = blockIdx.x * WG + threadIdx.x;
     if (t >= n_tiles) return;
@@ -1726,8 +1730,9 @@ __global__ __launch_bounds__(WG) void k_c8_tile_desc(const C8Sample cs, const Co
     d.olo = cs.o1[lo]; d.ohi = cs.o1[k0 + nbk];
     d.spare0 = d.spare1 = 0;
     desc[t] = d;
-    // a pile-up tile: k_direct_c8 will count the same candidates from this record and leave the tile to the int-window pass
-    if ((d.shi - d.slo) + (d.ohi - d.olo) > PD_C8_HEAVY_CAND) atomicAdd(n_heavy, 1u);
+    // a pile-up tile: k_direct_c8 will count the same candidates from this record and leave the tile to the int-window pass, whose list this is
+    // (at most one entry per tile: the slot is below n_tiles, the list's room)
+    if ((d.shi - d.slo) + (d.ohi - d.olo) > PD_C8_HEAVY_CAND) heavy_tiles[atomicAdd(n_heavy, 1u)] = t;
 }
 
 // a sorted stream of compact runs whose sample turned out not to be usable as one (the file's order does not hold after all): back to
@@ -2514,9 +2519,13 @@ __global__ __launch_bounds__(WG) void k_window_edges(const TilePart *part, const
 template <int WAVES>
 __global__ __launch_bounds__(WG) void k_window_gather(const TilePart *__restrict__ part, const TileMap tmap, int32_t n_contigs,
                                                       uint32_t w, uint64_t n_windows, uint32_t *cover,
-                                                      unsigned long long *sum)
+                                                      unsigned long long *sum, const GatherCall gc)
 {
     static_assert(WAVES == 1 || WAVES == 4, "a wave or the workgroup per window");
+    if (blockIdx.x == 0 && threadIdx.x == 0) {                   // (GatherCall in pd_kernels.h; the pointers are workgroup-uniform)
+        if (gc.next_words) for (int i = 0; i < PD_STATUS_WORDS; ++i) gc.next_words[i] = 0u;
+        if (gc.pin_words) for (int i = 0; i < PD_STATUS_READ; ++i) gc.pin_words[i] = gc.words[i];
+    }
     constexpr int GU = 5;                                         // (256 lanes x 5 take a 10 Mb bin's 1 222 tiles in one trip, 64 x 5 any window of the wave form)
     constexpr uint32_t NL = WAVES * 64;                          // lanes per window
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -2554,14 +2563,21 @@ __global__ __launch_bounds__(WG) void k_window_gather(const TilePart *__restrict
 #pragma unroll
     for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
     if (WAVES == 1) {
-        if (lane == 0) { cover[g] = c; sum[g] = s; }
+        if (lane == 0) {
+            cover[g] = c; sum[g] = s;
+            if (gc.pin_cover) { gc.pin_cover[g] = c; gc.pin_sum[g] = s; }
+        }
         return;
     }
     __shared__ uint32_t red_c[4];
     __shared__ unsigned long long red_s[4];
     if (lane == 0) { red_c[wv] = c; red_s[wv] = s; }
     __syncthreads();
-    if (threadIdx.x == 0) { cover[g] = red_c[0] + red_c[1] + red_c[2] + red_c[3]; sum[g] = red_s[0] + red_s[1] + red_s[2] + red_s[3]; }
+    if (threadIdx.x == 0) {
+        c = red_c[0] + red_c[1] + red_c[2] + red_c[3]; s = red_s[0] + red_s[1] + red_s[2] + red_s[3];
+        cover[g] = c; sum[g] = s;
+        if (gc.pin_cover) { gc.pin_cover[g] = c; gc.pin_sum[g] = s; }
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3331,14 +3347,14 @@ void launch_sweep_i4(hipStream_t st, const void *parts, uint32_t n_parts, uint64
 }
 
 void launch_window_gather(hipStream_t st, const TilePart *part, TileMap tm, int32_t n_contigs, uint32_t w,
-                          uint64_t n_windows, uint32_t *cover, unsigned long long *sum)
+                          uint64_t n_windows, uint32_t *cover, unsigned long long *sum, const GatherCall &gc)
 {
     if (!n_windows) return;
     // a workgroup per window once a window's tiles give each of its 256 lanes one (w >= 256 tiles), a wave per window below that
     if (w / (uint32_t)TILE >= (uint32_t)WG)
-        hipLaunchKernelGGL(k_window_gather<4>, dim3((unsigned)n_windows), dim3(WG), 0, st, part, tm, n_contigs, w, n_windows, cover, sum);
+        hipLaunchKernelGGL(k_window_gather<4>, dim3((unsigned)n_windows), dim3(WG), 0, st, part, tm, n_contigs, w, n_windows, cover, sum, gc);
     else
-        hipLaunchKernelGGL(k_window_gather<1>, dim3((unsigned)((n_windows + 3) / 4)), dim3(WG), 0, st, part, tm, n_contigs, w, n_windows, cover, sum);
+        hipLaunchKernelGGL(k_window_gather<1>, dim3((unsigned)((n_windows + 3) / 4)), dim3(WG), 0, st, part, tm, n_contigs, w, n_windows, cover, sum, gc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3494,9 +3510,9 @@ void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, cons
     hipLaunchKernelGGL(k_copy_planes, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, st, dst_lo, dst_hi, src_lo, src_hi, n);
 }
 
-void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc, uint32_t *n_heavy)
+void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc, uint32_t *n_heavy, uint32_t *heavy_tiles)
 {
-    if (n_tiles) hipLaunchKernelGGL(k_c8_tile_desc, dim3((n_tiles + WG - 1) / WG), dim3(WG), 0, st, cs, tab, tile_contig, n_tiles, desc, n_heavy);
+    if (n_tiles) hipLaunchKernelGGL(k_c8_tile_desc, dim3((n_tiles + WG - 1) / WG), dim3(WG), 0, st, cs, tab, tile_contig, n_tiles, desc, n_heavy, heavy_tiles);
 }
 
 void launch_r8_to_iv(hipStream_t st, const uint32_t *lo, const uint32_t *hi, uint64_t n, ContigTab tab, pd_iv *out)
@@ -3574,14 +3590,14 @@ void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_
 constexpr int HEAVY_UN = 8, HEAVY_NT = 1024;
 
 void launch_direct_c8_heavy(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w, uint32_t min_dep,
-                            TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, uint32_t n_heavy)
+                            TilePart *part, const uint32_t *heavy_tiles, uint32_t n_heavy)
 {
     if (!n_heavy) return;
     WinArgs wa; wa.w = w; wa.min_dep = min_dep; wa.inv_w = 1.0f / (float)w; wa.cover = nullptr; wa.sum = nullptr; wa.part = part;
     // a workgroup per listed tile (the sample's own count), so that no list is walked by a fixed few workgroups in turns
     const unsigned grid = n_heavy < 1024u ? n_heavy : 1024u;
-    hipLaunchKernelGGL((k_c8_heavy<false, HEAVY_UN, HEAVY_NT>), dim3(grid), dim3(HEAVY_NT), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, wa, (const uint32_t *)heavy_list,
-                       (const uint32_t *)heavy_count, DirectExport{});
+    hipLaunchKernelGGL((k_c8_heavy<false, HEAVY_UN, HEAVY_NT>), dim3(grid), dim3(HEAVY_NT), 0, st, cs, n_tiles, tab, tile_contig, wrap_mask, wa, heavy_tiles,
+                       (const uint32_t *)nullptr, n_heavy, DirectExport{});
 }
 
 void launch_direct_c8_export(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, void *img, pd_exc *exc,
@@ -3594,7 +3610,7 @@ void launch_direct_c8_export(hipStream_t st, C8Sample cs, const TileDesc *desc, 
     // (launched for a sample without pile-up tiles too, one workgroup then: this call has no check of the list's length behind it)
     const unsigned grid = n_heavy < 1024u ? (n_heavy ? n_heavy : 1u) : 1024u;
     hipLaunchKernelGGL((k_c8_heavy<true, HEAVY_UN, HEAVY_NT>), dim3(grid), dim3(HEAVY_NT), 0, st, cs, n_tiles, tab, tile_contig, 0xFFFFFFFFu, wa, (const uint32_t *)heavy_list,
-                       (const uint32_t *)heavy_count, de);
+                       (const uint32_t *)heavy_count, 0u, de);
 }
 
 void launch_direct_export(hipStream_t st, const PendSet &ps, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles,
