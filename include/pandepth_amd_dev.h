@@ -16,7 +16,8 @@ extern "C" {
  * tile kernels), "scatter_tile" (4096 | 8192), "accumulate_packed" (pd_accumulate_from's transport, default 1), "direct_un"
  * (which compiled variant of the direct kernels runs), "direct_cover" (default 1: the default variant of the compact sample's direct
  * kernel settles the tiles its runs cover without a window; 0: every tile through the window), "direct_cover_min" (default 2048: tiles
- * with fewer candidates are not tried), "decode_crc" (0: the device decoder skips the members' CRC-32 — kernel
+ * with fewer candidates are not tried), "cover_narrow" (default 1: that pass sweeps the sorted stream's 2-byte plane where no sorted run is longer
+ * than 255 cells; 0: the 4-byte words as before), "decode_crc" (0: the device decoder skips the members' CRC-32 — kernel
  * timing only), "decode_near_span" (split of the decoder's later-run stream), "decode_deletions" (0 | 1: this one DOES change results — pd_push_bgzf_units,
  * whose signature is fixed, opens its session with PD_DECODE_DELETIONS while it is 1; sessions opened with pd_decode_begin say so in their own flags and ignore it), "inflate_waves" (one-wave inflate workgroups per CU and
  * launch, 1..23: what the kernel's 7 KB of LDS a wave allow; default 20), "lz_group" (consecutive chunks per workgroup of pd_deflate_parse's LDS parse, 0..16; 0: every chunk reads its

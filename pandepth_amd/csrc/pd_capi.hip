@@ -676,6 +676,7 @@ int pd_set_param(pd_ctx *c, const char *name, uint64_t value)
     if (!strcmp(name, "accumulate_packed")) { c->accumulate_packed = value != 0; return PD_OK; }
     if (!strcmp(name, "direct_un")) { c->direct_un = (int)value; return PD_OK; }
     if (!strcmp(name, "direct_cover")) { c->direct_cover = value != 0; return PD_OK; }
+    if (!strcmp(name, "cover_narrow")) { c->cover_narrow = value != 0; return PD_OK; }
     if (!strcmp(name, "direct_cover_min")) { c->direct_cover_min = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "direct_sample")) { if (value < 1 || value > 65536) return fail(c, PD_EINVAL, "direct_sample must be in [1, 65536]"); c->direct_sample = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "decode_crc")) { c->dec_crc = value != 0; return PD_OK; }
@@ -726,7 +727,9 @@ uint32_t runs_bshift(const pd_ctx *c)
 // first run of every bucket has left its index in r->b1 (everything else 0xFFFFFFFF); `others` are the remaining runs as 12-byte arrays, any
 // order.  Fills the bucket starts of the sorted stream (a suffix minimum over the marks), counts the other runs per bucket, places them
 // behind o_base, and writes the per-tile descriptors (r->td) from the finished bucket starts.  words (device, 2 x uint32, already holding
-// the sorted stream's flags): [0] bad contig id, [1] runs longer than a bucket.
+// the sorted stream's flags): [0] bad contig id, [1] runs longer than a bucket, [2] pile-up tiles (k_c8_tile_desc), [3] sorted runs longer than 255 cells —
+// left there by whoever wrote the sorted stream (k_c8_from_sorted; a decode session's placing copies, through compact_to_sample) and read with the
+// others by the caller into pd_runs::n_wide_sorted.
 // Only enqueues on c->stream; `tmp` must hold 2 x (nb + 2) + (nb / 1024 + 4) words.
 void runs_finish(pd_ctx *c, pd_runs *r, const pd_iv *const *others, const size_t *n_others, int n_arr, uint32_t *tmp, uint32_t *words)
 {
@@ -761,23 +764,24 @@ int runs_make(pd_ctx *c, const pd_iv *sorted, size_t n_sorted, const pd_iv *cons
     const uint32_t nb = (uint32_t)nb64;
     const size_t nbw = (size_t)nb + 2;
     uint32_t *tmp = nullptr, *words = nullptr;
-    if (hipMalloc(&r->lo, n * sizeof(Run8) + 64) != hipSuccess || hipMalloc(&r->b1, c8_index_bytes(nbw, c->n_tiles)) != hipSuccess ||
+    if (hipMalloc(&r->lo, c8_planes_bytes(n, n_sorted)) != hipSuccess || hipMalloc(&r->b1, c8_index_bytes(nbw, c->n_tiles)) != hipSuccess ||
         hipMalloc(&tmp, (2 * nbw + nb / 1024 + 8) * 4) != hipSuccess || hipMalloc(&words, 16) != hipSuccess) {
         (void)hipGetLastError();
         for (void *q : {(void *)tmp, (void *)words}) if (q) (void)hipFree(q);
         runs_free(r);
         return fail(c, PD_ENOMEM, "pd_runs_create: allocation failed");
     }
-    r->hi = r->lo + n;                                            // one allocation: lo | hi, n words each
+    r->hi = r->lo + n;                                            // one allocation: lo | hi, n words each, then the sorted stream's narrow plane
+    r->nar = (uint16_t *)((uint8_t *)r->lo + c8_nar_offset(n));
     r->o1 = r->b1 + nbw; r->td = (TileDesc *)((uint8_t *)r->b1 + c8_desc_offset(nbw)); r->heavy_tiles = (uint32_t *)((uint8_t *)r->b1 + c8_heavy_offset(nbw, c->n_tiles));
-    uint32_t h[3] = {0, 0, 0};
+    uint32_t h[4] = {0, 0, 0, 0};
     hipStream_t st = c->stream;
     hipError_t e = hipMemsetAsync(words, 0, 16, st);
     if (e == hipSuccess) e = hipMemsetAsync(r->b1, 0xFF, nbw * 4, st);
     if (e == hipSuccess) {
         // (this first pass is what the GPU decoder's emit kernel does as it writes a file's runs: 8-byte runs in file order as two planes, the buckets'
         // first runs marked)
-        { ProfScope ps(c, "compact_runs"); launch_c8_from_sorted(st, sorted, (uint32_t)n_sorted, tab_of(c), r->bshift, r->lo, r->hi, r->b1, words); }
+        { ProfScope ps(c, "compact_runs"); launch_c8_from_sorted(st, sorted, (uint32_t)n_sorted, tab_of(c), r->bshift, r->lo, r->hi, r->nar, r->b1, words); }
         runs_finish(c, r, others, n_others, n_arr, tmp, words);
         e = hipGetLastError();
     }
@@ -788,6 +792,7 @@ int runs_make(pd_ctx *c, const pd_iv *sorted, size_t n_sorted, const pd_iv *cons
     if (h[0]) { runs_free(r); return fail(c, PD_EINVAL, "pd_runs_create: the first batch is not sorted by (tid, beg), or a contig id is out of range"); }
     r->n_long = h[1];
     r->n_heavy = h[2];
+    r->n_wide_sorted = h[3];
     *out = r;
     return PD_OK;
 }
@@ -1088,6 +1093,8 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
       if (c8) {
           const pd_runs *cr = c->pend[0].cr;
           const bool cover = c->direct_cover && all >= (uint64_t)c->direct_cover_min * c->n_tiles;   // a thin sample: the form without the pass (launch_direct_c8)
+          // ... and the pass sweeps the sorted stream's narrow plane, half the bytes, when every sorted run fits a half-word (counted when the sample was made)
+          const bool narrow = cover && c->cover_narrow && cr->nar && cr->n_wide_sorted == 0;
           // The cover form walks GROUPS of four tiles and a settled group costs a workgroup little more than its start, so its default grid is 64 workgroups
           // per CU, not one per 256 runs: on the bench sample (91 623 groups; ms per launch with the pile-up pass) 65 536 workgroups 0.985, one per group
           // 1.352, 32 768: 0.798, 16 384: 0.806, 7 168: 0.797 (profiles/r13_cover_wave_ab.txt).  "grid_tiles" still overrides it.
@@ -1100,7 +1107,7 @@ static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask
           // must not overtake what is queued before the call: the fills above, an upload of the offsets, the sample's making); join: main waits for the
           // pass before the section's end event, so "direct_tiles" still times both, and before the gather.  Every exit from here on is behind the join.
           if (cr->n_heavy) HIPOK(c, hipEventRecord(c->ev_fork, c->stream));
-          launch_direct_c8(c->stream, cr->view(), cr->td, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, c->direct_words + 16, d_words + 2, grid, c->direct_un, cover, c->direct_cover_min);
+          c->direct_narrow = launch_direct_c8(c->stream, cr->view(), cr->td, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, c->direct_words + 16, d_words + 2, grid, c->direct_un, cover, c->direct_cover_min, narrow) ? 1 : 0;
           // The int-window pass for the pile-up tiles k_direct_c8 lists, launched only for a sample that has some: the sample knows from its making
           // (pd_runs::n_heavy, counted by k_c8_tile_desc from the records k_direct_c8 reads), so no round trip decides.  The bench's 1e9-record sample HAS
           // pile-up tiles (12): the pass's 0.028 ms per call there (k_c8_heavy; 0.099 as the compact branch of k_direct_tiles_heavy, profiles/r12_pileup_gather_ab.txt) are its work; on the empty lists of the 1e8- and 3e8-record samples a launch took 0.004 ms, and
@@ -1161,7 +1168,7 @@ int pd_scan_reduce_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, unsigned wra
     std::lock_guard<std::mutex> lk(c->mu);
     if (int rs = need_state(c, 0, "pd_scan_reduce_windows")) return rs;
     HIPOK(c, hipSetDevice(c->device));
-    c->direct_settled = 0; c->direct_pileup = 0;
+    c->direct_settled = 0; c->direct_pileup = 0; c->direct_narrow = 0;
     if (c->direct_windows && c->pristine && !c->pend.empty() && w >= 64 && c->stile == PD_TILE) {
         const uint32_t m = (wrap_bits == 0 || wrap_bits == 32) ? 0xFFFFFFFFu : ((1u << wrap_bits) - 1u);
         bool done = false;
@@ -2573,6 +2580,7 @@ int pd_profile_get(pd_ctx *c, const char *name, double *ms, uint64_t *launches)
             {"decode_end_pending", pd_ctx::DN_END_PEND}, {"decode_guess_units", pd_ctx::DN_GUESS}};
         uint64_t v = 0; bool hit = false;
         for (auto &d : dn) if (!strcmp(name, d.name)) { v = c->dec_n[d.k].load(); hit = true; }
+        if (!strcmp(name, "direct_cover_narrow")) { v = c->direct_narrow; hit = true; }       // 1: the last direct window call's k_direct_c8 swept the narrow plane
         if (!strcmp(name, "direct_cover_settled")) { v = c->direct_settled; hit = true; }     // tiles of the last direct window call that k_direct_c8 settled without a window
         if (!strcmp(name, "direct_pileup_tiles")) { v = c->direct_pileup; hit = true; }       // ... and the tiles it left to the pile-up pass (k_c8_heavy)
         if (!strcmp(name, "decode_chain_device")) { v = c->dec_n_fast.load(); hit = true; }

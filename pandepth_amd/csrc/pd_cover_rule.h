@@ -89,4 +89,50 @@ PD_COVER_HD inline Tile combine(const Seg *sorted, int n_sorted, const Seg *othe
     return t;
 }
 
+// ---- the NARROW plane of the sorted stream: two bytes per run (C8Sample::nar) ----
+// nar[i] = (begin & 0xFF) | (min(len, 255) << 8), begin and len as in the lo word.  The narrow form of the cover pass sweeps a tile's sorted candidates
+// from these half-words alone: it knows the first candidate's begin (one lo word) and REBUILDS every other one by adding the differences of
+// consecutive low bytes, each taken modulo 256.  Lengths are exact for a sample without a sorted run longer than 255 cells (the producers count
+// those: pd_runs::n_wide_sorted, and only a sample with none is swept this way).
+// The stream is sorted, so every true difference is >= 0 and a rebuilt difference is the true one minus a multiple of 256: never larger.  Hence
+//   * every rebuilt begin is <= its true begin, and equal while no difference has reached 256;
+//   * the rebuilt begin of the LAST candidate equals its true begin (a second lo word) if and only if no difference reached 256: the END CHECK.
+// A too-small begin can by itself only close a true gap, never open one (behind the first hidden difference every begin and end is shifted down by the
+// same amount, those in front are exact), so a gap the narrow sweep meets is a true gap and needs no check; a tile is settled only when the sweep
+// met no gap AND the end check passed, and then every begin, end and clipped length it used was the true one.  A difference of exactly 256
+// rebuilds as 0: the case the check exists for.  The span of a tile's candidates is below a tile plus a bucket, so the comparison is exact in ints.
+PD_COVER_HD inline uint32_t nar_pack(uint32_t begin, uint32_t len) { return (begin & 0xFFu) | ((len < 255u ? len : 255u) << 8); }
+PD_COVER_HD inline uint32_t nar_of_lo(uint32_t lo_word) { return nar_pack(lo_word & 0xFFFFu, lo_word >> 16); }
+PD_COVER_HD inline bool nar_is_wide(uint32_t len) { return len > 255u; }          // a run the half-word cannot hold
+// the rebuild step: how far the run of half-word h begins behind its predecessor, whose half-word (or low byte) is prev
+PD_COVER_HD inline int nar_step(uint32_t h, uint32_t prev) { return (int)((h - prev) & 255u); }
+PD_COVER_HD inline int nar_len(uint32_t h) { return (int)((h >> 8) & 255u); }
+// what stands in a place of a partial chunk that holds no run of the lane's own: the predecessor's low byte with length 0 (a step of 0, an empty run)
+PD_COVER_HD inline uint32_t nar_neutral(uint32_t prev) { return prev & 255u; }
+// the end check: rebuilt_last is the rebuilt tile-relative begin of the tile's last sorted candidate, lo_last that candidate's lo word
+PD_COVER_HD inline bool nar_end_ok(int rebuilt_last, uint32_t lo_last, uint32_t p0) { return rebuilt_last == run_begin(lo_last, p0); }
+
+// One sweep of n sorted candidates from their half-words, as the kernel's narrow form does it (ONE segment); lo_first and lo_last are the lo
+// words of the first and the last of them.  begins (may be null) receives the rebuilt begins.  *end_ok: the end check.
+PD_COVER_HD inline Seg seg_sweep_nar(const uint16_t *nar, uint32_t n, uint32_t lo_first, uint32_t lo_last, uint32_t p0, int tile, bool *end_ok, int *begins)
+{
+    Seg s = seg_none();
+    *end_ok = true;
+    if (!n) return s;
+    int b = run_begin(lo_first, p0);
+    uint32_t prev = lo_first;
+    for (uint32_t i = 0; i < n; ++i) {
+        b += nar_step(nar[i], prev); prev = nar[i];
+        const int e = b + nar_len(nar[i]);
+        if (begins) begins[i] = b;
+        if (s.first == NONE) { s.first = b; s.maxend = b; }
+        if (b > s.maxend && b > 0) s.gap = 1;
+        if (e > s.maxend) s.maxend = e;
+        s.sum += run_clipped(b, e, tile);
+        s.carry += (b < 0 && e >= 0) ? 1u : 0u;
+    }
+    *end_ok = nar_end_ok(b, lo_last, p0);
+    return s;
+}
+
 } // namespace pdcover

@@ -72,6 +72,8 @@ struct pd_runs {
     pd_ctx *ctx = nullptr;
     uint32_t *lo = nullptr, *hi = nullptr;                       // the runs' two planes (C8Sample), one allocation with lo first; each [sorted stream: n_s runs, file order | ... | other runs by bucket at o_base]
     uint32_t n_s = 0, n_o = 0, o_base = 0, n = 0;                // n = n_s + n_o
+    uint16_t *nar = nullptr;                                     // the sorted stream's narrow plane, n_s half-words behind lo | hi in the same allocation (C8Sample::nar)
+    uint32_t n_wide_sorted = 0;                                  // sorted runs longer than 255 cells, which a half-word cannot hold: with any, k_direct_c8's narrow form is not launched
     uint32_t *b1 = nullptr, *o1 = nullptr;                       // (n_tiles << bshift) + 1 bucket starts per stream (one allocation: b1 | o1 | td, c8_index_bytes)
     TileDesc *td = nullptr;                                      // per tile: what k_direct_c8 reads before the tile's runs (made by runs_finish)
     uint32_t bshift = 4;                                         // 16 buckets of 512 cells per tile
@@ -80,7 +82,7 @@ struct pd_runs {
     uint32_t *heavy_tiles = nullptr;                             // ... and their numbers, n_heavy of them in no particular order (behind td in the index allocation; k_c8_tile_desc)
     pd_iv *iv12 = nullptr;                                       // the expanded copy, made on first need
     bool own_lo = true;                                          // the planes are this object's allocation (false: they live in the decode session's arena)
-    C8Sample view() const { return C8Sample{lo, hi, b1, o1, o_base, bshift}; }
+    C8Sample view() const { return C8Sample{lo, hi, b1, o1, o_base, bshift, nar}; }
 };
 
 static inline size_t slice_flag_bytes(uint64_t n_tiles) { return (size_t)((n_tiles + 16 + 15) / 16 * 16); }
@@ -137,6 +139,8 @@ struct pd_ctx {
     int direct_un = 0;                                           // 0 = the default form of the wide direct kernel (launch_direct_tiles)
     bool direct_cover = true;                                    // k_direct_c8's default form settles covered tiles from the runs (false: the window path for every tile)
     uint32_t direct_cover_min = 2048;                            // ... of tiles with at least this many candidates (launch_direct_c8)
+    bool cover_narrow = true;                                    // ... from the sorted stream's narrow plane where the sample allows it ("cover_narrow"; pd_runs::n_wide_sorted == 0)
+    uint64_t direct_narrow = 0;                                  // 1: the last direct_windows call launched the narrow form ("direct_cover_narrow")
     uint64_t direct_settled = 0;                                 // tiles the cover pass settled in the last direct_windows call
     uint64_t direct_pileup = 0;                                  // pile-up tiles k_direct_c8 listed in the last direct_windows call (the int-window pass did them)
     bool all_valid_host = false;
@@ -193,10 +197,11 @@ struct pd_ctx {
     // the end nothing is concatenated or converted: only the marks become indices and the later runs are sorted by bucket.
     struct C8Dec {
         bool on = false;
-        uint8_t *base = nullptr; size_t bytes = 0;               // ONE allocation: [lo plane x (cap_s + cap_o) | hi plane x (cap_s + cap_o) | pd_iv x cap_o]
+        uint8_t *base = nullptr; size_t bytes = 0;               // ONE allocation: [lo plane x (cap_s + cap_o) | hi plane x (cap_s + cap_o) | pd_iv x cap_o | 64 bytes, to a 16-byte boundary | narrow plane: half-word x cap_s | slack]
         size_t cap_s = 0, cap_o = 0;
         uint32_t *b1 = nullptr; size_t nbw = 0;                  // bucket starts: b1 | o1, nbw words each, then the sample's tile descriptors (c8_index_bytes)
-        unsigned long long *marks = nullptr;                     // per bucket: min (batch << 32 | index in the batch) of a run that begins there
+        unsigned long long *marks = nullptr;                     // per bucket: min (batch << 32 | index in the batch) of a run that begins there; behind the nbw marks one more
+                                                                 // 8 bytes: a word that counts the first runs longer than 255 cells as they are placed (wide())
         uint32_t bshift = 4;
         uint64_t n_s = 0, n_o = 0, turn = 0, n_batches = 0;
         struct Batch { bool counted = false; uint64_t nf = 0, no = 0; uint32_t *seg_s = nullptr; pd_iv *seg_o = nullptr; hipEvent_t ev = nullptr; };   // seg_s: the nf first runs' lo plane, their hi plane c8_plane_words(nf) behind it
@@ -208,6 +213,10 @@ struct pd_ctx {
         uint32_t *lo() const { return (uint32_t *)base; }
         uint32_t *hi() const { return (uint32_t *)base + cap_s + cap_o; }
         pd_iv *oth() const { return (pd_iv *)(base + (cap_s + cap_o) * sizeof(Run8)); }
+        static size_t nar_off(size_t cs, size_t co) { return ((cs + co) * sizeof(Run8) + co * sizeof(pd_iv) + 64 + 15) & ~(size_t)15; }
+        static size_t total_bytes(size_t cs, size_t co) { return nar_off(cs, co) + cs * 2 + 64 + 256; }
+        uint16_t *nar() const { return (uint16_t *)(base + nar_off(cap_s, cap_o)); }
+        uint32_t *wide() const { return (uint32_t *)(marks + nbw); }
     } c8;
     uint64_t *ovf = nullptr; uint32_t ovf_cap = 0;    // ends of runs longer than lmax (grown on demand)
     std::vector<Stage> stage;                        // grows on demand, up to N_STAGE

@@ -109,7 +109,7 @@ int c8_reserve(pd_ctx *c, uint64_t n_s, uint64_t n_o, bool exact = false)
     if (n_s <= x.cap_s && n_o <= x.cap_o && x.base) return PD_OK;
     const size_t slack = c->dec_c8_reserve ? 0 : (size_t)1 << 16;
     const size_t ns = std::max<size_t>((size_t)n_s + (exact ? 0 : (size_t)n_s / 2) + slack, x.cap_s), no = std::max<size_t>((size_t)n_o + (exact ? 0 : (size_t)n_o / 2) + slack, x.cap_o);
-    const size_t bytes = (ns + no) * sizeof(Run8) + no * sizeof(pd_iv) + 256;
+    const size_t bytes = pd_ctx::C8Dec::total_bytes(ns, no);
     uint8_t *nb = nullptr;
     if (x.base) (void)hipDeviceSynchronize();
     if (hipMalloc(&nb, bytes) != hipSuccess) { (void)hipGetLastError(); return PD_ENOMEM; }
@@ -119,6 +119,7 @@ int c8_reserve(pd_ctx *c, uint64_t n_s, uint64_t n_o, bool exact = false)
         if (x.n_s) e = hipMemcpy(nb, x.lo(), (size_t)x.n_s * 4, hipMemcpyDeviceToDevice);
         if (e == hipSuccess && x.n_s) e = hipMemcpy(nb + (ns + no) * 4, x.hi(), (size_t)x.n_s * 4, hipMemcpyDeviceToDevice);
         if (e == hipSuccess && x.n_o) e = hipMemcpy(nb + (ns + no) * sizeof(Run8), x.oth(), (size_t)x.n_o * sizeof(pd_iv), hipMemcpyDeviceToDevice);
+        if (e == hipSuccess && x.n_s) e = hipMemcpy(nb + pd_ctx::C8Dec::nar_off(ns, no), x.nar(), (size_t)x.n_s * 2, hipMemcpyDeviceToDevice);
         (void)hipFree(x.base);
         if (e != hipSuccess) { (void)hipFree(nb); x.base = nullptr; return PD_EHIP; }
     }
@@ -151,7 +152,9 @@ void c8_counted(pd_ctx *c, uint64_t order, uint64_t nf, uint64_t no, uint32_t *s
             }
             if (c8_reserve(c, x.n_s + b.nf, x.n_o + b.no) != PD_OK) e = hipErrorOutOfMemory;
             if (e == hipSuccess && b.ev) e = hipStreamWaitEvent(x.compose, b.ev, 0);
-            if (e == hipSuccess && b.nf) launch_copy_planes(x.compose, x.lo() + x.n_s, x.hi() + x.n_s, b.seg_s, b.seg_s + c8_plane_words((size_t)b.nf), b.nf);
+            // (EVERY first run of the session reaches the sample through this copy and no other way: it is where the narrow plane is written, from the
+            // lo words on their way, and where the runs that plane cannot hold are counted)
+            if (e == hipSuccess && b.nf) launch_copy_planes(x.compose, x.lo() + x.n_s, x.hi() + x.n_s, b.seg_s, b.seg_s + c8_plane_words((size_t)b.nf), b.nf, x.nar() + x.n_s, x.wide());
             if (e == hipSuccess && b.no) launch_copy_words(x.compose, x.oth() + x.n_o, b.seg_o, b.no * (sizeof(pd_iv) / 4));
             if (e == hipSuccess) e = hipGetLastError();
             if (e != hipSuccess && x.err.empty()) x.err = std::string("placing a batch's runs: ") + hipGetErrorString(e);
@@ -260,8 +263,9 @@ int begin_compact(pd_ctx *c, const pd_decode_cfg *cfg, uint64_t *tb)
     x.nbw = (size_t)nb64 + 2;
     if (x.b1) { (void)hipFree(x.b1); x.b1 = nullptr; }
     if (x.marks) { (void)hipFree(x.marks); x.marks = nullptr; }
-    if (hipMalloc(&x.b1, c8_index_bytes(x.nbw, c->n_tiles)) != hipSuccess || hipMalloc(&x.marks, x.nbw * 8) != hipSuccess) { (void)hipGetLastError(); return fail(c, PD_ENOMEM, "pd_decode_begin: allocation failed"); }
+    if (hipMalloc(&x.b1, c8_index_bytes(x.nbw, c->n_tiles)) != hipSuccess || hipMalloc(&x.marks, x.nbw * 8 + 8) != hipSuccess) { (void)hipGetLastError(); return fail(c, PD_ENOMEM, "pd_decode_begin: allocation failed"); }
     HIPOK(c, hipMemsetAsync(x.marks, 0xFF, x.nbw * 8, c->stream));
+    HIPOK(c, hipMemsetAsync(x.wide(), 0, 8, c->stream));
     HIPOK(c, hipStreamSynchronize(c->stream));                // (the batches' kernels run on other streams)
     if (!x.compose) HIPOK(c, hipStreamCreateWithFlags(&x.compose, hipStreamNonBlocking));
     tb[2] = tb[3] = dec_now_us();
@@ -1012,7 +1016,7 @@ int compact_to_sample(pd_ctx *c, uint64_t n_long)
 {
     pd_ctx::C8Dec &x = c->c8;
     pd_runs *r = new pd_runs;
-    r->ctx = c; r->lo = x.lo(); r->hi = x.hi(); r->own_lo = true; r->n_s = (uint32_t)x.n_s; r->n_o = (uint32_t)x.n_o; r->n = r->n_s + r->n_o; r->o_base = r->n_s;      // (the later runs go right behind the sorted stream, as in pd_runs_create: what counts is how many runs there ARE, not how many were reserved)
+    r->ctx = c; r->lo = x.lo(); r->hi = x.hi(); r->nar = x.nar(); r->own_lo = true; r->n_s = (uint32_t)x.n_s; r->n_o = (uint32_t)x.n_o; r->n = r->n_s + r->n_o; r->o_base = r->n_s;      // (the later runs go right behind the sorted stream, as in pd_runs_create: what counts is how many runs there ARE, not how many were reserved)
     r->b1 = x.b1; r->o1 = x.b1 + x.nbw; r->td = (TileDesc *)((uint8_t *)x.b1 + c8_desc_offset(x.nbw)); r->heavy_tiles = (uint32_t *)((uint8_t *)x.b1 + c8_heavy_offset(x.nbw, c->n_tiles)); r->bshift = x.bshift;
     const pd_iv *oth = x.oth(); const size_t no1 = (size_t)x.n_o;
     uint32_t *tmp = nullptr, *words = nullptr, *d_base = nullptr;
@@ -1025,8 +1029,9 @@ int compact_to_sample(pd_ctx *c, uint64_t n_long)
         (void)hipGetLastError(); for (void *q : {(void *)tmp, (void *)words, (void *)d_base, (void *)marks}) if (q) (void)hipFree(q); runs_free(r);
         return fail(c, PD_ENOMEM, "pd_decode_end: allocation failed");
     }
-    uint32_t h[3] = {0, 0, 0};
+    uint32_t h[4] = {0, 0, 0, 0};
     hipError_t e = hipMemsetAsync(words, 0, 16, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(words + 3, marks + nbw, 4, hipMemcpyDeviceToDevice, c->stream);      // the placing copies' count of first runs longer than 255 cells (C8Dec::wide; the compose stream has been waited for)
     if (e == hipSuccess) e = hipMemcpyAsync(d_base, base_s.data(), base_s.size() * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         // the marks (batch, index in the batch) of the buckets' first runs become indices into the sorted stream
@@ -1041,6 +1046,7 @@ int compact_to_sample(pd_ctx *c, uint64_t n_long)
     if (e != hipSuccess) { runs_free(r); return fail(c, PD_EHIP, std::string("pd_decode_end: ") + hipGetErrorString(e)); }
     r->n_long = (uint32_t)std::min<uint64_t>(n_long + h[1], 0xFFFFFFFFull);
     r->n_heavy = h[2];
+    r->n_wide_sorted = h[3];
     install_sample(c, r, pd_ctx::DN_END_COMPACT);
     return PD_OK;
 }

@@ -62,7 +62,12 @@ struct Run8 { uint32_t b; uint32_t len; };                       // a whole run,
 static inline __host__ __device__ uint32_t c8_lo(uint32_t b, uint32_t len) { return (b & 0xFFFFu) | (len << 16); }
 static inline __host__ __device__ uint32_t c8_hi(uint32_t b, uint32_t len) { return (b >> 16) | (len & 0xFFFF0000u); }
 static inline __host__ __device__ Run8 c8_join(uint32_t lo, uint32_t hi) { return Run8{(lo & 0xFFFFu) | (hi << 16), (lo >> 16) | (hi & 0xFFFF0000u)}; }
-struct C8Sample { const uint32_t *lo, *hi; const uint32_t *b1, *o1; uint32_t o_base, bshift; };
+//   nar[i] = (b & 0xFF) | (min(len, 255) << 8)    a THIRD plane of the sorted stream only, two bytes per run (pd_cover_rule.h): what the narrow form of
+//                                                 k_direct_c8's cover pass sweeps instead of lo, for a sample none of whose sorted runs is longer than 255 cells
+struct C8Sample { const uint32_t *lo, *hi; const uint32_t *b1, *o1; uint32_t o_base, bshift; const uint16_t *nar = nullptr; };
+// the narrow plane lies behind lo | hi (n words each) in the same allocation, on a 16-byte boundary behind lo's slack of 64 bytes, n_s half-words and the same slack
+static inline size_t c8_nar_offset(size_t n) { return (n * 8 + 64 + 15) & ~(size_t)15; }
+static inline size_t c8_planes_bytes(size_t n, size_t n_s) { return c8_nar_offset(n) + n_s * 2 + 64; }
 // a batch of n compact runs on its way (the decoder's segments): lo plane, then the hi plane on a 16-byte boundary
 static inline size_t c8_plane_words(size_t n) { return (n + 3) & ~(size_t)3; }
 // What k_direct_c8 needs to know about a tile before it can fetch the tile's runs, worked out once when the sample is finished (its inputs —
@@ -101,9 +106,9 @@ void launch_direct_tiles(hipStream_t st, const PendSet &ps, ContigTab tab, const
                          uint32_t wrap_mask, uint32_t w, uint32_t min_dep, TilePart *part, const uint64_t *win_off,
                          uint32_t *cover, unsigned long long *sum, uint32_t *n_long, uint32_t *fail,
                          uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un);
-// compact samples: the passes that make one (words: [0] not sorted / invalid contig, [1] runs longer than a bucket), the reverse
+// compact samples: the passes that make one (words: [0] not sorted / invalid contig, [1] runs longer than a bucket, [3] sorted runs longer than 255 cells), the reverse
 // (12-byte runs, bucket by bucket), and the direct kernels that read them
-void launch_c8_from_sorted(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *lo, uint32_t *hi, uint32_t *b1 /* pre-set to 0xFF */, uint32_t *words);
+void launch_c8_from_sorted(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *lo, uint32_t *hi, uint16_t *nar, uint32_t *b1 /* pre-set to 0xFF */, uint32_t *words);
 void launch_c8_hist(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *hist, uint32_t *words);
 void launch_excl_scan_u32(hipStream_t st, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *block_sums /* n / 1024 + 2 words */);
 void launch_c8_fill_starts(hipStream_t st, uint32_t *b1, uint32_t n_buckets, uint32_t n_runs, uint32_t *tmp /* n_buckets / 1024 + 2 words */);
@@ -117,14 +122,16 @@ void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint3
 void launch_c8_expand(hipStream_t st, C8Sample cs, const uint32_t *tile_contig, const uint64_t *contig_off, uint32_t n_tiles, pd_iv *out);
 void launch_r8_to_iv(hipStream_t st, const uint32_t *lo, const uint32_t *hi, uint64_t n, ContigTab tab, pd_iv *out);
 void launch_copy_words(hipStream_t st, void *dst, const void *src, uint64_t n_words);      // device-to-device, 4-byte words (both pointers 4-byte aligned)
-// ... and the two planes of n compact runs in ONE launch
-void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, const uint32_t *src_lo, const uint32_t *src_hi, uint64_t n);
+// ... and the two planes of n compact runs in ONE launch; dst_nar (may be null): the narrow plane of the same runs, made from the lo words on their way
+// (16-byte aligned when dst_lo is), and *n_wide += the runs among them that are longer than 255 cells
+void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, const uint32_t *src_lo, const uint32_t *src_hi, uint64_t n, uint16_t *dst_nar = nullptr, uint32_t *n_wide = nullptr);
 // (k_direct_c8 itself reads cs.lo, cs.o_base and desc only)
 // cover (with un = 0 only): the default form with the cover pass in front of the window path (pd_cover_rule.h); the tiles it settles are
-// added to heavy_count[PD_HEAVY_SETTLED]; tiles with fewer than cover_min candidates are not tried
+// added to heavy_count[PD_HEAVY_SETTLED]; tiles with fewer than cover_min candidates are not tried.  narrow (with cover only): the form whose pass
+// sweeps the sorted stream from cs.nar — the caller's promise that no sorted run is longer than 255 cells; returns whether that form was the one launched
 constexpr int PD_HEAVY_SETTLED = 10;
-void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
-                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min);
+bool launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
+                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min, bool narrow = false);
 // ... and the int-window pass for the pile-up tiles k_direct_c8 leaves: k_c8_heavy (it reads tab, tile_contig and the bucket starts in cs), a workgroup per
 // listed tile up to 1024.  Its own launcher: the caller launches it only for a sample that has pile-up tiles, with the SAMPLE's list and count
 // (pd_runs::heavy_tiles / n_heavy, made by k_c8_tile_desc) — nothing of it waits for k_direct_c8, whose TileParts are other tiles', so the two may run side by side.

@@ -1461,8 +1461,9 @@ __device__ __forceinline__ uint64_t c8_flat(const pd_iv v, const ContigTab tab, 
 // every run becomes 8 bytes — the low 32 bits of its flat begin, its clamped length, split over the two planes (C8Sample) —, its order is CHECKED against its predecessor
 // (words[0]: a contig id out of range, or a run that begins before the one in front of it), runs longer than a bucket are counted
 // (words[1]: such a sample is not used in this form), and the first run of every bucket leaves its index in b1[bucket] (pre-set to
-// 0xFFFFFFFF; the buckets nobody begins in are filled by launch_c8_fill_starts).
-__global__ __launch_bounds__(WG) void k_c8_from_sorted(const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *lo, uint32_t *hi, uint32_t *b1, uint32_t *words)
+// 0xFFFFFFFF; the buckets nobody begins in are filled by launch_c8_fill_starts).  The run's half-word goes to the narrow plane (C8Sample::nar) and the
+// runs that half-word cannot hold (longer than 255 cells) are counted in words[3], one atomic per wave that has some.
+__global__ __launch_bounds__(WG) void k_c8_from_sorted(const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *lo, uint32_t *hi, uint16_t *nar, uint32_t *b1, uint32_t *words)
 {
     const uint64_t i64 = (uint64_t)blockIdx.x * WG + threadIdx.x;
     const uint32_t i = i64 < n ? (uint32_t)i64 : n - 1;
@@ -1472,10 +1473,13 @@ __global__ __launch_bounds__(WG) void k_c8_from_sorted(const pd_iv *iv, uint32_t
     uint64_t prev = ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(gb >> 32), 1) << 32) | (uint32_t)__shfl_up((int)(uint32_t)gb, 1);
     bool pvalid = __shfl_up((int)valid, 1) != 0;
     if ((threadIdx.x & 63) == 0 && i > 0) { uint32_t pl; prev = c8_flat(iv[i - 1], tab, pl, pvalid); }
+    const unsigned long long wide = __builtin_amdgcn_ballot_w64(i64 < n && pdcover::nar_is_wide(len));      // (before any lane leaves)
+    if (wide != 0ull && (threadIdx.x & 63) == 0) atomicAdd(&words[3], (uint32_t)__builtin_popcountll(wide));
     if (i64 >= n) return;
     if (!valid || (i > 0 && (!pvalid || gb < prev))) atomicOr(&words[0], 1u);
     if (len > (1u << cshift)) atomicAdd(&words[1], 1u);
     lo[i] = c8_lo((uint32_t)gb, len); hi[i] = c8_hi((uint32_t)gb, len);
+    nar[i] = (uint16_t)pdcover::nar_pack((uint32_t)gb, len);
     if (valid && (i == 0 || !pvalid || (prev >> cshift) != (gb >> cshift))) atomicMin(&b1[gb >> cshift], i);
 }
 
@@ -1704,6 +1708,32 @@ __device__ __forceinline__ void copy_words(uint32_t *__restrict__ dst, const uin
     }
     for (uint64_t i = n4 * 4 + gid; i < n; i += stride) dst[i] = src[i];
 }
+// The same copy for the LO words of a sorted stream: every word also leaves its half-word in nar (same index; C8Sample::nar) — from the register it
+// is copied through, no second read — as one 8-byte store per four runs where the plane's place allows it; returns how many of this thread's words
+// were runs the half-word cannot hold.  (The count sees the lo word's 16 bits of length only: a run of 65 536 cells or more keeps its upper bits in
+// hi, but such a run is longer than a bucket, is counted in n_long by whoever emitted it, and the direct kernels — which read lengths from lo
+// alone — never see that sample.)
+__device__ __forceinline__ uint32_t copy_lo_words_nar(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, uint64_t n, uint16_t *__restrict__ nar)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256, gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t wide = 0;
+    auto half = [&](const uint32_t word) -> uint32_t { wide += pdcover::nar_is_wide(word >> 16) ? 1u : 0u; return pdcover::nar_of_lo(word); };
+    uint64_t head = ((0 - (uintptr_t)dst) >> 2) & 3; if (head > n) head = n;
+    if (gid < head) { const uint32_t v = src[gid]; dst[gid] = v; nar[gid] = (uint16_t)half(v); }
+    dst += head; src += head; nar += head; n -= head;
+    const uint64_t n4 = n / 4;
+    uint4 *d4 = reinterpret_cast<uint4 *>(dst);
+    const bool src16 = ((uintptr_t)src & 15) == 0, nar8 = ((uintptr_t)nar & 7) == 0;       // (kernel-uniform)
+    for (uint64_t i = gid; i < n4; i += stride) {
+        const uint4 v = src16 ? reinterpret_cast<const uint4 *>(src)[i] : make_uint4(src[4 * i], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]);
+        d4[i] = v;
+        const uint32_t h0 = half(v.x), h1 = half(v.y), h2 = half(v.z), h3 = half(v.w);
+        if (nar8) reinterpret_cast<uint2 *>(nar)[i] = make_uint2(h0 | (h1 << 16), h2 | (h3 << 16));
+        else { nar[4 * i] = (uint16_t)h0; nar[4 * i + 1] = (uint16_t)h1; nar[4 * i + 2] = (uint16_t)h2; nar[4 * i + 3] = (uint16_t)h3; }
+    }
+    for (uint64_t i = n4 * 4 + gid; i < n; i += stride) { const uint32_t v = src[i]; dst[i] = v; nar[i] = (uint16_t)half(v); }
+    return wide;
+}
 __global__ __launch_bounds__(256) void k_copy_words(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, uint64_t n) { copy_words(dst, src, n); }
 // the two planes of n compact runs (C8Sample) in one launch
 __global__ __launch_bounds__(256) void k_copy_planes(uint32_t *__restrict__ dst_lo, uint32_t *__restrict__ dst_hi, const uint32_t *__restrict__ src_lo,
@@ -1711,6 +1741,19 @@ __global__ __launch_bounds__(256) void k_copy_planes(uint32_t *__restrict__ dst_
 {
     copy_words(dst_lo, src_lo, n);
     copy_words(dst_hi, src_hi, n);
+}
+// ... of the SORTED stream on its way to the sample: the narrow plane is made from the lo words as they pass, and the runs longer than 255 cells
+// are counted (*n_wide, one atomic per wave that met some)
+__global__ __launch_bounds__(256) void k_copy_planes_nar(uint32_t *__restrict__ dst_lo, uint32_t *__restrict__ dst_hi, uint16_t *__restrict__ dst_nar,
+                                                         const uint32_t *__restrict__ src_lo, const uint32_t *__restrict__ src_hi, uint64_t n, uint32_t *n_wide)
+{
+    const uint32_t wide = copy_lo_words_nar(dst_lo, src_lo, n, dst_nar);
+    copy_words(dst_hi, src_hi, n);
+    const unsigned long long some = __builtin_amdgcn_ballot_w64(wide != 0u);      // (every lane is here again)
+    if (some != 0ull) {
+        const uint32_t total = (uint32_t)wave_total((int)wide);
+        if ((threadIdx.x & 63) == 0) atomicAdd(n_wide, total);
+    }
 }
 
 // The per-tile descriptors of a finished compact sample (TileDesc in pd_kernels.h): one thread per tile reads the bucket starts around the
@@ -1771,13 +1814,15 @@ __global__ __launch_bounds__(WG) void k_r8_to_iv(const uint32_t *lo, const uint3
 // settle (a declined tile costs a sweep on top of its window: launch_direct_c8).  A workgroup that walks consecutive tiles settles exactly the tiles it
 // would settle taking them one by one: a tile swept in a group in which an earlier tile's decline closed the gate is not counted and takes the window.
 constexpr uint32_t COVER_DECLINE = 2, COVER_CLOSE = 8, COVER_SKIP = 15;
-template <int WPE, int UN8, bool EXPORT, bool JOIN = false, int LW = 1, bool COVER = false>
+// NARROW (COVER only): the pass sweeps a tile's sorted candidates from the nar plane, two bytes per run, and checks at the end that it could (below).
+template <int WPE, int UN8, bool EXPORT, bool JOIN = false, int LW = 1, bool COVER = false, bool NARROW = false>
 __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const TileDesc *__restrict__ desc, uint32_t n_tiles,
                                                      uint32_t wrap_mask, const DirectWide args, uint32_t *__restrict__ heavy_list,
                                                      uint32_t *__restrict__ heavy_count, const DirectExport ex)
 {
     static_assert(LW == 1 || (JOIN && (LW == 2 || LW == 4) && UN8 % LW == 0), "wide loads: JOIN form, LW runs per load");
     static_assert(!(COVER && EXPORT), "the cover pass settles statistics, the export form needs every cell");
+    static_assert(COVER || !NARROW, "the narrow plane is the cover pass's");
     const uint32_t w = args.w, min_dep = args.min_dep; TilePart *const part = args.part;
     constexpr uint32_t ST = TILE, HT = TILE / 2;
     constexpr int ROWS = (int)(HT / (WG * 4));
@@ -1836,6 +1881,155 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
                 // (a stream of the tile that ends inside the first eight words of the sample's array — fewer than eight runs in all up to there — has
                 // no eight words to load: the window path does such a tile)
                 if ((ns && mine.shi < 8u) || (no && cs.o_base + mine.ohi < 8u)) eligible = false;
+                if constexpr (NARROW) { if (eligible) {
+                    // The NARROW sweep: the sorted candidates come from the nar plane, two bytes per run (pd_cover_rule.h), the other stream's from lo as in
+                    // the wide sweep below, behind them in the same sequence.  A chunk of the sorted stream is 512 runs, eight consecutive runs per lane; a chunk
+                    // of the other stream is 256 runs, four per lane.  So EVERY chunk is ONE 16-byte load per lane, no branch around it (a uniform choice of
+                    // where it points), three register buffers in turn: two chunks in flight behind the one worked on, 2 KB per wave, in 12 registers (with a
+                    // fourth buffer, or with chunks of two loads, the form needs 65 - 69 VGPRs: profiles/r15_cover_narrow_ab.txt, section 7).
+                    // Begins are REBUILT: within a lane d[k] = (c[k] - c[k-1]) & 255 over the runs' low bytes, the predecessor of a lane's first run being the
+                    // lane before's last (lane 0: the chunk before's last, carried wave-uniform in pb); the lane totals go through a wave scan and `base`, the
+                    // rebuilt begin of the last run swept so far (at first the tile-relative begin of the tile's first sorted candidate, from its lo word).
+                    // Ends are begin + the high byte: exact, the launcher takes this form only for a sample without a sorted run above 255 cells.
+                    // The rebuilt begins are right exactly when no consecutive difference reached 256, and the END CHECK says so without any help from whoever
+                    // made the sample: the stream is sorted (words[0] refuses a sample that is not), every rebuilt difference is <= the true one, so `base`
+                    // behind the last chunk equals the last candidate's true begin (its lo word) if and only if every difference was rebuilt as it is.  That
+                    // is enough: every rebuilt begin is <= its true one, so a wrong begin alone could only CLOSE a true gap, never open one — a gap met is a
+                    // true gap and declines the tile as in the wide form, without the check — and the equality at the end rules the closed gap out.  A tile is
+                    // settled only when the check passed; where it did not, the tile was NOT TRIED (COV_WINDOW: nothing for the gate's score).
+                    // In a partial chunk the places that are not the lane's own become the lane's predecessor byte with length 0 (a difference of 0, an empty
+                    // run: pdcover::nar_neutral); for the lanes behind the chunk's last run the predecessor is that run.
+                    constexpr uint32_t CWS = 512u, CWO = 256u;
+                    const bool any_gap_ends = min_dep != 0u;
+                    const uint32_t c_s = (ns + CWS - 1u) / CWS, nq = c_s + (no + CWO - 1u) / CWO;
+                    const uint32_t neutral = pdcover::run_neutral(p0);
+                    const uint32_t o_at = cs.o_base + mine.olo;
+                    uint32_t lo_first = 0u, lo_last = 0u;         // the lo words of the tile's first and last sorted candidate: issued in front of the first chunk's loads
+                    if (ns) { lo_first = cs.lo[mine.slo]; lo_last = cs.lo[mine.shi - 1u]; }
+                    // the runs of chunk q (wave-uniform)
+                    auto sorted_cnt = [&](const uint32_t q) -> uint32_t { const uint32_t left = ns - q * CWS; return left < CWS ? left : CWS; };
+                    auto other_cnt = [&](const uint32_t q) -> uint32_t { const uint32_t left = no - (q - c_s) * CWO; return left < CWO ? left : CWO; };
+                    // the lane's first element (of `per` to a lane), counted from `back` elements before the chunk: in a partial chunk of cnt runs a lane's load
+                    // begins at run min(per * lane, cnt - per) — still inside the sample's array, not before its first element
+                    auto lane_rel = [&](const uint32_t cnt, const uint32_t back, const uint32_t per) -> uint32_t {
+                        const int off = (int)(ln * per) < (int)cnt - (int)per ? (int)(ln * per) : (int)cnt - (int)per;
+                        const int rel = off + (int)back;
+                        return (uint32_t)(rel > 0 ? rel : 0) & 1023u;   // (at most 512: said so that the loads take a 32-bit offset, not an address pair)
+                    };
+                    typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(2)));     // (the half-words are 2-byte aligned, the 16-byte loads are not)
+                    auto load = [&](uint32_t (&x)[4], const uint32_t q) {
+                        const uint32_t qq = q < nq ? q : nq - 1u;
+                        const char *pq;                           // wave-uniform
+                        uint32_t r;                               // the lane's byte offset from it
+                        if (qq < c_s) {
+                            uint32_t cnt = sorted_cnt(qq);
+                            if (q >= nq && cnt > 8u) cnt = 8u;    // behind the last chunk: one place for all lanes
+                            const uint32_t at = mine.slo + qq * CWS, back = at < 8u ? at : 8u;
+                            pq = reinterpret_cast<const char *>(cs.nar + (at - back)); r = lane_rel(cnt, back, 8u) * 2u;
+                        } else {
+                            uint32_t cnt = other_cnt(qq);
+                            if (q >= nq && cnt > 4u) cnt = 4u;
+                            const uint32_t at = o_at + (qq - c_s) * CWO, back = at < 4u ? at : 4u;
+                            pq = reinterpret_cast<const char *>(cs.lo + (at - back)); r = lane_rel(cnt, back, 4u) * 4u;
+                        }
+                        const u32x4_u u = *reinterpret_cast<const u32x4_u *>(pq + r);
+                        x[0] = u.x; x[1] = u.y; x[2] = u.z; x[3] = u.w;
+                    };
+                    int reach = 0;                                // wave-uniform: [0, reach) is covered by the runs swept so far
+                    bool gap = false;
+                    uint32_t sum = 0;                             // this lane's clipped lengths
+                    int base = 0;                                 // wave-uniform: the rebuilt begin of the last sorted run swept
+                    uint32_t pb = 0u;                             // wave-uniform: that run's half-word (its low byte is what counts)
+                    auto work = [&](uint32_t (&x)[4], const uint32_t q) {
+                        if (q >= c_s) {                           // the other stream: clipped lengths only, 4 runs per lane
+                            const uint32_t cnt = other_cnt(q);
+                            if (cnt < CWO) {
+                                const uint32_t at = o_at + (q - c_s) * CWO, back = at < 4u ? at : 4u;
+                                const int mine0 = (int)(ln * 4u), got0 = (int)lane_rel(cnt, back, 4u) - (int)back;
+                                const int skip = mine0 < (int)cnt ? mine0 - got0 : 4;
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) x[k] = k >= skip ? x[k] : neutral;
+                            }
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) { const int b = pdcover::run_begin(x[k], p0); sum += pdcover::run_clipped(b, pdcover::run_end(x[k], b), (int)ST); }
+                            return;
+                        }
+                        const uint32_t cnt = sorted_cnt(q);
+                        uint32_t h[8] = {x[0] & 0xFFFFu, x[0] >> 16, x[1] & 0xFFFFu, x[1] >> 16, x[2] & 0xFFFFu, x[2] >> 16, x[3] & 0xFFFFu, x[3] >> 16};
+                        const uint32_t last_lane = (cnt - 1u) >> 3;                                 // the lane that holds the chunk's last run, in its last place
+                        const uint32_t lastb = (uint32_t)__builtin_amdgcn_readlane((int)h[7], (int)last_lane);
+                        uint32_t pred = (uint32_t)wave_shift_up((int)h[7], (int)pb);
+                        if (cnt < CWS) {                          // a partial chunk (wave-uniform): keep this lane's own runs
+                            const uint32_t at = mine.slo + q * CWS, back = at < 8u ? at : 8u;
+                            const int mine0 = (int)(ln * 8u), got0 = (int)lane_rel(cnt, back, 8u) - (int)back;
+                            const int skip = mine0 < (int)cnt ? mine0 - got0 : 8;
+                            if (ln > last_lane) pred = lastb;
+                            const uint32_t nt = pdcover::nar_neutral(pred);
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) h[k] = k >= skip ? h[k] : nt;
+                        }
+                        pb = lastb;
+                        // begins and ends relative to the lane's predecessor first (the half-words are done with before the scan), then moved by the lane's base
+                        int b[8], e[8];
+                        uint32_t lens = 0;
+                        b[0] = pdcover::nar_step(h[0], pred);
+#pragma unroll
+                        for (int k = 1; k < 8; ++k) b[k] = b[k - 1] + pdcover::nar_step(h[k], h[k - 1]);
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) { const int len = pdcover::nar_len(h[k]); e[k] = b[k] + len; lens += (uint32_t)len; }
+                        const int tot = wave_incl_scan(b[7]);
+                        const int lane_base = base + tot - b[7];
+                        base += __builtin_amdgcn_readlane(tot, 63);
+                        uint32_t neg = 0;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) { b[k] += lane_base; e[k] += lane_base; neg |= (uint32_t)b[k]; }
+                        // from here on the rule is the wide sweep's
+                        int m = e[0];
+#pragma unroll
+                        for (int k = 1; k < 8; ++k) m = m > e[k] ? m : e[k];
+                        const int incl = wave_incl_scan_max(m);
+                        const int before = wave_shift_up(incl, pdcover::NONE);      // the largest end of the lanes before this one
+                        int P = before > reach ? before : reach;
+                        unsigned long long g = 0ull;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) { g |= __builtin_amdgcn_ballot_w64(b[k] > P); P = P > e[k] ? P : e[k]; }
+                        if (g != 0ull) gap = true;
+                        const int top = __builtin_amdgcn_readlane(incl, 63);
+                        reach = top > reach ? top : reach;
+                        if (top <= (int)ST && __builtin_amdgcn_ballot_w64((int)neg < 0) == 0ull) { sum += lens; return; }      // no clipping needed (wave-uniform)
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) sum += pdcover::run_clipped(b[k], e[k], (int)ST);
+                    };
+                    bool end_ok = true;
+                    if (nq) {
+                        uint32_t A[4], B[4], C[4];
+                        uint32_t q = 0;
+                        load(A, 0u);
+                        load(B, 1u);
+                        base = __builtin_amdgcn_readfirstlane(pdcover::run_begin(lo_first, p0));
+                        pb = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo_first);
+                        const uint32_t lo_last_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo_last);
+#pragma unroll 1
+                        for (;;) {
+                            load(C, q + 2u);
+                            work(A, q);
+                            if (++q >= nq || (gap && any_gap_ends)) break;
+                            load(A, q + 2u);
+                            work(B, q);
+                            if (++q >= nq || (gap && any_gap_ends)) break;
+                            load(B, q + 2u);
+                            work(C, q);
+                            if (++q >= nq || (gap && any_gap_ends)) break;
+                        }
+                        __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0): nothing of this tile stays in flight (see the wide sweep)
+                        // the end check, for a sweep that reached the stream's end (one a gap ended declines the tile whatever the check would say)
+                        if (ns && !(gap && any_gap_ends)) end_ok = pdcover::nar_end_ok(base, lo_last_u, p0);
+                    }
+                    wsum = (uint32_t)wave_total((int)sum);
+                    if (gap && any_gap_ends) outcome = COV_DECLINED;
+                    else if (!end_ok) outcome = COV_WINDOW;
+                    else outcome = ((!gap && reach >= (int)ST) || !any_gap_ends) ? COV_SETTLED : COV_DECLINED;
+                } } else
                 if (eligible) {
                     // The tile's candidates as ONE sequence of chunks of CW = 512 runs, eight consecutive runs per lane: the sorted stream's full chunks,
                     // its last, partial chunk, then the other stream's (their order does not matter: what they cover is ignored, their lengths count).
@@ -3445,10 +3639,10 @@ void launch_direct_tiles(hipStream_t st, const PendSet &ps, ContigTab tab, const
 
 static unsigned grid_1k(uint64_t n) { return (unsigned)((n + 1023) / 1024 ? (n + 1023) / 1024 : 1); }
 
-void launch_c8_from_sorted(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *lo, uint32_t *hi, uint32_t *b1, uint32_t *words)
+void launch_c8_from_sorted(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *lo, uint32_t *hi, uint16_t *nar, uint32_t *b1, uint32_t *words)
 {
     if (!n) return;
-    hipLaunchKernelGGL(k_c8_from_sorted, dim3((unsigned)(((uint64_t)n + WG - 1) / WG)), dim3(WG), 0, st, iv, n, tab, bshift, lo, hi, b1, words);
+    hipLaunchKernelGGL(k_c8_from_sorted, dim3((unsigned)(((uint64_t)n + WG - 1) / WG)), dim3(WG), 0, st, iv, n, tab, bshift, lo, hi, nar, b1, words);
 }
 
 void launch_c8_hist(hipStream_t st, const pd_iv *iv, uint32_t n, ContigTab tab, uint32_t bshift, uint32_t *hist, uint32_t *words)
@@ -3503,11 +3697,12 @@ void launch_copy_words(hipStream_t st, void *dst, const void *src, uint64_t n_wo
     hipLaunchKernelGGL(k_copy_words, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, st, (uint32_t *)dst, (const uint32_t *)src, n_words);
 }
 
-void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, const uint32_t *src_lo, const uint32_t *src_hi, uint64_t n)
+void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, const uint32_t *src_lo, const uint32_t *src_hi, uint64_t n, uint16_t *dst_nar, uint32_t *n_wide)
 {
     if (!n) return;
     const uint64_t g = (n / 4 + 255) / 256 + 1;
-    hipLaunchKernelGGL(k_copy_planes, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, st, dst_lo, dst_hi, src_lo, src_hi, n);
+    if (dst_nar) hipLaunchKernelGGL(k_copy_planes_nar, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, st, dst_lo, dst_hi, dst_nar, src_lo, src_hi, n, n_wide);
+    else hipLaunchKernelGGL(k_copy_planes, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, st, dst_lo, dst_hi, src_lo, src_hi, n);
 }
 
 void launch_c8_tile_desc(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, TileDesc *desc, uint32_t *n_heavy, uint32_t *heavy_tiles)
@@ -3522,8 +3717,8 @@ void launch_r8_to_iv(hipStream_t st, const uint32_t *lo, const uint32_t *hi, uin
     hipLaunchKernelGGL(k_r8_to_iv, dim3((unsigned)(g > 65536 ? 65536 : g)), dim3(WG), 0, st, lo, hi, n, tab, out);
 }
 
-void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
-                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min)
+bool launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
+                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min, bool narrow)
 {
     // cover_min ("direct_cover_min", default 2048 candidates per tile): a tile visit costs the cover pass more than the window path before its first run
     // (measured on the bench genome, ms per launch with / without the pass tried on every tile: 1e9 records, 3 224 candidates per tile: 1.10 / 1.38; 3e8,
@@ -3538,6 +3733,7 @@ void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_
     // top of the window for most of its tiles — 1.480 -> 1.949 ms where every tile has gaps, 1.440 -> 1.624 where every other has
     // (profiles/r10_direct_cover_ab.txt, section 6); what it pays now: r13, section 5.  "direct_cover" 0 remains the way out.
     const DirectWide dw{w, min_dep, part, cover_min};
+    bool took_narrow = false;
     // "direct_un" for a compact sample: 100 x waves-per-SIMD target + loads in flight per thread (0 = default)
 #define PD_C8(WPE_, UN8_) hipLaunchKernelGGL((k_direct_c8<WPE_, UN8_, false>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{})
     switch (un) {
@@ -3578,12 +3774,15 @@ void launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_
     // round 9, 4-byte runs (lo plane), the same events on the bench sample: <7, 4> 1.390, <6, 8> with 8-byte loads 1.384, <8, 4> plain 1.390, <7, 8> 1.392, <7, 4> with 8- / 16-byte
     // loads 1.416 / 1.407, <6, 8> with 16-byte loads 1.438, <7, 8> with 8- / 16-byte loads 1.605 / 1.811 (spills) — loads in flight no longer decide (profiles/r09_runs_planes_ab.txt)
     default:
-        if (cover) hipLaunchKernelGGL((k_direct_c8<7, 4, false, true, 1, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{});
+        // narrow ("cover_narrow", and a sample whose sorted runs all fit a byte of length): the pass reads 2 bytes per sorted run instead of 4 (profiles/r15_cover_narrow_ab.txt)
+        if (cover && narrow && cs.nar) { took_narrow = true; hipLaunchKernelGGL((k_direct_c8<7, 4, false, true, 1, true, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{}); }
+        else if (cover) hipLaunchKernelGGL((k_direct_c8<7, 4, false, true, 1, true>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{});
         else PD_C8J(7, 4, 1);
         break;
     }
 #undef PD_C8J
 #undef PD_C8
+    return took_narrow;
 }
 
 // k_c8_heavy's form, by measurement on the bench's 12 pile-up tiles of 32 025 - 48 063 candidates (profiles/r12_pileup_gather_ab.txt): 1024 threads with 8 loads each
