@@ -204,16 +204,6 @@ int prof_collect(pd_ctx *c)
     return PD_OK;
 }
 
-int ensure_scratch(pd_ctx *c, size_t bytes)
-{
-    if (bytes <= c->scratch_bytes) return PD_OK;
-    if (c->scratch) { HIPOK(c, hipStreamSynchronize(c->stream)); HIPOK(c, hipFree(c->scratch)); c->scratch = nullptr; c->scratch_bytes = 0; }
-    size_t want = bytes + bytes / 4 + 4096;
-    if (hipMalloc(&c->scratch, want) != hipSuccess) return fail(c, PD_ENOMEM, "scratch allocation failed");
-    c->scratch_bytes = want;
-    return PD_OK;
-}
-
 // Reset = forget every cell: mark all half-tiles "not written" (the owner-tile kernel stores into
 // them without reading, the sweep reads them as zeros) and zero the tile sums.  No 12 GB fill.
 int do_reset(pd_ctx *c)
@@ -241,9 +231,23 @@ int ensure_all_valid(pd_ctx *c)
     return PD_OK;
 }
 
+} // namespace
+
+namespace pdi {
+
+int ensure_scratch(pd_ctx *c, size_t bytes)
+{
+    if (bytes <= c->scratch_bytes) return PD_OK;
+    if (c->scratch) { HIPOK(c, hipStreamSynchronize(c->stream)); HIPOK(c, hipFree(c->scratch)); c->scratch = nullptr; c->scratch_bytes = 0; }
+    size_t want = bytes + bytes / 4 + 4096;
+    if (hipMalloc(&c->scratch, want) != hipSuccess) return fail(c, PD_ENOMEM, "scratch allocation failed");
+    c->scratch_bytes = want;
+    return PD_OK;
+}
+
 // a compact pending sample that has to take a path that reads 12-byte runs: expanded once (the copy stays with the sample).
 // Inside a bucket the runs are in no particular order: the batch is sorted up to one bucket's cells of disorder.
-int expand_compact(pd_ctx *c, Pending &p)
+static int expand_compact(pd_ctx *c, Pending &p)
 {
     if (!p.cr || p.iv) return PD_OK;
     pd_runs *r = p.cr;
@@ -258,20 +262,32 @@ int expand_compact(pd_ctx *c, Pending &p)
     return PD_OK;
 }
 
-} // namespace
-
-namespace pdi {
+// the one preparation of the pending sample for a tile pass (flush_pending, direct_windows, direct_export: pd_ctx.h says what the arguments are)
+int pend_prepare(pd_ctx *c, uint32_t stride, uint32_t n_stiles, int stile, bool skip, PendSet *ps, uint64_t *all)
+{
+    *ps = PendSet{};
+    ps->nb = (int)c->pend.size(); ps->lmax = c->lmax;
+    *all = 0;
+    for (auto &p : c->pend) *all += p.n;
+    if (skip) return PD_OK;
+    for (auto &p : c->pend) { const int re = expand_compact(c, p); if (re) return re; }
+    for (int b = 0; b < ps->nb; ++b) {
+        const Pending &p = c->pend[b];
+        ps->b[b] = PendBatch{p.iv, c->ub_a[b], c->cand_lo[b], c->desc + b, p.n, 0};
+        ProfScope sc(c, "scatter_index");
+        launch_scatter_index(c->stream, p.iv, p.n, tab_of(c), c->lmax, p.disorder, stride, c->ub_a[b], c->cand_lo[b], n_stiles, stile, c->desc + b);
+    }
+    return PD_OK;
+}
 
 // one owner-tile pass over all pending sorted batches
 int flush_pending(pd_ctx *c)
 {
     if (c->pend.empty()) return PD_OK;
-    for (auto &p : c->pend) { const int re = expand_compact(c, p); if (re) return re; }
     if (c->sums_stale) {                      // a direct export wrote this (still deferred) sample's tile sums; the scatter adds to them
         HIPOK(c, hipMemsetAsync(c->sums, 0, (c->n_words - c->n_cells) * 4, c->stream));
         c->sums_stale = false;
     }
-    c->pristine = false;
     uint64_t total = 0;
     for (auto &p : c->pend) total += p.n;
     if (total > OVF_MAX) total = OVF_MAX;     // more long runs than this in ONE pass is reported (err bit 4):
@@ -283,27 +299,10 @@ int flush_pending(pd_ctx *c)
         c->ovf_cap = (uint32_t)cap;
     }
     const uint32_t n_stiles = (uint32_t)(c->n_cells / c->stile);
-    PendSet ps{};
-    ps.nb = (int)c->pend.size(); ps.lmax = c->lmax;
-    for (int b = 0; b < ps.nb; ++b) {
-        const Pending &p = c->pend[b];
-        ps.b[b] = PendBatch{p.iv, c->ub_a[b], c->cand_lo[b], c->desc + b, p.n, 0};
-        ProfScope sc(c, "scatter_index");
-        launch_scatter_index(c->stream, p.iv, p.n, tab_of(c), c->lmax, p.disorder, c->sample, c->ub_a[b], c->cand_lo[b],
-                             n_stiles, c->stile, c->desc + b);
-    }
-    // Grid of the tile pass: measured best is ~64 K workgroups for a whole-genome pass (each walks a
-    // handful of tiles; the hardware overlaps their load/flush phases); small streaming batches
-    // touch few tiles and get a proportionally smaller grid.
-    unsigned grid = c->grid_tiles;
-    if (!grid) {
-        uint64_t all = 0;
-        for (auto &p : c->pend) all += p.n;
-        uint64_t g = all / 256;
-        if (g < (uint64_t)c->n_cu * 4) g = (uint64_t)c->n_cu * 4;
-        if (g > 65536) g = 65536;
-        grid = (unsigned)g;
-    }
+    PendSet ps{}; uint64_t all = 0;
+    if (int rc = pend_prepare(c, c->sample, n_stiles, c->stile, false, &ps, &all)) return rc;
+    c->pristine = false;
+    const unsigned grid = pdwin::pass_grid(all, c->n_cu, c->grid_tiles, 0);
     { ProfScope sc(c, "scatter_tiles");
       launch_scatter_tiles(c->stream, ps, tab_of(c), c->d_tile_contig, n_stiles, c->stile, c->buf, c->sums, c->hstate,
                            c->ovf, c->ovf_cap, c->chk, grid); }
@@ -353,10 +352,6 @@ int scatter_device(pd_ctx *c, const pd_iv *d, size_t n, unsigned flags, int slot
     return PD_OK;
 }
 
-} // namespace pdi
-
-namespace {
-
 int check_words(pd_ctx *c)
 {
     CheckWords h;
@@ -371,6 +366,10 @@ int check_words(pd_ctx *c)
     }
     return PD_OK;
 }
+
+} // namespace pdi
+
+namespace {
 
 // caller holds c->mu
 int stage_acquire(pd_ctx *c, int *slot)
@@ -595,10 +594,10 @@ int pd_destroy(pd_ctx *c)
     for (void *p : {(void *)c->carry, (void *)c->bsum, (void *)c->d_off, (void *)c->d_len, (void *)c->d_tile_contig, (void *)c->ub_a[0], (void *)c->ub_a[1], (void *)c->ub_a[2],
                     (void *)c->ub_a[3], (void *)c->cand_lo[0], (void *)c->cand_lo[1], (void *)c->cand_lo[2], (void *)c->cand_lo[3], (void *)c->hstate, (void *)c->slice_flags,
                     (void *)c->direct_words, (void *)c->desc, (void *)c->chk}) pdguard::drop(p);            // (parts of the slab)
-    void *ptrs[] = {c->buf, c->slab, c->ovf, c->scratch, c->wk, c->d_woff};
+    void *ptrs[] = {c->buf, c->slab, c->ovf, c->scratch};
     t1 = dec_now_us();
     for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (void *p : {(void *)c->woff_host, (void *)c->wk_pin}) if (p) (void)hipHostFree(p);
+    c->win.release();
     t2 = dec_now_us();
     for (auto &sl : c->dec) {
         if (sl.st) (void)hipStreamSynchronize(sl.st);
@@ -632,7 +631,7 @@ int pd_reset(pd_ctx *c)
 {
     if (!c) return PD_EINVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    c->wk_valid = false;
+    c->win.valid = false;
     HIPOK(c, hipSetDevice(c->device));
     // deferred batches are forgotten with everything else (they used to be scattered first, a whole-genome pass for nothing);
     // their staging slots are free once the stream has passed this point
@@ -919,7 +918,7 @@ int pd_scan(pd_ctx *c, unsigned wrap_bits)
     if (rc) return rc;
     rc = check_words(c);
     if (rc) return rc;
-    const uint32_t mask = (wrap_bits == 0 || wrap_bits == 32) ? 0xFFFFFFFFu : ((1u << wrap_bits) - 1u);
+    const uint32_t mask = pdwin::wrap_mask(wrap_bits);
     { ProfScope ps(c, "tile_carry"); launch_tile_carry(c->stream, c->sums, c->bsum, c->carry, (uint32_t)c->n_tiles); }
     { ProfScope ps(c, "scan"); launch_scan_write(c->stream, c->buf, c->carry, (uint32_t)c->n_tiles, mask, c->hstate); }
     HIPOK(c, hipGetLastError());
@@ -928,268 +927,6 @@ int pd_scan(pd_ctx *c, unsigned wrap_bits)
     c->all_valid_host = true;
     c->state = 1;
     return PD_OK;
-}
-
-int pd_window_layout(const pd_ctx *c, uint32_t w, uint64_t *win_off)
-{
-    if (!c || !win_off || w == 0) return PD_EINVAL;
-    uint64_t o = 0;
-    for (int32_t i = 0; i < c->n_contigs; ++i) { win_off[i] = o; o += ((uint64_t)c->len[i] + w - 1) / w; }
-    win_off[c->n_contigs] = o;
-    return PD_OK;
-}
-
-// c->wk of a window call: [sums, 8 B per window | covers, 4 B per window, padded to 16 B | WK_WORDS bytes: the direct path's status words], so
-// that all a call hands back is one contiguous range
-constexpr size_t WK_WORDS = 64;
-static_assert(WK_WORDS == PD_STATUS_WORDS * 4, "the gather zeroes a whole set of status words");
-static int win_keep_fit(pd_ctx *c, size_t bytes)
-{
-    c->wk_valid = false;
-    c->wk_words_ok = false;                              // whoever calls writes c->wk: the direct call's status words are no longer known to be zero (direct_windows)
-    if (bytes <= c->wk_bytes) return PD_OK;
-    if (c->wk) { HIPOK(c, hipStreamSynchronize(c->stream)); HIPOK(c, hipFree(c->wk)); c->wk = nullptr; c->wk_bytes = 0; }
-    const size_t want = bytes + bytes / 8 + 4096;
-    if (hipMalloc(&c->wk, want) != hipSuccess) { (void)hipGetLastError(); return fail(c, PD_ENOMEM, "window statistics: device allocation failed"); }
-    c->wk_bytes = want;
-    return PD_OK;
-}
-
-// The device's copy of the window offsets `wo` of width w.  The offsets follow from the contig table, which is fixed at pd_create, and w, so the copy
-// is kept from call to call and uploaded only for another width — queued, from the context's page-locked copy: the call's final sync covers it.
-// (Until round 11 every window call uploaded a local vector and synchronised the stream before it queued anything else: in the traced bench step, 48 us
-// from the reset's last fill to the direct kernel's start, 29 us without the copy and the sync — profiles/r11_direct_call_ab.txt, sections 0 and 4.)
-static int win_offsets(pd_ctx *c, uint32_t w, const std::vector<uint64_t> &wo, const uint64_t **d_wo)
-{
-    const size_t b_off = wo.size() * 8;
-    if (!c->d_woff) {
-        if (hipMalloc(&c->d_woff, b_off) != hipSuccess) { (void)hipGetLastError(); c->d_woff = nullptr; return fail(c, PD_ENOMEM, "window offsets: device allocation failed"); }
-        if (hipHostMalloc((void **)&c->woff_host, b_off, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError(); (void)hipFree(c->d_woff); c->d_woff = nullptr; c->woff_host = nullptr;
-            return fail(c, PD_ENOMEM, "window offsets: page-locked allocation failed");
-        }
-    }
-    if (c->woff_w != w) {
-        c->woff_w = 0;                                   // (every call that used woff_host has synchronised the stream behind its upload)
-        memcpy(c->woff_host, wo.data(), b_off);
-        HIPOK(c, hipMemcpyAsync(c->d_woff, c->woff_host, b_off, hipMemcpyHostToDevice, c->stream));
-        c->woff_w = w;
-    }
-    *d_wo = c->d_woff;
-    return PD_OK;
-}
-
-static int windows_common(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask, bool from_depth,
-                          uint32_t *cover, uint64_t *sum)
-{
-    std::vector<uint64_t> wo((size_t)c->n_contigs + 1);
-    pd_window_layout(c, w, wo.data());
-    const uint64_t nw = wo[c->n_contigs];
-    const size_t b_sum = (size_t)nw * 8, b_cov = ((size_t)nw * 4 + 15) / 16 * 16;
-    const size_t b_part = (size_t)c->n_tiles * sizeof(TilePart);      // wide windows: every tile's shares; narrow ones: the shares of the windows across tile boundaries
-    int rc = ensure_scratch(c, b_part + 64);
-    if (rc) return rc;
-    rc = win_keep_fit(c, b_sum + b_cov + WK_WORDS);
-    if (rc) return rc;
-    const uint64_t *d_wo = nullptr;
-    rc = win_offsets(c, w, wo, &d_wo);
-    if (rc) return rc;
-    unsigned long long *d_sum = (unsigned long long *)c->wk;
-    uint32_t *d_cov = (uint32_t *)(c->wk + b_sum);
-    TilePart *d_part = (TilePart *)c->scratch;
-    if (w < PD_TILE) HIPOK(c, hipMemsetAsync(d_sum, 0, b_sum + b_cov, c->stream));   // windows nobody writes stay zero
-    if (!from_depth) { ProfScope ps(c, "tile_carry"); launch_tile_carry(c->stream, c->sums, c->bsum, c->carry, (uint32_t)c->n_tiles); }
-    {
-        ProfScope ps(c, from_depth ? "reduce_windows" : "scan_reduce_windows");
-        TileMap tm{c->d_tile_contig, c->d_off, c->d_len, d_wo};
-        int e = launch_sweep_windows(c->stream, c->buf, c->carry, (uint32_t)c->n_tiles, mask, tm, w, min_dep,
-                                     d_cov, d_sum, d_part, nw, c->n_contigs, from_depth, c->hstate);
-        if (e) return fail(c, PD_EHIP, "window sweep: cannot reserve LDS");
-    }
-    HIPOK(c, hipGetLastError());
-    HIPOK(c, hipMemcpyAsync(sum, d_sum, b_sum, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(c, hipMemcpyAsync(cover, d_cov, (size_t)nw * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));
-    c->wk_w = w; c->wk_nw = nw; c->wk_woff = wo; c->wk_valid = true;
-    return PD_OK;
-}
-
-// The direct whole-sample path (k_direct_tiles): every run of the sample is still pending and the
-// arrays hold nothing, so the windows are computed from the runs without ever materialising the
-// difference arrays.  *done = false (and nothing consumed) when the device found a run longer than
-// the look-back or a batch that was not sorted: the caller then takes the materialising path, which
-// reports real errors.
-static int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask, uint32_t *cover, uint64_t *sum, bool *done)
-{
-    *done = false;
-    std::vector<uint64_t> wo((size_t)c->n_contigs + 1);
-    pd_window_layout(c, w, wo.data());
-    const uint64_t nw = wo[c->n_contigs];
-    const size_t b_sum = (size_t)nw * 8, b_cov = ((size_t)nw * 4 + 15) / 16 * 16, b_res = b_sum + b_cov, b_all = b_res + WK_WORDS;
-    const size_t b_part = (size_t)c->n_tiles * sizeof(TilePart);
-    int rc = ensure_scratch(c, b_part + 64);
-    if (rc) return rc;
-    // Wide windows have TWO sets of status words behind the results, used in turn: the gather of one call zeroes the set the next call counts into, so
-    // that no call fills its own (a 64-byte fill was 2.5 us of every step and a boundary of its own in the stream).  The sets are known to be as a gather
-    // left them only while nothing else has been at c->wk since (win_keep_fit: every user calls it) and the results end where they did; any other
-    // call — the first, another width, one behind a call that failed, returned early or took another path — fills both.
-    const bool gathered = w >= PD_TILE && nw > 0;
-    const bool words_kept = gathered && c->wk_words_ok && c->wk_words_at == b_res;
-    rc = win_keep_fit(c, b_all + WK_WORDS);
-    if (rc) return rc;
-    const uint64_t *d_wo = nullptr;
-    rc = win_offsets(c, w, wo, &d_wo);
-    if (rc) return rc;
-    const unsigned turn = words_kept ? c->wk_turn : 0;
-    unsigned long long *d_sum = (unsigned long long *)c->wk;
-    uint32_t *d_cov = (uint32_t *)(c->wk + b_sum);
-    uint32_t *d_words = (uint32_t *)(c->wk + b_res + turn * WK_WORDS);      // [n_long, fail, heavy_count, diagnostics ..., [12] tiles settled by the cover pass]; the heavy tile list: c->direct_words + 16
-    uint32_t *d_words_next = (uint32_t *)(c->wk + b_res + (turn ^ 1u) * WK_WORDS);
-    TilePart *d_part = (TilePart *)c->scratch;
-    // Up to WK_PIN_BYTES the call's results come back in one copy through the context's page-locked buffer (three copies into the caller's pageable arrays
-    // were three staged round trips: 53 us from the gather's end to the last copy's, 10 us with the one copy — profiles/r11_direct_call_ab.txt, sections 0
-    // and 4); a larger result goes straight to the caller's arrays, so that no call pins memory in proportion to its output.
-    // Where a gather ends the call it stores every window to that buffer itself, through the buffer's device address, and one of its lanes copies the status
-    // words there: no copy is queued at all, and the call's sync is what makes the stores visible to the host.  c->wk still gets the windows
-    // (pd_text_append_window_rows formats from it).  Narrow windows (no gather) keep the one copy.
-    const bool pinned = b_all <= pd_ctx::WK_PIN_BYTES, pin_stores = pinned && gathered;
-    if (pinned && !c->wk_pin) {
-        if (hipHostMalloc((void **)&c->wk_pin, pd_ctx::WK_PIN_BYTES, hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void **)&c->wk_pin_dev, c->wk_pin, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            if (c->wk_pin) (void)hipHostFree(c->wk_pin);
-            c->wk_pin = c->wk_pin_dev = nullptr;
-            return fail(c, PD_ENOMEM, "window statistics: page-locked allocation failed");
-        }
-    }
-    if (w < PD_TILE) HIPOK(c, hipMemsetAsync(d_sum, 0, b_all, c->stream));   // edge windows are accumulated; the status words with them
-    else if (!words_kept) HIPOK(c, hipMemsetAsync(c->wk + b_res, 0, 2 * WK_WORDS, c->stream));
-    const uint32_t n_stiles = (uint32_t)c->n_tiles;
-    PendSet ps{};
-    ps.nb = (int)c->pend.size(); ps.lmax = c->lmax;
-    uint64_t all = 0;
-    // a compact sample that is ALL there is serves wide windows through k_direct_c8; anywhere else it goes on as 12-byte runs
-    const bool c8 = ps.nb == 1 && c->pend[0].cr && !c->pend[0].iv && w >= PD_TILE && !c->pend[0].cr->n_long;
-    if (!c8) for (auto &p : c->pend) { const int re = expand_compact(c, p); if (re) return re; }
-    for (int b = 0; b < ps.nb; ++b) {
-        const Pending &p = c->pend[b];
-        all += p.n;
-        if (c8) break;
-        ps.b[b] = PendBatch{p.iv, c->ub_a[b], c->cand_lo[b], c->desc + b, p.n, 0};
-        ProfScope sc(c, "scatter_index");
-        // a 4x sparser index than the arrays path's: measured neutral for the tile kernel, 0.43 -> 0.13 ms of index
-        launch_scatter_index(c->stream, p.iv, p.n, tab_of(c), c->lmax, p.disorder, c->direct_sample, c->ub_a[b],
-                             c->cand_lo[b], n_stiles, PD_TILE, c->desc + b);
-    }
-    unsigned grid = c->grid_tiles;
-    if (!grid) {
-        uint64_t g = all / 256;
-        if (g < (uint64_t)c->n_cu * 4) g = (uint64_t)c->n_cu * 4;
-        if (g > 65536) g = 65536;
-        grid = (unsigned)g;
-    }
-    if (grid > c->n_tiles) grid = (unsigned)c->n_tiles;
-    { ProfScope sc(c, "direct_tiles");
-      if (c8) {
-          const pd_runs *cr = c->pend[0].cr;
-          const bool cover = c->direct_cover && all >= (uint64_t)c->direct_cover_min * c->n_tiles;   // a thin sample: the form without the pass (launch_direct_c8)
-          // ... and the pass sweeps the sorted stream's narrow plane, half the bytes, when every sorted run fits a half-word (counted when the sample was made)
-          const bool narrow = cover && c->cover_narrow && cr->nar && cr->n_wide_sorted == 0;
-          // The cover form walks GROUPS of four tiles and a settled group costs a workgroup little more than its start, so its default grid is 64 workgroups
-          // per CU, not one per 256 runs: on the bench sample (91 623 groups; ms per launch with the pile-up pass) 65 536 workgroups 0.985, one per group
-          // 1.352, 32 768: 0.798, 16 384: 0.806, 7 168: 0.797 (profiles/r13_cover_wave_ab.txt).  "grid_tiles" still overrides it.
-          if (cover && !c->grid_tiles && !c->direct_un) {
-              const uint64_t groups = ((uint64_t)c->n_tiles + 3) / 4, g = (uint64_t)c->n_cu * 64;
-              grid = (unsigned)(g < groups ? g : groups);
-          }
-          // The pile-up pass runs BESIDE k_direct_c8 on the context's side stream: its list and count are the sample's (k_c8_tile_desc), it writes the
-          // TileParts of exactly the tiles k_direct_c8 skips, and neither touches what the other reads.  Fork: an event in front of k_direct_c8 (the pass
-          // must not overtake what is queued before the call: the fills above, an upload of the offsets, the sample's making); join: main waits for the
-          // pass before the section's end event, so "direct_tiles" still times both, and before the gather.  Every exit from here on is behind the join.
-          if (cr->n_heavy) HIPOK(c, hipEventRecord(c->ev_fork, c->stream));
-          c->direct_narrow = launch_direct_c8(c->stream, cr->view(), cr->td, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, c->direct_words + 16, d_words + 2, grid, c->direct_un, cover, c->direct_cover_min, narrow) ? 1 : 0;
-          // The int-window pass for the pile-up tiles k_direct_c8 lists, launched only for a sample that has some: the sample knows from its making
-          // (pd_runs::n_heavy, counted by k_c8_tile_desc from the records k_direct_c8 reads), so no round trip decides.  The bench's 1e9-record sample HAS
-          // pile-up tiles (12): the pass's 0.028 ms per call there (k_c8_heavy; 0.099 as the compact branch of k_direct_tiles_heavy, profiles/r12_pileup_gather_ab.txt) are its work; on the empty lists of the 1e8- and 3e8-record samples a launch took 0.004 ms, and
-          // deciding by the count that comes back with the results (a second gather, copy and sync) gained a 1e9-record step 0.024 ms where this form gains
-          // 0.069 (profiles/r11_direct_call_ab.txt, sections 2 and 3).
-          if (cr->n_heavy) {
-              hipError_t e = hipStreamWaitEvent(c->side_stream, c->ev_fork, 0);
-              if (e == hipSuccess) {
-                  launch_direct_c8_heavy(c->side_stream, cr->view(), tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, cr->heavy_tiles, cr->n_heavy);
-                  e = hipEventRecord(c->ev_join, c->side_stream);
-                  if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_join, 0);
-                  // (the pass may be in the side stream without main waiting for it: wait here, so that whoever syncs main afterwards is behind it)
-                  if (e != hipSuccess) (void)hipStreamSynchronize(c->side_stream);
-              }
-              if (e != hipSuccess) return fail(c, PD_EHIP, std::string("direct windows: the pile-up pass's stream: ") + hipGetErrorString(e));
-          }
-      }
-      else launch_direct_tiles(c->stream, ps, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, mask, w, min_dep, d_part, d_wo,
-                               d_cov, d_sum, d_words, d_words + 1, c->direct_words + 16, d_words + 2, grid, c->direct_un); }
-    if (w >= PD_TILE) {
-        ProfScope sc(c, "gather_windows");
-        TileMap tm{c->d_tile_contig, c->d_off, c->d_len, d_wo};
-        GatherCall gc{gathered ? d_words_next : nullptr, d_words, nullptr, nullptr, nullptr};
-        if (pin_stores) { gc.pin_sum = (unsigned long long *)c->wk_pin_dev; gc.pin_cover = (uint32_t *)(c->wk_pin_dev + b_sum); gc.pin_words = (uint32_t *)(c->wk_pin_dev + b_res); }
-        launch_window_gather(c->stream, d_part, tm, c->n_contigs, w, nw, d_cov, d_sum, gc);
-    }
-    HIPOK(c, hipGetLastError());
-    if (gathered) { c->wk_words_ok = true; c->wk_words_at = b_res; c->wk_turn = turn ^ 1u; }      // (the gather is in the stream: the other set is zero for whoever comes behind it)
-    uint32_t words[PD_STATUS_READ] = {0};                // [12]: heavy_count[PD_HEAVY_SETTLED]
-    if (pinned) { if (!pin_stores) HIPOK(c, hipMemcpyAsync(c->wk_pin, c->wk, b_all, hipMemcpyDeviceToHost, c->stream)); }
-    else {
-        HIPOK(c, hipMemcpyAsync(words, d_words, sizeof words, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(c, hipMemcpyAsync(sum, d_sum, b_sum, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(c, hipMemcpyAsync(cover, d_cov, (size_t)nw * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPOK(c, hipStreamSynchronize(c->stream));
-    if (pinned) memcpy(words, c->wk_pin + b_res, sizeof words);
-    if (c8 && words[2] != c->pend[0].cr->n_heavy)       // (k_direct_c8's own count of the tiles it listed: the same candidates, the same threshold)
-        return fail(c, PD_ESTATE, "direct windows: the kernel listed " + std::to_string(words[2]) + " pile-up tiles, the sample was made with " + std::to_string(c->pend[0].cr->n_heavy));
-    c->direct_settled = words[2 + pdk::PD_HEAVY_SETTLED];
-    c->direct_pileup = c8 ? words[2] : 0;
-    if (words[1]) {                                      // not applicable: batches stay pending
-        if (getenv("PANDEPTH_TIMING")) fprintf(stderr, "[timing]   direct window path declined: begins owned %llu of %llu runs, runs with cells %u vs ends owned %u (difference), index error bits 0x%x, "
-                            "long runs %u: the arrays are materialised\n", (unsigned long long)words[3] | ((unsigned long long)words[4] << 32),
-                    (unsigned long long)words[5] | ((unsigned long long)words[6] << 32), words[7], words[8], words[9], words[10]);
-        return PD_OK;
-    }
-    if (pinned) { memcpy(sum, c->wk_pin, b_sum); memcpy(cover, c->wk_pin + b_sum, (size_t)nw * 4); }
-    // the call READ the sample: it stays deferred (like pd_export_i4's direct form), every other call still works on it
-    *done = true;
-    c->wk_w = w; c->wk_nw = nw; c->wk_woff = wo; c->wk_valid = true;
-    return PD_OK;
-}
-
-int pd_scan_reduce_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, unsigned wrap_bits, uint32_t *cover, uint64_t *sum)
-{
-    if (!c || !cover || !sum || w == 0 || wrap_bits > 32) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 0, "pd_scan_reduce_windows")) return rs;
-    HIPOK(c, hipSetDevice(c->device));
-    c->direct_settled = 0; c->direct_pileup = 0; c->direct_narrow = 0;
-    if (c->direct_windows && c->pristine && !c->pend.empty() && w >= 64 && c->stile == PD_TILE) {
-        const uint32_t m = (wrap_bits == 0 || wrap_bits == 32) ? 0xFFFFFFFFu : ((1u << wrap_bits) - 1u);
-        bool done = false;
-        int rd = direct_windows(c, w, min_dep, m, cover, sum, &done);
-        if (rd || done) return rd;
-    }
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    rc = check_words(c);
-    if (rc) return rc;
-    const uint32_t mask = (wrap_bits == 0 || wrap_bits == 32) ? 0xFFFFFFFFu : ((1u << wrap_bits) - 1u);
-    return windows_common(c, w, min_dep, mask, false, cover, sum);
-}
-
-int pd_reduce_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t *cover, uint64_t *sum)
-{
-    if (!c || !cover || !sum || w == 0) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 1, "pd_reduce_windows")) return rs;
-    HIPOK(c, hipSetDevice(c->device));
-    return windows_common(c, w, min_dep, 0xFFFFFFFFu, true, cover, sum);
 }
 
 // ---- depth histograms ----
@@ -1213,7 +950,7 @@ int pd_scan_depth_histogram(pd_ctx *c, uint32_t n_bins, unsigned wrap_bits, uint
     if (rc) return rc;
     rc = check_words(c);
     if (rc) return rc;
-    const uint32_t mask = (wrap_bits == 0 || wrap_bits == 32) ? 0xFFFFFFFFu : ((1u << wrap_bits) - 1u);
+    const uint32_t mask = pdwin::wrap_mask(wrap_bits);
     const size_t b_hist = (size_t)c->n_contigs * n_bins * 8;
     rc = ensure_scratch(c, b_hist + 64);
     if (rc) return rc;
@@ -1583,9 +1320,8 @@ int pd_window_quantiles(pd_ctx *c, uint32_t w, const uint32_t *pct, uint32_t n_p
     if (int rs = need_state(c, 1, "pd_window_quantiles")) return rs;
     pdk::QPct P;
     if (int rc = quant_pct(c, pct, n_pct, "pd_window_quantiles", &P)) return rc;
-    std::vector<uint64_t> wo((size_t)c->n_contigs + 1);
-    pd_window_layout(c, w, wo.data());
-    const uint64_t nw = wo[c->n_contigs];
+    std::vector<uint64_t> wo;
+    const uint64_t nw = win_table(c, w, &wo).nw;
     if (nw == 0) return PD_OK;
     HIPOK(c, hipSetDevice(c->device));
     uint32_t maxlen = 0;
@@ -1746,9 +1482,8 @@ int pd_window_thresholds(pd_ctx *c, uint32_t w, const uint32_t *thr, uint32_t n_
     if (int rs = need_state(c, 1, "pd_window_thresholds")) return rs;
     pdk::ThrSet T;
     if (int rc = thr_set(c, thr, n_thr, "pd_window_thresholds", &T)) return rc;
-    std::vector<uint64_t> wo((size_t)c->n_contigs + 1);
-    pd_window_layout(c, w, wo.data());
-    const uint64_t nw = wo[c->n_contigs];
+    std::vector<uint64_t> wo;
+    const uint64_t nw = win_table(c, w, &wo).nw;
     if (nw == 0) return PD_OK;
     HIPOK(c, hipSetDevice(c->device));
     uint32_t maxlen = 0;
@@ -2000,90 +1735,6 @@ int pd_import_i8(pd_ctx *c, const void *dev_i8, int bias, const pd_exc *dev_exc,
     return PD_OK;
 }
 
-static_assert(sizeof(TilePart) == PD_TILE_PARTIAL_BYTES, "pd_gather_windows' partial layout");
-static_assert(PD_TILE == PD_TILE_CELLS, "tile size in the public header");
-
-// pd_export_i4 without the arrays ("direct_windows", sample entirely deferred, context pristine): the tile windows leave
-// as the 4-bit image straight from LDS (k_direct_tiles<DirectExport>), the tile sums are written beside it.  *done = false
-// (tile sums re-zeroed, batches still pending) when a tile was too heavy, a run too long or a batch not sorted.
-static int direct_export(pd_ctx *c, void *dev_i4, pd_exc *dev_exc, uint32_t exc_cap, uint32_t *dev_count, bool *done)
-{
-    *done = false;
-    HIPOK(c, hipMemsetAsync(dev_count, 0, 4, c->stream));
-    HIPOK(c, hipMemsetAsync(c->direct_words, 0, 64, c->stream));
-    PendSet ps{};
-    ps.nb = (int)c->pend.size(); ps.lmax = c->lmax;
-    uint64_t all = 0;
-    const bool c8 = ps.nb == 1 && c->pend[0].cr && !c->pend[0].iv && !c->pend[0].cr->n_long;
-    if (!c8) for (auto &p : c->pend) { const int re = expand_compact(c, p); if (re) return re; }
-    for (int b = 0; b < ps.nb; ++b) {
-        const Pending &p = c->pend[b];
-        all += p.n;
-        if (c8) break;
-        ps.b[b] = PendBatch{p.iv, c->ub_a[b], c->cand_lo[b], c->desc + b, p.n, 0};
-        ProfScope sc(c, "scatter_index");
-        launch_scatter_index(c->stream, p.iv, p.n, tab_of(c), c->lmax, p.disorder, c->sample < 256 ? 256 : c->sample, c->ub_a[b],
-                             c->cand_lo[b], (uint32_t)c->n_tiles, PD_TILE, c->desc + b);
-    }
-    unsigned grid = c->grid_tiles;
-    if (!grid) {
-        uint64_t g = all / 256;
-        if (g < (uint64_t)c->n_cu * 4) g = (uint64_t)c->n_cu * 4;
-        if (g > 65536) g = 65536;
-        grid = (unsigned)g;
-    }
-    if (grid > c->n_tiles) grid = (unsigned)c->n_tiles;
-    { ProfScope sc(c, "direct_export");
-      if (c8) launch_direct_c8_export(c->stream, c->pend[0].cr->view(), c->pend[0].cr->td, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, dev_i4, dev_exc, exc_cap,
-                                      dev_count, c->sums, c->direct_words + 16, c->direct_words + 2, grid, c->pend[0].cr->n_heavy);
-      else launch_direct_export(c->stream, ps, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, dev_i4, dev_exc, exc_cap, dev_count,
-                                c->sums, c->direct_words, c->direct_words + 1, c->direct_words + 16, c->direct_words + 2, grid); }
-    HIPOK(c, hipGetLastError());
-    uint32_t words[2] = {0, 0}, n_exc = 0;
-    HIPOK(c, hipMemcpyAsync(words, c->direct_words, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(c, hipMemcpyAsync(&n_exc, dev_count, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));
-    // more cells outside the 4-bit range than the caller's exception block holds (amplicon / very deep data): the image is
-    // not usable, and the sample must stay whole for whatever the caller does instead — it is materialised below like any
-    // other declined export, the arrays keep it
-    if (n_exc > exc_cap) words[1] = 1;
-    if (words[1]) {
-        HIPOK(c, hipMemsetAsync(c->sums, 0, (c->n_words - c->n_cells) * 4, c->stream));      // the kernel wrote them
-        c->sums_stale = false;
-        char m[160];
-        snprintf(m, sizeof m, "direct export declined (heavy tiles / long runs: %u; cells outside the 4-bit range: %u); the materialising path was used", words[0], n_exc);
-        c->err = m;                                          // informational: the call still succeeds
-        return PD_OK;
-    }
-    // The sample STAYS deferred: an export reads it.  (A caller that finds out later that the image is of no use — another
-    // rank's sample did not fit its exception block, pd_sliced_sum_finish -> PD_ERANGE — still has every context's sample and
-    // adds them up the general way.)  The tile sums now hold this sample's sums although the arrays hold nothing:
-    // flush_pending zeroes them before it scatters, pd_reset forgets them with everything else.
-    c->sums_stale = true;
-    *done = true;
-    return PD_OK;
-}
-
-int pd_export_i4(pd_ctx *c, void *dev_i4, pd_exc *dev_exc, uint32_t exc_cap, uint32_t *dev_count)
-{
-    if (!c || !dev_i4 || !dev_count || (exc_cap && !dev_exc)) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 0, "pd_export_i4")) return rs;
-    HIPOK(c, hipSetDevice(c->device));
-    if (c->direct_windows && c->pristine && !c->pend.empty() && c->stile == PD_TILE) {
-        bool done = false;
-        const int rd = direct_export(c, dev_i4, dev_exc, exc_cap, dev_count, &done);
-        if (rd || done) return rd;
-    }
-    int rc = flush_pending(c);
-    if (rc) return rc;
-    HIPOK(c, hipMemsetAsync(dev_count, 0, 4, c->stream));
-    { ProfScope ps(c, "export_i4");
-      launch_export_i4(c->stream, c->buf, c->hstate, dev_i4, c->n_cells, dev_exc, exc_cap, dev_count); }
-    HIPOK(c, hipGetLastError());
-    return PD_OK;
-}
-
 int pd_slice_sweep_i4(pd_ctx *c, const void *dev_parts, uint32_t n_parts, uint64_t part_stride, uint64_t tile_first,
                       uint64_t tile_count, const int32_t *dev_tile_sums, const pd_exc *dev_exc, uint64_t exc_stride,
                       const int32_t *dev_exc_counts, uint32_t w, uint32_t min_dep, unsigned wrap_bits, void *dev_partials)
@@ -2096,42 +1747,13 @@ int pd_slice_sweep_i4(pd_ctx *c, const void *dev_parts, uint32_t n_parts, uint64
     if (n_parts > 1 && part_stride < tile_count * (PD_TILE / 2)) return fail(c, PD_EINVAL, "pd_slice_sweep_i4: parts overlap");
     if (((uintptr_t)dev_parts | part_stride) & 15) return fail(c, PD_EINVAL, "pd_slice_sweep_i4: parts must be 16-byte aligned");
     HIPOK(c, hipSetDevice(c->device));
-    const uint32_t mask = (wrap_bits == 0 || wrap_bits == 32) ? 0xFFFFFFFFu : ((1u << wrap_bits) - 1u);
+    const uint32_t mask = pdwin::wrap_mask(wrap_bits);
     { ProfScope ps(c, "tile_carry"); launch_tile_carry(c->stream, dev_tile_sums, c->bsum, c->carry, (uint32_t)c->n_tiles); }
     { ProfScope ps(c, "slice_sweep");
       TileMap tm{c->d_tile_contig, c->d_off, c->d_len, nullptr};
       launch_sweep_i4(c->stream, dev_parts, n_parts, part_stride, (uint32_t)tile_first, (uint32_t)tile_count, dev_exc, exc_stride,
                       dev_exc_counts, c->slice_flags, slice_flag_bytes(c->n_tiles), c->carry, mask, tm, w, min_dep, (TilePart *)dev_partials, nullptr); }
     HIPOK(c, hipGetLastError());
-    return PD_OK;
-}
-
-int pd_gather_windows(pd_ctx *c, const void *dev_partials, uint32_t w, uint32_t *cover, uint64_t *sum)
-{
-    if (!c || !dev_partials || !cover || !sum) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (w < PD_TILE) return fail(c, PD_EINVAL, "pd_gather_windows: windows narrower than a tile are not sliced");
-    HIPOK(c, hipSetDevice(c->device));
-    std::vector<uint64_t> wo((size_t)c->n_contigs + 1);
-    pd_window_layout(c, w, wo.data());
-    const uint64_t nw = wo[c->n_contigs];
-    const size_t b_off = ((size_t)c->n_contigs + 1) * 8;
-    const size_t b_sum = (size_t)nw * 8, b_cov = ((size_t)nw * 4 + 15) / 16 * 16;
-    int rc = ensure_scratch(c, b_off + b_sum + b_cov + 64);
-    if (rc) return rc;
-    unsigned char *s = (unsigned char *)c->scratch;
-    uint64_t *d_wo = (uint64_t *)s;
-    unsigned long long *d_sum = (unsigned long long *)(s + b_off);
-    uint32_t *d_cov = (uint32_t *)(s + b_off + b_sum);
-    HIPOK(c, hipMemcpyAsync(d_wo, wo.data(), b_off, hipMemcpyHostToDevice, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));          // wo is a local
-    { ProfScope ps(c, "gather_windows");
-      TileMap tm{c->d_tile_contig, c->d_off, c->d_len, d_wo};
-      launch_window_gather(c->stream, (const TilePart *)dev_partials, tm, c->n_contigs, w, nw, d_cov, d_sum); }
-    HIPOK(c, hipGetLastError());
-    HIPOK(c, hipMemcpyAsync(sum, d_sum, b_sum, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(c, hipMemcpyAsync(cover, d_cov, (size_t)nw * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));
     return PD_OK;
 }
 
@@ -2436,9 +2058,9 @@ int pd_text_append_window_rows(pd_text *t, int32_t tid, uint32_t w, uint64_t row
     *n_bytes = 0;
     pd_ctx *c = t->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->wk_valid || c->wk_w != w) return fail(c, PD_ESTATE, "pd_text_append_window_rows: the last window call (pd_scan_reduce_windows / pd_reduce_windows) was not for this width");
+    if (!c->win.valid || c->win.w != w) return fail(c, PD_ESTATE, "pd_text_append_window_rows: the last window call (pd_scan_reduce_windows / pd_reduce_windows) was not for this width");
     if (tid < 0 || tid >= c->n_contigs) return fail(c, PD_EINVAL, "pd_text_append_window_rows: contig id out of range");
-    const uint64_t rows_here = c->wk_woff[(size_t)tid + 1] - c->wk_woff[(size_t)tid];
+    const uint64_t rows_here = c->win.n_rows(tid);
     if (row_first > rows_here || n_rows > rows_here - row_first) return fail(c, PD_EINVAL, "pd_text_append_window_rows: rows beyond the contig's windows");
     if (name_len > 4096 || n_rows > ((size_t)1 << 27)) return fail(c, PD_EINVAL, "pd_text_append_window_rows: at most 2^27 rows per call and 4096 bytes of name");
     if (n_rows == 0) return PD_OK;
@@ -2450,9 +2072,8 @@ int pd_text_append_window_rows(pd_text *t, int32_t tid, uint32_t w, uint64_t row
     char *d_name = (char *)s; uint32_t *d_cnt = (uint32_t *)(s + b_name); uint64_t *d_off = (uint64_t *)(s + b_name + b_cnt);
     ProfScope ps(c, "format_window_rows");
     if (name_len) HIPOK(c, hipMemcpyAsync(d_name, name, name_len, hipMemcpyHostToDevice, c->stream));
-    const uint64_t g0 = c->wk_woff[(size_t)tid] + row_first;
-    const unsigned long long *d_sum = (const unsigned long long *)c->wk + g0;
-    const uint32_t *d_cov = (const uint32_t *)(c->wk + (size_t)c->wk_nw * 8) + g0;
+    const unsigned long long *d_sum = nullptr; const uint32_t *d_cov = nullptr;
+    c->win.rows(tid, row_first, &d_sum, &d_cov);
     pdk::launch_window_rows(c->stream, d_cov, d_sum, row_first, n_rows, w, c->len[(size_t)tid], (uint32_t)name_len, d_name, d_cnt, d_off, nullptr, false);
     uint64_t total = 0;
     HIPOK(c, hipMemcpyAsync(&total, d_off + nb, 8, hipMemcpyDeviceToHost, c->stream));
@@ -2973,7 +2594,7 @@ static int sliced_depth(pd_comm *m, int slot, unsigned wrap_bits)
     }
     {
         std::lock_guard<std::mutex> lk(c->mu);          // (comm_fail takes this lock: nothing below fails under it)
-        const uint32_t mask = (wrap_bits == 0 || wrap_bits == 32) ? 0xFFFFFFFFu : ((1u << wrap_bits) - 1u);
+        const uint32_t mask = pdwin::wrap_mask(wrap_bits);
         { ProfScope ps(c, "tile_carry"); launch_tile_carry(st, s.meta, c->bsum, c->carry, (uint32_t)c->n_tiles); }
         { ProfScope ps(c, "slice_depth");
           TileMap tm{c->d_tile_contig, c->d_off, c->d_len, nullptr};
@@ -2996,22 +2617,21 @@ static int sliced_narrow_windows(pd_comm *m, uint32_t w, uint32_t min_dep, unsig
     hipStream_t st = c->stream, ln = m->links;
     // (the collective is the context's only user while it runs — one thread per rank; the context's lock is taken only where its
     // shared scratch and profile records are touched, never across a comm_fail, which takes it itself)
-    std::vector<uint64_t> wo((size_t)c->n_contigs + 1);
-    pd_window_layout(c, w, wo.data());
-    const uint64_t nw = wo[c->n_contigs];
-    const size_t b_off = ((size_t)c->n_contigs + 1) * 8, b_sum = (size_t)nw * 8, b_cov = ((size_t)nw * 4 + 15) / 16 * 16;
+    std::vector<uint64_t> wo;
+    const pdwin::WinLayout l = win_table(c, w, &wo);
+    const size_t b_off = wo.size() * 8;
     std::string emsg;
     { std::lock_guard<std::mutex> lk(c->mu);
       rc = ensure_scratch(c, b_off + 64);
-      if (!rc) rc = win_keep_fit(c, b_sum + b_cov + 64);
+      if (!rc) rc = c->win.fit(c, l.b_all);
       if (rc) emsg = c->err; }
     if (rc) return comm_fail(m, rc, emsg);
     uint64_t *d_wo = (uint64_t *)c->scratch;
-    unsigned long long *d_sum = (unsigned long long *)c->wk;
-    uint32_t *d_cov = (uint32_t *)(c->wk + b_sum);
+    unsigned long long *d_sum = c->win.sums();
+    uint32_t *d_cov = c->win.covers(l);
     HIPCM(m, hipMemcpyAsync(d_wo, wo.data(), b_off, hipMemcpyHostToDevice, st));
     HIPCM(m, hipStreamSynchronize(st));                 // wo is a local
-    HIPCM(m, hipMemsetAsync(d_sum, 0, b_sum + b_cov, st));
+    HIPCM(m, hipMemsetAsync(d_sum, 0, l.b_res, st));
     TileMap tm{c->d_tile_contig, c->d_off, c->d_len, d_wo};
     TilePart *parts = (TilePart *)m->part_all;           // indexed by tile of the genome: the ranks' slices are consecutive blocks of it
     int e_lds = 0;
@@ -3025,18 +2645,18 @@ static int sliced_narrow_windows(pd_comm *m, uint32_t w, uint32_t min_dep, unsig
         HIPCM(m, hipStreamWaitEvent(ln, m->swept, 0));
         const size_t pb = (size_t)m->slice_tiles * PD_TILE_PARTIAL_BYTES;
         NCCLOK(m, m->tp->AllGather(m->part_all + (size_t)m->rank * pb, m->part_all, pb, ncclUint8, m->nccl, ln));
-        NCCLOK(m, m->tp->AllReduce(d_sum, d_sum, (b_sum + b_cov) / 4, ncclInt32, ncclSum, m->nccl, ln));
+        NCCLOK(m, m->tp->AllReduce(d_sum, d_sum, l.b_res / 4, ncclInt32, ncclSum, m->nccl, ln));
         HIPCM(m, hipEventRecord(m->gathered, ln));
         HIPCM(m, hipStreamWaitEvent(st, m->gathered, 0));
     }
     launch_window_edges(st, parts, tm, (uint32_t)c->n_tiles, w, d_cov, d_sum);
     HIPCM(m, hipGetLastError());
     if (m->rank == root) {
-        HIPCM(m, hipMemcpyAsync(sum, d_sum, b_sum, hipMemcpyDeviceToHost, st));
-        HIPCM(m, hipMemcpyAsync(cover, d_cov, (size_t)nw * 4, hipMemcpyDeviceToHost, st));
+        HIPCM(m, hipMemcpyAsync(sum, d_sum, l.b_sum, hipMemcpyDeviceToHost, st));
+        HIPCM(m, hipMemcpyAsync(cover, d_cov, (size_t)l.nw * 4, hipMemcpyDeviceToHost, st));
     }
     HIPCM(m, hipStreamSynchronize(st));
-    { std::lock_guard<std::mutex> lk(c->mu); c->wk_w = w; c->wk_nw = nw; c->wk_woff = wo; c->wk_valid = true; }   // (every rank holds the merged statistics)
+    { std::lock_guard<std::mutex> lk(c->mu); c->win.commit(w, l, wo); }   // (every rank holds the merged statistics)
     return PD_OK;
 }
 

@@ -1,5 +1,6 @@
-// pd_ctx.h — what the library's own translation units (pd_capi.hip, pd_decode.hip) share: the guarded device allocator, the context
-// (struct pd_ctx, struct pd_runs) and the few helpers that cross the file boundary (namespace pdi).  Not installed; include/*.h is the interface.
+// pd_ctx.h — what the library's own translation units (pd_capi.hip, pd_decode.hip, pd_windows.hip) share: the guarded device allocator, the context
+// (struct pd_ctx, struct pd_runs, the window result buffer's owner WinKeep) and the few helpers that cross the file boundary (namespace pdi).  Not
+// installed; include/*.h is the interface.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,6 +17,7 @@
 #include <thread>
 #include <vector>
 #include "pd_kernels.h"
+#include "pd_win_rule.h"
 #include "../../include/pandepth_amd_dev.h"
 #include "pd_bamwalk.h"
 
@@ -85,6 +87,39 @@ struct pd_runs {
     C8Sample view() const { return C8Sample{lo, hi, b1, o1, o_base, bshift, nar}; }
 };
 
+// The window calls' result buffer and everything that goes with it: ONE owner (the methods that queue work are pd_windows.hip's).  The statistics of the
+// last window call stay on the device (pd_text_append_window_rows formats the table's rows from them): commit() says which call's they are, pd_reset
+// clears `valid` only.
+struct WinKeep {
+    static constexpr size_t PIN_BYTES = pdwin::PIN_BYTES;
+    unsigned char *buf = nullptr; size_t bytes = 0;              // [sums | covers | status words] of pdwin::WinLayout
+    uint32_t w = 0; pdwin::WinLayout lay; bool valid = false; std::vector<uint64_t> woff;      // what the last committed call left: its width, layout and window offsets
+    // the window offsets of width woff_w on the device: an allocation of their own (c->scratch is every other call's too), uploaded only when a call
+    // asks for another width, from woff_host — page-locked and the context's, so that no sync has to guard the upload's source (offsets)
+    uint64_t *d_woff = nullptr, *woff_host = nullptr; uint32_t woff_w = 0;
+    pdwin::WordsState words;                                     // the direct call's two sets of status words behind its results (pdwin::words_turn)
+    // the direct path's results (sums | covers | status words, contiguous in buf) come back in ONE copy into this page-locked buffer of PIN_BYTES,
+    // made by the first call that needs it (pin_fit); larger results go straight to the caller's arrays
+    unsigned char *pin = nullptr, *pin_dev = nullptr;            // (pin_dev: its device address, what k_window_gather stores through)
+
+    int fit(pd_ctx *c, size_t need);                             // room for `need` bytes; whoever calls writes the buffer: nothing kept is valid, the status words are unknown
+    int offsets(pd_ctx *c, uint32_t width, const std::vector<uint64_t> &wo, const uint64_t **d_wo);
+    int pin_fit(pd_ctx *c);
+    void commit(uint32_t width, const pdwin::WinLayout &l, const std::vector<uint64_t> &wo) { w = width; lay = l; woff = wo; valid = true; }
+    void release();                                              // pd_destroy: the buffer, the offsets and the page-locked memory
+    // of a call with layout l (before its commit) ...
+    unsigned long long *sums() const { return (unsigned long long *)buf; }
+    uint32_t *covers(const pdwin::WinLayout &l) const { return (uint32_t *)(buf + l.b_sum); }
+    uint32_t *status(const pdwin::WinLayout &l, unsigned turn) const { return (uint32_t *)(buf + l.b_res + turn * pdwin::STATUS_BYTES); }
+    // ... and of the committed call: contig tid's rows from row_first on
+    uint64_t n_rows(int32_t tid) const { return woff[(size_t)tid + 1] - woff[(size_t)tid]; }
+    void rows(int32_t tid, uint64_t row_first, const unsigned long long **sum, const uint32_t **cover) const
+    {
+        const uint64_t g0 = woff[(size_t)tid] + row_first;
+        *sum = sums() + g0; *cover = covers(lay) + g0;
+    }
+};
+
 static inline size_t slice_flag_bytes(uint64_t n_tiles) { return (size_t)((n_tiles + 16 + 15) / 16 * 16); }
 
 struct pd_ctx {
@@ -111,7 +146,7 @@ struct pd_ctx {
     bool pristine = true;                                         // nothing materialised in the arrays since the last reset
     bool sums_stale = false;                                      // the tile sums hold what a direct export wrote while the sample is still deferred
     uint32_t *direct_words = nullptr;                             // [n_long, fail, heavy_count, diagnostics ..., [12] tiles settled by the cover pass | heavy tile list at +16]
-                                                                  // (the status words of a direct WINDOW call lie behind its results in wk, so that one copy brings both back; the export's are here)
+                                                                  // (the status words of a direct WINDOW call lie behind its results in WinKeep::buf, so that one copy brings both back; the export's are here)
     bool dec_crc = true;                                          // the decoder checks every member's CRC-32 ("decode_crc")
     unsigned lz_group = 16;                                       // chunks per workgroup of the LDS parse ("lz_group", up to 16; 0: every chunk parses with its text in memory).  Round 5's default: sixteen
                                                                   // chunks of 8 + 2 KiB share a CU's LDS (158 KB: 32 KiB of history + their text), 16 waves per CU — 8.6 ms against 11.8 for the 60 MB call of
@@ -136,7 +171,7 @@ struct pd_ctx {
     uint32_t q_wave_max = 512, q_split = 262144;                  // "quantile_wave_max" / "quantile_split_cells": the cell counts up to which a quantile row takes the narrow / the workgroup kernel
     uint32_t t_wave_max = 65536;                                  // "threshold_wave_max": the cell count up to which a threshold row is counted by a group of lanes, not in pieces
     int hist_variant = 1;                                         // "hist_variant": the histogram kernels' LDS form (launch_sweep_hist): 1 = one copy per workgroup, folded (measured best)
-    int direct_un = 0;                                           // 0 = the default form of the wide direct kernel (launch_direct_tiles)
+    int direct_un = 0;                                           // 0 = the default form of the direct kernels (launch_direct_tiles, launch_direct_c8)
     bool direct_cover = true;                                    // k_direct_c8's default form settles covered tiles from the runs (false: the window path for every tile)
     uint32_t direct_cover_min = 2048;                            // ... of tiles with at least this many candidates (launch_direct_c8)
     bool cover_narrow = true;                                    // ... from the sorted stream's narrow plane where the sample allows it ("cover_narrow"; pd_runs::n_wide_sorted == 0)
@@ -248,18 +283,7 @@ struct pd_ctx {
     } lz[4];                                                      // (a round's provider calls in flight at once: two until round 6, up to four)
     std::atomic<unsigned> lz_turn{0}; unsigned lz_slots = 2;         // "lz_slots": 2 or 4 of lz[] in use
     bool lz_mix = false;                                          // "lz_mix": see lz_run
-    // the statistics of the last window call stay on the device (pd_text_append_window_rows formats the table's rows from them)
-    unsigned char *wk = nullptr; size_t wk_bytes = 0; uint32_t wk_w = 0; uint64_t wk_nw = 0; bool wk_valid = false; std::vector<uint64_t> wk_woff;
-    // the window offsets of width woff_w on the device: an allocation of their own (c->scratch is every other call's too), uploaded only when a call
-    // asks for another width, from woff_host — page-locked and the context's, so that no sync has to guard the upload's source (win_offsets)
-    uint64_t *d_woff = nullptr, *woff_host = nullptr; uint32_t woff_w = 0;
-    // the direct call's two sets of status words behind its results in wk (direct_windows): the last call's gather left set wk_turn zeroed for the next call,
-    // wk_words_at bytes into wk; not ok: nobody knows what the sets hold, the next call fills both
-    bool wk_words_ok = false; size_t wk_words_at = 0; unsigned wk_turn = 0;
-    // the direct path's results (sums | covers | status words, contiguous in wk) come back in ONE copy into this page-locked buffer of WK_PIN_BYTES,
-    // made by the first call that needs it; larger results go straight to the caller's arrays
-    static constexpr size_t WK_PIN_BYTES = (size_t)1 << 20;
-    unsigned char *wk_pin = nullptr, *wk_pin_dev = nullptr;      // (wk_pin_dev: its device address, what k_window_gather stores through)
+    WinKeep win;                                                  // the window calls' result buffer and what the last call left in it
     bool prof = false;
     std::vector<ProfRec> prof_pending;
     std::vector<hipEvent_t> ev_pool;
@@ -296,6 +320,13 @@ struct ProfScope {
 };
 
 int flush_pending(pd_ctx *c);
+int ensure_scratch(pd_ctx *c, size_t bytes);
+int check_words(pd_ctx *c);
+// the pending sample made ready for a tile pass: compact batches expanded, ps filled, every batch's sparse index (stride runs) launched; *all = its runs.
+// skip: the caller's kernel reads the lone compact sample as it is — only the count
+int pend_prepare(pd_ctx *c, uint32_t stride, uint32_t n_stiles, int stile, bool skip, PendSet *ps, uint64_t *all);
+// the windows of width w: the contigs' first windows into wo (pd_window_layout), the result layout returned
+pdwin::WinLayout win_table(const pd_ctx *c, uint32_t w, std::vector<uint64_t> *wo);
 int scatter_device(pd_ctx *c, const pd_iv *d, size_t n, unsigned flags, int slot, bool *deferred);
 uint8_t *pin_alloc(size_t bytes, bool *mapped);
 void pin_free(uint8_t *p, size_t bytes, bool mapped);

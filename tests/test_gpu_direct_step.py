@@ -331,35 +331,83 @@ def test_results_through_the_page_locked_buffer_and_above_it():
                     assert e.profile_get("direct_pileup_tiles")[1] == 1
 
 
+def rows_of(tid, w, woff, cov_ref, tot_ref):
+    """the rows of the `-w` table for contig tid, formatted from the model's windows"""
+    rows = []
+    for k in range(int(woff[tid + 1] - woff[tid])):
+        j = 1 + k * w
+        end = min(j - 1 + w, LENS[tid])
+        ln = end - j + 1
+        c, d = int(cov_ref[int(woff[tid]) + k]), int(tot_ref[int(woff[tid]) + k])
+        rows.append("c%d\t%d\t%d\t%d\t%d\t%d\t%.2f\t%.2f\n" % (tid, j, end, ln, c, d, c * 100.0 / ln, d * 1.0 / ln))
+    return rows
+
+
+def kept_rows_are(e, w, what):
+    """every contig's rows, formatted by the device from the kept windows of the last call, are the model's"""
+    cov_ref, tot_ref = windows_ref("tile0", w, 1, 0)
+    woff = e.window_layout(w)
+    with e.text_open(1 << 20) as t:
+        at = 0
+        for tid in range(len(LENS)):
+            rows = rows_of(tid, w, woff, cov_ref, tot_ref)
+            want = "".join(rows).encode()
+            assert t.append_window_rows(tid, w, 0, len(rows), "c%d" % tid) == len(want), (what, tid)
+            assert t.read(at, len(want)) == want, (what, tid)
+            at += len(want)
+
+
+def kept_rows_are_refused(e, w, what):
+    with e.text_open(1 << 20) as t:
+        for tid in range(len(LENS)):
+            try:
+                t.append_window_rows(tid, w, 0, 1, "c%d" % tid)
+            except pda.PdError:
+                continue
+            raise AssertionError("rows of width %d were served %s" % (w, what))
+
+
 @gpu
 @pytest.mark.parametrize("w", [8192, 3 * 8192 + 1])
 def test_the_kept_windows_are_what_the_text_rows_come_from(w):
     """pd_text_append_window_rows formats from the device's copy of the last call's windows, which the gather still writes beside the
-    page-locked buffer: the rows of the `-w` table, formatted here from the model's windows"""
+    page-locked buffer: the rows of the `-w` table, formatted here from the model's windows — behind every producer that commits its
+    windows (the direct wide call, a direct narrow call on 12-byte runs, the arrays path, pd_reduce_windows behind pd_scan), and refused
+    behind pd_reset, a call of another width and a call that failed on its arguments"""
     first, other = sample("tile0")
-    cov_ref, tot_ref = windows_ref("tile0", w, 1, 0)
+    ref = windows_ref("tile0", w, 1, 0)
     with pda.Engine(list(LENS)) as e:
         e.keep_deferred(True)
         with Compact(e, first, other) as runs:
             for call in range(2):                        # (the second call finds the other set, and every buffer in place)
-                e.reset()
-                e.push_runs(runs, pda.PD_PUSH_MORE)
-                woff, cover, tot = e.scan_reduce_windows(w, 1, 0)
-                assert same((cover, tot), (cov_ref, tot_ref))
-                with e.text_open(1 << 20) as t:
-                    at = 0
-                    for tid, L in enumerate(LENS):
-                        rows = []
-                        for k in range(int(woff[tid + 1] - woff[tid])):
-                            j = 1 + k * w
-                            end = min(j - 1 + w, L)
-                            ln = end - j + 1
-                            c, d = int(cov_ref[int(woff[tid]) + k]), int(tot_ref[int(woff[tid]) + k])
-                            rows.append("c%d\t%d\t%d\t%d\t%d\t%d\t%.2f\t%.2f\n" % (tid, j, end, ln, c, d, c * 100.0 / ln, d * 1.0 / ln))
-                        want = "".join(rows).encode()
-                        assert t.append_window_rows(tid, w, 0, len(rows), "c%d" % tid) == len(want), (call, tid)
-                        assert t.read(at, len(want)) == want, (call, tid)
-                        at += len(want)
+                cover, tot, passes = direct_call(e, runs, w, 1, 0)
+                assert passes == 1 and same((cover, tot), ref)
+                kept_rows_are(e, w, "direct wide call %d" % call)
+            kept_rows_are_refused(e, 4096, "behind a call of another width")
+            kept_rows_are_refused(e, w + 1, "behind a call of another width")
+            with pytest.raises(pda.PdError):             # wrap_bits
+                e.scan_reduce_windows(w, 1, 33)
+            kept_rows_are_refused(e, w, "behind a call that failed on its arguments")
+            cover, tot, passes = direct_call(e, runs, 4096, 1, 0)             # narrow windows: the sample goes on as 12-byte runs, no gather
+            assert passes == 1 and same((cover, tot), windows_ref("tile0", 4096, 1, 0))
+            kept_rows_are(e, 4096, "direct narrow call")
+            kept_rows_are_refused(e, w, "behind a call of another width")
+            e.reset()
+            kept_rows_are_refused(e, 4096, "behind pd_reset")
+            assert same(arrays_step(e, first, other, w, 1, 0), ref)
+            kept_rows_are(e, w, "arrays path")
+            e.reset()
+            kept_rows_are_refused(e, w, "behind pd_reset")
+            ft, ot = _device(first, other)
+            e.keep_deferred(False)
+            e.push_intervals_device(ft.data_ptr(), ft.shape[0], pda.PD_PUSH_SORTED)
+            e.push_intervals_device(ot.data_ptr(), ot.shape[0], pda.PD_PUSH_DEFAULT)
+            e.scan(0)
+            kept_rows_are_refused(e, w, "behind pd_scan alone")
+            _, cover, tot = e.reduce_windows(w, 1)
+            assert same((cover, tot), ref)
+            kept_rows_are(e, w, "pd_reduce_windows behind pd_scan")
+            e.keep_deferred(True)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
