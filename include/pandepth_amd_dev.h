@@ -17,7 +17,9 @@ extern "C" {
  * (which compiled variant of the direct kernels runs), "direct_cover" (default 1: the default variant of the compact sample's direct
  * kernel settles the tiles its runs cover without a window; 0: every tile through the window), "direct_cover_min" (default 2048: tiles
  * with fewer candidates are not tried), "cover_narrow" (default 1: that pass sweeps the sorted stream's 2-byte plane where no sorted run is longer
- * than 255 cells; 0: the 4-byte words as before), "decode_crc" (0: the device decoder skips the members' CRC-32 — kernel
+ * than 255 cells; 0: the 4-byte words as before), "cover_fast" (default 1: that narrow sweep first tries a full chunk of 512 sorted runs as a FAST CHUNK, judged
+ * from a summary per lane — pd_cover_rule.h; 0: every chunk through the rule run by run; pd_profile_get("direct_cover_fast"): the chunks the last call
+ * accepted that way), "decode_crc" (0: the device decoder skips the members' CRC-32 — kernel
  * timing only), "decode_near_span" (split of the decoder's later-run stream), "decode_deletions" (0 | 1: this one DOES change results — pd_push_bgzf_units,
  * whose signature is fixed, opens its session with PD_DECODE_DELETIONS while it is 1; sessions opened with pd_decode_begin say so in their own flags and ignore it), "inflate_waves" (one-wave inflate workgroups per CU and
  * launch, 1..23: what the kernel's 7 KB of LDS a wave allow; default 20), "lz_group" (consecutive chunks per workgroup of pd_deflate_parse's LDS parse, 0..16; 0: every chunk reads its

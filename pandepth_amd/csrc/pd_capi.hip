@@ -676,6 +676,7 @@ int pd_set_param(pd_ctx *c, const char *name, uint64_t value)
     if (!strcmp(name, "direct_un")) { c->direct_un = (int)value; return PD_OK; }
     if (!strcmp(name, "direct_cover")) { c->direct_cover = value != 0; return PD_OK; }
     if (!strcmp(name, "cover_narrow")) { c->cover_narrow = value != 0; return PD_OK; }
+    if (!strcmp(name, "cover_fast")) { c->cover_fast = value != 0; return PD_OK; }
     if (!strcmp(name, "direct_cover_min")) { c->direct_cover_min = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "direct_sample")) { if (value < 1 || value > 65536) return fail(c, PD_EINVAL, "direct_sample must be in [1, 65536]"); c->direct_sample = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "decode_crc")) { c->dec_crc = value != 0; return PD_OK; }
@@ -2202,6 +2203,7 @@ int pd_profile_get(pd_ctx *c, const char *name, double *ms, uint64_t *launches)
         uint64_t v = 0; bool hit = false;
         for (auto &d : dn) if (!strcmp(name, d.name)) { v = c->dec_n[d.k].load(); hit = true; }
         if (!strcmp(name, "direct_cover_narrow")) { v = c->direct_narrow; hit = true; }       // 1: the last direct window call's k_direct_c8 swept the narrow plane
+        if (!strcmp(name, "direct_cover_fast")) { v = c->direct_fast; hit = true; }           // chunks of the last direct window call that the narrow sweep accepted as fast chunks
         if (!strcmp(name, "direct_cover_settled")) { v = c->direct_settled; hit = true; }     // tiles of the last direct window call that k_direct_c8 settled without a window
         if (!strcmp(name, "direct_pileup_tiles")) { v = c->direct_pileup; hit = true; }       // ... and the tiles it left to the pile-up pass (k_c8_heavy)
         if (!strcmp(name, "decode_chain_device")) { v = c->dec_n_fast.load(); hit = true; }

@@ -135,4 +135,96 @@ PD_COVER_HD inline Seg seg_sweep_nar(const uint16_t *nar, uint32_t n, uint32_t l
     return s;
 }
 
+// ---- the FAST CHUNK of the narrow sweep: a full chunk (512 runs, eight consecutive runs per lane, 64 lanes) settled without a begin per run ----
+// A lane holds its eight half-words as four words x[0 .. 3] (run 2j in the low half of x[j]).  Everything below is relative to the lane's
+// PREDECESSOR, the run in front of the lane's first (the lane before's last; lane 0: the last run of the chunk before, or the tile's first candidate):
+//   rb[k]  the rebuilt begin of the lane's run k minus the predecessor's — the prefix sum of the low-byte differences, each modulo 256;
+//   T      = rb[7], the lane's last begin;   Mrel = max_k(rb[k] + len[k]), the lane's largest end;   lens = the sum of the eight lengths.
+// With `base` the rebuilt begin of the run before the chunk, lane l's last begin is lane_last = base + T_0 + .. + T_l and its largest end is
+// lane_last - T_l + Mrel_l: two wave scans give every lane P = max(reach, largest end of the lanes before it) and the chunk its largest end, top.
+// The chunk is ACCEPTED when base >= 0, every lane has lane_last <= P, and top <= tile.  Then the rule (seg_sweep_nar) leaves exactly: no new gap,
+// reach = max(reach, top), sum += the lengths, because
+//   * every begin of a lane is <= its last (the steps are >= 0) <= P <= the running maximum the rule would compare it with: no run is a gap;
+//   * the rebuilt begins never decrease, so base >= 0 puts every begin at or behind cell 0: nothing is clipped in front;
+//   * top <= tile: no end is clipped behind.  The clipped sum is the sum of the length bytes.
+// A chunk that is not accepted says nothing (a gap inside a lane may be closed by a long run of an earlier lane): it goes through the rule itself.
+struct NarLane { int T, Mrel; uint32_t lens; };
+
+// the two steps of a word: x holds two runs' half-words, y their predecessors' (y = (x << 16) | (the word before >> 16)); the low byte of each half of
+// the result is that run's step (nar_step), the high bytes mean nothing.  (A packed 16-bit subtraction: v_pk_sub_u16.)
+PD_COVER_HD inline uint32_t nar_pair_steps(uint32_t x, uint32_t y)
+{
+    typedef unsigned short u16x2 __attribute__((vector_size(4)));
+    u16x2 a, b;
+    __builtin_memcpy(&a, &x, 4); __builtin_memcpy(&b, &y, 4);
+    a -= b;
+    uint32_t d;
+    __builtin_memcpy(&d, &a, 4);
+    return d;
+}
+// the predecessors' word of x, `before` being the word in front of it (for a lane's first word: the lane before's last; the predecessor alone: << 16)
+PD_COVER_HD inline uint32_t nar_pred_word(uint32_t x, uint32_t before) { return (x << 16) | (before >> 16); }
+// x . (0, 1, 0, 1) over bytes: the two lengths of a word, added to acc (v_dot4_u32_u8 with the selector NAR_LEN_SEL)
+constexpr uint32_t NAR_LEN_SEL = 0x01000100u;
+PD_COVER_HD inline uint32_t nar_add_lens(uint32_t x, uint32_t acc)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_udot4(x, NAR_LEN_SEL, acc, false);
+#else
+    for (int k = 0; k < 4; ++k) acc += ((x >> (8 * k)) & 255u) * ((NAR_LEN_SEL >> (8 * k)) & 255u);
+    return acc;
+#endif
+}
+// the lane's summary from its four words and `before`, whose HIGH half is the predecessor's half-word
+PD_COVER_HD inline NarLane nar_lane_summary(const uint32_t (&x)[4], uint32_t before)
+{
+    NarLane s{0, NONE, 0u};
+    int rb = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t d = nar_pair_steps(x[j], nar_pred_word(x[j], j ? x[j - 1] : before));
+        rb += (int)(d & 255u);
+        const int e0 = rb + (int)((x[j] >> 8) & 255u);
+        rb += (int)((d >> 16) & 255u);
+        const int e1 = rb + (int)(x[j] >> 24);
+        const int m = e0 > e1 ? e0 : e1;
+        s.Mrel = s.Mrel > m ? s.Mrel : m;
+        s.lens = nar_add_lens(x[j], s.lens);
+    }
+    s.T = rb;
+    return s;
+}
+// may a chunk of cnt runs behind a run that begins at base be tried at all? (wave-uniform, known before any work)
+PD_COVER_HD inline bool chunk_fast_entry(uint32_t cnt, int base) { return cnt == 512u && base >= 0; }
+// one lane's part of the test: before = the largest end of the lanes before it (NONE for lane 0)
+PD_COVER_HD inline bool chunk_fast_lane_ok(int lane_last, int before, int reach) { return !(lane_last > (before > reach ? before : reach)); }
+// the acceptance test: every lane's part held, and the chunk's largest end lies in the tile
+PD_COVER_HD inline bool chunk_fast_ok(bool every_lane_ok, int top, int tile) { return every_lane_ok && top <= tile; }
+
+// The sweep's state between chunks, and the fast chunk on it, lane after lane (the kernel's wave does the two scans with DPP): true and the state
+// moved when the chunk was accepted, false and NOTHING changed otherwise.  nar: the chunk's 512 half-words; pb: the half-word of the run before it.
+struct NarState { int base, reach; uint32_t pb, sum; int gap; };
+PD_COVER_HD inline bool chunk_fast(const uint16_t *nar, NarState &st, int tile)
+{
+    if (!chunk_fast_entry(512u, st.base)) return false;
+    uint32_t before = st.pb << 16, lens = 0u;
+    int lane_last = st.base, incl = NONE;
+    bool every = true;
+    for (int l = 0; l < 64; ++l) {
+        uint32_t x[4];
+        for (int j = 0; j < 4; ++j) x[j] = (uint32_t)nar[8 * l + 2 * j] | ((uint32_t)nar[8 * l + 2 * j + 1] << 16);
+        const NarLane s = nar_lane_summary(x, before);
+        lane_last += s.T;
+        every = every && chunk_fast_lane_ok(lane_last, incl, st.reach);
+        const int m = lane_last - s.T + s.Mrel;
+        incl = incl > m ? incl : m;
+        lens += s.lens;
+        before = x[3];
+    }
+    if (!chunk_fast_ok(every, incl, tile)) return false;
+    st.reach = st.reach > incl ? st.reach : incl;
+    st.base = lane_last; st.pb = before >> 16; st.sum += lens;
+    return true;
+}
+
 } // namespace pdcover

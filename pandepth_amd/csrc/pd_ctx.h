@@ -175,6 +175,8 @@ struct pd_ctx {
     bool direct_cover = true;                                    // k_direct_c8's default form settles covered tiles from the runs (false: the window path for every tile)
     uint32_t direct_cover_min = 2048;                            // ... of tiles with at least this many candidates (launch_direct_c8)
     bool cover_narrow = true;                                    // ... from the sorted stream's narrow plane where the sample allows it ("cover_narrow"; pd_runs::n_wide_sorted == 0)
+    bool cover_fast = true;                                      // ... whose full chunks are first tried as fast chunks ("cover_fast"; pd_cover_rule.h)
+    uint64_t direct_fast = 0;                                    // chunks the narrow sweep accepted as fast chunks in the last direct_windows call ("direct_cover_fast")
     uint64_t direct_narrow = 0;                                  // 1: the last direct_windows call launched the narrow form ("direct_cover_narrow")
     uint64_t direct_settled = 0;                                 // tiles the cover pass settled in the last direct_windows call
     uint64_t direct_pileup = 0;                                  // pile-up tiles k_direct_c8 listed in the last direct_windows call (the int-window pass did them)

@@ -130,8 +130,11 @@ void launch_copy_planes(hipStream_t st, uint32_t *dst_lo, uint32_t *dst_hi, cons
 // added to heavy_count[PD_HEAVY_SETTLED]; tiles with fewer than cover_min candidates are not tried.  narrow (with cover only): the form whose pass
 // sweeps the sorted stream from cs.nar — the caller's promise that no sorted run is longer than 255 cells; returns whether that form was the one launched
 constexpr int PD_HEAVY_SETTLED = 10;
+// fast (narrow form only, "cover_fast"): full chunks of the sorted stream are first tried as FAST CHUNKS (pd_cover_rule.h); how many were accepted is added to
+// heavy_count[PD_HEAVY_FAST]
+constexpr int PD_HEAVY_FAST = 11;
 bool launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
-                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min, bool narrow = false);
+                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min, bool narrow = false, bool fast = true);
 // ... and the int-window pass for the pile-up tiles k_direct_c8 leaves: k_c8_heavy (it reads tab, tile_contig and the bucket starts in cs), a workgroup per
 // listed tile up to 1024.  Its own launcher: the caller launches it only for a sample that has pile-up tiles, with the SAMPLE's list and count
 // (pd_runs::heavy_tiles / n_heavy, made by k_c8_tile_desc) — nothing of it waits for k_direct_c8, whose TileParts are other tiles', so the two may run side by side.
@@ -175,7 +178,7 @@ void launch_window_edges(hipStream_t st, const TilePart *part, TileMap tm, uint3
 // the PD_STATUS_WORDS status words the NEXT call will use (next_words: that call's kernels are behind this one in the stream) and copies this
 // call's PD_STATUS_READ words, final when the gather starts, to the host's buffer; every window's cover and sum are stored to the page-locked
 // buffer as well (pin_cover / pin_sum / pin_words: its device address).
-constexpr int PD_STATUS_WORDS = 16, PD_STATUS_READ = 13;
+constexpr int PD_STATUS_WORDS = 16, PD_STATUS_READ = 14;
 struct GatherCall { uint32_t *next_words; const uint32_t *words; uint32_t *pin_words; uint32_t *pin_cover; unsigned long long *pin_sum; };
 void launch_window_gather(hipStream_t st, const TilePart *part, TileMap tm, int32_t n_contigs, uint32_t w,
                           uint64_t n_windows, uint32_t *cover, unsigned long long *sum, const GatherCall &gc = GatherCall{});

@@ -483,7 +483,8 @@ __device__ __forceinline__ void direct_candidate(const pd_iv v, int32_t ctg, uin
     c.carry += (mine && nonempty && bb < p0 && x >= p0) ? 1 : 0;  // covers the cell just before the tile
 }
 
-struct DirectWide { static constexpr bool narrow = false, exporting = false; uint32_t w, min_dep; TilePart *part; uint32_t cover_min = 0; /* k_direct_c8's cover pass: tiles with fewer candidates are left to the window */ };
+struct DirectWide { static constexpr bool narrow = false, exporting = false; uint32_t w, min_dep; TilePart *part; uint32_t cover_min = 0; /* k_direct_c8's cover pass: tiles with fewer candidates are left to the window */
+                    uint32_t cover_fast = 0; /* ... and its narrow sweep tries the fast chunk (pd_cover_rule.h) */ };
 struct DirectNarrow { static constexpr bool narrow = true, exporting = false; WinArgs wa; const uint64_t *win_off; };
 struct DirectExport {                  // the multi-GPU sum's 4-bit image straight from the tile windows (pd_export_i4)
     static constexpr bool narrow = false, exporting = true;
@@ -1833,6 +1834,7 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
     __shared__ int red_c[4][2];
     __shared__ __attribute__((aligned(16))) uint32_t s_cov[2][4];  // COVER: the outcome of each wave's tile (COV_*), two sets in turn
     uint32_t cov_flip = 0, cov_miss = 0, cov_skip = 0, cov_settled = 0;   // COVER, workgroup-uniform
+    uint32_t cov_fast = 0;                                        // NARROW, wave-uniform: the chunks this wave's sweeps accepted as fast chunks
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // COVER: a step of the walk is a GROUP of four consecutive tiles, one per wave in the cover pass, and the window path for those the pass left
     constexpr uint32_t GT = COVER ? 4u : 1u;
@@ -1955,6 +1957,28 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
                             return;
                         }
                         const uint32_t cnt = sorted_cnt(q);
+                        // The FAST CHUNK (pd_cover_rule.h, where the proof stands): a full chunk behind a run that begins at or behind cell 0, judged by
+                        // lanes — a lane whose LAST begin lies within P = max(reach, the ends of the lanes before it) has no gap (its other begins are no
+                        // larger, and the rule would compare them with no less than P); base >= 0 and top <= TILE mean that nothing is clipped, so the sum
+                        // is the sum of the length bytes.  An accepted chunk leaves reach, base, pb, sum and gap exactly as the rule below would; a refused
+                        // one has changed nothing and goes through the rule.
+                        if (args.cover_fast && pdcover::chunk_fast_entry(cnt, base)) {
+                            const uint32_t before_w = (uint32_t)wave_shift_up((int)x[3], (int)(pb << 16));
+                            const pdcover::NarLane s = pdcover::nar_lane_summary(x, before_w);
+                            const int lane_last = base + wave_incl_scan(s.T);
+                            const int incl = wave_incl_scan_max(lane_last - s.T + s.Mrel);
+                            const int before = wave_shift_up(incl, pdcover::NONE);
+                            const int top = __builtin_amdgcn_readlane(incl, 63);
+                            const bool every = __builtin_amdgcn_ballot_w64(!pdcover::chunk_fast_lane_ok(lane_last, before, reach)) == 0ull;
+                            if (pdcover::chunk_fast_ok(every, top, (int)ST)) {
+                                reach = top > reach ? top : reach;
+                                base = __builtin_amdgcn_readlane(lane_last, 63);
+                                pb = (uint32_t)__builtin_amdgcn_readlane((int)x[3], 63) >> 16;
+                                sum += s.lens;
+                                ++cov_fast;
+                                return;
+                            }
+                        }
                         uint32_t h[8] = {x[0] & 0xFFFFu, x[0] >> 16, x[1] & 0xFFFFu, x[1] >> 16, x[2] & 0xFFFFu, x[2] >> 16, x[3] & 0xFFFFu, x[3] >> 16};
                         const uint32_t last_lane = (cnt - 1u) >> 3;                                 // the lane that holds the chunk's last run, in its last place
                         const uint32_t lastb = (uint32_t)__builtin_amdgcn_readlane((int)h[7], (int)last_lane);
@@ -2396,6 +2420,13 @@ __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const 
     }
     if constexpr (COVER) {                                        // how many tiles the pass settled: one addition per workgroup, for the tests
         if (threadIdx.x == 0 && cov_settled) atomicAdd(heavy_count + PD_HEAVY_SETTLED, cov_settled);
+        if constexpr (NARROW) {                                   // ... and how many chunks went the fast way: the four waves' counts, one addition
+            __syncthreads();                                      // (wtot's last readers are done)
+            if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = (int)cov_fast;
+            __syncthreads();
+            const uint32_t n_fast = (uint32_t)(wtot[0] + wtot[1] + wtot[2] + wtot[3]);
+            if (threadIdx.x == 0 && n_fast) atomicAdd(heavy_count + PD_HEAVY_FAST, n_fast);
+        }
     }
 }
 
@@ -3718,7 +3749,7 @@ void launch_r8_to_iv(hipStream_t st, const uint32_t *lo, const uint32_t *hi, uin
 }
 
 bool launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
-                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min, bool narrow)
+                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min, bool narrow, bool fast)
 {
     // cover_min ("direct_cover_min", default 2048 candidates per tile): a tile visit costs the cover pass more than the window path before its first run
     // (measured on the bench genome, ms per launch with / without the pass tried on every tile: 1e9 records, 3 224 candidates per tile: 1.10 / 1.38; 3e8,
@@ -3732,7 +3763,7 @@ bool launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_
     // after the first of them where every tile has gaps.  With the quarter-per-wave pass and a workgroup per five or six tiles such a sample paid a sweep on
     // top of the window for most of its tiles — 1.480 -> 1.949 ms where every tile has gaps, 1.440 -> 1.624 where every other has
     // (profiles/r10_direct_cover_ab.txt, section 6); what it pays now: r13, section 5.  "direct_cover" 0 remains the way out.
-    const DirectWide dw{w, min_dep, part, cover_min};
+    const DirectWide dw{w, min_dep, part, cover_min, fast ? 1u : 0u};
     bool took_narrow = false;
     // "direct_un" for a compact sample: 100 x waves-per-SIMD target + loads in flight per thread (0 = default)
 #define PD_C8(WPE_, UN8_) hipLaunchKernelGGL((k_direct_c8<WPE_, UN8_, false>), dim3(grid_tiles), dim3(WG), 0, st, cs, desc, n_tiles, wrap_mask, dw, heavy_list, heavy_count, DirectExport{})

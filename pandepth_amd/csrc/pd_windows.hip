@@ -124,7 +124,7 @@ struct DirectCall {
     const uint64_t *d_wo; unsigned long long *d_sum; uint32_t *d_cov; TilePart *d_part;
     uint32_t *d_words, *d_words_next;                    // [n_long, fail, heavy_count, diagnostics ..., [12] tiles settled by the cover pass]; the heavy tile list: c->direct_words + 16
     bool c8; PendSet ps; uint64_t all; unsigned grid;
-    uint32_t words[PD_STATUS_READ];                      // ... as read back; [12]: heavy_count[PD_HEAVY_SETTLED]
+    uint32_t words[PD_STATUS_READ];                      // ... as read back; [12]: heavy_count[PD_HEAVY_SETTLED], [13]: [PD_HEAVY_FAST]
 };
 
 // step 1: the layout, the buffers it needs and the pointers into them
@@ -193,7 +193,7 @@ int direct_c8(pd_ctx *c, const DirectCall &d)
                                             c->n_cu, c->grid_tiles, c->direct_un}, d.grid);
     if (cr->n_heavy) HIPOK(c, heavy_fork(c));
     c->direct_narrow = launch_direct_c8(c->stream, cr->view(), cr->td, (uint32_t)c->n_tiles, d.mask, d.w, d.min_dep, d.d_part, c->direct_words + 16, d.d_words + 2,
-                                        cp.grid, c->direct_un, cp.cover, c->direct_cover_min, cp.narrow) ? 1 : 0;
+                                        cp.grid, c->direct_un, cp.cover, c->direct_cover_min, cp.narrow, c->cover_fast) ? 1 : 0;
     if (!cr->n_heavy) return PD_OK;
     hipError_t e = hipStreamWaitEvent(c->side_stream, c->ev_fork, 0);
     if (e == hipSuccess) {
@@ -272,6 +272,7 @@ int direct_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, uint32_t mask, uint3
     if (d.c8 && words[2] != c->pend[0].cr->n_heavy)      // step 7 (k_direct_c8's own count of the tiles it listed: the same candidates, the same threshold)
         return fail(c, PD_ESTATE, "direct windows: the kernel listed " + std::to_string(words[2]) + " pile-up tiles, the sample was made with " + std::to_string(c->pend[0].cr->n_heavy));
     c->direct_settled = words[2 + pdk::PD_HEAVY_SETTLED];
+    c->direct_fast = words[2 + pdk::PD_HEAVY_FAST];
     c->direct_pileup = d.c8 ? words[2] : 0;
     if (words[1]) { direct_decline_note(words); return PD_OK; }
     if (d.rb.pinned) { memcpy(sum, c->win.pin, d.lay.b_sum); memcpy(cover, c->win.pin + d.lay.b_sum, (size_t)d.lay.nw * 4); }
@@ -355,7 +356,7 @@ int pd_scan_reduce_windows(pd_ctx *c, uint32_t w, uint32_t min_dep, unsigned wra
     if (!cover || !sum || w == 0 || wrap_bits > 32) return PD_EINVAL;
     if (int rs = need_state(c, 0, "pd_scan_reduce_windows")) return rs;
     HIPOK(c, hipSetDevice(c->device));
-    c->direct_settled = 0; c->direct_pileup = 0; c->direct_narrow = 0;
+    c->direct_settled = 0; c->direct_pileup = 0; c->direct_narrow = 0; c->direct_fast = 0;
     const uint32_t mask = wrap_mask(wrap_bits);
     if (c->direct_windows && c->pristine && !c->pend.empty() && w >= 64 && c->stile == PD_TILE) {
         bool done = false;
