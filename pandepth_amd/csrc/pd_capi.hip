@@ -1,4 +1,4 @@
-// pd_capi.hip — implementation of include/pandepth_amd.h on top of pd_kernels.hip.
+// pd_capi.hip — implementation of include/pandepth_amd.h on top of pd_kernels.hip and pd_direct.hip.
 //
 // One context = one GPU, one compute stream, one copy stream, one int32 allocation holding all
 // contig difference arrays followed by the tile sums.  Host batches go through a small pool of

@@ -1,6 +1,6 @@
 // pd_cover_rule.h — when is a tile of the direct depth pass COVERED by its candidates, decided from the runs alone (no per-cell depth)?
 //
-// k_direct_c8's cover pass (pd_kernels.hip) and tests/harness/cover_rule_check.cpp (against a per-cell union, on the CPU) share this code.
+// k_direct_c8's cover pass (pd_direct.hip) and tests/harness/cover_rule_check.cpp (against a per-cell union, on the CPU) share this code.
 //
 // The candidates of a tile are lo words r = (b & 0xFFFF) | (len << 16) (pd_kernels.h) and p0 is the low 16 bits of the tile's first flat
 // cell.  In the kernel's own 16-bit arithmetic sb = (r - p0) & 0xFFFF is < tile for the tile's own runs and lies in [2^16 - bucket, 2^16)

@@ -1,4 +1,4 @@
-// pd_kernels.h — structs and launch wrappers shared by pd_kernels.hip and pd_capi.hip.
+// pd_kernels.h — structs and launch wrappers: launch_direct_* are defined in pd_direct.hip (the direct depth pass), the other launch_* of the first namespace block in pd_kernels.hip; callers are pd_capi.hip and pd_windows.hip.
 #ifndef PD_KERNELS_H_
 #define PD_KERNELS_H_
 #include <hip/hip_runtime.h>
@@ -133,15 +133,19 @@ constexpr int PD_HEAVY_SETTLED = 10;
 // fast (narrow form only, "cover_fast"): full chunks of the sorted stream are first tried as FAST CHUNKS (pd_cover_rule.h); how many were accepted is added to
 // heavy_count[PD_HEAVY_FAST]
 constexpr int PD_HEAVY_FAST = 11;
-bool launch_direct_c8(hipStream_t st, C8Sample cs, const TileDesc *desc, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w,
-                      uint32_t min_dep, TilePart *part, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, int un, bool cover, uint32_t cover_min, bool narrow = false, bool fast = true);
+// One record for both launches of k_direct_c8 (the caller fills it by field name; a form reads its own part and the common one).  un: "direct_un", 0 = default.
+struct DirectC8Launch {
+    hipStream_t st; C8Sample cs; const TileDesc *desc; uint32_t n_tiles; uint32_t *heavy_list, *heavy_count; unsigned grid_tiles;   // both forms
+    uint32_t wrap_mask, w, min_dep; TilePart *part; int un; bool cover; uint32_t cover_min; bool narrow, fast;                      // statistics (launch_direct_c8)
+    ContigTab tab; const uint32_t *tile_contig; void *img; pd_exc *exc; uint32_t cap; uint32_t *count; int *sums; uint32_t n_heavy;   // export (launch_direct_c8_export)
+};
+bool launch_direct_c8(const DirectC8Launch &L);
 // ... and the int-window pass for the pile-up tiles k_direct_c8 leaves: k_c8_heavy (it reads tab, tile_contig and the bucket starts in cs), a workgroup per
 // listed tile up to 1024.  Its own launcher: the caller launches it only for a sample that has pile-up tiles, with the SAMPLE's list and count
 // (pd_runs::heavy_tiles / n_heavy, made by k_c8_tile_desc) — nothing of it waits for k_direct_c8, whose TileParts are other tiles', so the two may run side by side.
 void launch_direct_c8_heavy(hipStream_t st, C8Sample cs, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, uint32_t wrap_mask, uint32_t w, uint32_t min_dep,
                             TilePart *part, const uint32_t *heavy_tiles, uint32_t n_heavy);
-void launch_direct_c8_export(hipStream_t st, C8Sample cs, const TileDesc *desc, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles, void *img, pd_exc *exc,
-                             uint32_t cap, uint32_t *count, int *sums, uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles, uint32_t n_heavy);
+void launch_direct_c8_export(const DirectC8Launch &L);
 void launch_direct_export(hipStream_t st, const PendSet &ps, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles,
                           void *img, pd_exc *exc, uint32_t cap, uint32_t *count, int *sums, uint32_t *n_long, uint32_t *fail,
                           uint32_t *heavy_list, uint32_t *heavy_count, unsigned grid_tiles);

@@ -1,6 +1,6 @@
 // pd_pile_rule.h — neighbouring lanes of a wave that add to the SAME cell add once: the grouping rule of the pile-up pass.
 //
-// k_c8_heavy (pd_kernels.hip) and tests/harness/pile_rule_check.cpp (against a window built run by run, on the CPU) share this code.
+// k_c8_heavy (pd_direct.hip) and tests/harness/pile_rule_check.cpp (against a window built run by run, on the CPU) share this code.
 //
 // A wave holds 64 values (the window cells its lanes would add 1 to, or take 1 from) and 64 validity bits (a lane whose run has no cells,
 // or whose cell lies outside the tile, adds nothing).  A GROUP is a maximal stretch of consecutive valid lanes with equal values; its first

@@ -192,8 +192,12 @@ int direct_c8(pd_ctx *c, const DirectCall &d)
     const CoverPlan cp = cover_plan(CoverIn{c->direct_cover, c->cover_narrow, cr->nar != nullptr, c->direct_cover_min, cr->n_wide_sorted, d.all, c->n_tiles,
                                             c->n_cu, c->grid_tiles, c->direct_un}, d.grid);
     if (cr->n_heavy) HIPOK(c, heavy_fork(c));
-    c->direct_narrow = launch_direct_c8(c->stream, cr->view(), cr->td, (uint32_t)c->n_tiles, d.mask, d.w, d.min_dep, d.d_part, c->direct_words + 16, d.d_words + 2,
-                                        cp.grid, c->direct_un, cp.cover, c->direct_cover_min, cp.narrow, c->cover_fast) ? 1 : 0;
+    DirectC8Launch L{};
+    L.st = c->stream; L.cs = cr->view(); L.desc = cr->td; L.n_tiles = (uint32_t)c->n_tiles;
+    L.heavy_list = c->direct_words + 16; L.heavy_count = d.d_words + 2; L.grid_tiles = cp.grid;
+    L.wrap_mask = d.mask; L.w = d.w; L.min_dep = d.min_dep; L.part = d.d_part;
+    L.un = c->direct_un; L.cover = cp.cover; L.cover_min = c->direct_cover_min; L.narrow = cp.narrow; L.fast = c->cover_fast;
+    c->direct_narrow = launch_direct_c8(L) ? 1 : 0;
     if (!cr->n_heavy) return PD_OK;
     hipError_t e = hipStreamWaitEvent(c->side_stream, c->ev_fork, 0);
     if (e == hipSuccess) {
@@ -297,9 +301,14 @@ int export_launch(pd_ctx *c, void *dev_i4, pd_exc *dev_exc, uint32_t exc_cap, ui
     if (int rc = pend_prepare(c, c->sample < 256 ? 256 : c->sample, (uint32_t)c->n_tiles, PD_TILE, c8, &ps, &all)) return rc;
     const unsigned grid = pass_grid(all, c->n_cu, c->grid_tiles, c->n_tiles);
     { ProfScope sc(c, "direct_export");
-      if (c8) launch_direct_c8_export(c->stream, p0.cr->view(), p0.cr->td, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, dev_i4, dev_exc, exc_cap,
-                                      dev_count, c->sums, c->direct_words + 16, c->direct_words + 2, grid, p0.cr->n_heavy);
-      else launch_direct_export(c->stream, ps, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, dev_i4, dev_exc, exc_cap, dev_count,
+      if (c8) {
+          DirectC8Launch L{};
+          L.st = c->stream; L.cs = p0.cr->view(); L.desc = p0.cr->td; L.n_tiles = (uint32_t)c->n_tiles;
+          L.heavy_list = c->direct_words + 16; L.heavy_count = c->direct_words + 2; L.grid_tiles = grid;
+          L.tab = tab_of(c); L.tile_contig = c->d_tile_contig; L.img = dev_i4; L.exc = dev_exc; L.cap = exc_cap; L.count = dev_count; L.sums = c->sums;
+          L.n_heavy = p0.cr->n_heavy;
+          launch_direct_c8_export(L);
+      } else launch_direct_export(c->stream, ps, tab_of(c), c->d_tile_contig, (uint32_t)c->n_tiles, dev_i4, dev_exc, exc_cap, dev_count,
                                 c->sums, c->direct_words, c->direct_words + 1, c->direct_words + 16, c->direct_words + 2, grid); }
     HIPOK(c, hipGetLastError());
     return PD_OK;

@@ -36,7 +36,7 @@ WS = (W1, 8192)
 MODES = ((1, 0), (0, 0))
 NO_END = -32768                                          # pdcover::NONE
 WINDOW, DECLINED, SETTLED = 1, 2, 3                      # a tile's outcome in the cover pass (k_direct_c8: COV_*)
-COVER_DECLINE, COVER_CLOSE, COVER_SKIP = 2, 8, 15        # the gate (pd_kernels.hip)
+COVER_DECLINE, COVER_CLOSE, COVER_SKIP = 2, 8, 15        # the gate (pd_direct.hip)
 
 
 def sweep_tile(b, ln, min_dep):

@@ -18,7 +18,7 @@ from test_gpu_direct_cover import T, _create, _device, sort_iv
 
 gpu = pytest.mark.gpu
 
-CW = 512                                                 # sorted runs per chunk of the narrow sweep (pd_kernels.hip: k_direct_c8, NARROW)
+CW = 512                                                 # sorted runs per chunk of the narrow sweep (pd_direct.hip: k_direct_c8, NARROW)
 W1 = 10000000
 LENS = [9 * T + 5, 3 * T]                                # contig 0: tiles 0 .. 8 whole (first flat cells 57344 and 65536 among them) + 5 cells; contig 1: tiles 10 .. 12
 NONE = np.zeros((0, 3), dtype=np.int32)

@@ -16,7 +16,7 @@ from test_gpu_direct_cover import GRIDS, LENS, MODES, T, WS, _create, _device, c
 
 gpu = pytest.mark.gpu
 
-CW = 512                                                 # runs per chunk of the sweep (pd_kernels.hip: k_direct_c8, COVER)
+CW = 512                                                 # runs per chunk of the sweep (pd_direct.hip: k_direct_c8, COVER)
 W1 = 10000000
 
 

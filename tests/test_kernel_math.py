@@ -3,7 +3,7 @@ import numpy as np
 
 
 def test_window_index_by_multiplication_is_exact():
-    """pd_kernels.hip: narrow_window_row takes floor(x / w) as __umulhi(x, ceil(2^32 / w)) for x = cell + phase < 2^14 and
+    """pd_dev.h: narrow_window_row takes floor(x / w) as __umulhi(x, ceil(2^32 / w)) for x = cell + phase < 2^14 and
     2 <= w < 8192 (k_sweep / the direct kernels' narrow windows): exact for every such pair (checked up to x < 24576)."""
     x = np.arange(0, 24576, dtype=np.uint64)
     for w in range(2, 8192):
