@@ -459,6 +459,15 @@ typedef struct pd_decode_cfg {
                                     /* after the runs are as without the flag; pd_decode_result::n_first / n_other count groups.       */
                                     /* (Long reads become runs longer than a bucket: a PD_DECODE_COMPACT session counts them and the   */
                                     /* compact sample takes them by its long-run path, as it does any such run.)                       */
+                                    /* PD_DECODE_FRAGMENTS — whole fragments of properly paired reads (the executable's -frag).  A kept  */
+                                    /* read is a FRAGMENT READ when flag & 0x3 == 0x3, flag & 0x908 == 0, next_refID == refID, tlen != 0 */
+                                    /* and |tlen| <= the bound (|tlen| unsigned: INT32_MIN never passes).  With tlen > 0 it adds exactly  */
+                                    /* ONE run [pos, (int32)((uint32)pos + (uint32)tlen)), its first run; its CIGAR is not walked and    */
+                                    /* that end is its endpos in the span test (pos + 1 where it equals pos).  With tlen < 0 it adds      */
+                                    /* nothing: n_records counts it, n_first / n_other do not.  Every other kept read is walked as       */
+                                    /* without the flag (by the group rule with PD_DECODE_DELETIONS: the two combine).  The bound is the   */
+                                    /* parameter pd_set_param("decode_frag_max", N) as pd_decode_begin finds it: N <= 2^31 - 1, 0 (the    */
+                                    /* default) = no bound; a pair above it counts as two ordinary reads.  This struct keeps its layout.  */
     uint64_t n_batches;             /* 0 = unknown.  Otherwise the caller promises to submit exactly this many batches, once each, with */
                                     /* pd_decode_batch::order = 0 .. n_batches - 1 in file order (a batch with nothing to decode is still   */
                                     /* submitted, empty; orders need not ARRIVE in order, but a thread must hold its buffer — pd_decode_-   */
@@ -469,6 +478,7 @@ typedef struct pd_decode_cfg {
 } pd_decode_cfg;
 #define PD_DECODE_COMPACT 1u
 #define PD_DECODE_DELETIONS 2u
+#define PD_DECODE_FRAGMENTS 4u
 typedef struct pd_decode_unit { uint64_t start, stop, avail; uint32_t first_block, n_blocks, flags, pad; } pd_decode_unit;
 typedef struct pd_decode_batch {
     void *host_buf; size_t n_bytes;                              /* from pd_decode_acquire: whole BGZF members           */

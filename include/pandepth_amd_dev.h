@@ -21,7 +21,8 @@ extern "C" {
  * from a summary per lane — pd_cover_rule.h; 0: every chunk through the rule run by run; pd_profile_get("direct_cover_fast"): the chunks the last call
  * accepted that way), "decode_crc" (0: the device decoder skips the members' CRC-32 — kernel
  * timing only), "decode_near_span" (split of the decoder's later-run stream), "decode_deletions" (0 | 1: this one DOES change results — pd_push_bgzf_units,
- * whose signature is fixed, opens its session with PD_DECODE_DELETIONS while it is 1; sessions opened with pd_decode_begin say so in their own flags and ignore it), "inflate_waves" (one-wave inflate workgroups per CU and
+ * whose signature is fixed, opens its session with PD_DECODE_DELETIONS while it is 1; sessions opened with pd_decode_begin say so in their own flags and ignore it), "decode_fragments" (0 | 1: the same for PD_DECODE_FRAGMENTS) and "decode_frag_max" (0 .. 2^31 - 1, 0: no bound: the largest |tlen|
+ * of a fragment read; every pd_decode_begin, the one inside pd_push_bgzf_units included, takes the value it finds for its whole session), "inflate_waves" (one-wave inflate workgroups per CU and
  * launch, 1..23: what the kernel's 7 KB of LDS a wave allow; default 20), "lz_group" (consecutive chunks per workgroup of pd_deflate_parse's LDS parse, 0..16; 0: every chunk reads its
  * text from memory), "lz_slots" (2 | 4 parse calls in flight).  Round 6, the decode pipeline: "decode_h2d_fifo" (default 1: the batches' host-to-device copies
  * first come, first served on the context's main stream, one copy per batch; 0: on the batch's own stream), "decode_h2d_lanes" (1 | 2 copies on the link at a

@@ -21,6 +21,7 @@ PD_TILE = 8192
 PD_UNIT_GUESS = 1
 PD_DECODE_COMPACT = 1
 PD_DECODE_DELETIONS = 2
+PD_DECODE_FRAGMENTS = 4
 PD_NONE = 0xFFFFFFFFFFFFFFFF                     # pd_decode_result::first_start / next_start: no such record
 
 
@@ -576,11 +577,13 @@ class Engine:
         self._ck(self.L.pd_gather_windows(self.h, ctypes.c_void_p(int(partials_ptr)), int(w), _ptr(cover), _ptr(tot)))
         return off, cover[:n], tot[:n]
 
-    def push_bgzf_units(self, blob, blocks, units, inflated_bytes, flag_mask=1796, min_mapq=-1, count_deletions=False):
+    def push_bgzf_units(self, blob, blocks, units, inflated_bytes, flag_mask=1796, min_mapq=-1, count_deletions=False, fragments=False, frag_max=0):
         """blocks: (n,4) uint64-compatible rows {in_off, out_off, in_len, out_len}; units: rows
         {start, stop, avail, first_block, n_blocks}.  Returns (unit_status int32 array, n_records).
         count_deletions: deletions count as covered (PD_DECODE_DELETIONS).  The C entry takes it from the parameter "decode_deletions",
-        which every call here sets to this argument's value: the argument alone decides, whatever set_param left there."""
+        which every call here sets to this argument's value: the argument alone decides, whatever set_param left there.
+        fragments, frag_max: whole fragments of properly paired reads (PD_DECODE_FRAGMENTS) and the bound on |tlen| (0: none), by the
+        parameters "decode_fragments" and "decode_frag_max" in the same way."""
         blob = np.frombuffer(blob, dtype=np.uint8)
         bd = np.zeros(len(blocks), dtype=np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4")]))
         for k, name in enumerate(("in_off", "out_off", "in_len", "out_len")):
@@ -592,6 +595,8 @@ class Engine:
         st = np.zeros(max(1, len(units)), dtype=np.int32)
         nrec = ctypes.c_uint64()
         self.set_param("decode_deletions", 1 if count_deletions else 0)
+        self.set_param("decode_fragments", 1 if fragments else 0)
+        self.set_param("decode_frag_max", int(frag_max))
         self._ck(self.L.pd_push_bgzf_units(self.h, _ptr(blob), blob.size, _ptr(bd), len(blocks), _ptr(ud), len(units),
                                            int(inflated_bytes), int(flag_mask), int(min_mapq), _ptr(st), ctypes.byref(nrec)))
         return st[:len(units)], int(nrec.value)
@@ -630,10 +635,15 @@ class DecodeSession:
         self.held = []                       # buffers acquired and not yet handed to submit / queue
 
     def begin(self, flag_mask=1796, min_mapq=-1, contig_on=None, span_off=None, spans=None, sorted=1, bytes_hint=0, batch_bytes=0,
-              batches_in_flight=0, flags=0, n_batches=0, count_deletions=False):
-        """count_deletions adds PD_DECODE_DELETIONS to `flags`: deletions count as covered, one run per group of M/=/X/D operations"""
+              batches_in_flight=0, flags=0, n_batches=0, count_deletions=False, fragments=False, frag_max=0):
+        """count_deletions adds PD_DECODE_DELETIONS to `flags`: deletions count as covered, one run per group of M/=/X/D operations.
+        fragments adds PD_DECODE_FRAGMENTS: a properly paired read with tlen > 0 is the one run [pos, pos + tlen), its mate none; frag_max
+        bounds |tlen| (0: no bound).  The bound travels as the parameter "decode_frag_max", set here from the argument at every call."""
         if count_deletions:
             flags = int(flags) | PD_DECODE_DELETIONS
+        if fragments:
+            flags = int(flags) | PD_DECODE_FRAGMENTS
+        self.e.set_param("decode_frag_max", int(frag_max))
         cfg = pd_decode_cfg()
         cfg.flag_mask, cfg.min_mapq, cfg.sorted = int(flag_mask), int(min_mapq), int(sorted)
         cfg.bytes_hint, cfg.batch_bytes, cfg.batches_in_flight, cfg.flags, cfg.n_batches = int(bytes_hint), int(batch_bytes), int(batches_in_flight), int(flags), int(n_batches)

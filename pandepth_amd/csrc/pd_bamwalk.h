@@ -26,6 +26,14 @@
 //     first operation to the cursor behind its last.  The group no N comes before is the record's first run (it begins at
 //     pos); every later group is an "other" run.  A read without N is one run.
 //
+// Beside the rule, a second compile-time parameter of the same functions, FRAG (`-frag`, Cfg::fragments says which instance a launch
+// takes): whole fragments of properly paired reads.  open_record<true> reads the mate fields of a kept record (next_refID at 24, tlen
+// at 32) and classes it: a FRAGMENT READ has flag & 0x3 == 0x3, flag & 0x908 == 0, next_refID == refID, tlen != 0 and
+// |tlen| <= Cfg::frag_max (|tlen| in unsigned arithmetic: INT32_MIN is 2^31 and never passes).  With tlen > 0 it CARRIES the fragment:
+// exactly one run [pos, (int32)((uint32)pos + (uint32)tlen)), its first and only one, and that end is its endpos for the span test; its
+// CIGAR is not walked, wherever it is kept and however long it is, so such a record is never left to the wave.  With tlen < 0 it is
+// SILENT: a record (n_rec) without runs.  Every other kept record is walked by the rule DEL names.  FRAG = false is the code it was.
+//
 // The same source compiles for gfx950 and for the host (tests/harness/bamwalk_check.cpp compares it with the host reader).
 #ifndef PD_BAMWALK_H_
 #define PD_BAMWALK_H_
@@ -75,6 +83,8 @@ struct Cfg {                              // wave-uniform
     const uint32_t *span_off; const int32_t *spans;                            // -g / -b: (begin0, end) per contig, sorted; or null
     uint32_t near_span;
     uint32_t count_del = 0;               // PD_DECODE_DELETIONS: the launch takes the DEL = true kernels (the walk itself reads the template parameter)
+    uint32_t fragments = 0;               // PD_DECODE_FRAGMENTS: the launch takes the FRAG = true kernels (likewise)
+    uint32_t frag_max = 0x7FFFFFFFu;      // ... and a pair with |tlen| above this is two ordinary reads (read by the FRAG = true instances only)
     C8Out c8;
 };
 
@@ -125,9 +135,12 @@ PW_FN bool plausible(const Cfg &c, uint64_t p, int depth)
     return true;
 }
 
-struct Rec { int32_t tid, pos; uint32_t keep, n_cig; const uint8_t *cig; uint32_t flags, unmapped; };
+enum { FR_NONE = 0, FR_CARRY = 1, FR_SILENT = 2 };                     // Rec::frag: not a fragment read / tlen > 0: the run [pos, fend) / tlen < 0: nothing
+struct Rec { int32_t tid, pos; uint32_t keep, n_cig; const uint8_t *cig; uint32_t flags, unmapped; uint32_t frag; int32_t fend; };
 
 // header of the record at p (p + 36 <= avail, block size already validated by the caller) + the filter
+// (FRAG: + the class of a kept record, from the mate fields among the same 36 bytes; without it frag is the constant FR_NONE)
+template <bool FRAG = false>
 PW_FN Rec open_record(const Cfg &c, uint64_t p, uint32_t bs)
 {
     const uint8_t *r = c.buf + p;
@@ -137,13 +150,22 @@ PW_FN Rec open_record(const Cfg &c, uint64_t p, uint32_t bs)
     x.n_cig = rd16(r + 16); x.cig = r + 36 + l_name; x.flags = 0; x.unmapped = flag & 4;
     x.keep = !(flag & c.flag_mask) && (int32_t)mapq >= c.min_mapq && x.tid >= 0 && x.tid < c.n_ref;
     if (x.keep && !c.contig_on[x.tid]) x.keep = 0;
+    x.frag = FR_NONE; x.fend = 0;
+    if (FRAG && x.keep) {
+        const int32_t mtid = (int32_t)rd32(r + 24), tlen = (int32_t)rd32(r + 32);
+        const uint32_t mag = tlen < 0 ? 0u - (uint32_t)tlen : (uint32_t)tlen;
+        if ((flag & 0x3) == 0x3 && !(flag & 0x908) && mtid == x.tid && tlen != 0 && mag <= c.frag_max) {
+            x.frag = tlen > 0 ? FR_CARRY : FR_SILENT;
+            x.fend = (int32_t)((uint32_t)x.pos + (uint32_t)tlen);         // (the spelled-out wrap of the CIGAR cursor)
+        }
+    }
     if ((uint64_t)32 + l_name + 4ull * x.n_cig > bs) { x.keep = 0; x.flags = WF_BAD; }      // the host reader fails such a record
     // CIGAR kept in the CG tag (more than 65 535 operations: long reads).  htslib's test (bam_tag2cigar), as host/bam.cpp restates it: a
     // first operation <l_seq>S on a placed read, and the FIRST CG tag of the record of type B,I or B,i with at least n_cigar entries that
     // lie inside the record — then the tag's operations are the CIGAR; without such a tag the placeholder is kept.  Until round 6 the
     // lane flagged the record (WF_HOST) and the whole unit went to the host reader: every batch of a long-read file.  The record's
     // bytes all lie below c.avail (the caller has checked p + 4 + bs), so the lane may walk its tags here; one record in a hundred.
-    else if (x.n_cig >= 1 && x.tid >= 0 && x.pos >= 0 && (rd32(x.cig) & 0xf) == 4 && (rd32(x.cig) >> 4) == l_seq && x.keep) {
+    else if (x.n_cig >= 1 && x.tid >= 0 && x.pos >= 0 && (rd32(x.cig) & 0xf) == 4 && (rd32(x.cig) >> 4) == l_seq && x.keep && !(FRAG && x.frag)) {
         const uint64_t end = p + 4 + (uint64_t)bs;
         uint64_t a = p + 36 + l_name + 4ull * x.n_cig + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq;
         if (a > end) a = end;
@@ -261,7 +283,7 @@ PW_FN void first_run(const Cfg &c, LaneWalk &w, int32_t tid, int32_t beg, int32_
 // stands (p, guard, w: its state, so that the walk can be taken up again).  Returns true when it has stopped AT a record whose CIGAR
 // the wave is to walk (`pend` says which; nothing of that record has been counted yet but ++n_rec) — the caller adds the record's
 // runs and calls again with p = pend.next_p — and false when the lane is through (w.e = where its chain ends).
-template <bool EMIT, bool DEL>
+template <bool EMIT, bool DEL, bool FRAG>
 PW_FN bool walk_lane(const Cfg &c, uint64_t &p, uint64_t b, uint32_t &guard, LaneWalk &w, Pending &pend, pd_iv *first, pd_iv *other, pd_iv *far, uint64_t of, uint64_t oo, uint64_t ofar)
 {
     for (; p < b && guard < SUB / 36 + 2; ++guard) {
@@ -270,9 +292,15 @@ PW_FN bool walk_lane(const Cfg &c, uint64_t &p, uint64_t b, uint32_t &guard, Lan
         const uint32_t bs = rd32(c.buf + p);
         if (bs < 32 || bs > (1u << 29)) { w.flags |= WF_BAD; p = STOPPED; break; }
         if (p + 4 + (uint64_t)bs > c.avail) { w.flags |= WF_MORE; p = STOPPED; break; }
-        const Rec x = open_record(c, p, bs);
+        const Rec x = open_record<FRAG>(c, p, bs);
         w.flags |= x.flags; ++w.n_rec;
-        if (x.keep && !x.flags) {
+        if (FRAG && x.frag && x.keep && !x.flags) {
+            // a fragment read, settled here before any hand-over: the carrying mate's one run is the record's first run, the silent mate has none
+            if (x.frag == FR_CARRY) {
+                const int32_t one = (int32_t)((uint32_t)x.pos + 1u);
+                if (!c.spans || span_hit(c, x.tid, x.pos, x.fend == x.pos ? one : x.fend)) { first_run<EMIT>(c, w, x.tid, x.pos, x.fend, first, of); ++w.n_first; }
+            }
+        } else if (x.keep && !x.flags) {
             if (x.n_cig >= (uint32_t)COOP_MIN && c.near_span == 0xFFFFFFFFu && !(c.spans && x.unmapped)) {
                 pend.cig_off = (uint64_t)(x.cig - c.buf); pend.next_p = p + 4 + (uint64_t)bs; pend.n_cig = x.n_cig; pend.tid = x.tid; pend.pos = x.pos;
                 ++guard;
@@ -447,7 +475,7 @@ PW_FN CoopOut coop_cigar(const Cfg &c, uint64_t cig_off, uint32_t n, int32_t tid
 // Every lane's walk of its stretch, to the end: the lanes walk on their own until each is through or stands at a record for the
 // wave; those records are walked by the wave one after the other, their runs added to their lanes' counts (or written behind the runs
 // the lane has written so far), and the lanes go on.  active[l] = 0: the lane has nothing to walk.
-template <class W, bool EMIT, bool DEL>
+template <class W, bool EMIT, bool DEL, bool FRAG>
 PW_FN void run_lanes(const Cfg &c, typename W::template Var<uint32_t> &active, typename W::template Var<uint64_t> &p, const typename W::template Var<uint64_t> &b,
                      typename W::template Var<LaneWalk> &lw, pd_iv *first, pd_iv *other, pd_iv *far, const typename W::template Var<uint64_t> &of,
                      const typename W::template Var<uint64_t> &oo, const typename W::template Var<uint64_t> &ofar)
@@ -462,7 +490,7 @@ PW_FN void run_lanes(const Cfg &c, typename W::template Var<uint32_t> &active, t
             if (!active[l]) return;
             Pending pd; pd.cig_off = 0; pd.next_p = 0; pd.n_cig = 0; pd.tid = 0; pd.pos = 0;
             uint64_t pp = p[l]; uint32_t g = guard[l];
-            const bool stop = walk_lane<EMIT, DEL>(c, pp, b[l], g, lw[l], pd, first, other, far, of[l], oo[l], ofar[l]);
+            const bool stop = walk_lane<EMIT, DEL, FRAG>(c, pp, b[l], g, lw[l], pd, first, other, far, of[l], oo[l], ofar[l]);
             p[l] = pp; guard[l] = g;
             pending[l] = stop ? 1u : 0u;
             if (stop) { pcig[l] = pd.cig_off; pnext[l] = pd.next_p; pn[l] = pd.n_cig; ptid[l] = (uint32_t)pd.tid; ppos[l] = (uint32_t)pd.pos; pob[l] = oo[l] + lw[l].n_other; }
@@ -505,7 +533,7 @@ PW_FN void run_lanes(const Cfg &c, typename W::template Var<uint32_t> &active, t
 // pass 1: one wave, one segment.  lanes[64] receives every lane's start and counts for pass 2.  `hint_in` (or null: the
 // segment's own) is the first record start to walk from — the chain kernel passes a corrected start in a register, so that
 // no lane has to read what another lane of the wave has just stored.
-template <class W, bool DEL = false>
+template <class W, bool DEL = false, bool FRAG = false>
 PW_FN WalkOut walk_segment(const Cfg &cfg, Seg &sg, LaneOut *lanes, const uint64_t *hint_in = nullptr)
 {
     Cfg c = cfg; c.avail = sg.avail;
@@ -572,7 +600,7 @@ PW_FN WalkOut walk_segment(const Cfg &cfg, Seg &sg, LaneOut *lanes, const uint64
         });
         U walked;
         W::each([&](int l) { walked[l] = active[l]; });
-        run_lanes<W, false, DEL>(c, active, wp, b, lw, nullptr, nullptr, nullptr, zero64, zero64, zero64);
+        run_lanes<W, false, DEL, FRAG>(c, active, wp, b, lw, nullptr, nullptr, nullptr, zero64, zero64, zero64);
         W::each([&](int l) {
             if (!walked[l]) return;
             const LaneWalk &w = lw[l];
@@ -613,7 +641,7 @@ PW_FN WalkOut walk_segment(const Cfg &cfg, Seg &sg, LaneOut *lanes, const uint64
 }
 
 // pass 2: the same lanes write their runs; sg.base_first / base_other say where the segment's runs go
-template <class W, bool DEL = false>
+template <class W, bool DEL = false, bool FRAG = false>
 PW_FN void emit_segment(const Cfg &cfg, const Seg &sg, const LaneOut *lanes, pd_iv *first, pd_iv *other, pd_iv *far, SegOut *seg_out = nullptr)
 {
     Cfg c = cfg; c.avail = sg.avail;
@@ -643,7 +671,7 @@ PW_FN void emit_segment(const Cfg &cfg, const Seg &sg, const LaneOut *lanes, pd_
     });
     U walked;
     W::each([&](int l) { walked[l] = active[l]; });
-    run_lanes<W, true, DEL>(c, active, wp, bb, lw, first, other, far, of, oo, ofr);
+    run_lanes<W, true, DEL, FRAG>(c, active, wp, bb, lw, first, other, far, of, oo, ofr);
     W::each([&](int l) {
         if (!walked[l]) return;
         const LaneWalk &w = lw[l];

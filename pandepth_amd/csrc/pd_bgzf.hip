@@ -68,42 +68,43 @@ __global__ __launch_bounds__(64, PD_INFLATE_MIN_WAVES) void k_inflate_wave(const
 // record and counts what it will emit; `only` (or null) lists the segments to (re)do.
 // DEL, here and in the three kernels below: the counting rule the walk is compiled for (false: the reference's; true: `-del`'s groups).
 // The launchers take the instance Cfg::count_del names, so the default kernels are the code they were before there was a second rule.
-template <bool DEL>
+// FRAG likewise (`-frag`: whole fragments of properly paired reads, Cfg::fragments): four instances of every kernel, PD_WALK_PICK chooses.
+template <bool DEL, bool FRAG>
 __global__ __launch_bounds__(64) void k_walk_segments(const pdb2::Cfg cfg, pdb2::Seg *segs, uint32_t n_seg, pdb2::LaneOut *lanes,
                                                       const uint32_t *only, uint32_t n_only)
 {
     const uint32_t k = blockIdx.x;
     if (k >= (only ? n_only : n_seg)) return;
     const uint32_t j = only ? only[k] : k;
-    pdb2::walk_segment<pdw::DevWave, DEL>(cfg, segs[j], lanes + (size_t)j * 64);
+    pdb2::walk_segment<pdw::DevWave, DEL, FRAG>(cfg, segs[j], lanes + (size_t)j * 64);
 }
 
 // Test hook ("decode_spoil" = k): every k-th segment behind a unit's first walks again from a start that is no record — what a wrong guess
 // of the header search looks like to whoever confirms the chain, planted far more often than real data ever shows one (one in ~1e8 records),
 // so that the suite exercises the repair (k_chain_segments' repeats, the host's rounds) on the device.
-template <bool DEL>
+template <bool DEL, bool FRAG>
 __global__ __launch_bounds__(64) void k_spoil_segments(const pdb2::Cfg cfg, pdb2::Seg *segs, uint32_t n_seg, pdb2::LaneOut *lanes, uint32_t k)
 {
     const uint32_t j = blockIdx.x;
     if (j >= n_seg || segs[j].unit_first || j % k != 0) return;
     const uint64_t h = segs[j].begin + 1 + (j % 7);
-    pdb2::walk_segment<pdw::DevWave, DEL>(cfg, segs[j], lanes + (size_t)j * 64, &h);
+    pdb2::walk_segment<pdw::DevWave, DEL, FRAG>(cfg, segs[j], lanes + (size_t)j * 64, &h);
 }
 
 // The chain across a batch's segments, confirmed by ONE wave on the device (pdb2::chain_device): segments whose guessed start is not
 // where the chain before them ends walk again right here, every segment gets the places of its runs, and `out` says how many runs
 // there are — or that the batch is out of the ordinary and the host must go through it (ChainOut::slow; pass 2 then writes nothing).
-template <bool DEL>
+template <bool DEL, bool FRAG>
 __global__ __launch_bounds__(64) void k_chain_segments(const pdb2::Cfg cfg, pdb2::Seg *segs, uint32_t n_seg, pdb2::LaneOut *lanes, const int *member_status,
                                                        uint32_t n_members, uint64_t cap_first, uint64_t cap_other, uint32_t max_redo, pdb2::ChainOut *out)
 {
     pdb2::chain_device<pdw::DevWave>(segs, n_seg, member_status, n_members, cap_first, cap_other, max_redo,
-        [&](uint32_t j, uint64_t start) { return pdb2::walk_segment<pdw::DevWave, DEL>(cfg, segs[j], lanes + (size_t)j * 64, &start); }, out);
+        [&](uint32_t j, uint64_t start) { return pdb2::walk_segment<pdw::DevWave, DEL, FRAG>(cfg, segs[j], lanes + (size_t)j * 64, &start); }, out);
 }
 
 // pass 2: the runs, at the offsets every segment was given (base_first / base_other: by the host, or by k_chain_segments — `gate`
 // is then its verdict, and a batch it left to the host writes nothing)
-template <bool DEL>
+template <bool DEL, bool FRAG>
 __global__ __launch_bounds__(64) void k_emit_segments(const pdb2::Cfg cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes,
                                                       pd_iv *first, pd_iv *other, pd_iv *far, const pdb2::ChainOut *gate)
 {
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(64) void k_emit_segments(const pdb2::Cfg cfg, const
         if (so && threadIdx.x == 0) { so->first_key = pdb2::NONE; so->last_key = 0; so->unsorted = 0; so->n_long = 0; }
         return;
     }
-    pdb2::emit_segment<pdw::DevWave, DEL>(cfg, segs[j], lanes + (size_t)j * 64, first, other, far, so);
+    pdb2::emit_segment<pdw::DevWave, DEL, FRAG>(cfg, segs[j], lanes + (size_t)j * 64, first, other, far, so);
 }
 
 // are the first runs of a batch in (tid, begin) order?  out[0] = 1 if not; out[2..3] / out[4..5] = first / last key
@@ -152,28 +153,29 @@ void launch_bgzf_inflate_wave(hipStream_t st, const uint8_t *comp, const pd_bgzf
 }
 size_t bgzf_wave_scratch_bytes(unsigned n_wg) { return (size_t)n_wg * PD_WAVE_TOKENS * sizeof(pdw::Token) + 64; }
 
+#define PD_WALK_PICK(K) (cfg.fragments ? (cfg.count_del ? K<true, true> : K<false, true>) : (cfg.count_del ? K<true, false> : K<false, false>))
 void launch_walk_segments(hipStream_t st, const pdb2::Cfg &cfg, pdb2::Seg *segs, uint32_t n_seg, pdb2::LaneOut *lanes,
                           const uint32_t *only, uint32_t n_only)
 {
     const uint32_t n = only ? n_only : n_seg;
     if (!n) return;
-    hipLaunchKernelGGL((cfg.count_del ? k_walk_segments<true> : k_walk_segments<false>), dim3(n), dim3(64), 0, st, cfg, segs, n_seg, lanes, only, n_only);
+    hipLaunchKernelGGL(PD_WALK_PICK(k_walk_segments), dim3(n), dim3(64), 0, st, cfg, segs, n_seg, lanes, only, n_only);
 }
 void launch_emit_segments(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes,
                           pd_iv *first, pd_iv *other, pd_iv *far, const pdb2::ChainOut *gate)
 {
     if (!n_seg) return;
-    hipLaunchKernelGGL((cfg.count_del ? k_emit_segments<true> : k_emit_segments<false>), dim3(n_seg), dim3(64), 0, st, cfg, segs, n_seg, lanes, first, other, far, gate);
+    hipLaunchKernelGGL(PD_WALK_PICK(k_emit_segments), dim3(n_seg), dim3(64), 0, st, cfg, segs, n_seg, lanes, first, other, far, gate);
 }
 void launch_spoil_segments(hipStream_t st, const pdb2::Cfg &cfg, pdb2::Seg *segs, uint32_t n_seg, pdb2::LaneOut *lanes, uint32_t k)
 {
     if (!n_seg || !k) return;
-    hipLaunchKernelGGL((cfg.count_del ? k_spoil_segments<true> : k_spoil_segments<false>), dim3(n_seg), dim3(64), 0, st, cfg, segs, n_seg, lanes, k);
+    hipLaunchKernelGGL(PD_WALK_PICK(k_spoil_segments), dim3(n_seg), dim3(64), 0, st, cfg, segs, n_seg, lanes, k);
 }
 void launch_chain_segments(hipStream_t st, const pdb2::Cfg &cfg, pdb2::Seg *segs, uint32_t n_seg, pdb2::LaneOut *lanes, const int *member_status,
                            uint32_t n_members, uint64_t cap_first, uint64_t cap_other, uint32_t max_redo, pdb2::ChainOut *out)
 {
-    hipLaunchKernelGGL((cfg.count_del ? k_chain_segments<true> : k_chain_segments<false>), dim3(1), dim3(64), 0, st, cfg, segs, n_seg, lanes, member_status, n_members, cap_first, cap_other, max_redo, out);
+    hipLaunchKernelGGL(PD_WALK_PICK(k_chain_segments), dim3(1), dim3(64), 0, st, cfg, segs, n_seg, lanes, member_status, n_members, cap_first, cap_other, max_redo, out);
 }
 
 void launch_bgzf_inflate(hipStream_t st, const uint8_t *comp, const pd_bgzf_block *blk, uint32_t n_blk, uint8_t *out,

@@ -699,6 +699,8 @@ int pd_set_param(pd_ctx *c, const char *name, uint64_t value)
     if (!strcmp(name, "threshold_wave_max")) { if (value > 0xFFFFFFFFull) return fail(c, PD_EINVAL, "threshold_wave_max must be below 2^32"); c->t_wave_max = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "quantile_split_cells")) { if (value > 0xFFFFFFFFull) return fail(c, PD_EINVAL, "quantile_split_cells must be below 2^32"); c->q_split = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "decode_deletions")) { c->dec_deletions = value != 0; return PD_OK; }
+    if (!strcmp(name, "decode_fragments")) { c->dec_fragments = value != 0; return PD_OK; }
+    if (!strcmp(name, "decode_frag_max")) { if (value > 0x7FFFFFFFull) return fail(c, PD_EINVAL, "decode_frag_max must be below 2^31 (0: no bound)"); c->dec_frag_max = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "decode_near_span")) { c->dec_near_span = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
     return fail(c, PD_EINVAL, std::string("unknown parameter ") + name);
 }

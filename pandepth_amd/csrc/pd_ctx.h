@@ -223,6 +223,9 @@ struct pd_ctx {
     void *dec_warm_word = nullptr;
     uint32_t dec_near_span = 0xFFFFFFFFu;                         // "decode_near_span": split the later runs into two streams (off)
     bool dec_deletions = false;                                   // "decode_deletions": pd_push_bgzf_units opens its session with PD_DECODE_DELETIONS
+    bool dec_fragments = false;                                   // "decode_fragments": ... with PD_DECODE_FRAGMENTS
+    uint32_t dec_frag_max = 0;                                    // "decode_frag_max": a PD_DECODE_FRAGMENTS session's bound on |tlen| (0: none), read by pd_decode_begin ...
+    uint32_t dec_frag_bound = 0x7FFFFFFFu;                        // ... into this, the open session's bound
     pd_decode_cfg dec_cfg{}; uint8_t *d_contig_on = nullptr; uint32_t *d_span_off = nullptr; int32_t *d_spans = nullptr;
     std::vector<RunSeg> run_segs;
     pd_iv *run_first = nullptr, *run_other = nullptr, *run_far = nullptr;   // the concatenated sample (owned until the next reset)

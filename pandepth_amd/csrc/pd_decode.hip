@@ -369,6 +369,7 @@ int pd_decode_begin(pd_ctx *c, const pd_decode_cfg *cfg)
     const uint64_t tb0 = dec_now_us(); uint64_t tb[6] = {tb0, tb0, tb0, tb0, tb0, tb0};
     struct BeginMarks { const uint64_t *t; ~BeginMarks() { if (getenv("PANDEPTH_TIMING") && t[5] - t[0] > 20000) fprintf(stderr, "[timing]   pd_decode_begin: tables %.3f s, marks + compose stream %.3f s, sample arrays %.3f s, arena %.3f s, buffers %.3f s\n", (t[1] - t[0]) / 1e6, (t[2] - t[1]) / 1e6, (t[3] - t[2]) / 1e6, (t[4] - t[3]) / 1e6, (t[5] - t[4]) / 1e6); } } begin_marks{tb};
     c->dec_cfg = *cfg;
+    c->dec_frag_bound = c->dec_frag_max ? c->dec_frag_max : 0x7FFFFFFFu;      // ("decode_frag_max" as it stands now holds for the whole session; 0: no bound)
     if (int rc = begin_filters(c, cfg)) return rc;
     tb[1] = tb[2] = tb[3] = dec_now_us();
     if (int rc = begin_compact(c, cfg, tb)) return rc;
@@ -559,6 +560,8 @@ int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t 
     cfg.flag_mask = c->dec_cfg.flag_mask; cfg.min_mapq = c->dec_cfg.min_mapq; cfg.span_off = c->d_span_off; cfg.spans = c->d_spans;
     cfg.near_span = c8 ? 0xFFFFFFFFu : c->dec_near_span;                   // (a compact session has one stream of later runs)
     cfg.count_del = c->dec_cfg.flags & PD_DECODE_DELETIONS ? 1u : 0u;      // (`-del`: every launch of this batch takes the kernels of the group rule)
+    cfg.fragments = c->dec_cfg.flags & PD_DECODE_FRAGMENTS ? 1u : 0u;      // (`-frag`: ... the kernels that class every kept record by its mate fields)
+    cfg.frag_max = c->dec_frag_bound;
     cfg.c8 = pdb2::C8Out{};
     launch_bgzf_inflate_wave(st, members, (const pd_bgzf_block *)(d_tab + J.o.blk), bt->n_blocks, d_inf, (int *)sl.d[DS_ST], sl.d_tok, n_wg, c->dec_crc,
                              (uint32_t *)(d_tab + J.o.next), false);
@@ -1202,6 +1205,7 @@ int pd_push_bgzf_units(pd_ctx *c, const void *blob, size_t n_bytes, const pd_bgz
     if (n_units == 0 || n_blocks == 0) return PD_OK;
     pd_decode_cfg cfg{}; cfg.flag_mask = flag_mask; cfg.min_mapq = min_mapq; cfg.sorted = 1;
     if (c->dec_deletions) cfg.flags |= PD_DECODE_DELETIONS;               // (pd_set_param "decode_deletions": this entry's signature has no room for flags)
+    if (c->dec_fragments) cfg.flags |= PD_DECODE_FRAGMENTS;               // (likewise "decode_fragments"; the bound is "decode_frag_max", which pd_decode_begin reads)
     int rc = pd_decode_begin(c, &cfg);
     if (rc) return rc;
     // the session this call opens is closed on every path out of it (its batch is taken out of the list below, so the

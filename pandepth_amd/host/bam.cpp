@@ -145,10 +145,10 @@ int AlnReader::next_sam(AlnRec *r)
         if (line.empty() || line[0] == '@') continue;
         break;
     }
-    // QNAME FLAG RNAME POS MAPQ CIGAR ...
-    const char *f[6]; size_t fl[6];
+    // QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN ... (the last three are read where the line has them)
+    const char *f[9]; size_t fl[9];
     size_t o = 0; int k = 0;
-    while (k < 6) {
+    while (k < 9) {
         size_t e = line.find('\t', o); if (e == std::string::npos) e = line.size();
         f[k] = line.c_str() + o; fl[k] = e - o; ++k;
         if (e == line.size()) break;
@@ -165,6 +165,14 @@ int AlnReader::next_sam(AlnRec *r)
     }
     r->pos = (int32_t)strtol(f[3], nullptr, 10) - 1;
     r->mapq = (uint8_t)strtoul(f[4], nullptr, 10);
+    r->mtid = -1; r->tlen = 0;
+    if (k >= 9) {
+        // RNEXT: '=' names the read's own reference, '*' none; a name the header does not have counts as none (no pair test passes)
+        if (fl[6] == 1 && f[6][0] == '=') r->mtid = r->tid;
+        else if (!(fl[6] == 1 && f[6][0] == '*')) { auto it = name2tid_.find(std::string(f[6], fl[6])); if (it != name2tid_.end()) r->mtid = it->second; }
+        const long long t = strtoll(f[8], nullptr, 10);
+        r->tlen = t < INT32_MIN ? INT32_MIN : t > INT32_MAX ? INT32_MAX : (int32_t)t;
+    }
     cig_.clear();
     if (!(fl[5] == 1 && f[5][0] == '*')) {
         uint32_t num = 0;
@@ -211,6 +219,7 @@ int AlnReader::next(AlnRec *r)
     r->mapq = rec[9];
     uint32_t n_cigar = rec[12] | (rec[13] << 8);
     r->flag = (uint16_t)(rec[14] | (rec[15] << 8));
+    r->mtid = (int32_t)le32(rec + 20); r->tlen = (int32_t)le32(rec + 28);
     if (32 + l_read_name + 4 * (size_t)n_cigar > bs) { err_ = "corrupt BAM record"; return -1; }
     const uint8_t *cg = rec + 32 + l_read_name;
     // CIGARs with > 65535 operations are stored in the CG:B,I tag behind a <l_seq>S<ref_len>N

@@ -1,5 +1,5 @@
-// bam.h — alignment input: BAM (SAM spec §4.2), text SAM and CRAM 3.0 (cram.h) records reduced to the five fields
-// the depth path reads (refID, pos, mapq, flag, CIGAR), plus the BAI index (§5.2) used to cut a
+// bam.h — alignment input: BAM (SAM spec §4.2), text SAM and CRAM 3.0 (cram.h) records reduced to the fields
+// the depth path reads (refID, pos, mapq, flag, CIGAR; for -frag the mate's refID and tlen), plus the BAI index (§5.2) used to cut a
 // coordinate-sorted BAM into independent, record-aligned virtual-offset ranges.
 // The reference obtains all of this from htslib (sam_hdr_read / sam_read1 / sam_index_load,
 // PD:3483-3507, PD:434, PD:378); this is an independent implementation from the specification.
@@ -28,6 +28,7 @@ struct AlnRec {
     uint8_t mapq;
     uint32_t n_cigar;
     const uint32_t *cigar;                  // BAM encoding: len << 4 | op ("MIDNSHP=XB"); valid until next()
+    int32_t mtid = -1, tlen = 0;            // the mate's refID (RNEXT: '=' is tid, '*' is -1) and the template length; BAM and SAM fill them, CRAM leaves (-1, 0)
     // htslib's bam_endpos: pos + reference length, where unmapped reads and zero-length
     // alignments count as length 1
     int32_t endpos() const;

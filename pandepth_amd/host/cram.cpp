@@ -1145,7 +1145,7 @@ int CramReader::next(AlnRec *r)
         if (!cur_batch_.err.empty()) { fail(cur_batch_.err); return -1; }
     }
     const Rec &x = cur_batch_.recs[cur_++];
-    r->tid = x.tid; r->pos = x.pos; r->flag = x.flag; r->mapq = x.mapq;
+    r->tid = x.tid; r->pos = x.pos; r->flag = x.flag; r->mapq = x.mapq; r->mtid = -1; r->tlen = 0;     // (mate fields are not decoded: -frag refuses CRAM)
     r->n_cigar = x.n_cig; r->cigar = cur_batch_.cigs.data() + x.cig_off;
     return 1;
 }

@@ -121,6 +121,7 @@ int parse_options(int argc, char **argv, Options *o)
 {
     if (argc <= 1) { print_help(); return 0; }
     int bed_count = 0, n_inputs = 0;
+    bool fragmax_given = false;
     std::vector<std::string> bed_list;
     auto lack = [](const std::string &f) { std::cerr << "Error: Lack argument for [ -" << f << " ]" << std::endl; };
     for (int i = 1; i < argc; ++i) {
@@ -233,9 +234,19 @@ int parse_options(int argc, char **argv, Options *o)
             if (!good) { o->thresholds.clear(); std::cerr << "Error: -thresholds should be 1 to 16 ascending depths, such as 1,10,20,30" << std::endl; return 0; }
         }
         else if (flag == "del") o->count_del = true;                             // not in the reference: deletions count as covered (README)
+        else if (flag == "frag") o->frag = true;                                 // not in the reference: whole fragments of properly paired reads (README)
+        else if (flag == "fragmax") {                                            // ... and the largest |tlen| that still makes a fragment
+            if (!arg(&v)) return 0;
+            uint64_t x = 0; bool good = !v.empty() && v.size() <= 10;
+            for (size_t k = 0; good && k < v.size(); ++k) { if (v[k] < '0' || v[k] > '9') good = false; else x = x * 10 + (uint64_t)(v[k] - '0'); }
+            if (!good || x < 1 || x > 0x7FFFFFFFull) { std::cerr << "Error: -fragmax should be between 1 and 2147483647" << std::endl; return 0; }
+            o->frag_max = (uint32_t)x; fragmax_given = true;
+        }
         else if (flag == "help" || flag == "h") { print_help(); return 0; }
         else { std::cerr << "Error UnKnow argument -" << flag << std::endl; return 0; }
     }
+    if (fragmax_given && !o->frag) { std::cerr << "Error: -fragmax needs -frag" << std::endl; return 0; }
+    if (o->frag) o->use_index = false;                                           // a left mate that ends before a region can still cover it: no index fetch
     if (n_inputs > 0) o->input = o->inputs[0];
     if (o->input.empty() || o->out.empty()) { std::cerr << "Error: lack argument -i or -o " << std::endl; return 0; }
     if (bed_count != 0 && o->region_file.empty()) {

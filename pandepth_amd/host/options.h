@@ -1,4 +1,4 @@
-// options.h — the command-line surface of `pandepth` (-i -o -g -f -b -w -a -q -d -x -t -s -c -r -h; of its own: -dist -levels -quantile -thresholds -del);
+// options.h — the command-line surface of `pandepth` (-i -o -g -f -b -w -a -q -d -x -t -s -c -r -h; of its own: -dist -levels -quantile -thresholds -del -frag -fragmax);
 // -i takes SAM / BAM / CRAM 2.1 / 3.0 / 3.1 / PAF files or a #.list of them.
 // Behaviour follows the reference's parser (PD:84-293) including its quirks: every '-' is
 // stripped from a flag, `*.list`/`*.List` expands to one input per non-empty line, -w < 1 and
@@ -33,6 +33,8 @@ struct Options {
     std::vector<uint32_t> levels_edges;  // the classes' lower edges, strictly ascending, at most 64
     std::vector<uint32_t> quantile;      // -quantile SPEC (not in the reference): <out>.quantile.stat.gz, per-row depth percentiles; 1..16 values in 0..100, strictly ascending
     bool count_del = false;              // -del (not in the reference): deletions count as covered — one run per group of M/=/X/D operations that no N splits, instead of one per M/=/X
+    bool frag = false;                   // -frag (not in the reference): a properly paired read with tlen > 0 counts as the one run [pos, pos + tlen), its mate as nothing; clears use_index
+    uint32_t frag_max = 0x7FFFFFFFu;     // -fragmax N, 1 .. 2^31 - 1 (needs -frag): pairs with |tlen| above it are two ordinary reads
     std::vector<uint32_t> thresholds;    // -thresholds SPEC (not in the reference): <out>.thresholds.stat.gz, per-row counts of cells at or above each depth; 1..16 values below 2^31, strictly ascending
 };
 

@@ -92,12 +92,41 @@ private:
     uint64_t s_last_ = 0, o_max_ = 0, o_dis_ = 0;
 };
 
+// The -frag rule: what a kept read is.  0: not a fragment read (walked as ever); 1: it carries its fragment, the one run [pos, *end);
+// 2: the right mate, silent.  |tlen| is taken in unsigned arithmetic, so INT32_MIN is 2^31 and never passes the bound.
+struct FragRule {
+    bool on = false; uint32_t max = 0x7FFFFFFFu;
+    inline int cls(const AlnRec &r, int32_t *end) const
+    {
+        if (!on || (r.flag & 0x3) != 0x3 || (r.flag & 0x908) || r.mtid != r.tid || r.tlen == 0) return 0;
+        const uint32_t mag = r.tlen < 0 ? 0u - (uint32_t)r.tlen : (uint32_t)r.tlen;
+        if (mag > max) return 0;
+        *end = (int32_t)((uint32_t)r.pos + (uint32_t)r.tlen);                  // (the CIGAR cursor's spelled-out wrap)
+        return r.tlen > 0 ? 1 : 2;
+    }
+    // the end the -g / -b region tests take: the fragment's for the read that carries it (one base where it is empty), else bam_endpos
+    inline int32_t endpos(const AlnRec &r) const
+    {
+        int32_t e = 0;
+        if (cls(r, &e) != 1) return r.endpos();
+        return e == r.pos ? (int32_t)((uint32_t)r.pos + 1u) : e;
+    }
+};
+
 // PD:438-460: CIGAR walk with an int32 cursor; one run per M/=/X operation, D/N advance only.
 // count_del (-del): D counts as covered, and the walk emits one run per GROUP — a maximal sequence of M/=/X/D operations with no N
 // between them (I/S/H/P do not split it; an N of any length, 0 included, does; a group of length 0 is still a run, as 0M is).
-inline void emit_runs(const AlnRec &r, RunSink *sink, bool count_del)
+// frag (-frag): a fragment read with tlen > 0 is the one run [pos, pos + tlen) and its CIGAR is not walked; one with tlen < 0 adds
+// nothing; every other read is walked by the rule count_del names.
+inline void emit_runs(const AlnRec &r, RunSink *sink, bool count_del, const FragRule &frag)
 {
     int32_t cur = r.pos;
+    if (frag.on) {
+        int32_t fend = 0;
+        const int k = frag.cls(r, &fend);
+        if (k == 1) sink->emit(r.tid, r.pos, fend);
+        if (k) return;
+    }
     if (count_del) {
         bool open = false; int32_t gbeg = 0;
         for (uint32_t i = 0; i < r.n_cigar; ++i) {
@@ -148,7 +177,7 @@ struct SpanIndex {
             if (synth) whole[kv.first] = 1;    // bins tile [1,len] (minus at most the last base): widened, they cover every read
         }
     }
-    inline bool hit(const AlnRec &r) const
+    inline bool hit(const AlnRec &r, const FragRule &frag) const
     {
         const auto &v = per_tid[r.tid];
         if (v.empty()) return false;
@@ -156,7 +185,7 @@ struct SpanIndex {
         // spans are disjoint and ordered, so region ends increase: first span whose end is past pos
         size_t lo = 0, hi = v.size();
         while (lo < hi) { const size_t m = (lo + hi) / 2; if (v[m].second > r.pos) hi = m; else lo = m + 1; }
-        return lo < v.size() && r.endpos() > v[lo].first;
+        return lo < v.size() && frag.endpos(r) > v[lo].first;
     }
 };
 
@@ -165,7 +194,7 @@ bool index_exists(const std::string &p) { return file_exists(p + ".bai") || file
 // ---- readers ---------------------------------------------------------------------------------
 // records that START in [begin, stop) of an open BAM, through the host decoder
 bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter &flt, const struct SpanIndex &spans,
-                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del);
+                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag);
 
 struct DevRange;
 int read_bam_device(const std::string &path, const Options &o, const AlnHeader &main_hdr, const SpanIndex &spans, const RegionModel &rm,
@@ -174,6 +203,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
 bool read_indexed(const std::string &path, const Options &o, const AlnHeader &main_hdr, const SpanIndex &spans,
                   Engine *eng, const RegionModel *rm = nullptr)
 {
+    FragRule frag; frag.on = o.frag; frag.max = o.frag_max;
     ReadFilter flt{o.flag_mask, o.min_mapq, (int32_t)main_hdr.names.size()};
     BaiIndex bai;
     std::string err;
@@ -200,7 +230,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
             });
         while ((k = probe.next(&r)) == 1) {
             ++n;
-            if (flt.pass(r) && spans.hit(r)) emit_runs(r, &sink, o.count_del);
+            if (flt.pass(r) && spans.hit(r, frag)) emit_runs(r, &sink, o.count_del, frag);
         }
         if (k < 0) { eng->fail(probe.error() + " (" + path + ")"); return false; }
         if (getenv("PANDEPTH_TIMING"))
@@ -263,7 +293,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
             if (t >= n_tasks || !eng->ok()) break;
             for (size_t w = tasks[t].first; w < tasks[t].second; ++w) {
                 std::string e3;
-                if (!decode_range(rd, work[w].first, work[w].second, flt, spans, &sink, &my_rec, &e3, o.count_del)) { eng->fail(e3 + " (" + path + ")"); return; }
+                if (!decode_range(rd, work[w].first, work[w].second, flt, spans, &sink, &my_rec, &e3, o.count_del, frag)) { eng->fail(e3 + " (" + path + ")"); return; }
             }
         }
     };
@@ -280,7 +310,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
 }
 
 bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter &flt, const SpanIndex &spans,
-                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del)
+                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag)
 {
     if (!rd.seek(begin)) { *err = "seek failed"; return false; }
     AlnRec r;
@@ -291,8 +321,8 @@ bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter
         if (k < 0) { *err = rd.error(); return false; }
         ++*n_rec;
         if (!flt.pass(r)) continue;
-        if (!spans.hit(r)) continue;
-        emit_runs(r, sink, count_del);
+        if (!spans.hit(r, frag)) continue;
+        emit_runs(r, sink, count_del, frag);
     }
     return true;
 }
@@ -315,6 +345,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
                     int kind, uint64_t first_voff, const BaiIndex *bai, bool sorted, Engine *eng)
 {
     const pd_engine_api *api = eng->api;
+    FragRule frag; frag.on = o.frag; frag.max = o.frag_max;     // (for the units the host reader takes back)
     const auto t_enter = std::chrono::steady_clock::now();
     if (!api->decode_begin || !api->decode_acquire || !api->decode_submit || !api->decode_end || !api->decode_abort) return 0;
     if (const char *e = tune("device_decode")) if (e[0] == '0') return 0;
@@ -399,6 +430,10 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
     // engine's compact form; every other mode needs the arrays and keeps 12-byte runs
     if (spans.synthetic && !o.site_out && (o.mode == 0 || (o.mode == 5 && o.win >= 8192))) cfg.flags |= PD_DECODE_COMPACT;
     if (o.count_del) cfg.flags |= PD_DECODE_DELETIONS;
+    if (o.frag) {                                            // (the bound travels as a parameter: pd_decode_cfg keeps its layout)
+        cfg.flags |= PD_DECODE_FRAGMENTS;
+        if (!api->set_param || api->set_param(eng->ctx, "decode_frag_max", o.frag_max) != 0) return 0;      // (an engine without the mode: the host reader has it)
+    }
     { uint64_t b = 0; for (auto &v : batches) for (auto &r : v) b += ((r.vend == UINT64_MAX ? F : (r.vend >> 16)) - (r.vbeg >> 16)) + 65536; cfg.bytes_hint = std::min(b, 2 * F); }
     if (!spans.synthetic) {
         soff.assign(on.size() + 1, 0);
@@ -715,7 +750,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
                 const size_t i = nb.fetch_add(1);
                 if (i >= backlog.size() || !eng->ok()) break;
                 uint64_t nr = 0;
-                if (!decode_range(rd, backlog[i].first, backlog[i].second, flt, spans, &sink, &nr, &e2, o.count_del)) { eng->fail(e2 + " (" + path + ")"); break; }
+                if (!decode_range(rd, backlog[i].first, backlog[i].second, flt, spans, &sink, &nr, &e2, o.count_del, frag)) { eng->fail(e2 + " (" + path + ")"); break; }
                 n_host += nr;
             }
         };
@@ -735,6 +770,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
 // No index, header says SO:coordinate (PD:4604-4671): one cursor per contig over its merged spans.
 bool read_sorted_stream(AlnReader *rd, const Options &o, const AlnHeader &main_hdr, const RegionModel &rm, Engine *eng)
 {
+    FragRule frag; frag.on = o.frag; frag.max = o.frag_max;
     const int32_t n = (int32_t)main_hdr.names.size();
     std::vector<char> done(n, 1);
     std::vector<const std::vector<std::pair<int32_t, int32_t>> *> sp(n, nullptr);
@@ -749,7 +785,7 @@ bool read_sorted_stream(AlnReader *rd, const Options &o, const AlnHeader &main_h
         if ((int)r.mapq < o.min_mapq) continue;
         if (r.flag & o.flag_mask) continue;
         const auto &v = *sp[r.tid];
-        if (r.endpos() < v[cur[r.tid]].first) continue;
+        if (frag.endpos(r) < v[cur[r.tid]].first) continue;
         if (r.pos > v[cur[r.tid]].second) {
             size_t c = cur[r.tid] + 1;
             while (c < v.size() && !(r.pos <= v[c].second)) ++c;
@@ -761,7 +797,7 @@ bool read_sorted_stream(AlnReader *rd, const Options &o, const AlnHeader &main_h
                 if (all) break;                      // this read is NOT counted (PD:4641-4644)
             }
         }
-        emit_runs(r, &sink, o.count_del);            // counted even when the cursor just ran off the end
+        emit_runs(r, &sink, o.count_del, frag);      // counted even when the cursor just ran off the end
     }
     if (k < 0) eng->fail(rd->error());
     return eng->ok();
@@ -770,6 +806,7 @@ bool read_sorted_stream(AlnReader *rd, const Options &o, const AlnHeader &main_h
 // No index, not coordinate sorted (PD:4677-4711): every read that passes the filter.
 bool read_all(AlnReader *rd, const Options &o, const AlnHeader &main_hdr, const RegionModel &rm, Engine *eng)
 {
+    FragRule frag; frag.on = o.frag; frag.max = o.frag_max;
     ReadFilter flt{o.flag_mask, o.min_mapq, (int32_t)main_hdr.names.size()};
     RunSink sink(eng);
     AlnRec r;
@@ -777,7 +814,7 @@ bool read_all(AlnReader *rd, const Options &o, const AlnHeader &main_hdr, const 
     while ((k = rd->next(&r)) > 0) {
         if (!flt.pass(r)) continue;
         if (!rm.has(r.tid)) continue;                // depth on contigs without targets is never reported
-        emit_runs(r, &sink, o.count_del);
+        emit_runs(r, &sink, o.count_del, frag);
     }
     if (k < 0) eng->fail(rd->error());
     return eng->ok();
@@ -2020,6 +2057,13 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
     r.list_mode = n_files > 1;
     if (r.list_mode) std::cout << "INFO: Run multi-file data " << std::endl;
     if (r.o.input.empty()) { std::cerr << "Error: Failed to open the BAM/CRAM file: " << r.o.input << std::endl; return 1; }
+    if (r.o.frag)
+        // -frag: CRAM records come without their mate fields and PAF has no pairs — refused per input, before any output file exists
+        for (const std::string &fp : r.o.inputs)
+            if (is_paf_path(fp) || CramReader::is_cram(fp)) {
+                std::cerr << "Error: -frag reads SAM and BAM only (the mate fields of " << (is_paf_path(fp) ? "PAF" : "CRAM") << " input are not available): " << fp << std::endl;
+                return 1;
+            }
     r.paf = is_paf_path(r.o.input);                      // PD:3466-3479 / PD:3420-3432: the first input's extension decides
     plan_contexts(r, n_files);
     Comms comm(r);                                       // (goes before the contexts do)

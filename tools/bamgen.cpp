@@ -2,10 +2,13 @@
 // short-read BAM files with a realistic payload, plus their .bai, for the end-to-end benchmarks (a 4.6 GB file in
 // seconds instead of minutes with the numpy writer in tools/synth.py).
 //
-//   bamgen -o out.bam -n RECORDS [-s genome_scale] [-t threads] [-l level] [-S seed] [-z] [-Q 40] [--long]
+//   bamgen -o out.bam -n RECORDS [-s genome_scale] [-t threads] [-l level] [-S seed] [-z] [-Q 40] [--long] [--pairs]
 //
 //   -Q 40    unbinned qualities (40 levels with a position-dependent decay, HiSeq-2500-like) instead of the NovaSeq-like four bins in
 //            runs: the same records in about twice the compressed bytes (~95 B per record instead of 53)
+//   --pairs  the short reads' template lengths take the sign of a pair's two mates: a forward-strand record keeps its tlen of 300-499 (the left
+//            mate), a reverse-strand record carries the negative (the right mate) — about half and half, for `pandepth -frag`.  Without it every
+//            record has a positive tlen, as always (the other bytes are the same either way)
 //   --long   long reads (HiFi / ONT shape) instead of 150-base ones: 10-20 kb, an insertion or deletion every 8-15 bases (~2 600 CIGAR
 //            operations per read), 5 % soft-clipped, 2 % with one N gap of 50-180 kb (reference span up to 200 kb), 1 % with MORE THAN
 //            65 535 operations — stored the way htslib writes them: <l_seq>S<ref_len>N in the record, the real CIGAR in a CG:B,I tag —
@@ -75,13 +78,13 @@ static void bgzf_member(std::vector<uint8_t> &out, const uint8_t *d, size_t n, i
 int main(int argc, char **argv)
 {
     std::string outp; uint64_t R = 1000000; double scale = -1; int threads = 8, level = 6; uint64_t seed = 42; bool use_zlib = false;
-    bool long_mode = false; int qlevels = 4;
+    bool long_mode = false, pairs = false; int qlevels = 4;
     for (int a = 1; a < argc; ++a) {
         if (!strcmp(argv[a], "-o")) outp = argv[++a]; else if (!strcmp(argv[a], "-n")) R = (uint64_t)atof(argv[++a]);
         else if (!strcmp(argv[a], "-s")) scale = atof(argv[++a]); else if (!strcmp(argv[a], "-t")) threads = atoi(argv[++a]);
         else if (!strcmp(argv[a], "-l")) level = atoi(argv[++a]); else if (!strcmp(argv[a], "-S")) seed = strtoull(argv[++a], nullptr, 10);
         else if (!strcmp(argv[a], "-z")) use_zlib = true;
-        else if (!strcmp(argv[a], "--long")) long_mode = true; else if (!strcmp(argv[a], "-Q")) qlevels = atoi(argv[++a]);
+        else if (!strcmp(argv[a], "--long")) long_mode = true; else if (!strcmp(argv[a], "--pairs")) pairs = true; else if (!strcmp(argv[a], "-Q")) qlevels = atoi(argv[++a]);
     }
     if (outp.empty()) { fprintf(stderr, "usage: bamgen -o out.bam -n records [-s scale] [-t threads] [-l level] [-S seed] [-z]\n"); return 2; }
     if (scale < 0) scale = long_mode ? std::min(1.0, (double)R / 1e7) : (double)R / 1e9;      // (long reads: 1e7 records of 15 kb = 50x of the 3 Gb genome)
@@ -245,7 +248,7 @@ int main(int argc, char **argv)
             put32(rec, (uint32_t)p.tid); put32(rec, pos[i]);
             rec.push_back((uint8_t)ln); rec.push_back((uint8_t)mq); put16(rec, (uint32_t)reg2bin(pos[i], pos[i] + span));
             put16(rec, (uint32_t)nc); put16(rec, flag); put32(rec, 150);
-            put32(rec, (uint32_t)p.tid); const int32_t mpos = (int32_t)pos[i] + (int32_t)r.below(400) - 100; put32(rec, (uint32_t)(mpos < 0 ? 0 : mpos)); put32(rec, (uint32_t)(300 + r.below(200)));
+            put32(rec, (uint32_t)p.tid); const int32_t mpos = (int32_t)pos[i] + (int32_t)r.below(400) - 100; put32(rec, (uint32_t)(mpos < 0 ? 0 : mpos)); { const int32_t tl = (int32_t)(300 + r.below(200)); put32(rec, (uint32_t)(pairs && (flag & 16) ? -tl : tl)); }
             rec.insert(rec.end(), name, name + ln);
             for (int k = 0; k < nc; ++k) put32(rec, cig[k]);
             // SEQ: the reference under the aligned bases (inserted / clipped bases random), 0.5 % mismatches
