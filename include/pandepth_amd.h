@@ -209,6 +209,20 @@ int pd_depth_thresholds(pd_ctx *ctx, const pd_region *segs, size_t n_segs, const
 /* the same for the windows of pd_window_layout(w) (row = window win_off[t] + k), without a region list crossing the link */
 int pd_window_thresholds(pd_ctx *ctx, uint32_t w, const uint32_t *thr, uint32_t n_thr, uint32_t *counts);
 
+/* Depth by GC content of fixed windows (the -gcbias file), binned on the device in one pass over the depth cells and the bases.  After
+ * pd_scan.  regs == NULL / n == 0: whole contigs; otherwise the cells [first-1, second) of the given regions, clipped to their contig,
+ * sorted by (tid, first) and not overlapping (pd_depth_histogram's rule and errors); touching regions are allowed.  Every contig or
+ * region is tiled from its first cell by windows of exactly w cells (1 <= w <= 2^20, else PD_EINVAL); a trailing stretch shorter than w
+ * belongs to no window.  bases[t] is a HOST pointer to the n_bases[t] bases of contig t (NULL: none; bases == NULL: no contig has any).
+ * After case folding c / g count as GC and a / t as AT; every other byte, and every cell at or beyond n_bases[t], is invalid.  A window
+ * with an invalid cell adds one to *skipped; any other window with g GC cells goes to bin (200 g + w) / (2 w) — its percentage rounded
+ * half up —, adding one to windows[bin] and the sum of its depth cells to sum[bin] (101 entries each).  The outputs are set, not added to;
+ * only they come back over the link.  The bases go up in pieces of whole windows ("gcbias_piece_cells", pandepth_amd_dev.h) through
+ * page-locked buffers of the call's own, the copy of a piece under the kernel of the piece before; device scratch stays below 256 MiB.
+ * All arithmetic is integer: the results do not depend on the piece size or the launch shape.  The context is left as it was found. */
+int pd_depth_gc_bias(pd_ctx *ctx, const pd_region *regs, size_t n, uint32_t w, const char *const *bases, const uint32_t *n_bases,
+                     uint64_t *windows /*101*/, uint64_t *sum /*101*/, uint64_t *skipped);
+
 /* Replaces the per-site read loop PD:4278-4281: copies depth cells [beg, beg+n) of contig tid
  * to the host.  Requires pd_scan first. */
 int pd_read_depth(pd_ctx *ctx, int32_t tid, uint32_t beg, size_t n, uint32_t *out);

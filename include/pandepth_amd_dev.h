@@ -33,7 +33,10 @@ extern "C" {
  * over many workgroups).  0 / 0 sends every row through the pieces, 0 / 2^32-1 every row through one workgroup.
  * Thresholds: "threshold_wave_max" (below 2^32, default 65536: rows of up to that many cells are counted by a group of lanes with one
  * writer per row; longer rows are cut into pieces of 16384 cells, a wave each, that add into the row).  0 sends every row with cells
- * through the pieces, 2^32-1 every row through the lanes. */
+ * through the pieces, 2^32-1 every row through the lanes.
+ * GC bias: "gcbias_piece_cells" (1..2^26, default 2^25: the cells — and base bytes — of one piece of pd_depth_gc_bias, rounded down to
+ * whole windows, at least one; two pieces are staged at a time), "gcbias_wave_max" (below 2^32, default 4096: windows of up to that many
+ * cells are read by a group of 1 .. 64 lanes, wider ones by a workgroup each).  Neither changes a result. */
 int pd_set_param(pd_ctx *ctx, const char *name, uint64_t value);
 
 /* ---- GPU-side BAM decode, the one-call synchronous form (round 1's entry point, kept on top of

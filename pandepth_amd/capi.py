@@ -111,6 +111,7 @@ def load():
         "pd_window_quantiles": (I, [P, ctypes.c_uint32, P, ctypes.c_uint32, P]),
         "pd_depth_thresholds": (I, [P, P, SZ, P, SZ, P, ctypes.c_uint32, P, P]),
         "pd_window_thresholds": (I, [P, ctypes.c_uint32, P, ctypes.c_uint32, P]),
+        "pd_depth_gc_bias": (I, [P, P, SZ, ctypes.c_uint32, P, P, P, P, P]),
         "pd_read_depth": (I, [P, ctypes.c_int32, ctypes.c_uint32, SZ, P]),
         "pd_format_sites": (I, [P, ctypes.c_int32, ctypes.c_uint32, SZ, ctypes.c_char_p, SZ, P, SZ, ctypes.POINTER(SZ)]),
         "pd_deflate_parse": (I, [P, P, SZ, P, ctypes.c_uint32, P, SZ, P]),
@@ -173,7 +174,7 @@ def load():
 
 EXPORTS = ["pd_abi_version", "pd_create", "pd_destroy", "pd_strerror", "pd_reset", "pd_push_intervals",
            "pd_push_intervals_device", "pd_runs_create", "pd_runs_destroy", "pd_push_runs", "pd_stage_acquire", "pd_stage_submit", "pd_set_param", "pd_keep_deferred", "pd_scan",
-           "pd_reduce_intervals", "pd_window_layout", "pd_scan_reduce_windows", "pd_reduce_windows", "pd_scan_depth_histogram", "pd_depth_histogram", "pd_depth_levels", "pd_depth_quantiles", "pd_window_quantiles", "pd_depth_thresholds", "pd_window_thresholds",
+           "pd_reduce_intervals", "pd_window_layout", "pd_scan_reduce_windows", "pd_reduce_windows", "pd_scan_depth_histogram", "pd_depth_histogram", "pd_depth_levels", "pd_depth_quantiles", "pd_window_quantiles", "pd_depth_thresholds", "pd_window_thresholds", "pd_depth_gc_bias",
            "pd_read_depth", "pd_format_sites", "pd_deflate_parse", "pd_host_register", "pd_host_unregister", "pd_text_open", "pd_text_close", "pd_text_append_sites", "pd_text_parse", "pd_text_read", "pd_text_release", "pd_text_append_window_rows", "pd_text_append_bytes", "pd_device_buffer", "pd_device_count", "pd_accumulate_from", "pd_device_layout", "pd_export_i8", "pd_import_i8", "pd_export_i4",
            "pd_slice_sweep_i4", "pd_gather_windows", "pd_push_bgzf_units", "pd_decode_begin", "pd_decode_acquire", "pd_decode_submit", "pd_decode_queue", "pd_decode_collect", "pd_decode_end", "pd_decode_abort", "pd_comm_unique_id", "pd_comm_init", "pd_comm_init_all", "pd_comm_init_local", "pd_comm_preinit", "pd_comm_prepare", "pd_comm_destroy",
            "pd_comm_strerror", "pd_sliced_window_sum", "pd_sliced_interval_sum", "pd_sliced_sum_start", "pd_sliced_sum_finish", "pd_x_bgzf_inflate", "pd_stream", "pd_synchronize", "pd_profile",
@@ -514,6 +515,27 @@ class Engine:
         thb = th if nt else np.zeros(1, dtype=np.uint32)
         self._ck(self.L.pd_window_thresholds(self.h, int(w), _ptr(thb), nt, _ptr(counts)))
         return off, counts[:n]
+
+    def depth_gc_bias(self, w, bases, regs=None):
+        """pd_depth_gc_bias after scan: windows of w cells tiled from the first cell of every contig (regs None / empty) or of
+        every region ((n, 3) int32: tid, first, second; sorted by (tid, first), disjoint).  bases: one bytes-like object (bytes,
+        uint8 array) or None per contig.  Returns (windows uint64 (101,), sum uint64 (101,), skipped int)."""
+        keep = [None if b is None else np.ascontiguousarray(np.frombuffer(b, dtype=np.uint8) if isinstance(b, (bytes, bytearray)) else b, dtype=np.uint8)
+                for b in bases]
+        assert len(keep) == self.n_contigs
+        ptrs = (ctypes.c_void_p * max(self.n_contigs, 1))(*[None if b is None else b.ctypes.data for b in keep])
+        nb = np.array([0 if b is None else b.size for b in keep] + [0], dtype=np.uint32)
+        windows = np.zeros(101, dtype=np.uint64)
+        tot = np.zeros(101, dtype=np.uint64)
+        skipped = ctypes.c_uint64(0)
+        if regs is None or len(regs) == 0:
+            r, n = None, 0
+        else:
+            r = np.ascontiguousarray(regs, dtype=np.int32).reshape(-1, 3)
+            n = r.shape[0]
+        self._ck(self.L.pd_depth_gc_bias(self.h, None if r is None else _ptr(r), n, int(w), ctypes.cast(ptrs, ctypes.c_void_p), _ptr(nb), _ptr(windows), _ptr(tot),
+                                         ctypes.cast(ctypes.byref(skipped), ctypes.c_void_p)))
+        return windows, tot, int(skipped.value)
 
     def read_depth(self, tid, beg=0, n=None):
         if n is None:

@@ -697,6 +697,8 @@ int pd_set_param(pd_ctx *c, const char *name, uint64_t value)
     if (!strcmp(name, "hist_variant")) { if (value > 3) return fail(c, PD_EINVAL, "hist_variant must be in [0, 3]"); c->hist_variant = (int)value; return PD_OK; }
     if (!strcmp(name, "quantile_wave_max")) { if (value > 2048) return fail(c, PD_EINVAL, "quantile_wave_max must be in [0, 2048]"); c->q_wave_max = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "threshold_wave_max")) { if (value > 0xFFFFFFFFull) return fail(c, PD_EINVAL, "threshold_wave_max must be below 2^32"); c->t_wave_max = (uint32_t)value; return PD_OK; }
+    if (!strcmp(name, "gcbias_piece_cells")) { if (value < 1 || value > (1ull << 26)) return fail(c, PD_EINVAL, "gcbias_piece_cells must be in [1, 2^26]"); c->gc_piece_cells = value; return PD_OK; }
+    if (!strcmp(name, "gcbias_wave_max")) { if (value > 0xFFFFFFFFull) return fail(c, PD_EINVAL, "gcbias_wave_max must be below 2^32"); c->gc_wave_max = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "quantile_split_cells")) { if (value > 0xFFFFFFFFull) return fail(c, PD_EINVAL, "quantile_split_cells must be below 2^32"); c->q_split = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "decode_deletions")) { c->dec_deletions = value != 0; return PD_OK; }
     if (!strcmp(name, "decode_fragments")) { c->dec_fragments = value != 0; return PD_OK; }

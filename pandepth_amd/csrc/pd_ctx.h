@@ -170,7 +170,9 @@ struct pd_ctx {
     uint32_t direct_sample = 256;                                 // index stride of the direct path (runs)
     uint32_t q_wave_max = 512, q_split = 262144;                  // "quantile_wave_max" / "quantile_split_cells": the cell counts up to which a quantile row takes the narrow / the workgroup kernel
     uint32_t t_wave_max = 65536;                                  // "threshold_wave_max": the cell count up to which a threshold row is counted by a group of lanes, not in pieces
-    int hist_variant = 1;                                         // "hist_variant": the histogram kernels' LDS form (launch_sweep_hist): 1 = one copy per workgroup, folded (measured best)
+    uint64_t gc_piece_cells = (uint64_t)1 << 25;                  // "gcbias_piece_cells": the cells (= base bytes) of one piece of pd_depth_gc_bias, rounded down to whole windows (at least one)
+    uint32_t gc_wave_max = 4096;                                  // "gcbias_wave_max": the window width up to which a window is read by a group of lanes, not by a workgroup
+    int hist_variant = 1;                                        // "hist_variant": the histogram kernels' LDS form (launch_sweep_hist): 1 = one copy per workgroup, folded (measured best)
     int direct_un = 0;                                           // 0 = the default form of the direct kernels (launch_direct_tiles, launch_direct_c8)
     bool direct_cover = true;                                    // k_direct_c8's default form settles covered tiles from the runs (false: the window path for every tile)
     uint32_t direct_cover_min = 2048;                            // ... of tiles with at least this many candidates (launch_direct_c8)

@@ -1,4 +1,4 @@
-// extras.cpp — the outputs the reference does not have: -dist, -levels, -quantile and -thresholds.  Each is made after the main table is
+// extras.cpp — the outputs the reference does not have: -dist, -levels, -quantile, -thresholds and -gcbias.  Each is made after the main table is
 // written and the per-site job started, so that their path and timing stay as they are; each is one entry of EXTRAS, which the
 // finish step of every table family and the exit for a PAF without targets (pipeline.cpp) walk in order.
 #include <string.h>
@@ -471,6 +471,111 @@ bool write_thresholds(Run &r)
     return true;
 }
 
+constexpr uint32_t GC_BINS = 101;
+
+// -gcbias' file from the 203 numbers: 101 rows, GC 0 .. 100, and the closing line
+std::string gcbias_text(uint32_t W, const uint64_t *win, const uint64_t *sum, uint64_t skipped)
+{
+    auto f = [](const char *fmt, double v) { char b[64]; snprintf(b, sizeof b, fmt, v); return std::string(b); };
+    uint64_t n = 0, total = 0;
+    for (uint32_t b = 0; b < GC_BINS; ++b) { n += win[b]; total += sum[b]; }
+    const double mean_all = n ? (double)total / (double)(n * W) : 0.0;
+    std::string txt = "#GC\tWindows\tTotalDepth\tMeanDepth\tNormalized\n";
+    for (uint32_t b = 0; b < GC_BINS; ++b) {
+        txt += std::to_string(b); txt += '\t'; txt += std::to_string(win[b]); txt += '\t'; txt += std::to_string(sum[b]); txt += '\t';
+        if (!win[b]) { txt += "NA\tNA\n"; continue; }
+        const double mean = (double)sum[b] / (double)(win[b] * W);
+        txt += f("%.2f", mean); txt += '\t';
+        txt += total ? f("%.4f", mean / mean_all) : std::string("NA");
+        txt += '\n';
+    }
+    txt += "##WindowSize: " + std::to_string(W) + "\tWindows: " + std::to_string(n) + "\tSkipped: " + std::to_string(skipped) + "\tMeanDepth: " + (n ? f("%.2f", mean_all) : std::string("NA")) + "\n";
+    return txt;
+}
+
+std::string gcbias_empty(const Run &r)
+{
+    const uint64_t zero[GC_BINS] = {};
+    return gcbias_text(r.o.gcbias, zero, zero, 0);
+}
+
+// -gcbias on engines without the entry point: the spans' cells are read back, a stretch of whole windows at a time, and binned here
+bool host_gc_bias(Run &r, const std::vector<pd_region> &regs, const std::vector<const char *> &bases,
+                  const std::vector<uint32_t> &n_bases, uint64_t *win, uint64_t *sum, uint64_t *skipped)
+{
+    const uint64_t W = r.o.gcbias, per = std::max<uint64_t>(1, ((uint64_t)1 << 22) / W);          // windows per read
+    std::vector<uint32_t> d;
+    auto span = [&](int32_t t, uint64_t b, uint64_t e) {
+        const unsigned char *s = (const unsigned char *)bases[(size_t)t];
+        const uint64_t have = s ? n_bases[(size_t)t] : 0;
+        for (uint64_t left = (e - b) / W, p = b; left;) {
+            const uint64_t take = std::min(left, per);
+            d.resize((size_t)(take * W));
+            if (!r.read_cells(t, p, take * W, d.data())) return false;
+            for (uint64_t k = 0; k < take; ++k, p += W) {
+                if (p + W > have) { ++*skipped; continue; }
+                uint64_t g = 0, tot = 0; bool bad = false;
+                for (uint64_t i = 0; i < W && !bad; ++i) {
+                    const unsigned c = s[p + i] | 0x20u;
+                    if (c == 'c' || c == 'g') ++g; else if (c != 'a' && c != 't') bad = true;
+                    tot += d[(size_t)(k * W + i)];
+                }
+                if (bad) { ++*skipped; continue; }
+                const uint64_t bin = (200 * g + W) / (2 * W);
+                ++win[bin]; sum[bin] += tot;
+            }
+            left -= take;
+        }
+        return true;
+    };
+    for (const pd_region &g : regs) if (!span(g.tid, (uint64_t)g.first - 1, (uint64_t)g.second)) return false;
+    return true;
+}
+
+// -gcbias W: depth by GC content, in <prefix>.gcbias.stat.gz.  The cells are -dist's (covered_cells); every contig — in -g / -b every
+// merged region — is tiled from its first cell by windows of exactly W cells, a shorter rest belonging to none (simpler than Picard's
+// window sliding by one base).  A contig's bases are those of the first FASTA record that carries its name (RefSeqs::named); a window
+// with a cell that is not A / C / G / T in either case, or that the record does not reach, is skipped; any other goes to the bin of its GC
+// percentage rounded half up.  Binned on the engine (pd_depth_gc_bias: the bases go up, 203 numbers come back) or, without that member,
+// on the host from cells read back.  The arena has been kept for this and is given back here.
+bool write_gcbias(Run &r)
+{
+    const pd_engine_api *api = r.api;
+    Engine &eng = *r.eng;
+    const uint32_t W = r.o.gcbias;
+    std::vector<int32_t> tids;
+    std::vector<pd_region> regs;
+    covered_cells(r, tids, regs);
+    if (!r.need_scan()) return false;
+    const size_t nc = r.hdr.names.size();
+    std::vector<const char *> bases(nc ? nc : 1, nullptr);
+    std::vector<uint32_t> n_bases(nc ? nc : 1, 0);
+    for (size_t t = 0; t < nc; ++t) {
+        const char *p; size_t n;
+        if (r.ref.named(r.hdr.names[t], &p, &n)) { bases[t] = p; n_bases[t] = (uint32_t)std::min<size_t>(n, 0xFFFFFFFFu); }
+    }
+    uint64_t win[GC_BINS] = {}, sum[GC_BINS] = {}, skipped = 0;
+    const bool dev = api->depth_gc_bias && !(tune("gcbias_device") && tune("gcbias_device")[0] == '0');
+    if (dev && api->set_param)
+        for (const char *k : {"gcbias_piece_cells", "gcbias_wave_max"})
+            if (const char *e = tune(k)) (void)api->set_param(eng.ctx, k, (uint64_t)strtoull(e, nullptr, 10));
+    if (r.synthetic) {                                       // whole contigs, but only the table's: one region each
+        regs.clear();
+        for (int32_t t : tids) if (r.hdr.lens[(size_t)t]) regs.push_back(pd_region{t, 1, (int32_t)r.hdr.lens[(size_t)t]});
+    }
+    if (dev) {
+        if (!regs.empty() && !eng.ck(api->depth_gc_bias(eng.ctx, regs.data(), regs.size(), W, bases.data(), n_bases.data(), win, sum, &skipped), "pd_depth_gc_bias")) return false;
+    } else if (!host_gc_bias(r, regs, bases, n_bases, win, sum, &skipped)) return false;
+    r.ref.clear();
+    GzWriter G;
+    const std::string path = r.prefix + ".gcbias.stat.gz";
+    if (!G.open(path)) { eng.fail("cannot open " + path); return false; }
+    G.write(gcbias_text(W, win, sum, skipped));
+    if (!G.close()) { ::remove(path.c_str()); eng.fail("cannot write " + path); return false; }
+    r.tm.mark("gc bias");
+    return true;
+}
+
 } // namespace
 
 const Extra EXTRAS[] = {
@@ -478,6 +583,7 @@ const Extra EXTRAS[] = {
     {".levels.bed.gz", [](const Options &o) { return o.levels; }, [](const Run &) { return std::string(); }, write_levels},
     {".quantile.stat.gz", [](const Options &o) { return !o.quantile.empty(); }, quantile_header, write_quantile},
     {".thresholds.stat.gz", [](const Options &o) { return !o.thresholds.empty(); }, thresholds_header, write_thresholds},
+    {".gcbias.stat.gz", [](const Options &o) { return o.gcbias != 0; }, gcbias_empty, write_gcbias},
 };
 const size_t N_EXTRAS = sizeof(EXTRAS) / sizeof(EXTRAS[0]);
 

@@ -115,6 +115,7 @@ bool load_reference(const std::string &path, std::map<std::string, int32_t> *chr
     out->loaded = true;
     std::string *arena = out->arena();
     return read_fasta_records(path, arena, [&](const std::string &name, size_t off, size_t n) {
+        out->note(name, off, n);
         const void *z = memchr(arena->data() + off, 0, n);     // `string seqBB = seq->seq.s` stops at a NUL
         if (z) n = (size_t)((const char *)z - (arena->data() + off));
         auto it = chr2tid->find(name);
@@ -124,11 +125,36 @@ bool load_reference(const std::string &path, std::map<std::string, int32_t> *chr
     });
 }
 
+bool load_reference_named(const std::string &path, RefSeqs *out)
+{
+    out->keep_named(true);
+    std::string *arena = out->arena();
+    return read_fasta_records(path, arena, [&](const std::string &name, size_t off, size_t n) {
+        out->note(name, off, n);
+        out->drop(off);
+    });
+}
+
 bool RefSeqs::claim(int32_t tid, size_t off, size_t n)
 {
-    if (span_.find(tid) != span_.end()) { arena_.resize(off); return false; }
+    if (span_.find(tid) != span_.end()) { drop(off); return false; }
     span_[tid] = {off, n};
-    arena_.resize(off + n);
+    arena_.resize(std::max(hold_, off + n));
+    return true;
+}
+
+void RefSeqs::note(const std::string &name, size_t off, size_t n)
+{
+    if (!keep_named_ || named_.find(name) != named_.end()) return;
+    named_[name] = {off, n};
+    hold_ = off + n;
+}
+
+bool RefSeqs::named(const std::string &name, const char **p, size_t *n) const
+{
+    auto it = named_.find(name);
+    if (it == named_.end()) return false;
+    *p = arena_.data() + it->second.first; *n = it->second.second;
     return true;
 }
 

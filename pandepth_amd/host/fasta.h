@@ -11,6 +11,7 @@
 #ifndef PD_FASTA_H_
 #define PD_FASTA_H_
 #include <stdint.h>
+#include <algorithm>
 #include <functional>
 #include <map>
 #include <string>
@@ -28,10 +29,21 @@ struct RefSeqs {
     std::string *arena() { return &arena_; }
     bool claim(int32_t tid, size_t off, size_t n);
     size_t n_seqs() const { return span_.size(); }
-    void clear() { std::string().swap(arena_); span_.clear(); }
+    void clear() { std::string().swap(arena_); span_.clear(); named_.clear(); hold_ = 0; }
+    // The view BY NAME (-gcbias): with keep_named(true) set before loading, note(), called for every record ahead of claim(),
+    // remembers the first record of each name with ALL its bases and keeps them in the arena whatever claim() then decides — so
+    // that a contig finds the record that carries its name even where the tid view above gave its slot to another record (the
+    // unknown-name quirk, a repeated name).  The tid view, and with it the GC(%) column, is the same with and without.
+    void keep_named(bool on) { keep_named_ = on; }
+    void note(const std::string &name, size_t off, size_t n);
+    void drop(size_t off) { arena_.resize(std::max(hold_, off)); }       // the bases from `off` on, unless a noted record holds them
+    bool named(const std::string &name, const char **p, size_t *n) const;
 private:
     std::string arena_;
     std::map<int32_t, std::pair<size_t, size_t>> span_;
+    bool keep_named_ = false;
+    size_t hold_ = 0;                       // the arena is never cut below this
+    std::map<std::string, std::pair<size_t, size_t>> named_;
 };
 
 // every record of a FASTA/FASTQ file (plain or gzip) in file order: the bases are APPENDED to *dst (reserved from the file
@@ -42,6 +54,9 @@ bool read_fasta_records(const std::string &path, std::string *dst, const std::fu
 // false when the file cannot be opened (the reference never returns from that: its reader spins on a
 // NULL gzFile); chr2tid gains the unknown names (-> 0)
 bool load_reference(const std::string &path, std::map<std::string, int32_t> *chr2tid, RefSeqs *out);
+
+// the view by name alone (-gcbias without -c): no name table is touched, no contig id claimed, RefSeqs::loaded stays as it is
+bool load_reference_named(const std::string &path, RefSeqs *out);
 
 } // namespace pdh
 #endif

@@ -233,7 +233,16 @@ int parse_options(int argc, char **argv, Options *o)
             }
             if (!good) { o->thresholds.clear(); std::cerr << "Error: -thresholds should be 1 to 16 ascending depths, such as 1,10,20,30" << std::endl; return 0; }
         }
-        else if (flag == "del") o->count_del = true;                             // not in the reference: deletions count as covered (README)
+        else if (flag == "gcbias") {                                             // not in the reference: the .gcbias.stat.gz curve (README)
+            const char *msg = "Error: -gcbias should be a window size from 1 to 1048576";
+            if (i + 1 == argc) { std::cerr << msg << std::endl; return 0; }
+            v = argv[++i];
+            uint64_t x = 0; bool good = !v.empty() && v.size() <= 7;
+            for (size_t k = 0; good && k < v.size(); ++k) { if (v[k] < '0' || v[k] > '9') good = false; else x = x * 10 + (uint64_t)(v[k] - '0'); }
+            if (!good || x < 1 || x > (1u << 20)) { std::cerr << msg << std::endl; return 0; }
+            o->gcbias = (uint32_t)x;
+        }
+        else if (flag == "del") o->count_del = true;                            // not in the reference: deletions count as covered (README)
         else if (flag == "frag") o->frag = true;                                 // not in the reference: whole fragments of properly paired reads (README)
         else if (flag == "fragmax") {                                            // ... and the largest |tlen| that still makes a fragment
             if (!arg(&v)) return 0;
@@ -246,6 +255,7 @@ int parse_options(int argc, char **argv, Options *o)
         else { std::cerr << "Error UnKnow argument -" << flag << std::endl; return 0; }
     }
     if (fragmax_given && !o->frag) { std::cerr << "Error: -fragmax needs -frag" << std::endl; return 0; }
+    if (o->gcbias && o->reference.empty()) { std::cerr << "Error: -gcbias needs the reference sequence (-r)" << std::endl; return 0; }
     if (o->frag) o->use_index = false;                                           // a left mate that ends before a region can still cover it: no index fetch
     if (n_inputs > 0) o->input = o->inputs[0];
     if (o->input.empty() || o->out.empty()) { std::cerr << "Error: lack argument -i or -o " << std::endl; return 0; }

@@ -1,4 +1,4 @@
-// options.h — the command-line surface of `pandepth` (-i -o -g -f -b -w -a -q -d -x -t -s -c -r -h; of its own: -dist -levels -quantile -thresholds -del -frag -fragmax);
+// options.h — the command-line surface of `pandepth` (-i -o -g -f -b -w -a -q -d -x -t -s -c -r -h; of its own: -dist -levels -quantile -thresholds -gcbias -del -frag -fragmax);
 // -i takes SAM / BAM / CRAM 2.1 / 3.0 / 3.1 / PAF files or a #.list of them.
 // Behaviour follows the reference's parser (PD:84-293) including its quirks: every '-' is
 // stripped from a flag, `*.list`/`*.List` expands to one input per non-empty line, -w < 1 and
@@ -35,6 +35,7 @@ struct Options {
     bool count_del = false;              // -del (not in the reference): deletions count as covered — one run per group of M/=/X/D operations that no N splits, instead of one per M/=/X
     bool frag = false;                   // -frag (not in the reference): a properly paired read with tlen > 0 counts as the one run [pos, pos + tlen), its mate as nothing; clears use_index
     uint32_t frag_max = 0x7FFFFFFFu;     // -fragmax N, 1 .. 2^31 - 1 (needs -frag): pairs with |tlen| above it are two ordinary reads
+    uint32_t gcbias = 0;                 // -gcbias W (not in the reference; needs -r): <out>.gcbias.stat.gz, depth by GC content of windows of W cells, 1 .. 2^20 (0: off)
     std::vector<uint32_t> thresholds;    // -thresholds SPEC (not in the reference): <out>.thresholds.stat.gz, per-row counts of cells at or above each depth; 1..16 values below 2^31, strictly ascending
 };
 
@@ -62,6 +63,8 @@ void print_help();
 //   quantile_device=0 (the -quantile rows selected on the host threads from cells read back, as an engine without the entry points does)
 //   threshold_wave_max=N (pd_set_param key of the -thresholds kernels: the row size above which a row is counted in pieces, see pandepth_amd_dev.h)
 //   thresholds_device=0 (the -thresholds rows counted on the host threads from cells read back, as an engine without the entry points does)
+//   gcbias_piece_cells=N  gcbias_wave_max=N (pd_set_param keys of the -gcbias pass: the piece size and the width at which the launch shape changes, see pandepth_amd_dev.h)
+//   gcbias_device=0 (the -gcbias windows binned on the host threads from cells read back, as an engine without the entry point does)
 //   environment: PANDEPTH_DEVTRACE=1 (a [devtrace] line per batch: host-clock times of its stage events; first batches: what pd_decode_queue's own time went to)
 // -X is not part of the reference's command line (which answers an unknown flag with "Error UnKnow argument"): it is accepted only in this
 // spelling, is not listed by -h, and a PANDEPTH_* variable of the earlier rounds that is still set gets a note on stderr.

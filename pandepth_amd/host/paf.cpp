@@ -85,6 +85,7 @@ bool paf_targets(const Options &o, AlnHeader *hdr, std::map<std::string, int32_t
         std::string *arena = ref->arena();
         return read_fasta_records(o.reference, arena, [&](const std::string &name, size_t off, size_t n) {
             const int32_t id = (int32_t)hdr->names.size();
+            ref->note(name, off, n);
             (*chr2tid)[name] = id;
             hdr->names.push_back(name);
             hdr->lens.push_back((uint32_t)n);

@@ -1567,6 +1567,7 @@ int open_targets(Run &r, AlnReader *first, std::map<std::string, int32_t> *paf_n
 {
     Options &o = r.o;
     bool regions_ok = true;
+    r.ref.keep_named(o.gcbias != 0);
     if (r.paf) {
         std::cout << (r.list_mode ? "INFO: Run PAF format data " : "INFO: Run paf Format data ") << std::endl;
         if (o.gc && o.reference.empty()) { std::cerr << "Error: lack reference sequence (-r) for GC parse" << std::endl; return 0; }   // PD:909-913
@@ -1590,7 +1591,13 @@ int open_targets(Run &r, AlnReader *first, std::map<std::string, int32_t> *paf_n
         return 1;
     }
     r.gc = r.ref.loaded;
-    if (r.gc && o.mode != 6) r.ref.clear();              // PD:4095-4097 (the bins and genes hold their counts by now)
+    // -gcbias reads the bases after the tables: the arena (a byte per base of the FASTA, 3 GB of host memory for a human genome)
+    // stays until write_gcbias has run, and is loaded here, by name alone, when no GC(%) column has loaded it
+    if (o.gcbias && !r.ref.loaded && !load_reference_named(o.reference, &r.ref)) {
+        std::cerr << "Error: Cannot open the reference sequence file: " << o.reference << std::endl;
+        return 1;
+    }
+    if (r.gc && o.mode != 6 && !o.gcbias) r.ref.clear(); // PD:4095-4097 (the bins and genes hold their counts by now)
     r.synthetic = o.mode == 0 || o.mode == 5 || o.mode == 6;
     return GO_ON;
 }

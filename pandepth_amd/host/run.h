@@ -129,7 +129,7 @@ inline std::vector<const GeneEntry *> genes_in_table_order(const std::map<std::s
     return order;
 }
 
-// extras.cpp — the outputs the reference does not have (-dist, -levels, -quantile, -thresholds), one entry each
+// extras.cpp — the outputs the reference does not have (-dist, -levels, -quantile, -thresholds, -gcbias), one entry each
 struct Extra {
     const char *suffix;                          // <prefix><suffix>
     bool (*enabled)(const Options &o);
