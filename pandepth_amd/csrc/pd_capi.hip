@@ -1,4 +1,4 @@
-// pd_capi.hip — implementation of include/pandepth_amd.h on top of pd_kernels.hip and pd_direct.hip.
+// pd_capi.hip — implementation of include/pandepth_amd.h on top of pd_kernels.hip and pd_direct.hip, all but the window calls (pd_windows.hip), the decode session (pd_decode.hip), the row statistics (pd_rows.hip) and -gcbias (pd_gcbias.hip).
 //
 // One context = one GPU, one compute stream, one copy stream, one int32 allocation holding all
 // contig difference arrays followed by the tile sums.  Host batches go through a small pool of
@@ -934,156 +934,6 @@ int pd_scan(pd_ctx *c, unsigned wrap_bits)
     return PD_OK;
 }
 
-// ---- depth histograms ----
-// The rows go to a zeroed uint64 array in the scratch buffer (behind `lead` bytes the caller uses), the kernels add into it, the
-// host gets it back.  Grid: eight workgroups per CU, each a run of tiles / pieces (one flush of its non-zero bins per contig).
-static int hist_finish(pd_ctx *c, uint64_t *d_hist, size_t b_hist, uint64_t *hist)
-{
-    HIPOK(c, hipGetLastError());
-    HIPOK(c, hipMemcpyAsync(hist, d_hist, b_hist, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));
-    return PD_OK;
-}
-
-int pd_scan_depth_histogram(pd_ctx *c, uint32_t n_bins, unsigned wrap_bits, uint64_t *hist)
-{
-    if (!c || !hist || n_bins < 2 || n_bins > 4097 || wrap_bits > 32) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 0, "pd_scan_depth_histogram")) return rs;
-    HIPOK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c);                                   // a deferred sample is materialised (later calls see it as before)
-    if (rc) return rc;
-    rc = check_words(c);
-    if (rc) return rc;
-    const uint32_t mask = pdwin::wrap_mask(wrap_bits);
-    const size_t b_hist = (size_t)c->n_contigs * n_bins * 8;
-    rc = ensure_scratch(c, b_hist + 64);
-    if (rc) return rc;
-    uint64_t *d_hist = (uint64_t *)c->scratch;
-    HIPOK(c, hipMemsetAsync(d_hist, 0, b_hist, c->stream));
-    { ProfScope ps(c, "tile_carry"); launch_tile_carry(c->stream, c->sums, c->bsum, c->carry, (uint32_t)c->n_tiles); }
-    {
-        ProfScope ps(c, "scan_depth_histogram");
-        TileMap tm{c->d_tile_contig, c->d_off, c->d_len, nullptr};
-        if (launch_sweep_hist(c->stream, c->buf, c->carry, (uint32_t)c->n_tiles, mask, tm, c->hstate, false, n_bins,
-                              (unsigned long long *)d_hist, (unsigned)c->n_cu * 8, c->hist_variant))
-            return fail(c, PD_EHIP, "histogram sweep: cannot reserve LDS");
-    }
-    return hist_finish(c, d_hist, b_hist, hist);
-}
-
-int pd_depth_histogram(pd_ctx *c, const pd_region *regs, size_t n, uint32_t n_bins, uint64_t *hist)
-{
-    if (!c || !hist || (n && !regs) || n_bins < 2 || n_bins > 4097) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 1, "pd_depth_histogram")) return rs;
-    HIPOK(c, hipSetDevice(c->device));
-    const size_t b_hist = (size_t)c->n_contigs * n_bins * 8, b_histr = (b_hist + 15) / 16 * 16;
-    if (!regs || n == 0) {                                       // whole contigs: the histogram sweep over the depth (int4 rows)
-        int rc = ensure_scratch(c, b_hist + 64);
-        if (rc) return rc;
-        uint64_t *d_hist = (uint64_t *)c->scratch;
-        HIPOK(c, hipMemsetAsync(d_hist, 0, b_hist, c->stream));
-        {
-            ProfScope ps(c, "depth_histogram");
-            TileMap tm{c->d_tile_contig, c->d_off, c->d_len, nullptr};
-            if (launch_sweep_hist(c->stream, c->buf, nullptr, (uint32_t)c->n_tiles, 0xFFFFFFFFu, tm, nullptr, true, n_bins,
-                                  (unsigned long long *)d_hist, (unsigned)c->n_cu * 8, c->hist_variant))
-                return fail(c, PD_EHIP, "histogram sweep: cannot reserve LDS");
-        }
-        return hist_finish(c, d_hist, b_hist, hist);
-    }
-    // regions: checked, clipped to [0, len), cut into pieces of at most 16384 cells (Piece.region = the contig)
-    constexpr uint32_t PIECE = 16384;
-    std::vector<Piece> pieces;
-    pieces.reserve(n + n / 8);
-    int32_t prev_tid = -1; int64_t prev_first = 0, prev_end = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const pd_region &r = regs[i];
-        if (r.tid < 0 || r.tid >= c->n_contigs) return fail(c, PD_EINVAL, "pd_depth_histogram: contig id out of range");
-        const int64_t b0 = (int64_t)r.first - 1, e0 = r.second;
-        if (r.tid < prev_tid || (r.tid == prev_tid && r.first < prev_first))
-            return fail(c, PD_EINVAL, "pd_depth_histogram: regions not sorted by (tid, first)");
-        if (r.tid != prev_tid) prev_end = INT64_MIN;
-        if (e0 > b0) {
-            if (b0 < prev_end) return fail(c, PD_EINVAL, "pd_depth_histogram: regions overlap");
-            prev_end = e0;
-        }
-        prev_tid = r.tid; prev_first = r.first;
-        int64_t b = b0 < 0 ? 0 : b0, e = e0;
-        if (e > (int64_t)c->len[r.tid]) e = (int64_t)c->len[r.tid];
-        for (int64_t p = b; p < e; p += PIECE) {
-            Piece pc; pc.start = c->off[r.tid] + (uint64_t)p;
-            pc.count = (uint32_t)((e - p) < PIECE ? (e - p) : PIECE); pc.region = (uint32_t)r.tid;
-            pieces.push_back(pc);
-        }
-    }
-    if (pieces.size() > 0xFFFFFFF0ull) return fail(c, PD_EINVAL, "pd_depth_histogram: too many regions");
-    const size_t b_p = pieces.size() * sizeof(Piece);
-    int rc = ensure_scratch(c, b_histr + b_p + 64);
-    if (rc) return rc;
-    unsigned char *s = (unsigned char *)c->scratch;
-    uint64_t *d_hist = (uint64_t *)s;
-    Piece *d_p = (Piece *)(s + b_histr);
-    HIPOK(c, hipMemsetAsync(d_hist, 0, b_hist, c->stream));
-    if (!pieces.empty()) HIPOK(c, hipMemcpyAsync(d_p, pieces.data(), b_p, hipMemcpyHostToDevice, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));          // pieces is a local
-    {
-        ProfScope ps(c, "depth_histogram_regions");
-        if (launch_hist_pieces(c->stream, c->buf, d_p, (uint32_t)pieces.size(), n_bins, (unsigned long long *)d_hist,
-                               (unsigned)c->n_cu * 8, c->hist_variant))
-            return fail(c, PD_EHIP, "histogram of regions: cannot reserve LDS");
-    }
-    return hist_finish(c, d_hist, b_hist, hist);
-}
-
-int pd_reduce_intervals(pd_ctx *c, const pd_region *regs, size_t n, uint32_t min_dep, int32_t *cover, uint64_t *sum)
-{
-    if (!c || (n && (!regs || !cover || !sum))) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 1, "pd_reduce_intervals")) return rs;
-    if (n == 0) return PD_OK;
-    if (n > 0xFFFFFFF0ull) return fail(c, PD_EINVAL, "too many regions");
-    HIPOK(c, hipSetDevice(c->device));
-    constexpr uint32_t PIECE = 16384;
-    std::vector<Piece> pieces;
-    pieces.reserve(n + n / 8);
-    for (size_t i = 0; i < n; ++i) {
-        const pd_region &r = regs[i];
-        if (r.tid < 0 || r.tid >= c->n_contigs) return fail(c, PD_EINVAL, "pd_reduce_intervals: contig id out of range");
-        // cells [first-1, second), clipped to the slot (the reference reads its padding; it is zero here)
-        int64_t b = (int64_t)r.first - 1, e = r.second;
-        const int64_t slot = (int64_t)(c->off[r.tid + 1] - c->off[r.tid]);
-        if (b < 0) b = 0;
-        if (e > slot) e = slot;
-        for (int64_t p = b; p < e; p += PIECE) {
-            Piece pc; pc.start = c->off[r.tid] + (uint64_t)p;
-            pc.count = (uint32_t)((e - p) < PIECE ? (e - p) : PIECE); pc.region = (uint32_t)i;
-            pieces.push_back(pc);
-        }
-    }
-    const size_t b_p = pieces.size() * sizeof(Piece), b_sum = n * 8, b_cov = n * 4;
-    int rc = ensure_scratch(c, b_p + b_sum + b_cov + 64);
-    if (rc) return rc;
-    unsigned char *s = (unsigned char *)c->scratch;
-    unsigned long long *d_sum = (unsigned long long *)s;
-    Piece *d_p = (Piece *)(s + b_sum);
-    int *d_cov = (int *)(s + b_sum + b_p);
-    if (!pieces.empty()) HIPOK(c, hipMemcpyAsync(d_p, pieces.data(), b_p, hipMemcpyHostToDevice, c->stream));
-    HIPOK(c, hipMemsetAsync(d_sum, 0, b_sum, c->stream));
-    HIPOK(c, hipMemsetAsync(d_cov, 0, b_cov, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));          // pieces is a local
-    {
-        ProfScope ps(c, "reduce_intervals");
-        launch_reduce_pieces(c->stream, c->buf, d_p, (uint32_t)pieces.size(), min_dep, d_cov, d_sum);
-    }
-    HIPOK(c, hipGetLastError());
-    HIPOK(c, hipMemcpyAsync(sum, d_sum, b_sum, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(c, hipMemcpyAsync(cover, d_cov, b_cov, hipMemcpyDeviceToHost, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));
-    return PD_OK;
-}
-
 int pd_read_depth(pd_ctx *c, int32_t tid, uint32_t beg, size_t n, uint32_t *out)
 {
     if (!c || (!out && n)) return PD_EINVAL;
@@ -1132,454 +982,6 @@ int pd_format_sites(pd_ctx *c, int32_t tid, uint32_t beg, size_t n, const char *
     *n_bytes = (size_t)total;
     return PD_OK;
 }
-
-// ---- depth levels ----
-// Scratch: the edges, the waves' run counts, their offsets, then the pairs.  The pairs' size is known only after the count, so the
-// count runs first with the head alone; when the buffer then has to grow (it is freed for that), the count is simply run again.
-int pd_depth_levels(pd_ctx *c, int32_t tid, uint32_t beg, size_t n, const uint32_t *edges, uint32_t n_edges, pd_level *out, size_t cap, size_t *n_levels)
-{
-    if (!c || !n_levels || (!out && cap) || (!edges && n_edges)) return PD_EINVAL;
-    *n_levels = 0;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 1, "pd_depth_levels")) return rs;
-    if (tid < 0 || tid >= c->n_contigs) return fail(c, PD_EINVAL, "pd_depth_levels: contig id out of range");
-    if ((uint64_t)beg + n > (uint64_t)c->len[tid]) return fail(c, PD_EINVAL, "pd_depth_levels: range past the contig's end");
-    if (n > ((size_t)1 << 27)) return fail(c, PD_EINVAL, "pd_depth_levels: at most 2^27 cells per call");
-    if (n_edges > 64) return fail(c, PD_EINVAL, "pd_depth_levels: at most 64 edges");
-    for (uint32_t k = 1; k < n_edges; ++k)
-        if (edges[k] <= edges[k - 1]) return fail(c, PD_EINVAL, "pd_depth_levels: edges not strictly ascending");
-    if (n == 0) return PD_OK;
-    HIPOK(c, hipSetDevice(c->device));
-    const uint32_t a0 = beg & ~3u, lo = beg - a0, hi = lo + (uint32_t)n;        // int4-aligned start; the range relative to it
-    const uint32_t nw = pdk::levels_waves(hi);
-    const size_t b_edge = 256, b_cnt = (size_t)nw * 4, b_off = ((size_t)nw * 4 + 4 + 15) / 16 * 16, b_head = b_edge + b_cnt + b_off;
-    const uint32_t *src = (const uint32_t *)(c->buf + c->off[tid] + a0);
-    const uint32_t kcap = (uint32_t)(cap < n ? cap : n);         // (a range of n cells has at most n runs)
-    uint32_t total = 0;
-    uint32_t *d_edge = nullptr, *d_cnt = nullptr, *d_off = nullptr;
-    for (int round = 0; ; ++round) {
-        int rc = ensure_scratch(c, round == 0 ? b_head + 64 : b_head + (size_t)(total < kcap ? total : kcap) * 8 + 64);
-        if (rc) return rc;
-        unsigned char *s = (unsigned char *)c->scratch;
-        d_edge = (uint32_t *)s; d_cnt = (uint32_t *)(s + b_edge); d_off = (uint32_t *)(s + b_edge + b_cnt);
-        if (n_edges) HIPOK(c, hipMemcpyAsync(d_edge, edges, (size_t)n_edges * 4, hipMemcpyHostToDevice, c->stream));
-        {
-            ProfScope ps(c, "depth_levels");
-            pdk::launch_levels(c->stream, src, a0, lo, hi, d_edge, n_edges, d_cnt, d_off, nullptr, 0, false);
-        }
-        HIPOK(c, hipGetLastError());
-        HIPOK(c, hipMemcpyAsync(&total, d_off + nw, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(c, hipStreamSynchronize(c->stream));
-        if (b_head + (size_t)(total < kcap ? total : kcap) * 8 + 64 <= c->scratch_bytes) break;
-        if (round) return fail(c, PD_EHIP, "pd_depth_levels: scratch did not grow");
-    }
-    *n_levels = total;
-    const uint32_t n_out = total < kcap ? total : kcap;
-    if (n_out) {
-        uint2 *d_out = (uint2 *)((unsigned char *)c->scratch + b_head);
-        {
-            ProfScope ps(c, "depth_levels");
-            pdk::launch_levels(c->stream, src, a0, lo, hi, d_edge, n_edges, d_cnt, d_off, d_out, n_out, true);
-        }
-        HIPOK(c, hipGetLastError());
-        HIPOK(c, hipMemcpyAsync(out, d_out, (size_t)n_out * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(c, hipStreamSynchronize(c->stream));
-    }
-    if ((size_t)total > cap) return fail(c, PD_ERANGE, "pd_depth_levels: more runs than the output holds");
-    return PD_OK;
-}
-
-} // extern "C"
-
-// ---- depth quantiles ----
-// Rows go to the device in batches whose scratch does not grow with the row count: at most 2^20 rows (2^22 windows) and 2^21
-// segments a batch, 1024 histogram rows and 2^21 pieces a wide launch.  A row takes the narrow kernel up to "quantile_wave_max"
-// cells, the workgroup kernel up to "quantile_split_cells", and is cut into pieces over many workgroups above that.
-namespace {
-constexpr uint32_t Q_PIECE = 16384, Q_WIDE_ROWS = 1024;
-constexpr size_t Q_PIECE_CHUNK = (size_t)1 << 21, Q_SEG_BATCH = (size_t)1 << 21;
-inline size_t q_al(size_t b) { return (b + 255) / 256 * 256; }
-
-int quant_pct(pd_ctx *c, const uint32_t *pct, uint32_t n_pct, const char *fn, pdk::QPct *P)
-{
-    if (!pct || n_pct < 1 || n_pct > 16) return fail(c, PD_EINVAL, std::string(fn) + ": 1 to 16 percentages");
-    P->n = n_pct;
-    for (uint32_t j = 0; j < 16; ++j) P->p[j] = 0;
-    for (uint32_t j = 0; j < n_pct; ++j) {
-        if (pct[j] > 100 || (j && pct[j] <= pct[j - 1])) return fail(c, PD_EINVAL, std::string(fn) + ": percentages must be 0..100, strictly ascending");
-        P->p[j] = pct[j];
-    }
-    return PD_OK;
-}
-
-// the pieces collected so far into the histograms (Piece.region = the row's number in the wide launch)
-int quant_flush_pieces(pd_ctx *c, std::vector<Piece> &pieces, Piece *d_pieces, unsigned long long *d_hist)
-{
-    if (pieces.empty()) return PD_OK;
-    HIPOK(c, hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(Piece), hipMemcpyHostToDevice, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));          // pieces is refilled by the caller
-    {
-        ProfScope ps(c, "quantile_pieces");
-        if (launch_hist_pieces(c->stream, c->buf, d_pieces, (uint32_t)pieces.size(), 4096, d_hist, (unsigned)c->n_cu * 8, c->hist_variant))
-            return fail(c, PD_EHIP, "quantile histograms: cannot reserve LDS");
-    }
-    HIPOK(c, hipGetLastError());
-    pieces.clear();
-    return PD_OK;
-}
-inline int quant_add_pieces(pd_ctx *c, std::vector<Piece> &pieces, uint64_t start, uint64_t count, uint32_t slot, Piece *d_pieces, unsigned long long *d_hist)
-{
-    for (uint64_t p = 0; p < count; p += Q_PIECE) {
-        Piece pc; pc.start = start + p; pc.count = (uint32_t)std::min<uint64_t>(Q_PIECE, count - p); pc.region = slot;
-        pieces.push_back(pc);
-        if (pieces.size() == Q_PIECE_CHUNK) if (int rc = quant_flush_pieces(c, pieces, d_pieces, d_hist)) return rc;
-    }
-    return PD_OK;
-}
-
-// What pd_depth_quantiles and pd_depth_thresholds share: the checks of a row list, the clipping of a segment to its contig, and
-// the batches in which the rows go up (at most 2^20 rows and 2^21 segments; a row alone always fits).
-constexpr size_t ROW_BATCH = (size_t)1 << 20;
-
-int rows_check(pd_ctx *c, const char *fn, const pd_region *segs, size_t n_segs, const uint64_t *row_off, size_t n_rows)
-{
-    const std::string f(fn);
-    if (row_off[0] != 0 || row_off[n_rows] != n_segs) return fail(c, PD_EINVAL, f + ": row_off must run from 0 to n_segs");
-    for (size_t i = 0; i < n_rows; ++i) {
-        if (row_off[i + 1] < row_off[i] || row_off[i + 1] > n_segs) return fail(c, PD_EINVAL, f + ": row_off must not decrease");
-        if (row_off[i + 1] - row_off[i] > Q_SEG_BATCH) return fail(c, PD_EINVAL, f + ": at most 2^21 segments per row");
-    }
-    for (size_t i = 0; i < n_segs; ++i)
-        if (segs[i].tid < 0 || segs[i].tid >= c->n_contigs) return fail(c, PD_EINVAL, f + ": contig id out of range");
-    return PD_OK;
-}
-
-inline void seg_clip(const pd_ctx *c, const pd_region &r, uint64_t *start, uint64_t *count)
-{
-    int64_t b = (int64_t)r.first - 1, e = r.second;
-    if (b < 0) b = 0;
-    if (e > (int64_t)c->len[(size_t)r.tid]) e = (int64_t)c->len[(size_t)r.tid];
-    *start = c->off[(size_t)r.tid] + (uint64_t)b; *count = e > b ? (uint64_t)(e - b) : 0;
-}
-
-// the batch at hand, on the host (rows [r0, r1): their clipped segments, the segment offsets, the rows of every launch shape by
-// their number in the batch, the largest row of shape 0) and its copies in the scratch
-struct RowBatches {
-    Piece *d_seg; uint64_t *d_off; uint32_t *d_list[3];
-    std::vector<Piece> hseg; std::vector<uint64_t> hoff; std::vector<uint32_t> list[3];
-    size_t r0 = 0, r1 = 0; uint32_t cap = 0;
-    static size_t b_seg(size_t n_segs) { return q_al(std::min<size_t>(Q_SEG_BATCH, n_segs) * sizeof(Piece)); }
-    static size_t b_off(size_t n_rows) { return q_al((std::min(ROW_BATCH, n_rows) + 1) * 8); }
-    static size_t b_list(size_t n_rows) { return q_al(std::min(ROW_BATCH, n_rows) * 4); }
-    static size_t bytes(size_t n_rows, size_t n_segs) { return b_seg(n_segs) + b_off(n_rows) + 3 * b_list(n_rows); }
-    unsigned char *carve(unsigned char *s, size_t n_rows, size_t n_segs)
-    {
-        d_seg = (Piece *)s; s += b_seg(n_segs);
-        d_off = (uint64_t *)s; s += b_off(n_rows);
-        for (int k = 0; k < 3; ++k) { d_list[k] = (uint32_t *)s; s += b_list(n_rows); }
-        return s;
-    }
-};
-
-// regime(cells of a row) = its launch shape, 0 .. 2; serve(R) launches over the batch in B and brings its results back
-template <class Regime, class Serve>
-int rows_serve(pd_ctx *c, const pd_region *segs, const uint64_t *row_off, size_t n_rows, const uint64_t *cells, RowBatches &B, Regime regime, Serve serve)
-{
-    for (size_t r0 = 0; r0 < n_rows;) {
-        size_t r1 = r0;
-        while (r1 < n_rows && r1 - r0 < ROW_BATCH && row_off[r1 + 1] - row_off[r0] <= Q_SEG_BATCH) ++r1;     // (a row alone always fits)
-        B.r0 = r0; B.r1 = r1; B.cap = 0;
-        B.hseg.clear(); B.hoff.clear(); for (auto &l : B.list) l.clear();
-        for (size_t i = r0; i < r1; ++i) {
-            B.hoff.push_back(B.hseg.size());
-            for (uint64_t k = row_off[i]; k < row_off[i + 1]; ++k) {
-                uint64_t st, cn; seg_clip(c, segs[k], &st, &cn);
-                Piece pc; pc.start = st; pc.count = (uint32_t)cn; pc.region = 0;
-                B.hseg.push_back(pc);
-            }
-            const uint64_t C = cells[i];
-            const int rg = regime(C);
-            if (rg == 0) B.cap = std::max(B.cap, (uint32_t)C);
-            B.list[rg].push_back((uint32_t)(i - r0));
-        }
-        B.hoff.push_back(B.hseg.size());
-        if (!B.hseg.empty()) HIPOK(c, hipMemcpyAsync(B.d_seg, B.hseg.data(), B.hseg.size() * sizeof(Piece), hipMemcpyHostToDevice, c->stream));
-        HIPOK(c, hipMemcpyAsync(B.d_off, B.hoff.data(), B.hoff.size() * 8, hipMemcpyHostToDevice, c->stream));
-        for (int k = 0; k < 3; ++k)
-            if (!B.list[k].empty()) HIPOK(c, hipMemcpyAsync(B.d_list[k], B.list[k].data(), B.list[k].size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(c, hipStreamSynchronize(c->stream));          // the host arrays are refilled by the next batch
-        const pdk::QRows R{B.d_seg, B.d_off, nullptr, c->d_off, c->d_len, 0, 0, c->n_contigs};
-        if (int rc = serve(R)) return rc;
-        r0 = r1;
-    }
-    return PD_OK;
-}
-} // namespace
-
-extern "C" {
-
-int pd_window_quantiles(pd_ctx *c, uint32_t w, const uint32_t *pct, uint32_t n_pct, uint32_t *q)
-{
-    if (!c || !q || w == 0) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 1, "pd_window_quantiles")) return rs;
-    pdk::QPct P;
-    if (int rc = quant_pct(c, pct, n_pct, "pd_window_quantiles", &P)) return rc;
-    std::vector<uint64_t> wo;
-    const uint64_t nw = win_table(c, w, &wo).nw;
-    if (nw == 0) return PD_OK;
-    HIPOK(c, hipSetDevice(c->device));
-    uint32_t maxlen = 0;
-    for (uint32_t l : c->len) maxlen = std::max(maxlen, l);
-    const uint32_t weff = std::min(w, maxlen);
-    const int regime = weff <= c->q_wave_max ? 0 : weff <= c->q_split ? 1 : 2;
-    const uint64_t BR = regime == 2 ? Q_WIDE_ROWS : std::min<uint64_t>((uint64_t)1 << 22, ((uint64_t)1 << 24) / n_pct);
-    const uint64_t nbmax = std::min(BR, nw);
-    const size_t b_wo = q_al(wo.size() * 8), b_q = q_al((size_t)nbmax * n_pct * 4);
-    const size_t b_hist = regime == 2 ? q_al((size_t)nbmax * 4096 * 8) : 0, b_pc = regime == 2 ? Q_PIECE_CHUNK * sizeof(Piece) : 0;
-    if (int rc = ensure_scratch(c, b_wo + b_q + b_hist + b_pc + 256)) return rc;
-    unsigned char *s = (unsigned char *)c->scratch;
-    uint64_t *d_wo = (uint64_t *)s; uint32_t *d_q = (uint32_t *)(s + b_wo);
-    unsigned long long *d_hist = (unsigned long long *)(s + b_wo + b_q); Piece *d_pc = (Piece *)(s + b_wo + b_q + b_hist);
-    HIPOK(c, hipMemcpyAsync(d_wo, wo.data(), wo.size() * 8, hipMemcpyHostToDevice, c->stream));
-    std::vector<Piece> pieces;
-    int32_t t = 0;
-    for (uint64_t row0 = 0; row0 < nw; row0 += BR) {
-        const uint32_t nb = (uint32_t)std::min<uint64_t>(BR, nw - row0);
-        pdk::QRows R{nullptr, nullptr, d_wo, c->d_off, c->d_len, row0, w, c->n_contigs};
-        if (regime == 0) {
-            uint32_t gshift = 3; while (gshift < 6 && (1u << gshift) < weff) ++gshift;
-            ProfScope ps(c, "quantile_narrow");
-            if (pdk::launch_quant_narrow(c->stream, c->buf, R, nullptr, nb, weff, gshift, P, d_q)) return fail(c, PD_EHIP, "quantile kernel: cannot reserve LDS");
-        } else if (regime == 1) {
-            ProfScope ps(c, "quantile_block");
-            pdk::launch_quant_block(c->stream, c->buf, R, nullptr, nb, P, d_q, nullptr);
-        } else {
-            HIPOK(c, hipMemsetAsync(d_hist, 0, (size_t)nb * 4096 * 8, c->stream));
-            for (uint64_t g = row0; g < row0 + nb; ++g) {
-                while (wo[(size_t)t + 1] <= g) ++t;
-                const uint64_t b = (g - wo[(size_t)t]) * w, e = std::min<uint64_t>(b + w, c->len[(size_t)t]);
-                if (int rc = quant_add_pieces(c, pieces, c->off[(size_t)t] + b, e - b, (uint32_t)(g - row0), d_pc, d_hist)) return rc;
-            }
-            if (int rc = quant_flush_pieces(c, pieces, d_pc, d_hist)) return rc;
-            ProfScope ps(c, "quantile_pick");
-            pdk::launch_quant_block(c->stream, c->buf, R, nullptr, nb, P, d_q, d_hist);
-        }
-        HIPOK(c, hipGetLastError());
-        HIPOK(c, hipMemcpyAsync(q + row0 * n_pct, d_q, (size_t)nb * n_pct * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(c, hipStreamSynchronize(c->stream));
-    }
-    return PD_OK;
-}
-
-int pd_depth_quantiles(pd_ctx *c, const pd_region *segs, size_t n_segs, const uint64_t *row_off, size_t n_rows,
-                       const uint32_t *pct, uint32_t n_pct, uint64_t *cells, uint32_t *q)
-{
-    if (!c || (n_segs && !segs) || !row_off || (n_rows && !q)) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 1, "pd_depth_quantiles")) return rs;
-    pdk::QPct P;
-    if (int rc = quant_pct(c, pct, n_pct, "pd_depth_quantiles", &P)) return rc;
-    if (int rc = rows_check(c, "pd_depth_quantiles", segs, n_segs, row_off, n_rows)) return rc;
-    if (n_rows == 0) return PD_OK;
-    HIPOK(c, hipSetDevice(c->device));
-    std::vector<uint64_t> own_cells;
-    if (!cells) { own_cells.resize(n_rows); cells = own_cells.data(); }
-    size_t n_wide = 0; uint64_t wide_pieces = 0;
-    for (size_t i = 0; i < n_rows; ++i) {
-        uint64_t C = 0, np = 0;
-        for (uint64_t k = row_off[i]; k < row_off[i + 1]; ++k) { uint64_t st, cn; seg_clip(c, segs[k], &st, &cn); C += cn; np += (cn + Q_PIECE - 1) / Q_PIECE; }
-        cells[i] = C;
-        if (C > c->q_wave_max && C > c->q_split) { ++n_wide; wide_pieces += np; }
-    }
-    RowBatches B;
-    const size_t nbmax = std::min(ROW_BATCH, n_rows), nwmax = std::min<size_t>(Q_WIDE_ROWS, n_wide);
-    const size_t b_rows = RowBatches::bytes(n_rows, n_segs), b_q = q_al(nbmax * n_pct * 4);
-    const size_t b_hist = q_al(nwmax * 4096 * 8), b_pc = q_al((size_t)std::min<uint64_t>(Q_PIECE_CHUNK, wide_pieces) * sizeof(Piece));
-    if (int rc = ensure_scratch(c, b_rows + b_q + b_hist + b_pc + 256)) return rc;
-    unsigned char *s = B.carve((unsigned char *)c->scratch, n_rows, n_segs);
-    uint32_t *d_q = (uint32_t *)s; s += b_q;
-    unsigned long long *d_hist = (unsigned long long *)s; s += b_hist;
-    Piece *d_pc = (Piece *)s;
-    std::vector<Piece> pieces;
-    return rows_serve(c, segs, row_off, n_rows, cells, B,
-        [&](uint64_t C) { return C <= c->q_wave_max ? 0 : C <= c->q_split ? 1 : 2; },
-        [&](const pdk::QRows &R) -> int {
-            const std::vector<uint32_t> *list = B.list;
-            if (!list[0].empty()) {
-                ProfScope ps(c, "quantile_narrow");
-                if (pdk::launch_quant_narrow(c->stream, c->buf, R, B.d_list[0], (uint32_t)list[0].size(), B.cap, 6, P, d_q)) return fail(c, PD_EHIP, "quantile kernel: cannot reserve LDS");
-            }
-            if (!list[1].empty()) {
-                ProfScope ps(c, "quantile_block");
-                pdk::launch_quant_block(c->stream, c->buf, R, B.d_list[1], (uint32_t)list[1].size(), P, d_q, nullptr);
-            }
-            for (size_t w0 = 0; w0 < list[2].size(); w0 += Q_WIDE_ROWS) {
-                const uint32_t nwr = (uint32_t)std::min<size_t>(Q_WIDE_ROWS, list[2].size() - w0);
-                HIPOK(c, hipMemsetAsync(d_hist, 0, (size_t)nwr * 4096 * 8, c->stream));
-                for (uint32_t k = 0; k < nwr; ++k) {
-                    const uint32_t lr = list[2][w0 + k];
-                    for (uint64_t j = B.hoff[lr]; j < B.hoff[lr + 1]; ++j)
-                        if (int rc = quant_add_pieces(c, pieces, B.hseg[j].start, B.hseg[j].count, k, d_pc, d_hist)) return rc;
-                }
-                if (int rc = quant_flush_pieces(c, pieces, d_pc, d_hist)) return rc;
-                ProfScope ps(c, "quantile_pick");
-                pdk::launch_quant_block(c->stream, c->buf, R, B.d_list[2] + w0, nwr, P, d_q, d_hist);
-            }
-            HIPOK(c, hipGetLastError());
-            HIPOK(c, hipMemcpyAsync(q + B.r0 * n_pct, d_q, (size_t)(B.r1 - B.r0) * n_pct * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPOK(c, hipStreamSynchronize(c->stream));
-            return PD_OK;
-        });
-}
-
-} // extern "C"
-
-// ---- depth thresholds ----
-// The quantiles' rows and batches with two launch shapes: a row of up to "threshold_wave_max" cells is counted by a group of
-// lanes, a longer one is cut into pieces that add into the batch's zeroed result rows.
-namespace {
-int thr_set(pd_ctx *c, const uint32_t *thr, uint32_t n_thr, const char *fn, pdk::ThrSet *T)
-{
-    if (!thr || n_thr < 1 || n_thr > 16) return fail(c, PD_EINVAL, std::string(fn) + ": 1 to 16 thresholds");
-    T->n = n_thr;
-    for (uint32_t j = 0; j < 16; ++j) T->t[j] = 0xFFFFFFFFu;
-    for (uint32_t j = 0; j < n_thr; ++j) {
-        if (j && thr[j] <= thr[j - 1]) return fail(c, PD_EINVAL, std::string(fn) + ": thresholds must be strictly ascending");
-        T->t[j] = thr[j];
-    }
-    return PD_OK;
-}
-
-// the pieces collected so far, added into `out` (Piece.region = the row's slot in it)
-template <typename OutT>
-int thr_flush_pieces(pd_ctx *c, std::vector<Piece> &pieces, Piece *d_pieces, const pdk::ThrSet &T, OutT *out)
-{
-    if (pieces.empty()) return PD_OK;
-    HIPOK(c, hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(Piece), hipMemcpyHostToDevice, c->stream));
-    HIPOK(c, hipStreamSynchronize(c->stream));          // pieces is refilled by the caller
-    {
-        ProfScope ps(c, "threshold_pieces");
-        pdk::launch_thr_pieces(c->stream, c->buf, d_pieces, (uint32_t)pieces.size(), T, out, (unsigned)c->n_cu * 8);
-    }
-    HIPOK(c, hipGetLastError());
-    pieces.clear();
-    return PD_OK;
-}
-template <typename OutT>
-int thr_add_pieces(pd_ctx *c, std::vector<Piece> &pieces, uint64_t start, uint64_t count, uint32_t slot, Piece *d_pieces, const pdk::ThrSet &T, OutT *out)
-{
-    for (uint64_t p = 0; p < count; p += Q_PIECE) {
-        Piece pc; pc.start = start + p; pc.count = (uint32_t)std::min<uint64_t>(Q_PIECE, count - p); pc.region = slot;
-        pieces.push_back(pc);
-        if (pieces.size() == Q_PIECE_CHUNK) if (int rc = thr_flush_pieces(c, pieces, d_pieces, T, out)) return rc;
-    }
-    return PD_OK;
-}
-} // namespace
-
-extern "C" {
-
-int pd_window_thresholds(pd_ctx *c, uint32_t w, const uint32_t *thr, uint32_t n_thr, uint32_t *counts)
-{
-    if (!c || !counts || w == 0) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 1, "pd_window_thresholds")) return rs;
-    pdk::ThrSet T;
-    if (int rc = thr_set(c, thr, n_thr, "pd_window_thresholds", &T)) return rc;
-    std::vector<uint64_t> wo;
-    const uint64_t nw = win_table(c, w, &wo).nw;
-    if (nw == 0) return PD_OK;
-    HIPOK(c, hipSetDevice(c->device));
-    uint32_t maxlen = 0;
-    for (uint32_t l : c->len) maxlen = std::max(maxlen, l);
-    const uint32_t weff = std::min(w, maxlen);
-    const bool wide = weff > c->t_wave_max;
-    const uint64_t BR = std::min<uint64_t>((uint64_t)1 << 22, ((uint64_t)1 << 24) / n_thr), nbmax = std::min(BR, nw);
-    const size_t b_wo = q_al(wo.size() * 8), b_cnt = q_al((size_t)nbmax * n_thr * 4), b_pc = wide ? Q_PIECE_CHUNK * sizeof(Piece) : 0;
-    if (int rc = ensure_scratch(c, b_wo + b_cnt + b_pc + 256)) return rc;
-    unsigned char *s = (unsigned char *)c->scratch;
-    uint64_t *d_wo = (uint64_t *)s; uint32_t *d_cnt = (uint32_t *)(s + b_wo); Piece *d_pc = (Piece *)(s + b_wo + b_cnt);
-    HIPOK(c, hipMemcpyAsync(d_wo, wo.data(), wo.size() * 8, hipMemcpyHostToDevice, c->stream));
-    std::vector<Piece> pieces;
-    int32_t t = 0;
-    for (uint64_t row0 = 0; row0 < nw; row0 += BR) {
-        const uint32_t nb = (uint32_t)std::min<uint64_t>(BR, nw - row0);
-        if (!wide) {
-            const pdk::QRows R{nullptr, nullptr, d_wo, c->d_off, c->d_len, row0, w, c->n_contigs};
-            uint32_t gshift = 3; while (gshift < 6 && (8u << gshift) < weff) ++gshift;      // a lane takes 8 cells before the group grows
-            const uint32_t rpg = std::min(16u, std::max(1u, 8192u / weff));                  // rows a group takes one after the other
-            ProfScope ps(c, "threshold_narrow");
-            pdk::launch_thr_narrow(c->stream, c->buf, R, nullptr, nb, gshift, rpg, T, d_cnt);
-        } else {
-            HIPOK(c, hipMemsetAsync(d_cnt, 0, (size_t)nb * n_thr * 4, c->stream));
-            for (uint64_t g = row0; g < row0 + nb; ++g) {
-                while (wo[(size_t)t + 1] <= g) ++t;
-                const uint64_t b = (g - wo[(size_t)t]) * w, e = std::min<uint64_t>(b + w, c->len[(size_t)t]);
-                if (int rc = thr_add_pieces(c, pieces, c->off[(size_t)t] + b, e - b, (uint32_t)(g - row0), d_pc, T, d_cnt)) return rc;
-            }
-            if (int rc = thr_flush_pieces(c, pieces, d_pc, T, d_cnt)) return rc;
-        }
-        HIPOK(c, hipGetLastError());
-        HIPOK(c, hipMemcpyAsync(counts + row0 * n_thr, d_cnt, (size_t)nb * n_thr * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPOK(c, hipStreamSynchronize(c->stream));
-    }
-    return PD_OK;
-}
-
-int pd_depth_thresholds(pd_ctx *c, const pd_region *segs, size_t n_segs, const uint64_t *row_off, size_t n_rows,
-                        const uint32_t *thr, uint32_t n_thr, uint64_t *cells, uint64_t *counts)
-{
-    if (!c || (n_segs && !segs) || !row_off || (n_rows && !counts)) return PD_EINVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (int rs = need_state(c, 1, "pd_depth_thresholds")) return rs;
-    pdk::ThrSet T;
-    if (int rc = thr_set(c, thr, n_thr, "pd_depth_thresholds", &T)) return rc;
-    if (int rc = rows_check(c, "pd_depth_thresholds", segs, n_segs, row_off, n_rows)) return rc;
-    if (n_rows == 0) return PD_OK;
-    HIPOK(c, hipSetDevice(c->device));
-    std::vector<uint64_t> own_cells;
-    if (!cells) { own_cells.resize(n_rows); cells = own_cells.data(); }
-    uint64_t wide_pieces = 0;
-    for (size_t i = 0; i < n_rows; ++i) {
-        uint64_t C = 0, np = 0;
-        for (uint64_t k = row_off[i]; k < row_off[i + 1]; ++k) { uint64_t st, cn; seg_clip(c, segs[k], &st, &cn); C += cn; np += (cn + Q_PIECE - 1) / Q_PIECE; }
-        cells[i] = C;
-        if (C > c->t_wave_max) wide_pieces += np;
-    }
-    RowBatches B;
-    const size_t b_rows = RowBatches::bytes(n_rows, n_segs), b_cnt = q_al(std::min(ROW_BATCH, n_rows) * n_thr * 8);
-    const size_t b_pc = q_al((size_t)std::min<uint64_t>(Q_PIECE_CHUNK, wide_pieces) * sizeof(Piece));
-    if (int rc = ensure_scratch(c, b_rows + b_cnt + b_pc + 256)) return rc;
-    unsigned char *s = B.carve((unsigned char *)c->scratch, n_rows, n_segs);
-    unsigned long long *d_cnt = (unsigned long long *)s; s += b_cnt;
-    Piece *d_pc = (Piece *)s;
-    std::vector<Piece> pieces;
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counts are copied as they are");
-    return rows_serve(c, segs, row_off, n_rows, cells, B,
-        [&](uint64_t C) { return C <= c->t_wave_max ? 0 : 1; },
-        [&](const pdk::QRows &R) -> int {
-            const size_t nb = B.r1 - B.r0;
-            if (!B.list[1].empty()) HIPOK(c, hipMemsetAsync(d_cnt, 0, nb * n_thr * 8, c->stream));       // (the narrow rows are written, not added to)
-            if (!B.list[0].empty()) {
-                uint32_t gshift = 3; while (gshift < 6 && (8u << gshift) < B.cap) ++gshift;
-                ProfScope ps(c, "threshold_narrow");
-                pdk::launch_thr_narrow(c->stream, c->buf, R, B.d_list[0], (uint32_t)B.list[0].size(), gshift, 1, T, d_cnt);
-            }
-            for (uint32_t lr : B.list[1])
-                for (uint64_t j = B.hoff[lr]; j < B.hoff[lr + 1]; ++j)
-                    if (int rc = thr_add_pieces(c, pieces, B.hseg[j].start, B.hseg[j].count, lr, d_pc, T, d_cnt)) return rc;
-            if (int rc = thr_flush_pieces(c, pieces, d_pc, T, d_cnt)) return rc;
-            HIPOK(c, hipGetLastError());
-            HIPOK(c, hipMemcpyAsync(counts + B.r0 * n_thr, d_cnt, nb * n_thr * 8, hipMemcpyDeviceToHost, c->stream));
-            HIPOK(c, hipStreamSynchronize(c->stream));
-            return PD_OK;
-        });
-}
-
-} // extern "C"
-
-extern "C" {
 
 int pd_device_buffer(pd_ctx *c, void **dev_ptr, uint64_t *n_words, uint64_t *contig_off)
 {

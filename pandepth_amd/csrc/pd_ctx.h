@@ -1,4 +1,4 @@
-// pd_ctx.h — what the library's own translation units (pd_capi.hip, pd_decode.hip, pd_windows.hip) share: the guarded device allocator, the context
+// pd_ctx.h — what the library's own translation units (pd_capi.hip, pd_decode.hip, pd_windows.hip, pd_rows.hip, pd_gcbias.hip) share: the guarded device allocator, the context
 // (struct pd_ctx, struct pd_runs, the window result buffer's owner WinKeep) and the few helpers that cross the file boundary (namespace pdi).  Not
 // installed; include/*.h is the interface.
 #pragma once

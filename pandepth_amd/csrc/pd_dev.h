@@ -1,4 +1,4 @@
-// pd_dev.h — what the kernels of pd_kernels.hip and pd_direct.hip both use: device-only, included by those two files alone.
+// pd_dev.h — what the kernels of pd_kernels.hip, pd_direct.hip and pd_rows.hip share: device code and its launch helpers, included by those three files alone.
 #ifndef PD_DEV_H_
 #define PD_DEV_H_
 #include <hip/hip_runtime.h>
@@ -63,6 +63,42 @@ __device__ __forceinline__ int wave_incl_scan_max(int x)
     x = mx(x, __builtin_amdgcn_update_dpp(ID, x, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2,3
     return x;
 }
+typedef int v4i_nt __attribute__((ext_vector_type(4)));
+
+// the first n (0..4) of a lane's four consecutive cells, as bins, into LDS counters h (wave-uniform call)
+template <bool FOLD>
+__device__ __forceinline__ void hist_lane4(uint32_t *h, const uint32_t (&b)[4], uint32_t n, int lane)
+{
+    const uint32_t b0 = __builtin_amdgcn_readfirstlane(b[0]);
+    const bool uni = n == 4 && b[0] == b0 && b[1] == b0 && b[2] == b0 && b[3] == b0;
+    if (__all(uni)) { if (lane == 0) atomicAdd(&h[b0], 256u); return; }
+    if (!FOLD) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) if ((uint32_t)q < n) atomicAdd(&h[b[q]], 1u);
+        return;
+    }
+    if (!n) return;
+    uint32_t cur = b[0], c = 1;
+#pragma unroll
+    for (int q = 1; q < 4; ++q) {
+        if ((uint32_t)q >= n) break;
+        if (b[q] == cur) ++c; else { atomicAdd(&h[cur], c); cur = b[q]; c = 1; }
+    }
+    atomicAdd(&h[cur], c);
+}
+
+// Before the barrier that hands the LDS counters to hist_flush: every ds_add this wave issued has completed (s_waitcnt
+// lgkmcnt(0); vmcnt / expcnt left alone).  The compiler put no such wait in front of the barrier on the contig-change path, and
+// the workgroup-wide copy lost adds of other waves there (tools/dist_bench.py on the 3 Gb sample: profiles/r07_dist_bench_before_lds_wait.json).
+__device__ __forceinline__ void lds_drain() { __builtin_amdgcn_s_waitcnt(0xC07F); }
+
+template <typename K>
+static int hist_lds_reserve(K kern, size_t lds)
+{
+    if (lds <= 48 * 1024) return 0;
+    return (int)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 // lane i takes lane i - 1's value, lane 0 takes `first` (wave_shr:1)
 __device__ __forceinline__ int wave_shift_up(int x, int first) { return __builtin_amdgcn_update_dpp(first, x, 0x138, 0xf, 0xf, false); }
 // wave totals through the DPP scan (no LDS crossbar): the last lane holds the sum

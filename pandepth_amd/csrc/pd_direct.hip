@@ -1717,7 +1717,7 @@ __global__ void k_finish_direct(const PendSet ps, const uint32_t *n_long, uint32
 }
 
 // ------------------------------------------------------------------------------------------
-// launch wrappers (called from pd_windows.hip and pd_capi.hip)
+// launch wrappers (called from pd_windows.hip and pd_capi.hip; the row statistics of pd_rows.hip launch nothing of this file)
 // ------------------------------------------------------------------------------------------
 void launch_direct_tiles(hipStream_t st, const PendSet &ps, ContigTab tab, const uint32_t *tile_contig, uint32_t n_tiles,
                          uint32_t wrap_mask, uint32_t w, uint32_t min_dep, TilePart *part, const uint64_t *win_off,

@@ -1,4 +1,4 @@
-// pd_kernels.h — structs and launch wrappers: launch_direct_* are defined in pd_direct.hip (the direct depth pass), the other launch_* of the first namespace block in pd_kernels.hip; callers are pd_capi.hip and pd_windows.hip.
+// pd_kernels.h — structs and launch wrappers: launch_direct_* are defined in pd_direct.hip (the direct depth pass), the other launch_* of the first namespace block in pd_kernels.hip; callers are pd_capi.hip, pd_windows.hip and pd_rows.hip (the row statistics, which keeps its own kernels' launchers to itself).
 #ifndef PD_KERNELS_H_
 #define PD_KERNELS_H_
 #include <hip/hip_runtime.h>
@@ -196,43 +196,6 @@ int launch_sweep_hist(hipStream_t st, const int *buf, const int *carry, uint32_t
                       const uint8_t *hstate, bool from_depth, uint32_t n_bins, unsigned long long *hist, unsigned grid, int variant);
 int launch_hist_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, uint32_t n_bins,
                        unsigned long long *hist, unsigned grid, int variant);
-
-// depth levels (pd_depth_levels): runs of equal depth (n_edges == 0) or equal depth class over cells [lo, hi) behind `src`, an
-// int4-aligned cell pointer with lo < 4; first_cell = the contig-local index of src[0].  write = false: the waves' run counts and
-// their exclusive scan (wave_off[levels_waves(hi)] = the total); write = true: out[j] = (start, class) for j < cap.
-// wave_cnt: levels_waves(hi) words, wave_off: one more; edges: n_edges ascending device words.
-uint32_t levels_waves(uint64_t span);
-void launch_levels(hipStream_t st, const uint32_t *src, uint32_t first_cell, uint32_t lo, uint32_t hi, const uint32_t *edges, uint32_t n_edges,
-                   uint32_t *wave_cnt, uint32_t *wave_off, uint2 *out, uint32_t cap, bool write);
-
-// depth quantiles (pd_depth_quantiles / pd_window_quantiles) over the depth left by pd_scan.  Row r of a batch is the segments
-// segs[seg_off[r] .. seg_off[r + 1]) (Piece.start = flat cell, Piece.count; region unused) or, with segs == nullptr, window
-// row0 + r of pd_window_layout(w), found on the device.  `list` (may be null: rows 0 .. n - 1) names the rows a launch takes;
-// q[r * P.n + j] = the nearest-rank P.p[j] quantile, 0xFFFFFFFF for a row without cells.
-//   launch_quant_narrow : rows of at most `cap` cells, a group of 1 << gshift lanes (3 .. 6) per row; returns a hipError_t (LDS)
-//   launch_quant_block  : a workgroup per row; ghist != nullptr: the row's 4096 bins (last: >= 4095) were counted by
-//                         launch_hist_pieces into ghist[slot * 4096 ..) with Piece.region = slot, the launch's row number
-struct QRows {
-    const Piece *segs; const uint64_t *seg_off;
-    const uint64_t *win_off, *contig_off; const uint32_t *contig_len;
-    uint64_t row0; uint32_t w; int32_t n_contigs;
-};
-struct QPct { uint32_t n; uint32_t p[16]; };
-int launch_quant_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t cap, uint32_t gshift,
-                        const QPct &P, uint32_t *q);
-void launch_quant_block(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, const QPct &P, uint32_t *q,
-                        const unsigned long long *ghist);
-
-// depth thresholds (pd_depth_thresholds / pd_window_thresholds): out[r * T.n + j] = the cells of row r that are >= T.t[j]; rows as
-// above.  T.t[T.n ..) is 2^32-1.  out is uint64 for segment rows, uint32 for windows.
-//   launch_thr_narrow : a group of 1 << gshift lanes (3 .. 6) takes `rpg` consecutive rows of the launch, one writer per row (rows of
-//                       less than 2^32 cells)
-//   launch_thr_pieces : Piece.region = the row's slot in `out`, which the caller has zeroed; a wave per piece, T.n atomics per piece
-struct ThrSet { uint32_t n; uint32_t t[16]; };
-void launch_thr_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t gshift, uint32_t rpg, const ThrSet &T, uint32_t *out);
-void launch_thr_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t gshift, uint32_t rpg, const ThrSet &T, unsigned long long *out);
-void launch_thr_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, const ThrSet &T, uint32_t *out, unsigned grid);
-void launch_thr_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, const ThrSet &T, unsigned long long *out, unsigned grid);
 
 // GPU-side BAM decode (pd_bgzf.hip)
 void launch_bgzf_inflate(hipStream_t st, const uint8_t *comp, const pd_bgzf_block *blk, uint32_t n_blk, uint8_t *out,

@@ -1,5 +1,5 @@
-// pd_kernels.hip — hand-written gfx950 kernels of the per-base depth engine, all but the direct depth pass (pd_direct.hip;
-// what the two files' kernels share is pd_dev.h).
+// pd_kernels.hip — hand-written gfx950 kernels of the per-base depth engine, all but the direct depth pass (pd_direct.hip) and the levels, quantile and threshold kernels of the row statistics (pd_rows.hip;
+// what the three files' kernels share is pd_dev.h).
 //
 // Everything here is HBM-bound integer work (no MFMA): a zero fill, the +1/-1 difference-array
 // scatter (owner-tile LDS accumulation with plain int4 read-modify-write flush for sorted
@@ -739,8 +739,6 @@ __global__ __launch_bounds__(1024) void k_tile_carry(const int *sums, const int 
 //   FROM_DEPTH : input already holds depth (reduction only)
 // ------------------------------------------------------------------------------------------
 
-typedef int v4i_nt __attribute__((ext_vector_type(4)));
-
 // Load one tile (8 rows of int4 per wave) and, unless FROM_DEPTH, turn its difference array into wrapped depth in registers:
 // the scan shared by k_sweep and k_sweep_hist.  `p4` points at this lane's first int4 of the tile, `t` is the tile's global
 // index (hstate / carry), `wtot` four ints of LDS.  Contains one __syncthreads (not FROM_DEPTH): every thread must call it.
@@ -1019,34 +1017,7 @@ __global__ __launch_bounds__(WG) void k_reduce_pieces(const int *depth, const Pi
 // a lane folds equal neighbours of its four cells into one add (FOLD), and a row whose 256 cells
 // share one bin (empty stretches, piles above the last bin) is one add by lane 0.
 // ------------------------------------------------------------------------------------------
-struct HistArgs { uint32_t n_bins, nbp; unsigned long long *hist; };   // nbp: counters per LDS copy
-
-// the first n (0..4) of a lane's four consecutive cells, as bins, into LDS counters h (wave-uniform call)
-template <bool FOLD>
-__device__ __forceinline__ void hist_lane4(uint32_t *h, const uint32_t (&b)[4], uint32_t n, int lane)
-{
-    const uint32_t b0 = __builtin_amdgcn_readfirstlane(b[0]);
-    const bool uni = n == 4 && b[0] == b0 && b[1] == b0 && b[2] == b0 && b[3] == b0;
-    if (__all(uni)) { if (lane == 0) atomicAdd(&h[b0], 256u); return; }
-    if (!FOLD) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) if ((uint32_t)q < n) atomicAdd(&h[b[q]], 1u);
-        return;
-    }
-    if (!n) return;
-    uint32_t cur = b[0], c = 1;
-#pragma unroll
-    for (int q = 1; q < 4; ++q) {
-        if ((uint32_t)q >= n) break;
-        if (b[q] == cur) ++c; else { atomicAdd(&h[cur], c); cur = b[q]; c = 1; }
-    }
-    atomicAdd(&h[cur], c);
-}
-
-// Before the barrier that hands the LDS counters to hist_flush: every ds_add this wave issued has completed (s_waitcnt
-// lgkmcnt(0); vmcnt / expcnt left alone).  The compiler put no such wait in front of the barrier on the contig-change path, and
-// the workgroup-wide copy lost adds of other waves there (tools/dist_bench.py on the 3 Gb sample: profiles/r07_dist_bench_before_lds_wait.json).
-__device__ __forceinline__ void lds_drain() { __builtin_amdgcn_s_waitcnt(0xC07F); }
+struct HistArgs { uint32_t n_bins, nbp; unsigned long long *hist; };   // nbp: counters per LDS copy (hist_lane4 and lds_drain: pd_dev.h)
 
 // the workgroup's counters of one contig into its row of the histogram, zeroed behind (between two __syncthreads)
 template <int COPIES>
@@ -1765,7 +1736,7 @@ void launch_window_gather(hipStream_t st, const TilePart *part, TileMap tm, int3
 }
 
 // ------------------------------------------------------------------------------------------
-// launch wrappers (called from pd_capi.hip)
+// launch wrappers (called from pd_capi.hip, pd_windows.hip and pd_rows.hip)
 // ------------------------------------------------------------------------------------------
 void launch_fill(hipStream_t st, void *p, size_t bytes)
 {
@@ -1997,13 +1968,6 @@ static size_t hist_lds_bytes(uint32_t n_bins, int copies, uint32_t *nbp)
     return (size_t)copies * *nbp * 4;
 }
 
-template <typename K>
-static int hist_lds_reserve(K kern, size_t lds)
-{
-    if (lds <= 48 * 1024) return 0;
-    return (int)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
 // variant: bit 0 = one LDS copy for the workgroup (else one per wave), bit 1 = no folding of equal neighbours
 int launch_sweep_hist(hipStream_t st, const int *buf, const int *carry, uint32_t n_tiles, uint32_t wrap_mask, TileMap tm,
                       const uint8_t *hstate, bool from_depth, uint32_t n_bins, unsigned long long *hist, unsigned grid, int variant)
@@ -2060,532 +2024,5 @@ int launch_hist_pieces(hipStream_t st, const int *depth, const Piece *pieces, ui
 #undef PD_HIST_GO
     return 0;
 }
-
-// ------------------------------------------------------------------------------------------
-// depth levels (pd_depth_levels): the materialised depth of one contig range as runs of equal depth, or of equal depth class —
-// an ORDERED stream compaction.  Cell i opens a run when it is the range's first or class(d[i]) != class(d[i-1]).
-//   k_levels<EDGES, false> : every wave counts the runs that open in its 2048 cells
-//   k_levels_scan          : exclusive scan of the waves' counts (one workgroup), total behind the last
-//   k_levels<EDGES, true>  : every wave with runs writes its (start, class) pairs at its offset, in cell order
-// A wave owns 8 rows of 64 int4 (lane = four consecutive cells, non-temporal loads); waves are independent — the unit of the
-// count / offset arrays is the wave, so neither pass needs a workgroup-wide exchange, and the emit pass does not even load the
-// cells of a wave in which no run opens (quantised output: most of them).  The left neighbour of a lane's first cell comes from
-// the lane below (__shfl_up), of a row's first cell from the row before (readlane), of the wave's first cell from one extra
-// load.  `src` points at an int4-aligned cell at most three cells in front of the range; the range is [lo, hi) relative to it,
-// and nothing outside it is read (cell lo always opens a run, so it needs no neighbour).
-// class(): the identity (EDGES = false), else the index of the last edge <= d (0xFFFFFFFF below the first): a 256-entry LDS
-// table for low depths, and — for a row in which ANY lane holds a deeper cell, a wave-uniform choice — a branch-free six-step
-// search of the edges in LDS (edge[0] apart, edge[1 .. 63] padded with 0xFFFFFFFF).
-// ------------------------------------------------------------------------------------------
-namespace {
-constexpr int LV_ROWS = 8;
-constexpr uint32_t LV_WAVE = LV_ROWS * 256;          // cells per wave
-constexpr uint32_t LV_LUT = 256;                     // depths classified by table
-static_assert(LV_LUT == WG, "one table entry per thread");
-}
-
-__device__ __forceinline__ uint32_t level_search(uint32_t d, const uint32_t *edge, uint32_t n_edges)
-{
-    uint32_t pos = 0;                                            // edges among edge[1 .. 63] that are <= d
-#pragma unroll
-    for (uint32_t s = 32; s; s >>= 1) pos += edge[pos + s] <= d ? s : 0u;
-    pos = min(pos, n_edges - 1u);                                // (d = 0xFFFFFFFF meets the padding)
-    return d < edge[0] ? 0xFFFFFFFFu : pos;
-}
-
-template <bool EDGES, bool WRITE>
-__global__ __launch_bounds__(WG) void k_levels(const uint32_t *src, uint32_t first_cell, uint32_t lo, uint32_t hi, const uint32_t *edges,
-                                               uint32_t n_edges, uint32_t *wave_cnt, const uint32_t *wave_off, uint2 *out, uint32_t cap)
-{
-    __shared__ uint32_t s_edge[64];
-    __shared__ uint32_t s_lut[LV_LUT];
-    const int lane = threadIdx.x & 63;
-    const uint32_t g = blockIdx.x * (WG / 64) + (threadIdx.x >> 6);
-    if (EDGES) {
-        if (threadIdx.x < 64) s_edge[threadIdx.x] = threadIdx.x < n_edges ? edges[threadIdx.x] : 0xFFFFFFFFu;
-        __syncthreads();
-        s_lut[threadIdx.x] = level_search(threadIdx.x, s_edge, n_edges);
-        __syncthreads();
-    }
-    const uint32_t w0 = g * LV_WAVE;                             // (wave-uniform from here on: no barrier below)
-    uint32_t run = 0;
-    if (WRITE) {
-        run = wave_off[g];
-        if (wave_off[g + 1] == run) return;                      // no run opens here (or the wave lies behind the range)
-    } else if (w0 >= hi) {
-        if (lane == 0) wave_cnt[g] = 0;
-        return;
-    }
-    uint32_t c[LV_ROWS][4];
-#pragma unroll
-    for (int r = 0; r < LV_ROWS; ++r) {
-        const uint32_t rel = w0 + r * 256 + lane * 4;
-        if (rel >= lo && rel + 4 <= hi) {
-            const v4i_nt x = __builtin_nontemporal_load(reinterpret_cast<const v4i_nt *>(src + rel));
-            c[r][0] = (uint32_t)x.x; c[r][1] = (uint32_t)x.y; c[r][2] = (uint32_t)x.z; c[r][3] = (uint32_t)x.w;
-        } else {                                                 // the range's unaligned head and tail, and what lies outside
-#pragma unroll
-            for (int k = 0; k < 4; ++k) c[r][k] = (rel + k >= lo && rel + k < hi) ? src[rel + k] : 0u;
-        }
-    }
-    uint32_t left_row = w0 > lo ? src[w0 - 1] : 0u;              // (w0 - 1 is inside [lo, hi) then)
-    if (EDGES) left_row = level_search(left_row, s_edge, n_edges);
-    uint32_t total = 0;
-#pragma unroll
-    for (int r = 0; r < LV_ROWS; ++r) {
-        if (EDGES) {
-            const uint32_t m = max(max(c[r][0], c[r][1]), max(c[r][2], c[r][3]));
-            if (__ballot(m >= LV_LUT) == 0ull) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) c[r][k] = s_lut[c[r][k]];
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) c[r][k] = level_search(c[r][k], s_edge, n_edges);
-            }
-        }
-        const uint32_t rel = w0 + r * 256 + lane * 4;
-        uint32_t left = (uint32_t)__shfl_up((int)c[r][3], 1);
-        if (lane == 0) left = left_row;
-        left_row = (uint32_t)__builtin_amdgcn_readlane((int)c[r][3], 63);
-        bool f[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t x = rel + k;
-            f[k] = x >= lo && x < hi && (x == lo || c[r][k] != (k ? c[r][k - 1] : left));
-        }
-        if (!WRITE) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) total += (uint32_t)__popcll(__ballot(f[k]));
-        } else {
-            const uint32_t cnt = (uint32_t)f[0] + (uint32_t)f[1] + (uint32_t)f[2] + (uint32_t)f[3];
-            if (__ballot(cnt != 0u) == 0ull) continue;
-            const uint32_t incl = (uint32_t)wave_incl_scan((int)cnt);
-            uint32_t o = run + incl - cnt;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (f[k]) { if (o < cap) out[o] = make_uint2(first_cell + rel + k, c[r][k]); ++o; }
-            run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-    }
-    if (!WRITE && lane == 0) wave_cnt[g] = total;
-}
-
-// exclusive scan of the waves' run counts: one workgroup, 16 consecutive entries per thread and round; off[n] = the total
-__global__ __launch_bounds__(WG) void k_levels_scan(const uint32_t *cnt, uint32_t n, uint32_t *off)
-{
-    constexpr int PER = 16;
-    __shared__ uint32_t wsum[WG / 64];
-    __shared__ uint32_t carry;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t b0 = 0; b0 < n; b0 += WG * PER) {
-        const uint32_t i0 = b0 + threadIdx.x * PER;
-        uint32_t v[PER], mine = 0;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) { v[k] = i0 + k < n ? cnt[i0 + k] : 0u; mine += v[k]; }
-        const uint32_t incl = (uint32_t)wave_incl_scan((int)mine);
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        uint32_t base = carry + incl - mine;
-        for (int k = 0; k < wv; ++k) base += wsum[k];
-#pragma unroll
-        for (int k = 0; k < PER; ++k) { if (i0 + k < n) off[i0 + k] = base; base += v[k]; }
-        __syncthreads();
-        if (threadIdx.x == WG - 1) carry = base;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) off[n] = carry;
-}
-
-uint32_t levels_waves(uint64_t span) { return (uint32_t)((span + LV_WAVE - 1) / LV_WAVE + 3) / 4 * 4; }
-
-void launch_levels(hipStream_t st, const uint32_t *src, uint32_t first_cell, uint32_t lo, uint32_t hi, const uint32_t *edges, uint32_t n_edges,
-                   uint32_t *wave_cnt, uint32_t *wave_off, uint2 *out, uint32_t cap, bool write)
-{
-    const uint32_t nw = levels_waves(hi), nb = nw / 4;
-    if (!write) {
-        if (n_edges) hipLaunchKernelGGL((k_levels<true, false>), dim3(nb), dim3(WG), 0, st, src, first_cell, lo, hi, edges, n_edges, wave_cnt, wave_off, out, cap);
-        else hipLaunchKernelGGL((k_levels<false, false>), dim3(nb), dim3(WG), 0, st, src, first_cell, lo, hi, edges, n_edges, wave_cnt, wave_off, out, cap);
-        hipLaunchKernelGGL(k_levels_scan, dim3(1), dim3(WG), 0, st, wave_cnt, nw, wave_off);
-    } else {
-        if (n_edges) hipLaunchKernelGGL((k_levels<true, true>), dim3(nb), dim3(WG), 0, st, src, first_cell, lo, hi, edges, n_edges, wave_cnt, wave_off, out, cap);
-        else hipLaunchKernelGGL((k_levels<false, true>), dim3(nb), dim3(WG), 0, st, src, first_cell, lo, hi, edges, n_edges, wave_cnt, wave_off, out, cap);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// depth quantiles (pd_depth_quantiles / pd_window_quantiles): exact nearest-rank order statistics of the cells of many rows.
-// A row is a multiset of segments of the materialised depth (QRows: a segment list, or the windows of pd_window_layout(w) found
-// on the device).  Three launch shapes, chosen per row by its cell count on the host:
-//   k_quant_narrow        a GROUP of 8 .. 64 lanes per row: the cells go to LDS once, every rank is found by a bitwise radix
-//                         descent from the highest bit set in the row (ballot + popcount per 64 cells and bit); exact for any uint32
-//   k_quant_block<.., 0>  a workgroup per row: LDS histogram of min(v, 4095), block prefix, every rank picked from it
-//   k_hist_pieces + k_quant_block<.., 1>   rows cut into pieces over many workgroups, added into the row's uint64 histogram in
-//                         memory (the -dist kernel, one row of 4096 bins per quantile row), then a workgroup per row picks
-// A rank that falls into the last bin (v >= 4095) is refined by the workgroup that found it (q_deep): three more passes over the
-// row's cells, histograms of bits 31..20, 19..8 and 7..0 of the cells that are >= 4095 and share the bits fixed so far.
-// ------------------------------------------------------------------------------------------
-struct QSel { unsigned long long below[16], total, dbelow; uint32_t bin[16], dbin; };
-
-// window g of pd_window_layout: the last contig whose first window is <= g, and the window's cells in it
-__device__ __forceinline__ int q_win_contig(const QRows &R, uint64_t g)
-{
-    int lo = 0, hi = R.n_contigs - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (R.win_off[mid] <= g) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-__device__ __forceinline__ void q_win_cells(const QRows &R, uint64_t g, int t, uint64_t *ws, uint32_t *wc)
-{
-    const uint64_t b = (g - R.win_off[t]) * R.w, clen = R.contig_len[t];
-    *ws = R.contig_off[t] + b;
-    *wc = b >= clen ? 0u : (uint32_t)(clen - b < (uint64_t)R.w ? clen - b : (uint64_t)R.w);
-}
-
-// the cells of row r: segments [s0, s0 + ns) of R.segs, or (window mode) the one stretch (ws, wc)
-__device__ __forceinline__ void q_row_begin(const QRows &R, uint64_t r, uint64_t *s0, uint32_t *ns, uint64_t *ws, uint32_t *wc)
-{
-    if (R.segs) { *s0 = R.seg_off[r]; *ns = (uint32_t)(R.seg_off[r + 1] - *s0); *ws = 0; *wc = 0; return; }
-    const uint64_t g = R.row0 + r;
-    *s0 = 0; *ns = 1;
-    q_win_cells(R, g, q_win_contig(R, g), ws, wc);
-}
-__device__ __forceinline__ void q_seg(const QRows &R, uint64_t s0, uint32_t i, uint64_t ws, uint32_t wc, uint64_t *start, uint32_t *count)
-{
-    if (R.segs) { const Piece pc = R.segs[s0 + i]; *start = pc.start; *count = pc.count; }
-    else { *start = ws; *count = wc; }
-}
-__device__ __forceinline__ unsigned long long q_rank(uint32_t p, unsigned long long cells)
-{
-    const unsigned long long r = ((unsigned long long)p * cells + 99ull) / 100ull;
-    return r ? r : 1ull;
-}
-
-__global__ __launch_bounds__(WG) void k_quant_narrow(const uint32_t *depth, const QRows R, const uint32_t *list, uint32_t n, uint32_t cap,
-                                                     uint32_t gshift, const QPct P, uint32_t *q)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uint32_t G = 1u << gshift, gl = threadIdx.x & (G - 1), grp = threadIdx.x >> gshift;
-    const uint64_t slot = (uint64_t)blockIdx.x * (WG >> gshift) + grp;
-    if (slot >= n) return;                                       // (whole groups leave; nothing below synchronises the workgroup)
-    const uint64_t r = list ? list[slot] : slot;
-    uint32_t *v = reinterpret_cast<uint32_t *>(smem) + (size_t)grp * cap;
-    uint64_t s0, ws; uint32_t ns, wc;
-    q_row_begin(R, r, &s0, &ns, &ws, &wc);
-    uint32_t C = 0, any = 0;
-    for (uint32_t i = 0; i < ns; ++i) {
-        uint64_t start; uint32_t count;
-        q_seg(R, s0, i, ws, wc, &start, &count);
-        const uint32_t *d = depth + start;
-        for (uint32_t k = gl; k < count && C + k < cap; k += G) { const uint32_t x = d[k]; v[C + k] = x; any |= x; }
-        C += count;
-    }
-    if (C > cap) C = cap;                                        // (the host sends no such row here)
-    __threadfence_block();                                       // the group's lanes read each other's cells: same wave, LDS writes drained
-    for (uint32_t o = G >> 1; o; o >>= 1) any |= (uint32_t)__shfl_xor((int)any, (int)o);
-    uint32_t *out = q + r * P.n;
-    if (C == 0) { if (gl < P.n) out[gl] = 0xFFFFFFFFu; return; }
-    const int hb = any ? 31 - __clz((int)any) : -1;
-    const uint32_t gbase = (threadIdx.x & 63u) & ~(G - 1);
-    const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << G) - 1ull);
-    for (uint32_t j = 0; j < P.n; ++j) {
-        uint32_t rank = (uint32_t)q_rank(P.p[j], C), prefix = 0;
-        for (int bit = hb; bit >= 0; --bit) {
-            uint32_t cnt = 0;                                    // cells that share the bits fixed so far and have this one clear
-            for (uint32_t k0 = 0; k0 < C; k0 += G) {
-                const uint32_t k = k0 + gl;
-                const bool z = k < C && ((v[k] ^ prefix) >> bit) == 0;
-                cnt += (uint32_t)__popcll((__ballot(z) >> gbase) & gmask);
-            }
-            if (rank > cnt) { rank -= cnt; prefix |= 1u << bit; }
-        }
-        if (gl == 0) out[j] = prefix;
-    }
-}
-
-__device__ __forceinline__ unsigned long long q_block_scan(unsigned long long mine, unsigned long long *sc, unsigned long long *total)
-{
-    sc[threadIdx.x] = mine;
-    __syncthreads();
-    for (int o = 1; o < WG; o <<= 1) {
-        const unsigned long long a = (int)threadIdx.x >= o ? sc[threadIdx.x - o] : 0ull;
-        __syncthreads();
-        sc[threadIdx.x] += a;
-        __syncthreads();
-    }
-    const unsigned long long incl = sc[threadIdx.x];
-    *total = sc[WG - 1];
-    __syncthreads();
-    return incl;
-}
-
-// the thread whose `per` bins hold the r-th smallest writes the bin and the number of cells below it
-template <typename T>
-__device__ __forceinline__ void q_pick(const T *h, uint32_t per, unsigned long long excl, unsigned long long mine, unsigned long long r,
-                                       uint32_t *bin, unsigned long long *below)
-{
-    if (r <= excl || r > excl + mine) return;
-    unsigned long long acc = excl;
-    for (uint32_t k = 0; k < per; ++k) {
-        const unsigned long long x = h[threadIdx.x * per + k];
-        if (r <= acc + x) { *bin = threadIdx.x * per + k; *below = acc; return; }
-        acc += x;
-    }
-}
-
-// the r-th smallest of the row's cells that are >= 4095 (whole workgroup; h: 4096 LDS counters)
-template <typename T>
-__device__ uint32_t q_deep(const uint32_t *depth, const QRows &R, uint64_t s0, uint32_t ns, uint64_t ws, uint32_t wc, unsigned long long r,
-                           T *h, unsigned long long *sc, QSel *sel)
-{
-    uint32_t prefix = 0;
-    for (int pass = 0; pass < 3; ++pass) {
-        const uint32_t shift = pass == 0 ? 20u : pass == 1 ? 8u : 0u, nb = pass == 2 ? 256u : 4096u, fixed = pass == 1 ? 20u : 8u;
-        for (uint32_t j = threadIdx.x; j < 4096; j += WG) h[j] = 0;
-        __syncthreads();
-        for (uint32_t i = 0; i < ns; ++i) {
-            uint64_t start; uint32_t count;
-            q_seg(R, s0, i, ws, wc, &start, &count);
-            const uint32_t *d = depth + start;
-            for (uint32_t k = threadIdx.x; k < count; k += WG) {
-                const uint32_t x = d[k];
-                if (x >= 4095u && (pass == 0 || (x >> fixed) == (prefix >> fixed))) atomicAdd(&h[(x >> shift) & (nb - 1)], (T)1);
-            }
-        }
-        lds_drain();
-        __syncthreads();
-        const uint32_t per = nb / WG;
-        unsigned long long mine = 0, total;
-        for (uint32_t k = 0; k < per; ++k) mine += h[threadIdx.x * per + k];
-        const unsigned long long incl = q_block_scan(mine, sc, &total);
-        q_pick(h, per, incl - mine, mine, r, &sel->dbin, &sel->dbelow);
-        __syncthreads();
-        prefix |= sel->dbin << shift;
-        r -= sel->dbelow;
-        __syncthreads();
-    }
-    return prefix;
-}
-
-// A workgroup per row.  FROM_HIST: the row's 4096 uint64 bins are in memory already (ghist + slot * 4096); else they are counted here.
-template <typename T, bool FROM_HIST>
-__global__ __launch_bounds__(WG) void k_quant_block(const uint32_t *depth, const QRows R, const uint32_t *list, const QPct P, uint32_t *q,
-                                                    const unsigned long long *ghist)
-{
-    __shared__ T h[4096];
-    __shared__ unsigned long long sc[WG];
-    __shared__ QSel sel;
-    const int lane = threadIdx.x & 63;
-    const uint64_t r = list ? list[blockIdx.x] : blockIdx.x;
-    uint64_t s0, ws; uint32_t ns, wc;
-    q_row_begin(R, r, &s0, &ns, &ws, &wc);
-    const T *src = h;
-    if constexpr (FROM_HIST) src = reinterpret_cast<const T *>(ghist) + (size_t)blockIdx.x * 4096;
-    else {
-        for (uint32_t j = threadIdx.x; j < 4096; j += WG) h[j] = 0;
-        __syncthreads();
-        for (uint32_t i = 0; i < ns; ++i) {
-            uint64_t start; uint32_t count;
-            q_seg(R, s0, i, ws, wc, &start, &count);
-            const uint32_t *d = depth + start;
-            for (uint32_t base = 0; base < count; base += WG * 4) {
-                const uint32_t c0 = base + threadIdx.x * 4;
-                const uint32_t n = c0 >= count ? 0u : (count - c0 < 4u ? count - c0 : 4u);
-                uint32_t b[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) b[k] = (uint32_t)k < n ? min(d[c0 + k], 4095u) : 0u;
-                hist_lane4<true>(reinterpret_cast<uint32_t *>(h), b, n, lane);
-            }
-        }
-        lds_drain();
-        __syncthreads();
-    }
-    unsigned long long mine = 0, total;
-    for (uint32_t k = 0; k < 16; ++k) mine += src[threadIdx.x * 16 + k];
-    const unsigned long long incl = q_block_scan(mine, sc, &total);
-    uint32_t *out = q + r * P.n;
-    if (total == 0) { if (threadIdx.x < P.n) out[threadIdx.x] = 0xFFFFFFFFu; return; }
-    for (uint32_t j = 0; j < P.n; ++j) q_pick(src, 16, incl - mine, mine, q_rank(P.p[j], total), &sel.bin[j], &sel.below[j]);
-    __syncthreads();
-    unsigned long long last_r = 0; uint32_t last_v = 0;
-    for (uint32_t j = 0; j < P.n; ++j) {
-        uint32_t val = sel.bin[j];
-        if (val == 4095u) {                                      // cells >= 4095: refine (uniform over the workgroup; q_deep leaves bin[] / below[] alone)
-            const unsigned long long rd = q_rank(P.p[j], total) - sel.below[j];
-            if (rd != last_r) { last_v = q_deep<T>(depth, R, s0, ns, ws, wc, rd, h, sc, &sel); last_r = rd; }
-            val = last_v;
-        }
-        if (threadIdx.x == 0) out[j] = val;
-    }
-}
-
-int launch_quant_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t cap, uint32_t gshift,
-                        const QPct &P, uint32_t *q)
-{
-    if (!n) return 0;
-    if (cap < 1) cap = 1;
-    const uint32_t gpb = (uint32_t)WG >> gshift;
-    const size_t lds = (size_t)gpb * cap * 4;
-    if (int e = hist_lds_reserve(k_quant_narrow, lds)) return e;
-    hipLaunchKernelGGL(k_quant_narrow, dim3((n + gpb - 1) / gpb), dim3(WG), lds, st, reinterpret_cast<const uint32_t *>(depth), R, list, n, cap, gshift, P, q);
-    return 0;
-}
-
-void launch_quant_block(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, const QPct &P, uint32_t *q,
-                        const unsigned long long *ghist)
-{
-    if (!n) return;
-    const uint32_t *d = reinterpret_cast<const uint32_t *>(depth);
-    if (ghist) hipLaunchKernelGGL((k_quant_block<unsigned long long, true>), dim3(n), dim3(WG), 0, st, d, R, list, P, q, ghist);
-    else hipLaunchKernelGGL((k_quant_block<uint32_t, false>), dim3(n), dim3(WG), 0, st, d, R, list, P, q, ghist);
-}
-
-// ------------------------------------------------------------------------------------------
-// depth thresholds (pd_depth_thresholds / pd_window_thresholds): for every row (QRows, as the quantiles have them) the number of
-// cells >= T.t[j], j < T.n.  A cell is read once; a lane keeps NT counters in registers (NT = 1, 4 or 16, the thresholds padded
-// with 2^32-1 and the padding's counters never written), the thresholds sit in scalar registers.  A stretch of cells is read by
-// thr_span: scalar head to the first 16-byte boundary, 16-byte loads (four in flight per lane), scalar tail.  Two launch shapes:
-//   k_thr_narrow   a GROUP of 8 .. 64 lanes per row, many rows per wave, `rpg` consecutive rows per group one after the other (a
-//                  window's contig is found by bisection for the group's first row and by stepping for the rest); the group's
-//                  counters are summed with __shfl_xor and the row has one writer (no atomics, the result need not be zeroed)
-//   k_thr_pieces   rows cut into pieces of at most 16384 cells (Piece.region = the row's slot); a WAVE per piece, every wave of
-//                  `grid` workgroups takes a run of consecutive pieces; at the end of a row's pieces the wave's counters are summed
-//                  with __shfl_xor and added to the zeroed result row with T.n atomics
-// ------------------------------------------------------------------------------------------
-template <int NT>
-__device__ __forceinline__ void thr_count(uint32_t v, const ThrSet &T, uint32_t (&cnt)[NT])
-{
-#pragma unroll
-    for (int j = 0; j < NT; ++j) cnt[j] += v >= T.t[j] ? 1u : 0u;
-}
-template <int NT>
-__device__ __forceinline__ void thr_count4(const uint4 x, const ThrSet &T, uint32_t (&cnt)[NT])
-{
-    thr_count<NT>(x.x, T, cnt); thr_count<NT>(x.y, T, cnt); thr_count<NT>(x.z, T, cnt); thr_count<NT>(x.w, T, cnt);
-}
-
-// cells d[0 .. count) by lanes gl = 0 .. G - 1 (G >= 4); d is a cell of the depth array, whose base is 16-byte aligned
-template <int NT>
-__device__ __forceinline__ void thr_span(const uint32_t *d, uint32_t count, uint32_t gl, uint32_t G, const ThrSet &T, uint32_t (&cnt)[NT])
-{
-    uint32_t head = (4u - (uint32_t)((reinterpret_cast<uintptr_t>(d) >> 2) & 3u)) & 3u;     // cells before the first 16-byte boundary
-    if (head > count) head = count;
-    const uint32_t n4 = (count - head) >> 2, tail0 = head + (n4 << 2);
-    if (gl < head) thr_count<NT>(d[gl], T, cnt);
-    const uint4 *d4 = reinterpret_cast<const uint4 *>(d + head);
-    for (uint32_t k0 = 0; k0 < n4; k0 += 4 * G) {               // the same trips for every lane of the group; a lane past the end reads d4[0] and skips the count
-        const uint32_t k = k0 + gl;
-        const bool ok0 = k < n4, ok1 = k + G < n4, ok2 = k + 2 * G < n4, ok3 = k + 3 * G < n4;
-        const uint4 x0 = d4[ok0 ? k : 0u], x1 = d4[ok1 ? k + G : 0u], x2 = d4[ok2 ? k + 2 * G : 0u], x3 = d4[ok3 ? k + 3 * G : 0u];
-        if (ok0) thr_count4<NT>(x0, T, cnt);
-        if (ok1) thr_count4<NT>(x1, T, cnt);
-        if (ok2) thr_count4<NT>(x2, T, cnt);
-        if (ok3) thr_count4<NT>(x3, T, cnt);
-    }
-    if (tail0 + gl < count) thr_count<NT>(d[tail0 + gl], T, cnt);                           // (fewer than 4 cells)
-}
-
-template <int NT, typename OutT>
-__global__ __launch_bounds__(WG) void k_thr_narrow(const uint32_t *depth, const QRows R, const uint32_t *list, uint32_t n, uint32_t gshift,
-                                                   uint32_t rpg, const ThrSet T, OutT *out)
-{
-    const uint32_t G = 1u << gshift, gl = threadIdx.x & (G - 1);
-    const uint64_t slot0 = ((uint64_t)blockIdx.x * (WG >> gshift) + (threadIdx.x >> gshift)) * rpg;
-    int t = -1;                                                  // window mode: the contig of the row before
-    for (uint32_t i = 0; i < rpg; ++i) {
-        const uint64_t slot = slot0 + i;
-        if (slot >= n) break;                                    // (whole groups leave; nothing below synchronises the workgroup)
-        const uint64_t r = list ? list[slot] : slot;
-        uint32_t cnt[NT];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) cnt[j] = 0;
-        if (R.segs) {
-            const uint64_t s0 = R.seg_off[r], s1 = R.seg_off[r + 1];
-            for (uint64_t s = s0; s < s1; ++s) { const Piece pc = R.segs[s]; thr_span<NT>(depth + pc.start, pc.count, gl, G, T, cnt); }
-        } else {
-            const uint64_t g = R.row0 + r;
-            if (t < 0) t = q_win_contig(R, g);
-            else while (R.win_off[t + 1] <= g) ++t;              // (g is below win_off[n_contigs]: t stays a contig)
-            uint64_t ws; uint32_t wc;
-            q_win_cells(R, g, t, &ws, &wc);
-            thr_span<NT>(depth + ws, wc, gl, G, T, cnt);
-        }
-        OutT *o = out + r * T.n;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            int x = (int)cnt[j];                                 // (constant distances: the first steps are DPP moves)
-            if (G > 32) x += __shfl_xor(x, 32);
-            if (G > 16) x += __shfl_xor(x, 16);
-            if (G > 8) x += __shfl_xor(x, 8);
-            x += __shfl_xor(x, 4); x += __shfl_xor(x, 2); x += __shfl_xor(x, 1);
-            if ((uint32_t)j < T.n && gl == (uint32_t)j % G) o[j] = (OutT)x;
-        }
-    }
-}
-
-template <int NT, typename OutT>
-__device__ __forceinline__ void thr_add_row(uint32_t (&cnt)[NT], uint32_t lane, const ThrSet &T, OutT *o)
-{
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const uint32_t x = (uint32_t)wave_sum((int)cnt[j]);
-        if ((uint32_t)j < T.n && lane == (uint32_t)j && x) atomicAdd(&o[j], (OutT)x);
-        cnt[j] = 0;
-    }
-}
-
-// wave k of the grid takes pieces [k * ppw, (k + 1) * ppw): consecutive pieces of one row are added to it once
-template <int NT, typename OutT>
-__global__ __launch_bounds__(WG) void k_thr_pieces(const uint32_t *depth, const Piece *pieces, uint32_t n_pieces, uint32_t ppw, const ThrSet T, OutT *out)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t p0 = ((uint64_t)blockIdx.x * (WG / 64) + (threadIdx.x >> 6)) * ppw;
-    if (p0 >= n_pieces) return;
-    const uint32_t p1 = (uint32_t)(p0 + ppw < n_pieces ? p0 + ppw : n_pieces);
-    uint32_t cnt[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) cnt[j] = 0;
-    uint32_t cur = pieces[p0].region;
-    for (uint32_t pi = (uint32_t)p0; pi < p1; ++pi) {
-        const Piece pc = pieces[pi];
-        if (pc.region != cur) { thr_add_row<NT>(cnt, lane, T, out + (size_t)cur * T.n); cur = pc.region; }
-        thr_span<NT>(depth + pc.start, pc.count, lane, 64u, T, cnt);
-    }
-    thr_add_row<NT>(cnt, lane, T, out + (size_t)cur * T.n);
-}
-
-template <typename OutT>
-static void thr_narrow_any(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t gshift, uint32_t rpg, const ThrSet &T, OutT *out)
-{
-    if (!n) return;
-    if (rpg < 1) rpg = 1;
-    const uint32_t rpb = ((uint32_t)WG >> gshift) * rpg;         // rows per workgroup
-    const dim3 grid((n + rpb - 1) / rpb);
-    const uint32_t *d = reinterpret_cast<const uint32_t *>(depth);
-    if (T.n == 1) hipLaunchKernelGGL((k_thr_narrow<1, OutT>), grid, dim3(WG), 0, st, d, R, list, n, gshift, rpg, T, out);
-    else if (T.n <= 4) hipLaunchKernelGGL((k_thr_narrow<4, OutT>), grid, dim3(WG), 0, st, d, R, list, n, gshift, rpg, T, out);
-    else hipLaunchKernelGGL((k_thr_narrow<16, OutT>), grid, dim3(WG), 0, st, d, R, list, n, gshift, rpg, T, out);
-}
-template <typename OutT>
-static void thr_pieces_any(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, const ThrSet &T, OutT *out, unsigned grid)
-{
-    if (!n_pieces) return;
-    if (grid < 1) grid = 1;
-    const uint32_t waves = grid * (WG / 64), ppw = (n_pieces + waves - 1) / waves;           // pieces per wave
-    const dim3 g((n_pieces + ppw * (WG / 64) - 1) / (ppw * (WG / 64)));
-    const uint32_t *d = reinterpret_cast<const uint32_t *>(depth);
-    if (T.n == 1) hipLaunchKernelGGL((k_thr_pieces<1, OutT>), g, dim3(WG), 0, st, d, pieces, n_pieces, ppw, T, out);
-    else if (T.n <= 4) hipLaunchKernelGGL((k_thr_pieces<4, OutT>), g, dim3(WG), 0, st, d, pieces, n_pieces, ppw, T, out);
-    else hipLaunchKernelGGL((k_thr_pieces<16, OutT>), g, dim3(WG), 0, st, d, pieces, n_pieces, ppw, T, out);
-}
-
-void launch_thr_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t gshift, uint32_t rpg, const ThrSet &T, uint32_t *out)
-{ thr_narrow_any(st, depth, R, list, n, gshift, rpg, T, out); }
-void launch_thr_narrow(hipStream_t st, const int *depth, const QRows &R, const uint32_t *list, uint32_t n, uint32_t gshift, uint32_t rpg, const ThrSet &T, unsigned long long *out)
-{ thr_narrow_any(st, depth, R, list, n, gshift, rpg, T, out); }
-void launch_thr_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, const ThrSet &T, uint32_t *out, unsigned grid)
-{ thr_pieces_any(st, depth, pieces, n_pieces, T, out, grid); }
-void launch_thr_pieces(hipStream_t st, const int *depth, const Piece *pieces, uint32_t n_pieces, const ThrSet &T, unsigned long long *out, unsigned grid)
-{ thr_pieces_any(st, depth, pieces, n_pieces, T, out, grid); }
 
 } // namespace pdk

@@ -219,6 +219,41 @@ def test_regimes_agree(ctx0):
     set_regime(ctx0.e, *REGIMES[0])
 
 
+def test_more_wide_rows_than_one_launch(ctx0):
+    """1024 + 7 rows that all go in pieces: two pieces + pick launches in one batch (1024 histogram rows a launch), the second with
+    the seven rows left over, two of them with a second segment on another contig"""
+    n = 1024 + 7
+    rows = [[(0, 37 * i + 1, 37 * i + 17 + i % 23)] for i in range(n)]
+    rows[-2].append((1, 8185, 8200))                           # across the tile edge of contig 1, inside its pile
+    rows[-1].append((1, 100, 130))
+    segs, roff = flat(rows)
+    pct = [0, 50, 100]
+    cells_ref, q_exp = rows_ref(LENS, ctx0.d, ctx0.off, rows, pct)
+    assert cells_ref[0] == 17 and cells_ref[22] == 39 and cells_ref[-2] == 17 + (n - 2) % 23 + 16 and cells_ref[-1] == 17 + (n - 1) % 23 + 31
+    set_regime(ctx0.e, *REGIMES[2])
+    try:
+        cells, q = ctx0.e.depth_quantiles(segs, roff, pct)
+    finally:
+        set_regime(ctx0.e, *REGIMES[0])
+    assert np.array_equal(cells, cells_ref)
+    assert np.array_equal(q, q_exp), np.argwhere(q != q_exp)[:5]
+    assert q_exp[-2, 2] >= 500                                 # the second launch's rows are not all alike
+
+
+def test_row_batch_edge(ctx0):
+    """2^20 + 5 single-cell rows: the last five are a second batch; every quantile of a row is its one cell's depth"""
+    n = 2 ** 20 + 5
+    pos = np.arange(n, dtype=np.int64) % LENS[0]
+    segs = np.stack([np.zeros(n, dtype=np.int64), pos + 1, pos + 1], axis=1).astype(np.int32)
+    roff = np.arange(n + 1, dtype=np.uint64)
+    ref = ctx0.d[ctx0.off[0] + pos].astype(np.uint32).reshape(n, 1)
+    set_regime(ctx0.e, *REGIMES[0])
+    cells, q = ctx0.e.depth_quantiles(segs, roff, [50])
+    assert (cells == 1).all()
+    assert q.shape == ref.shape and np.array_equal(q, ref), np.argwhere(q != ref)[:5]
+    assert ref[20000:20100].min() >= 300000                    # the pile is among the rows
+
+
 @pytest.mark.parametrize("regime", REGIMES[:3], ids=lambda r: "wave%d_split%d" % r)
 def test_ties_and_tiny_rows(regime):
     """C in {1, 2, 3, 100, 101} and every p in 0 .. 100: an all-zero context (every cell ties), then a staircase (cell k of a

@@ -9,7 +9,7 @@ cd "$(dirname "$0")/../../pandepth_amd"
 REV=${1:-0f4c6db}
 OUT=../tools/ubench
 HIPCC=/opt/rocm/bin/hipcc; FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
-OBJS="csrc/pd_kernels.o csrc/pd_direct.o csrc/pd_capi.o csrc/pd_windows.o csrc/pd_decode.o csrc/pd_format.o csrc/pd_deflate.o"
+OBJS="csrc/pd_kernels.o csrc/pd_direct.o csrc/pd_capi.o csrc/pd_windows.o csrc/pd_rows.o csrc/pd_gcbias.o csrc/pd_decode.o csrc/pd_format.o csrc/pd_deflate.o"
 T=$(mktemp -d); cp csrc/*.h csrc/pd_bgzf.hip $T/; mkdir -p $T/../../include; 
 build() { name=$1; shift; $HIPCC $FL "$@" -I$PWD/csrc -c $T/pd_bgzf_$name.hip -o $T/pd_bgzf_$name.o && $HIPCC --offload-arch=gfx950 -shared -fPIC $OBJS $T/pd_bgzf_$name.o -ldl -o $OUT/libpd_inflate_$name.so; }
 sed "s#\"../../include/pandepth_amd.h\"#\"$PWD/../include/pandepth_amd.h\"#" csrc/pd_bgzf.hip > $T/pd_bgzf_v1.hip
