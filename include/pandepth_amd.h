@@ -421,7 +421,8 @@ int pd_synchronize(pd_ctx *ctx);
  * general path), "decode_end_unsorted" (the first runs pushed as PD_PUSH_DEFAULT: the records were not in order), "decode_end_pending"
  * (a compact session that found other runs deferred) —, "decode_c8_grow" (times the compact sample's arrays grew and moved),
  * "decode_chain_device" / "decode_chain_host" (batches whose record chain the device / the host confirmed), "decode_segments_redone",
- * "decode_guess_units" (units submitted with PD_UNIT_GUESS). */
+ * "decode_guess_units" (units submitted with PD_UNIT_GUESS), "decode_record_stats" (launches of k_record_stats that counted a batch: one per batch with counted records, 0 in a session
+ * without PD_DECODE_RECORD_STATS; a launch that the chain kernel's verdict stopped at once is not among them — and, as *ms, their summed time where the batches are timed: PANDEPTH_TIMING). */
 int pd_profile(pd_ctx *ctx, int enable);
 int pd_profile_get(pd_ctx *ctx, const char *name, double *ms, uint64_t *launches);
 
@@ -493,6 +494,7 @@ typedef struct pd_decode_cfg {
 #define PD_DECODE_COMPACT 1u
 #define PD_DECODE_DELETIONS 2u
 #define PD_DECODE_FRAGMENTS 4u
+#define PD_DECODE_RECORD_STATS 8u   /* the session also counts its RECORDS (the executable's -readstats): see pd_decode_record_stats below */
 typedef struct pd_decode_unit { uint64_t start, stop, avail; uint32_t first_block, n_blocks, flags, pad; } pd_decode_unit;
 typedef struct pd_decode_batch {
     void *host_buf; size_t n_bytes;                              /* from pd_decode_acquire: whole BGZF members           */
@@ -534,6 +536,28 @@ int pd_decode_queue(pd_ctx *ctx, const pd_decode_batch *batch, uint64_t *ticket)
 int pd_decode_collect(pd_ctx *ctx, uint64_t ticket, int32_t *unit_status /* batch->n_units entries */, pd_decode_result *res);
 int pd_decode_end(pd_ctx *ctx);
 int pd_decode_abort(pd_ctx *ctx);          /* forget the batches decoded since pd_decode_begin (nothing is counted) */
+
+/* ---- the records' statistics of a session opened with PD_DECODE_RECORD_STATS (csrc/pd_recstats.h: k_record_stats, one more pass over every
+ * batch's confirmed record chain; it reads the 36 fixed bytes of a record and no CIGAR, and a session without the flag does not launch it).
+ * Every record of every unit the device COUNTED (unit_status 0) is counted exactly once — a batch adds pd_decode_result::n_reads to
+ * sums[0]; the records of units that are handed back are the caller's to count.  The number of insert bins N travels as
+ * pd_set_param("decode_isize_bins", N), 1 <= N <= 65536, which pd_decode_begin reads (and requires) as it reads "decode_frag_max"; this keeps
+ * pd_decode_cfg's layout.  The classes of a record, in this order, disjoint (n_ref: the context's contigs):
+ *   unplaced      refID < 0 || refID >= n_ref
+ *   dropped_flag  flag & flag_mask
+ *   dropped_mapq  mapq < min_mapq
+ *   kept          everything else — the FILTER's verdict: contig_on, contigs shorter than two bases and the spans play no part.
+ * An INSERT PAIR is a kept record with flag & 0x3 == 0x3, flag & 0x908 == 0, next_refID == refID and tlen > 0; its bin is min(tlen, N).
+ * sums (n_sums = PD_RECSTAT_FIXED + N + 1 words):
+ *   [0] records  [1] unplaced  [2] dropped_flag  [3] dropped_mapq  [4] kept  [5] insert pairs  [6] the sum of the insert pairs' tlen
+ *   [7 + k], k = 0 .. 11: records with flag bit (1 << k) set, over ALL records
+ *   [19 + q], q = 0 .. 255: placed records that pass the flag mask (the records min_mapq chooses among) with mapq q
+ *   [PD_RECSTAT_FIXED + b], b = 0 .. N: insert pairs of bin b (bin 0 is always 0; bin N holds every tlen >= N)
+ * per_contig (3 words per contig of the context, in its order): records with that refID, the kept ones, the sum of the kept ones' mapq.
+ * Valid after pd_decode_end until the next pd_decode_begin (pd_decode_abort clears the numbers); PD_EINVAL with a message for a session
+ * without the flag or a wrong n_sums.  pd_push_bgzf_units (pandepth_amd_dev.h) does not collect these statistics. */
+#define PD_RECSTAT_FIXED 275
+int pd_decode_record_stats(pd_ctx *ctx, uint64_t *sums, size_t n_sums, uint64_t *per_contig);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,7 @@ int pd_set_param(pd_ctx *ctx, const char *name, uint64_t value);
  *   unit_status[u]  OUT: 0 = counted on the device; 1 = not counted, decode this unit on the host
  *                   (a record runs past `avail`, or a CIGAR lives in the CG tag); 2 = corrupt data
  * Synchronous: returns when the batch has been scattered.  The executable uses pd_decode_* (below). */
+/* (It opens no PD_DECODE_RECORD_STATS session: the records' statistics come from pd_decode_* sessions only.) */
 typedef struct pd_bgzf_unit { uint64_t start, stop, avail; uint32_t first_block, n_blocks; } pd_bgzf_unit;
 int pd_push_bgzf_units(pd_ctx *ctx, const void *blob, size_t n_bytes, const pd_bgzf_block *blocks, uint32_t n_blocks,
                        const pd_bgzf_unit *units, uint32_t n_units, uint64_t inflated_bytes, uint32_t flag_mask,

@@ -22,6 +22,8 @@ PD_UNIT_GUESS = 1
 PD_DECODE_COMPACT = 1
 PD_DECODE_DELETIONS = 2
 PD_DECODE_FRAGMENTS = 4
+PD_DECODE_RECORD_STATS = 8
+PD_RECSTAT_FIXED = 275                   # pd_decode_record_stats: the sums before the insert bins (include/pandepth_amd.h)
 PD_NONE = 0xFFFFFFFFFFFFFFFF                     # pd_decode_result::first_start / next_start: no such record
 
 
@@ -156,6 +158,7 @@ def load():
         "pd_decode_collect": (I, [P, U64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(pd_decode_result)]),
         "pd_decode_end": (I, [P]),
         "pd_decode_abort": (I, [P]),
+        "pd_decode_record_stats": (I, [P, ctypes.POINTER(U64), SZ, ctypes.POINTER(U64)]),
         "pd_x_bgzf_inflate": (I, [I, P, SZ, P, SZ, ctypes.POINTER(SZ), I, I, ctypes.POINTER(ctypes.c_double),
                               ctypes.POINTER(ctypes.c_uint32)]),
         "pd_stream": (P, [P]),
@@ -176,7 +179,7 @@ EXPORTS = ["pd_abi_version", "pd_create", "pd_destroy", "pd_strerror", "pd_reset
            "pd_push_intervals_device", "pd_runs_create", "pd_runs_destroy", "pd_push_runs", "pd_stage_acquire", "pd_stage_submit", "pd_set_param", "pd_keep_deferred", "pd_scan",
            "pd_reduce_intervals", "pd_window_layout", "pd_scan_reduce_windows", "pd_reduce_windows", "pd_scan_depth_histogram", "pd_depth_histogram", "pd_depth_levels", "pd_depth_quantiles", "pd_window_quantiles", "pd_depth_thresholds", "pd_window_thresholds", "pd_depth_gc_bias",
            "pd_read_depth", "pd_format_sites", "pd_deflate_parse", "pd_host_register", "pd_host_unregister", "pd_text_open", "pd_text_close", "pd_text_append_sites", "pd_text_parse", "pd_text_read", "pd_text_release", "pd_text_append_window_rows", "pd_text_append_bytes", "pd_device_buffer", "pd_device_count", "pd_accumulate_from", "pd_device_layout", "pd_export_i8", "pd_import_i8", "pd_export_i4",
-           "pd_slice_sweep_i4", "pd_gather_windows", "pd_push_bgzf_units", "pd_decode_begin", "pd_decode_acquire", "pd_decode_submit", "pd_decode_queue", "pd_decode_collect", "pd_decode_end", "pd_decode_abort", "pd_comm_unique_id", "pd_comm_init", "pd_comm_init_all", "pd_comm_init_local", "pd_comm_preinit", "pd_comm_prepare", "pd_comm_destroy",
+           "pd_slice_sweep_i4", "pd_gather_windows", "pd_push_bgzf_units", "pd_decode_begin", "pd_decode_acquire", "pd_decode_submit", "pd_decode_queue", "pd_decode_collect", "pd_decode_end", "pd_decode_abort", "pd_decode_record_stats", "pd_comm_unique_id", "pd_comm_init", "pd_comm_init_all", "pd_comm_init_local", "pd_comm_preinit", "pd_comm_prepare", "pd_comm_destroy",
            "pd_comm_strerror", "pd_sliced_window_sum", "pd_sliced_interval_sum", "pd_sliced_sum_start", "pd_sliced_sum_finish", "pd_x_bgzf_inflate", "pd_stream", "pd_synchronize", "pd_profile",
            "pd_profile_get", "pd_guard_check", "pd_guard_selftest", "pd_runs_pileup_tiles"]
 
@@ -653,12 +656,15 @@ class DecodeSession:
 
     def __init__(self, eng):
         self.e, self.L = eng, eng.L
+        self.n_isize = 0                     # begin's record_stats (the insert bins of pd_decode_record_stats)
         self._keep = []                      # arrays the C side reads during a call (and, for begin, until it returns)
         self.held = []                       # buffers acquired and not yet handed to submit / queue
 
     def begin(self, flag_mask=1796, min_mapq=-1, contig_on=None, span_off=None, spans=None, sorted=1, bytes_hint=0, batch_bytes=0,
-              batches_in_flight=0, flags=0, n_batches=0, count_deletions=False, fragments=False, frag_max=0):
-        """count_deletions adds PD_DECODE_DELETIONS to `flags`: deletions count as covered, one run per group of M/=/X/D operations.
+              batches_in_flight=0, flags=0, n_batches=0, count_deletions=False, fragments=False, frag_max=0, record_stats=0):
+        """record_stats=N (1 .. 65536) adds PD_DECODE_RECORD_STATS: the session also counts its records, with N insert bins (the parameter
+        "decode_isize_bins"); record_stats() returns the numbers after end().
+        count_deletions adds PD_DECODE_DELETIONS to `flags`: deletions count as covered, one run per group of M/=/X/D operations.
         fragments adds PD_DECODE_FRAGMENTS: a properly paired read with tlen > 0 is the one run [pos, pos + tlen), its mate none; frag_max
         bounds |tlen| (0: no bound).  The bound travels as the parameter "decode_frag_max", set here from the argument at every call."""
         if count_deletions:
@@ -666,6 +672,10 @@ class DecodeSession:
         if fragments:
             flags = int(flags) | PD_DECODE_FRAGMENTS
         self.e.set_param("decode_frag_max", int(frag_max))
+        self.n_isize = int(record_stats)
+        if record_stats:
+            flags = int(flags) | PD_DECODE_RECORD_STATS
+            self.e.set_param("decode_isize_bins", int(record_stats))
         cfg = pd_decode_cfg()
         cfg.flag_mask, cfg.min_mapq, cfg.sorted = int(flag_mask), int(min_mapq), int(sorted)
         cfg.bytes_hint, cfg.batch_bytes, cfg.batches_in_flight, cfg.flags, cfg.n_batches = int(bytes_hint), int(batch_bytes), int(batches_in_flight), int(flags), int(n_batches)
@@ -754,6 +764,15 @@ class DecodeSession:
         self.held = []
         self.e._ck(self.L.pd_decode_abort(self.e.h))
         self._keep = []
+
+    def record_stats(self):
+        """pd_decode_record_stats -> (sums: uint64[PD_RECSTAT_FIXED + N + 1], per_contig: uint64[n_contigs, 3]) of the session that
+        end() closed; PdError for a session begun without record_stats=N"""
+        sums = np.zeros(PD_RECSTAT_FIXED + self.n_isize + 1, dtype=np.uint64)
+        per = np.zeros((max(self.e.n_contigs, 1), 3), dtype=np.uint64)
+        U64P = ctypes.POINTER(ctypes.c_uint64)
+        self.e._ck(self.L.pd_decode_record_stats(self.e.h, sums.ctypes.data_as(U64P), sums.size, per.ctypes.data_as(U64P)))
+        return sums, per[:self.e.n_contigs]
 
 
 class TextStream:

@@ -12,6 +12,7 @@
 #include "pd_inflate_core.h"
 #include "pd_inflate_wave.h"
 #include "pd_bamwalk.h"
+#include "pd_recstats.h"
 #include "pd_kernels.h"
 #include "../../include/pandepth_amd.h"
 #include "../../include/pandepth_amd_dev.h"
@@ -119,6 +120,26 @@ __global__ __launch_bounds__(64) void k_emit_segments(const pdb2::Cfg cfg, const
     pdb2::emit_segment<pdw::DevWave, DEL, FRAG>(cfg, segs[j], lanes + (size_t)j * 64, first, other, far, so);
 }
 
+// The records' statistics (pd_recstats.h; sessions with PD_DECODE_RECORD_STATS only): behind pass 2, over the same confirmed lanes.  RS_WAVES segments
+// per workgroup, a wave each, share one LDS copy of the sums' first words — 9 KiB, so the LDS bounds no occupancy, and the flush (one global atomic
+// per non-zero word) is paid once for four segments whose MAPQ values and insert sizes are largely the same few hundred.  `gate` as in
+// k_emit_segments; a segment marked RS_SKIP belongs to a unit the host takes back and counts itself.
+enum { RS_WAVES = 4 };
+__global__ __launch_bounds__(64 * RS_WAVES) void k_record_stats(const pdb2::Cfg cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes, uint32_t n_bins,
+                                                                unsigned long long *sums, unsigned long long *per_contig, const pdb2::ChainOut *gate)
+{
+    __shared__ uint32_t hist[pdrs::RS_LDS_WORDS];
+    if (gate && gate->slow) return;
+    const uint32_t words = pdrs::lds_words(n_bins);
+    for (uint32_t i = threadIdx.x; i < words; i += 64 * RS_WAVES) hist[i] = 0;
+    __syncthreads();
+    const uint32_t j = blockIdx.x * RS_WAVES + (threadIdx.x >> 6);
+    if (j < n_seg && segs[j].pad2 != pdrs::RS_SKIP && segs[j].n_rec != 0)
+        pdrs::stats_segment<pdw::DevWave>(cfg, segs[j], lanes + (size_t)j * 64, n_bins, sums, per_contig, hist);
+    __syncthreads();
+    pdrs::flush_hist(hist, words, sums, threadIdx.x, 64 * RS_WAVES);
+}
+
 // are the first runs of a batch in (tid, begin) order?  out[0] = 1 if not; out[2..3] / out[4..5] = first / last key
 __global__ __launch_bounds__(256) void k_runs_sorted(const pd_iv *runs, uint64_t n, uint32_t *out)
 {
@@ -166,6 +187,12 @@ void launch_emit_segments(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg 
 {
     if (!n_seg) return;
     hipLaunchKernelGGL(PD_WALK_PICK(k_emit_segments), dim3(n_seg), dim3(64), 0, st, cfg, segs, n_seg, lanes, first, other, far, gate);
+}
+void launch_record_stats(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes, uint32_t n_bins,
+                         unsigned long long *sums, unsigned long long *per_contig, const pdb2::ChainOut *gate)
+{
+    if (!n_seg) return;
+    hipLaunchKernelGGL(k_record_stats, dim3((n_seg + RS_WAVES - 1) / RS_WAVES), dim3(64 * RS_WAVES), 0, st, cfg, segs, n_seg, lanes, n_bins, sums, per_contig, gate);
 }
 void launch_spoil_segments(hipStream_t st, const pdb2::Cfg &cfg, pdb2::Seg *segs, uint32_t n_seg, pdb2::LaneOut *lanes, uint32_t k)
 {

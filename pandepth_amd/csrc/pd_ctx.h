@@ -190,6 +190,7 @@ struct pd_ctx {
         bool warming = false;                                     // the session's warm-up thread is still making this slot's buffer and stream (dec_mu)
         hipStream_t st = nullptr;
         hipEvent_t ev[6] = {};
+        hipEvent_t ev_rs[2] = {};                                 // around k_record_stats (PD_DECODE_RECORD_STATS sessions that are timed; made on first need)
         hipEvent_t ev_done = nullptr;                             // recorded behind everything pd_decode_queue puts on the stream: what pd_decode_collect waits for
         uint8_t *h_blob = nullptr; size_t h_cap = 0;              // page-locked (pin_alloc)
         bool h_mapped = false;                                    // ... as huge pages of its own registered with the runtime (freed by pin_free)
@@ -201,6 +202,7 @@ struct pd_ctx {
         // a batch between pd_decode_queue and pd_decode_collect (pd_decode_submit: the two back to back)
         struct Job {
             bool open = false, queued = false, c8 = false, fast = false, owes_count = false, timed = false;
+            bool segs_sent = false, rs_timed = false;              // the host's segments (bases, RS_SKIP marks) are on the device; ev_rs were recorded for this batch
             bool collecting = false;                               // some thread is inside dec_collect on this slot (set and tested under dec_mu): one ticket, one collect
             uint64_t order = 0; size_t n_bytes = 0; uint64_t inflated = 0; uint32_t n_seg = 0;
             std::vector<pd_bgzf_block> blocks; std::vector<pd_decode_unit> units; std::vector<pdb2::Seg> segs; std::vector<uint32_t> seg0;
@@ -228,6 +230,12 @@ struct pd_ctx {
     bool dec_fragments = false;                                   // "decode_fragments": ... with PD_DECODE_FRAGMENTS
     uint32_t dec_frag_max = 0;                                    // "decode_frag_max": a PD_DECODE_FRAGMENTS session's bound on |tlen| (0: none), read by pd_decode_begin ...
     uint32_t dec_frag_bound = 0x7FFFFFFFu;                        // ... into this, the open session's bound
+    // PD_DECODE_RECORD_STATS: the open (or last ended) session's sums — PD_RECSTAT_FIXED + rs_bins + 1 words, then 3 per contig (pd_recstats.h) —, zeroed by
+    // pd_decode_begin, added to by every batch's k_record_stats, read by pd_decode_record_stats between pd_decode_end and the next pd_decode_begin
+    uint32_t dec_isize_bins = 0;                                  // "decode_isize_bins": the insert bins of the next such session (1 .. 65536), read by pd_decode_begin ...
+    uint32_t rs_bins = 0;                                         // ... into this
+    unsigned long long *d_recstat = nullptr; size_t recstat_words = 0; bool rs_ready = false;
+    std::atomic<uint64_t> rs_launches{0}, rs_ns{0};               // "decode_record_stats": launches of the session, and their summed time where the batches are timed
     pd_decode_cfg dec_cfg{}; uint8_t *d_contig_on = nullptr; uint32_t *d_span_off = nullptr; int32_t *d_spans = nullptr;
     std::vector<RunSeg> run_segs;
     pd_iv *run_first = nullptr, *run_other = nullptr, *run_far = nullptr;   // the concatenated sample (owned until the next reset)

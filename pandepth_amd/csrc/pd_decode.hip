@@ -4,6 +4,7 @@
 // pd_decode_end.  A batch is dec_queue (everything it needs goes onto its slot's stream) and dec_collect (wait, finish, report); each is a
 // short list of steps, and every step is a function of this file.
 #include "pd_ctx.h"
+#include "pd_recstats.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // GPU-side BAM decode in asynchronous batches (include/pandepth_amd.h: pd_decode_*)
@@ -241,6 +242,20 @@ int begin_filters(pd_ctx *c, const pd_decode_cfg *cfg)
     return PD_OK;
 }
 
+// PD_DECODE_RECORD_STATS: the session's sums and contig triples, zeroed (on c->stream, which begin_filters waits for)
+int begin_record_stats(pd_ctx *c)
+{
+    c->rs_bins = c->dec_isize_bins;
+    const size_t words = (size_t)PD_RECSTAT_FIXED + c->rs_bins + 1 + 3 * (size_t)c->n_contigs;
+    if (words != c->recstat_words) {
+        if (c->d_recstat) { (void)hipFree(c->d_recstat); c->d_recstat = nullptr; c->recstat_words = 0; }
+        if (hipMalloc(&c->d_recstat, words * 8 + 64) != hipSuccess) { (void)hipGetLastError(); return fail(c, PD_ENOMEM, "pd_decode_begin: allocation failed"); }
+        c->recstat_words = words;
+    }
+    HIPOK(c, hipMemsetAsync(c->d_recstat, 0, words * 8, c->stream));
+    return PD_OK;
+}
+
 // A sorted file read for whole-contig statistics (PD_DECODE_COMPACT), its batches numbered 0 .. n_batches - 1: the batches' runs go
 // straight to their final places in a compact sample (C8Dec).  Sized from the compressed bytes
 // (>= 32 B of BGZF per record of a real file; denser files make it grow): a first run per record, a later run for every fourth.
@@ -368,8 +383,12 @@ int pd_decode_begin(pd_ctx *c, const pd_decode_cfg *cfg)
     HIPOK(c, hipSetDevice(c->device));
     const uint64_t tb0 = dec_now_us(); uint64_t tb[6] = {tb0, tb0, tb0, tb0, tb0, tb0};
     struct BeginMarks { const uint64_t *t; ~BeginMarks() { if (getenv("PANDEPTH_TIMING") && t[5] - t[0] > 20000) fprintf(stderr, "[timing]   pd_decode_begin: tables %.3f s, marks + compose stream %.3f s, sample arrays %.3f s, arena %.3f s, buffers %.3f s\n", (t[1] - t[0]) / 1e6, (t[2] - t[1]) / 1e6, (t[3] - t[2]) / 1e6, (t[4] - t[3]) / 1e6, (t[5] - t[4]) / 1e6); } } begin_marks{tb};
+    if ((cfg->flags & PD_DECODE_RECORD_STATS) && !c->dec_isize_bins)      // (refused before anything of the context changes)
+        return fail(c, PD_EINVAL, "pd_decode_begin: PD_DECODE_RECORD_STATS needs pd_set_param(\"decode_isize_bins\", N) with 1 <= N <= 65536 first");
     c->dec_cfg = *cfg;
     c->dec_frag_bound = c->dec_frag_max ? c->dec_frag_max : 0x7FFFFFFFu;      // ("decode_frag_max" as it stands now holds for the whole session; 0: no bound)
+    c->rs_ready = false; c->rs_launches = 0; c->rs_ns = 0;
+    if (cfg->flags & PD_DECODE_RECORD_STATS) if (int rc = begin_record_stats(c)) return rc;
     if (int rc = begin_filters(c, cfg)) return rc;
     tb[1] = tb[2] = tb[3] = dec_now_us();
     if (int rc = begin_compact(c, cfg, tb)) return rc;
@@ -543,6 +562,30 @@ int dec_upload(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, bool one_copy,
     return PD_OK;
 }
 
+// The records' statistics of the batch's counted segments (sessions with PD_DECODE_RECORD_STATS), on the slot's stream behind the emission.  gate:
+// the chain kernel's verdict on the device (a batch it leaves to the host counts nothing here), or null behind the host's chain check.
+int dec_record_stats(pd_ctx *c, DecSlot &sl, const pdb2::Seg *d_seg, const pdb2::ChainOut *gate)
+{
+    Job &J = sl.job;
+    if (J.timed) {
+        for (auto &e : sl.ev_rs) if (!e) HIPDEC(hipEventCreate(&e));
+        HIPDEC(hipEventRecord(sl.ev_rs[0], sl.st));
+    }
+    launch_record_stats(sl.st, J.cfg, d_seg, J.n_seg, (const pdb2::LaneOut *)sl.d[DS_LANE], c->rs_bins, c->d_recstat, c->d_recstat + PD_RECSTAT_FIXED + c->rs_bins + 1, gate);
+    if (J.timed) { HIPDEC(hipEventRecord(sl.ev_rs[1], sl.st)); J.rs_timed = true; }
+    if (!gate) ++c->rs_launches;                                          // (a gated launch counts once its batch is known to be confirmed: dec_collect)
+    return PD_OK;
+}
+
+// ... and its time, once the stream has been waited for
+void dec_record_stats_time(pd_ctx *c, DecSlot &sl)
+{
+    if (!sl.job.rs_timed) return;
+    sl.job.rs_timed = false;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, sl.ev_rs[0], sl.ev_rs[1]) == hipSuccess) c->rs_ns += (uint64_t)((double)ms * 1e6);
+}
+
 // Inflate, pass 1 and — where the device confirms the record chain itself — the chain and the emission; otherwise the member statuses and
 // the segments come back for the host's chain check.  *t_inflate (PANDEPTH_DEVTRACE): when the inflate kernel had been launched.
 int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t *members, unsigned n_wg, uint64_t *t_inflate)
@@ -581,6 +624,7 @@ int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t 
         launch_emit_segments(st, c2, d_seg, n_seg, d_lane, c8 ? nullptr : (pd_iv *)sl.d[DS_R8], (pd_iv *)sl.d[DS_OTH], nullptr, d_co);
         HIPDEC(hipMemcpyAsync(pin + J.o.co, d_co, sizeof(pdb2::ChainOut) + (size_t)n_seg * sizeof(pdb2::SegOut), hipMemcpyDeviceToHost, st));
         if (J.timed) HIPDEC(hipEventRecord(sl.ev[4], st));
+        if (c->dec_cfg.flags & PD_DECODE_RECORD_STATS) if (int rc = dec_record_stats(c, sl, d_seg, d_co)) return rc;
     } else {
         HIPDEC(hipMemcpyAsync(pin + J.o.bst, sl.d[DS_ST], (size_t)bt->n_blocks * 4, hipMemcpyDeviceToHost, st));
         HIPDEC(hipMemcpyAsync(pin + J.o.seg, d_seg, (size_t)n_seg * sizeof(pdb2::Seg), hipMemcpyDeviceToHost, st));
@@ -592,7 +636,7 @@ int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t 
 int dec_queue(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt)
 {
     Job &J = sl.job;                                                  // (claimed by dec_slot_of: J.open is set)
-    J.queued = false; J.fast = false; J.timed = false; J.t_q0 = dec_now_us(); J.order = bt->order; J.n_bytes = bt->n_bytes; J.inflated = bt->inflated_bytes; J.n_seg = 0;
+    J.queued = false; J.fast = false; J.timed = false; J.segs_sent = false; J.rs_timed = false; J.t_q0 = dec_now_us(); J.order = bt->order; J.n_bytes = bt->n_bytes; J.inflated = bt->inflated_bytes; J.n_seg = 0;
     J.blocks.clear(); J.units.clear(); J.segs.clear(); J.seg0.clear();
     const bool c8 = J.c8 = c->c8.on;
     J.owes_count = c8 && bt->order < c->c8.n_batches;
@@ -752,6 +796,9 @@ int collect_chain(pd_ctx *c, DecSlot &sl)
     return PD_OK;
 }
 
+// does the batch have a counted unit with records?  (after unit_outcomes: the segments of a unit that is handed back carry RS_SKIP)
+bool counted_records(const Job &J) { for (auto &s : J.segs) if (s.pad2 != (uint32_t)pdrs::RS_SKIP && s.n_rec) return true; return false; }
+
 // Unit outcomes (units handed back emit nothing) and the bases of the segments' runs in the batch's arrays; host only.  bst: the members'
 // statuses.  -> the batch's totals, its arrays not yet taken
 RunSeg unit_outcomes(Job &J, const int *bst, int32_t *unit_status, pd_decode_result *res)
@@ -769,6 +816,7 @@ RunSeg unit_outcomes(Job &J, const int *bst, int32_t *unit_status, pd_decode_res
         }
         unit_status[u] = stt;
         for (uint32_t j = seg0[u]; j < seg0[u + 1]; ++j) {
+            segs[j].pad2 = stt ? (uint32_t)pdrs::RS_SKIP : 0u;          // (k_record_stats: a unit that is handed back is counted by whoever decodes it)
             if (stt) { segs[j].n_first = segs[j].n_other = segs[j].n_far = 0; } else nrec += segs[j].n_rec;
             segs[j].base_first = nf; segs[j].base_other = no; segs[j].base_far = nfar;
             nf += segs[j].n_first; no += segs[j].n_other; nfar += segs[j].n_far;
@@ -799,6 +847,7 @@ int collect_emit(pd_ctx *c, DecSlot &sl, RunSeg &rs, Owned &own, bool *have_so)
     const auto segs_up = [&]() -> int {                                   // the segments with their bases
         memcpy(pin + J.o.seg, J.segs.data(), (size_t)n_seg * sizeof(pdb2::Seg));
         HIPDEC(hipMemcpyAsync(d_seg, pin + J.o.seg, (size_t)n_seg * sizeof(pdb2::Seg), hipMemcpyHostToDevice, st));
+        J.segs_sent = true;
         return PD_OK;
     };
     if (J.c8) {
@@ -840,11 +889,15 @@ int dec_collect(pd_ctx *c, DecSlot &sl, int32_t *unit_status, pd_decode_result *
     uint8_t *const pin = sl.h_small;
     J.t_mark = dec_now_us();
     if (int rc = dec_wait(c, sl)) return rc;
+    dec_record_stats_time(c, sl);
     if (J.fast) {
         pdb2::ChainOut co;
         memcpy(&co, pin + J.o.co, sizeof co);
         c->dec_n_redo += co.n_redo;
-        if (!co.slow) return collect_confirmed(c, sl, co, res);
+        if (!co.slow) {
+            if (c->dec_cfg.flags & PD_DECODE_RECORD_STATS) ++c->rs_launches;      // (the gated k_record_stats of dec_launch counted this batch; one the gate stopped is not a launch of the counter)
+            return collect_confirmed(c, sl, co, res);
+        }
         // ---- out of the ordinary (ChainOut::slow says why; nothing was emitted): the member statuses and the segments as they stand come
         // to the host, which goes through the batch the way it always has
         // (more later runs than the batch's array holds — reads with thousands of CIGAR operations: the batches queued from now on get
@@ -871,8 +924,19 @@ int dec_collect(pd_ctx *c, DecSlot &sl, int32_t *unit_status, pd_decode_result *
         HIPDEC(hipMemcpyAsync(pin + J.o.ord, sl.d[DS_ONLY], 24, hipMemcpyDeviceToHost, st));
     }
     if (J.timed) HIPDEC(hipEventRecord(sl.ev[4], st));
+    if ((c->dec_cfg.flags & PD_DECODE_RECORD_STATS) && counted_records(J)) {
+        // the records of the counted units (the segments of the others carry RS_SKIP); the segments go up where the emission had none to send
+        pdb2::Seg *d_seg = (pdb2::Seg *)((J.d_tab ? J.d_tab : (uint8_t *)sl.d[DS_BLK]) + J.o.seg);
+        if (!J.segs_sent) {
+            memcpy(pin + J.o.seg, J.segs.data(), (size_t)J.n_seg * sizeof(pdb2::Seg));
+            HIPDEC(hipMemcpyAsync(d_seg, pin + J.o.seg, (size_t)J.n_seg * sizeof(pdb2::Seg), hipMemcpyHostToDevice, st));
+            J.segs_sent = true;
+        }
+        if (int rc = dec_record_stats(c, sl, d_seg, nullptr)) return rc;
+    }
     HIPDEC(hipStreamSynchronize(st));
     HIPDEC(hipGetLastError());
+    dec_record_stats_time(c, sl);
     if (nf && !J.c8) {
         memcpy(order_words, pin + J.o.ord, 24);
         rs.unsorted = order_words[0];
@@ -1162,6 +1226,7 @@ int pd_decode_end(pd_ctx *c)
     if (int rs = need_state(c, 0, "pd_decode_end")) return rs;
     HIPOK(c, hipSetDevice(c->device));
     for (auto &sl : c->dec) if (sl.st) HIPOK(c, hipStreamSynchronize(sl.st));      // (the last copies of the batches' runs to their arrays)
+    c->rs_ready = (c->dec_cfg.flags & PD_DECODE_RECORD_STATS) != 0;                // (every batch's k_record_stats is through: pd_decode_record_stats)
     std::vector<RunSeg> segs;
     { std::lock_guard<std::mutex> l2(c->dec_mu); segs.swap(c->run_segs); }
     std::sort(segs.begin(), segs.end(), [](const RunSeg &a, const RunSeg &b) { return a.order < b.order; });
@@ -1181,6 +1246,8 @@ int pd_decode_end(pd_ctx *c)
                         "decode_end_scatter %llu, decode_end_unsorted %llu, decode_end_pending %llu\n", (unsigned long long)nf, (unsigned long long)(no + nfar),
                 (unsigned long long)c->dec_n[pd_ctx::DN_END_COMPACT], (unsigned long long)c->dec_n[pd_ctx::DN_END_C8_FALLBACK], (unsigned long long)c->dec_n[pd_ctx::DN_END_RUNS_MAKE],
                 (unsigned long long)c->dec_n[pd_ctx::DN_END_SCATTER], (unsigned long long)c->dec_n[pd_ctx::DN_END_UNSORTED], (unsigned long long)c->dec_n[pd_ctx::DN_END_PEND]);
+    if (getenv("PANDEPTH_TIMING") && c->rs_ready)                    // (the records' statistics pass: decode_record_stats)
+        fprintf(stderr, "[timing]   k_record_stats: %llu launches, %.3f ms summed over the batches\n", (unsigned long long)c->rs_launches.load(), (double)c->rs_ns.load() / 1e6);
     return rc;
 }
 
@@ -1191,6 +1258,26 @@ int pd_decode_abort(pd_ctx *c)
     (void)hipSetDevice(c->device);
     { std::lock_guard<std::mutex> lk(c->dec_mu); for (auto &r : c->run_segs) r.release(c); c->run_segs.clear(); }
     { std::lock_guard<std::mutex> l8(c->c8.mu); if (c->c8.on || c->c8.base) { (void)hipDeviceSynchronize(); c8_drop(c); } }
+    c->rs_ready = false;
+    if (c->d_recstat && (c->dec_cfg.flags & PD_DECODE_RECORD_STATS)) {            // (the statistics of the batches that are forgotten)
+        for (auto &sl : c->dec) if (sl.st) (void)hipStreamSynchronize(sl.st);
+        (void)hipMemset(c->d_recstat, 0, c->recstat_words * 8);
+    }
+    return PD_OK;
+}
+
+int pd_decode_record_stats(pd_ctx *c, uint64_t *sums, size_t n_sums, uint64_t *per_contig)
+{
+    if (!c) return PD_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!(c->dec_cfg.flags & PD_DECODE_RECORD_STATS) || !c->rs_ready || !c->d_recstat)
+        return fail(c, PD_EINVAL, "pd_decode_record_stats: no session with PD_DECODE_RECORD_STATS has been ended by pd_decode_end since the last pd_decode_begin");
+    const size_t want = (size_t)PD_RECSTAT_FIXED + c->rs_bins + 1;
+    if (!sums || n_sums != want || (!per_contig && c->n_contigs))
+        return fail(c, PD_EINVAL, "pd_decode_record_stats: sums must hold PD_RECSTAT_FIXED + decode_isize_bins + 1 = " + std::to_string(want) + " words and per_contig 3 per contig");
+    HIPOK(c, hipSetDevice(c->device));
+    HIPOK(c, hipMemcpy(sums, c->d_recstat, want * 8, hipMemcpyDeviceToHost));
+    if (c->n_contigs) HIPOK(c, hipMemcpy(per_contig, c->d_recstat + want, 3 * (size_t)c->n_contigs * 8, hipMemcpyDeviceToHost));
     return PD_OK;
 }
 

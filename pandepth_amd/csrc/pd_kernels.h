@@ -246,5 +246,8 @@ void launch_spoil_segments(hipStream_t st, const pdb2::Cfg &cfg, pdb2::Seg *segs
 void launch_chain_segments(hipStream_t st, const pdb2::Cfg &cfg, pdb2::Seg *segs, uint32_t n_seg, pdb2::LaneOut *lanes, const int *member_status,
                            uint32_t n_members, uint64_t cap_first, uint64_t cap_other, uint32_t max_redo, pdb2::ChainOut *out);
 void launch_runs_sorted(hipStream_t st, const pd_iv *runs, uint64_t n, uint32_t *out);
+// the records' statistics of a batch's counted segments (pd_recstats.h; k_record_stats), behind the emission: n_bins insert bins, the session's sums and contig triples
+void launch_record_stats(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes, uint32_t n_bins,
+                         unsigned long long *sums, unsigned long long *per_contig, const pdb2::ChainOut *gate /* as launch_emit_segments' */);
 }
 #endif

@@ -84,6 +84,8 @@ typedef struct pd_engine_api {
     int (*window_thresholds)(pd_ctx *, uint32_t, const uint32_t *, uint32_t, uint32_t *);
     /* optional (NULL = the host reads the depth back and bins the windows from the bases it holds): the -gcbias file, see pd_depth_gc_bias */
     int (*depth_gc_bias)(pd_ctx *, const pd_region *, size_t, uint32_t, const char *const *, const uint32_t *, uint64_t *, uint64_t *, uint64_t *);
+    /* optional (NULL = the host readers take an input under -readstats): the records' statistics of a decode session, see pd_decode_record_stats */
+    int (*decode_record_stats)(pd_ctx *, uint64_t *, size_t, uint64_t *);
 } pd_engine_api;
 
 /* Runs one `pandepth` invocation (argv as given to main) on the engine behind `api`. */

@@ -576,6 +576,29 @@ bool write_gcbias(Run &r)
     return true;
 }
 
+// -readstats N: what the records were, in <prefix>.reads.stat.gz.  The numbers are the contexts' accumulators (Engine::rs, fed by the
+// device's k_record_stats or by the host readers as every input was read), not the engine's depth: nothing is asked of the engine here.
+std::string readstats_empty(const Run &r)
+{
+    RecStats z;
+    z.init(r.o.flag_mask, r.o.min_mapq, r.o.readstats, (int32_t)r.hdr.names.size());
+    return z.text(r.hdr.names, r.hdr.lens);
+}
+
+bool write_readstats(Run &r)
+{
+    RecStats all;
+    all.init(r.o.flag_mask, r.o.min_mapq, r.o.readstats, (int32_t)r.hdr.names.size());
+    for (auto &e : r.engs) all.merge(e->rs);
+    GzWriter G;
+    const std::string path = r.prefix + ".reads.stat.gz";
+    if (!G.open(path)) { r.eng->fail("cannot open " + path); return false; }
+    G.write(all.text(r.hdr.names, r.hdr.lens));
+    if (!G.close()) { ::remove(path.c_str()); r.eng->fail("cannot write " + path); return false; }
+    r.tm.mark("read statistics");
+    return true;
+}
+
 } // namespace
 
 const Extra EXTRAS[] = {
@@ -584,6 +607,7 @@ const Extra EXTRAS[] = {
     {".quantile.stat.gz", [](const Options &o) { return !o.quantile.empty(); }, quantile_header, write_quantile},
     {".thresholds.stat.gz", [](const Options &o) { return !o.thresholds.empty(); }, thresholds_header, write_thresholds},
     {".gcbias.stat.gz", [](const Options &o) { return o.gcbias != 0; }, gcbias_empty, write_gcbias},
+    {".reads.stat.gz", [](const Options &o) { return o.readstats != 0; }, readstats_empty, write_readstats},
 };
 const size_t N_EXTRAS = sizeof(EXTRAS) / sizeof(EXTRAS[0]);
 

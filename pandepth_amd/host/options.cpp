@@ -242,6 +242,15 @@ int parse_options(int argc, char **argv, Options *o)
             if (!good || x < 1 || x > (1u << 20)) { std::cerr << msg << std::endl; return 0; }
             o->gcbias = (uint32_t)x;
         }
+        else if (flag == "readstats") {                                          // not in the reference: the .reads.stat.gz statistics of the records (README)
+            const char *msg = "Error: -readstats should be the number of insert-size bins, from 1 to 65536";
+            if (i + 1 == argc) { std::cerr << msg << std::endl; return 0; }
+            v = argv[++i];
+            uint64_t x = 0; bool good = !v.empty() && v.size() <= 5;
+            for (size_t k = 0; good && k < v.size(); ++k) { if (v[k] < '0' || v[k] > '9') good = false; else x = x * 10 + (uint64_t)(v[k] - '0'); }
+            if (!good || x < 1 || x > 65536) { std::cerr << msg << std::endl; return 0; }
+            o->readstats = (uint32_t)x;
+        }
         else if (flag == "del") o->count_del = true;                            // not in the reference: deletions count as covered (README)
         else if (flag == "frag") o->frag = true;                                 // not in the reference: whole fragments of properly paired reads (README)
         else if (flag == "fragmax") {                                            // ... and the largest |tlen| that still makes a fragment

@@ -155,6 +155,14 @@ struct ReadFilter {
     }
 };
 
+// -readstats in a threaded reader: the thread's own accumulator, merged into its context's when the thread is through
+struct RecStatsPart {
+    Engine *e; RecStats mine;
+    explicit RecStatsPart(Engine *eng) : e(eng) { mine.init_like(eng->rs); }
+    ~RecStatsPart() { if (mine.on) { std::lock_guard<std::mutex> lk(e->rs_mu); e->rs.merge(mine); } }
+    RecStats *ptr() { return mine.on ? &mine : nullptr; }
+};
+
 // htslib multi-region fetch of "chr:max(s-1,1)-min(e+1,len)" for every merged span (PD:419-430):
 // a read is returned when pos < region_end && endpos > region_begin0.
 struct SpanIndex {
@@ -194,7 +202,7 @@ bool index_exists(const std::string &p) { return file_exists(p + ".bai") || file
 // ---- readers ---------------------------------------------------------------------------------
 // records that START in [begin, stop) of an open BAM, through the host decoder
 bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter &flt, const struct SpanIndex &spans,
-                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag);
+                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag, RecStats *rs);
 
 struct DevRange;
 int read_bam_device(const std::string &path, const Options &o, const AlnHeader &main_hdr, const SpanIndex &spans, const RegionModel &rm,
@@ -284,6 +292,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
         struct Tally { std::atomic<uint64_t> &n, &us; uint64_t &mine; std::chrono::steady_clock::time_point t0;
                        ~Tally() { n += mine; us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count(); } }
             tally{n_rec, busy_us, my_rec, w0};
+        RecStatsPart part(eng);                              // (-readstats: this thread's records, merged when it is through — like the tally)
         AlnReader rd;
         std::string e2;
         if (!rd.open(path, &e2)) { eng->fail(e2); return; }
@@ -293,7 +302,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
             if (t >= n_tasks || !eng->ok()) break;
             for (size_t w = tasks[t].first; w < tasks[t].second; ++w) {
                 std::string e3;
-                if (!decode_range(rd, work[w].first, work[w].second, flt, spans, &sink, &my_rec, &e3, o.count_del, frag)) { eng->fail(e3 + " (" + path + ")"); return; }
+                if (!decode_range(rd, work[w].first, work[w].second, flt, spans, &sink, &my_rec, &e3, o.count_del, frag, part.ptr())) { eng->fail(e3 + " (" + path + ")"); return; }
             }
         }
     };
@@ -310,7 +319,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
 }
 
 bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter &flt, const SpanIndex &spans,
-                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag)
+                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag, RecStats *rs)
 {
     if (!rd.seek(begin)) { *err = "seek failed"; return false; }
     AlnRec r;
@@ -320,6 +329,7 @@ bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter
         if (k == 0) break;
         if (k < 0) { *err = rd.error(); return false; }
         ++*n_rec;
+        if (rs) rs->add(r);
         if (!flt.pass(r)) continue;
         if (!spans.hit(r, frag)) continue;
         emit_runs(r, sink, count_del, frag);
@@ -348,6 +358,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
     FragRule frag; frag.on = o.frag; frag.max = o.frag_max;     // (for the units the host reader takes back)
     const auto t_enter = std::chrono::steady_clock::now();
     if (!api->decode_begin || !api->decode_acquire || !api->decode_submit || !api->decode_end || !api->decode_abort) return 0;
+    if (o.readstats && (!api->decode_record_stats || !api->set_param)) return 0;      // (an engine that does not count records: the host readers do)
     if (const char *e = tune("device_decode")) if (e[0] == '0') return 0;
     if (kind != 0 && !spans.synthetic) return 0;            // the no-index span cursor (PD:4608-4646) stays on the host
     const uint64_t F = file_size(path);
@@ -433,6 +444,10 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
     if (o.frag) {                                            // (the bound travels as a parameter: pd_decode_cfg keeps its layout)
         cfg.flags |= PD_DECODE_FRAGMENTS;
         if (!api->set_param || api->set_param(eng->ctx, "decode_frag_max", o.frag_max) != 0) return 0;      // (an engine without the mode: the host reader has it)
+    }
+    if (o.readstats) {                                       // (the bins travel as a parameter, like -fragmax)
+        cfg.flags |= PD_DECODE_RECORD_STATS;
+        if (api->set_param(eng->ctx, "decode_isize_bins", o.readstats) != 0) return 0;
     }
     { uint64_t b = 0; for (auto &v : batches) for (auto &r : v) b += ((r.vend == UINT64_MAX ? F : (r.vend >> 16)) - (r.vbeg >> 16)) + 65536; cfg.bytes_hint = std::min(b, 2 * F); }
     if (!spans.synthetic) {
@@ -743,6 +758,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
         std::sort(backlog.begin(), backlog.end());
         std::atomic<size_t> nb{0};
         auto host_worker = [&]() {
+            RecStatsPart part(eng);                          // (-readstats: the device did not count the units it handed back; the host reader that decodes them does)
             AlnReader rd; std::string e2;
             if (!rd.open(path, &e2)) { eng->fail(e2); return; }
             RunSink sink(eng);
@@ -750,7 +766,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
                 const size_t i = nb.fetch_add(1);
                 if (i >= backlog.size() || !eng->ok()) break;
                 uint64_t nr = 0;
-                if (!decode_range(rd, backlog[i].first, backlog[i].second, flt, spans, &sink, &nr, &e2, o.count_del, frag)) { eng->fail(e2 + " (" + path + ")"); break; }
+                if (!decode_range(rd, backlog[i].first, backlog[i].second, flt, spans, &sink, &nr, &e2, o.count_del, frag, part.ptr())) { eng->fail(e2 + " (" + path + ")"); break; }
                 n_host += nr;
             }
         };
@@ -764,6 +780,13 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
     const uint64_t t_e = now_us();
     if (!eng->ck(api->decode_end(eng->ctx), "pd_decode_end")) return -1;
     if (getenv("PANDEPTH_TIMING")) fprintf(stderr, "[timing]   pd_decode_end (concatenate the batches' runs) %.3f s\n", (now_us() - t_e) / 1e6);
+    if (o.readstats) {
+        // the session's record statistics (every unit the device counted; the backlog's records were added above)
+        RecStats dev; dev.init_like(eng->rs);
+        if (!eng->ck(api->decode_record_stats(eng->ctx, dev.sums.data(), dev.sums.size(), dev.per.data()), "pd_decode_record_stats")) return -1;
+        { std::lock_guard<std::mutex> lk(eng->rs_mu); eng->rs.merge(dev); }
+        if (getenv("PANDEPTH_TIMING")) fprintf(stderr, "[timing]   record statistics: %llu records counted on the device\n", (unsigned long long)dev.sums[RecStats::RECORDS]);
+    }
     return 1;
 }
 
@@ -779,7 +802,10 @@ bool read_sorted_stream(AlnReader *rd, const Options &o, const AlnHeader &main_h
     RunSink sink(eng);
     AlnRec r;
     int k;
+    bool over = false;                               // -readstats: every cursor has run off — the rest of the input is only counted
     while ((k = rd->next(&r)) > 0) {
+        if (eng->rs.on) eng->rs.add(r);
+        if (over) continue;
         if (r.tid < 0 || r.tid >= n) continue;       // the reference indexes EndChr[tid] here (UB for tid = -1)
         if (done[r.tid]) continue;
         if ((int)r.mapq < o.min_mapq) continue;
@@ -794,7 +820,10 @@ bool read_sorted_stream(AlnReader *rd, const Options &o, const AlnHeader &main_h
                 done[r.tid] = 1;
                 bool all = true;
                 for (int32_t i = 0; i < n; ++i) if (!done[i]) { all = false; break; }
-                if (all) break;                      // this read is NOT counted (PD:4641-4644)
+                if (all) {                           // this read is NOT counted (PD:4641-4644)
+                    if (!eng->rs.on) break;
+                    over = true; continue;           // (-readstats reads on to the end of the input)
+                }
             }
         }
         emit_runs(r, &sink, o.count_del, frag);      // counted even when the cursor just ran off the end
@@ -812,6 +841,7 @@ bool read_all(AlnReader *rd, const Options &o, const AlnHeader &main_hdr, const 
     AlnRec r;
     int k;
     while ((k = rd->next(&r)) > 0) {
+        if (eng->rs.on) eng->rs.add(r);
         if (!flt.pass(r)) continue;
         if (!rm.has(r.tid)) continue;                // depth on contigs without targets is never reported
         emit_runs(r, &sink, o.count_del, frag);
@@ -1673,6 +1703,7 @@ int create_contexts(Run &r)
             return 2;
         }
     r.eng = r.engs[0].get();
+    if (r.o.readstats) for (auto &e : r.engs) e->rs.init(r.o.flag_mask, r.o.min_mapq, r.o.readstats, (int32_t)r.hdr.names.size());
     r.OUT.set_parse(engine_parse(r.eng));        // the table's gzip stream: zlib's LZ77 parse on the engine (large -w tables)
     // whole-contig statistics straight from the runs when a sample ends up resident and deferred (pd_scan_reduce_windows)
     if (api->keep_deferred) for (auto &e : r.engs) api->keep_deferred(e->ctx, 1);
@@ -2071,6 +2102,19 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
                 std::cerr << "Error: -frag reads SAM and BAM only (the mate fields of " << (is_paf_path(fp) ? "PAF" : "CRAM") << " input are not available): " << fp << std::endl;
                 return 1;
             }
+    if (r.o.readstats)
+        // -readstats counts every record of every input once, which takes a run that reads the whole file: an index fetch of -g / -b targets reads
+        // only the targets' records; CRAM records come without their mate fields and PAF has neither flags nor pairs — refused per input, likewise
+        for (const std::string &fp : r.o.inputs) {
+            if (is_paf_path(fp) || CramReader::is_cram(fp)) {
+                std::cerr << "Error: -readstats reads SAM and BAM only (" << (is_paf_path(fp) ? "PAF has neither flags nor pairs" : "the mate fields of CRAM input are not available") << "): " << fp << std::endl;
+                return 1;
+            }
+            if (r.o.mode >= 1 && r.o.mode <= 4 && r.o.use_index && index_exists(fp)) {
+                std::cerr << "Error: -readstats with -g/-b needs -s (an index fetch reads only the targets' records): " << fp << std::endl;
+                return 1;
+            }
+        }
     r.paf = is_paf_path(r.o.input);                      // PD:3466-3479 / PD:3420-3432: the first input's extension decides
     plan_contexts(r, n_files);
     Comms comm(r);                                       // (goes before the contexts do)

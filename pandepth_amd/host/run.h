@@ -19,6 +19,7 @@
 #include "engine_api.h"
 #include "fasta.h"
 #include "options.h"
+#include "recstats.h"
 #include "regions.h"
 #include "report.h"
 
@@ -43,6 +44,7 @@ struct Engine {
     pd_ctx *ctx = nullptr;
     std::mutex err_mu;
     std::string err;
+    RecStats rs; std::mutex rs_mu;              // -readstats: the records of this context's inputs (threaded readers merge theirs under rs_mu)
     std::atomic<bool> cancel{false};            // the run is being abandoned: a writer working behind the statistics stops where it is
     void fail(const std::string &m) { std::lock_guard<std::mutex> lk(err_mu); if (err.empty()) err = m; }
     bool ok() { std::lock_guard<std::mutex> lk(err_mu); return err.empty(); }
@@ -129,7 +131,7 @@ inline std::vector<const GeneEntry *> genes_in_table_order(const std::map<std::s
     return order;
 }
 
-// extras.cpp — the outputs the reference does not have (-dist, -levels, -quantile, -thresholds, -gcbias), one entry each
+// extras.cpp — the outputs the reference does not have (-dist, -levels, -quantile, -thresholds, -gcbias, -readstats), one entry each
 struct Extra {
     const char *suffix;                          // <prefix><suffix>
     bool (*enabled)(const Options &o);
