@@ -422,7 +422,8 @@ int pd_synchronize(pd_ctx *ctx);
  * (a compact session that found other runs deferred) —, "decode_c8_grow" (times the compact sample's arrays grew and moved),
  * "decode_chain_device" / "decode_chain_host" (batches whose record chain the device / the host confirmed), "decode_segments_redone",
  * "decode_guess_units" (units submitted with PD_UNIT_GUESS), "decode_record_stats" (launches of k_record_stats that counted a batch: one per batch with counted records, 0 in a session
- * without PD_DECODE_RECORD_STATS; a launch that the chain kernel's verdict stopped at once is not among them — and, as *ms, their summed time where the batches are timed: PANDEPTH_TIMING). */
+ * without PD_DECODE_RECORD_STATS; a launch that the chain kernel's verdict stopped at once is not among them — and, as *ms, their summed time where the batches are timed: PANDEPTH_TIMING),
+ * "decode_row_counts" (the same for k_row_counts and PD_DECODE_ROW_COUNTS). */
 int pd_profile(pd_ctx *ctx, int enable);
 int pd_profile_get(pd_ctx *ctx, const char *name, double *ms, uint64_t *launches);
 
@@ -495,6 +496,7 @@ typedef struct pd_decode_cfg {
 #define PD_DECODE_DELETIONS 2u
 #define PD_DECODE_FRAGMENTS 4u
 #define PD_DECODE_RECORD_STATS 8u   /* the session also counts its RECORDS (the executable's -readstats): see pd_decode_record_stats below */
+#define PD_DECODE_ROW_COUNTS 16u    /* the session also counts its records per row of a table (the executable's -rowreads): see pd_decode_row_bins below */
 typedef struct pd_decode_unit { uint64_t start, stop, avail; uint32_t first_block, n_blocks, flags, pad; } pd_decode_unit;
 typedef struct pd_decode_batch {
     void *host_buf; size_t n_bytes;                              /* from pd_decode_acquire: whole BGZF members           */
@@ -558,6 +560,29 @@ int pd_decode_abort(pd_ctx *ctx);          /* forget the batches decoded since p
  * without the flag or a wrong n_sums.  pd_push_bgzf_units (pandepth_amd_dev.h) does not collect these statistics. */
 #define PD_RECSTAT_FIXED 275
 int pd_decode_record_stats(pd_ctx *ctx, uint64_t *sums, size_t n_sums, uint64_t *per_contig);
+
+/* ---- the records per ROW of a table, of a session opened with PD_DECODE_ROW_COUNTS (csrc/pd_rowcounts.h: k_row_counts, one more pass over
+ * every batch's confirmed record chain; it reads refID, pos, mapq and flag of a record and no CIGAR, and a session without the flag does not
+ * launch it).  A record STARTS AT cell (refID, pos) when 0 <= refID < n_ref and 0 <= pos < the contig's length; every other record starts
+ * nowhere and is in no bin.  Every record of every unit the device COUNTED (unit_status 0) that starts somewhere is counted in exactly one
+ * bin; the records of units that are handed back are the caller's to count.
+ * pd_decode_row_bins sets the bin table of the sessions BEGUN AFTER it (it is copied: the arrays need not outlive the call; an open session
+ * keeps the table it began with).  Bins are elementary intervals of the contigs:
+ *   w > 0 (edge_off and edges NULL)   bin = win_off[t] + pos / w, win_off = pd_window_layout(w); n_bins = win_off[n_contigs]
+ *   w == 0                            edge_off[t] .. edge_off[t + 1] index contig t's edges, strictly ascending; contig t with k edges has
+ *                                     k + 1 bins and a start at (t, pos) goes to bin edge_off[t] + t + j, j = the number of t's edges
+ *                                     <= pos; n_bins = edge_off[n_contigs] + n_contigs.  edge_off NULL: no edges, one bin per contig.
+ * PD_EINVAL with a message: w > 0 together with edges, an edge_off that does not begin at 0 or descends, edges of a contig that are not
+ * strictly ascending, more than 2^28 bins.  pd_decode_begin with the flag and no table fails with PD_EINVAL before anything of the context
+ * changes; it zeroes the session's bins.
+ * A bin is PD_ROWCOUNT_WORDS words, over the records that start in it (flag_mask / min_mapq: the session's):
+ *   [0] records  [1] passed: flag & flag_mask == 0  [2] mapq0: passed with mapq == 0  [3] kept: passed with mapq >= min_mapq — the FILTER's
+ *   verdict, as pd_decode_record_stats' —  [4] forward: kept with flag & 0x10 == 0  [5] the sum of the kept ones' mapq
+ * pd_decode_row_counts: valid after pd_decode_end until the next pd_decode_begin (pd_decode_abort clears the bins); PD_EINVAL with a
+ * message for a session without the flag or an n_bins that is not the table's.  pd_push_bgzf_units does not count rows. */
+#define PD_ROWCOUNT_WORDS 6
+int pd_decode_row_bins(pd_ctx *ctx, uint32_t w, const uint64_t *edge_off /* n_contigs + 1, or NULL */, const uint32_t *edges);
+int pd_decode_row_counts(pd_ctx *ctx, uint64_t *counts /* n_bins * PD_ROWCOUNT_WORDS */, size_t n_bins);
 
 #ifdef __cplusplus
 }

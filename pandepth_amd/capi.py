@@ -23,6 +23,8 @@ PD_DECODE_COMPACT = 1
 PD_DECODE_DELETIONS = 2
 PD_DECODE_FRAGMENTS = 4
 PD_DECODE_RECORD_STATS = 8
+PD_DECODE_ROW_COUNTS = 16
+PD_ROWCOUNT_WORDS = 6                    # pd_decode_row_counts: the words of a bin (include/pandepth_amd.h)
 PD_RECSTAT_FIXED = 275                   # pd_decode_record_stats: the sums before the insert bins (include/pandepth_amd.h)
 PD_NONE = 0xFFFFFFFFFFFFFFFF                     # pd_decode_result::first_start / next_start: no such record
 
@@ -159,6 +161,8 @@ def load():
         "pd_decode_end": (I, [P]),
         "pd_decode_abort": (I, [P]),
         "pd_decode_record_stats": (I, [P, ctypes.POINTER(U64), SZ, ctypes.POINTER(U64)]),
+        "pd_decode_row_bins": (I, [P, ctypes.c_uint32, ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_uint32)]),
+        "pd_decode_row_counts": (I, [P, ctypes.POINTER(U64), SZ]),
         "pd_x_bgzf_inflate": (I, [I, P, SZ, P, SZ, ctypes.POINTER(SZ), I, I, ctypes.POINTER(ctypes.c_double),
                               ctypes.POINTER(ctypes.c_uint32)]),
         "pd_stream": (P, [P]),
@@ -179,7 +183,7 @@ EXPORTS = ["pd_abi_version", "pd_create", "pd_destroy", "pd_strerror", "pd_reset
            "pd_push_intervals_device", "pd_runs_create", "pd_runs_destroy", "pd_push_runs", "pd_stage_acquire", "pd_stage_submit", "pd_set_param", "pd_keep_deferred", "pd_scan",
            "pd_reduce_intervals", "pd_window_layout", "pd_scan_reduce_windows", "pd_reduce_windows", "pd_scan_depth_histogram", "pd_depth_histogram", "pd_depth_levels", "pd_depth_quantiles", "pd_window_quantiles", "pd_depth_thresholds", "pd_window_thresholds", "pd_depth_gc_bias",
            "pd_read_depth", "pd_format_sites", "pd_deflate_parse", "pd_host_register", "pd_host_unregister", "pd_text_open", "pd_text_close", "pd_text_append_sites", "pd_text_parse", "pd_text_read", "pd_text_release", "pd_text_append_window_rows", "pd_text_append_bytes", "pd_device_buffer", "pd_device_count", "pd_accumulate_from", "pd_device_layout", "pd_export_i8", "pd_import_i8", "pd_export_i4",
-           "pd_slice_sweep_i4", "pd_gather_windows", "pd_push_bgzf_units", "pd_decode_begin", "pd_decode_acquire", "pd_decode_submit", "pd_decode_queue", "pd_decode_collect", "pd_decode_end", "pd_decode_abort", "pd_decode_record_stats", "pd_comm_unique_id", "pd_comm_init", "pd_comm_init_all", "pd_comm_init_local", "pd_comm_preinit", "pd_comm_prepare", "pd_comm_destroy",
+           "pd_slice_sweep_i4", "pd_gather_windows", "pd_push_bgzf_units", "pd_decode_begin", "pd_decode_acquire", "pd_decode_submit", "pd_decode_queue", "pd_decode_collect", "pd_decode_end", "pd_decode_abort", "pd_decode_record_stats", "pd_decode_row_bins", "pd_decode_row_counts", "pd_comm_unique_id", "pd_comm_init", "pd_comm_init_all", "pd_comm_init_local", "pd_comm_preinit", "pd_comm_prepare", "pd_comm_destroy",
            "pd_comm_strerror", "pd_sliced_window_sum", "pd_sliced_interval_sum", "pd_sliced_sum_start", "pd_sliced_sum_finish", "pd_x_bgzf_inflate", "pd_stream", "pd_synchronize", "pd_profile",
            "pd_profile_get", "pd_guard_check", "pd_guard_selftest", "pd_runs_pileup_tiles"]
 
@@ -657,13 +661,16 @@ class DecodeSession:
     def __init__(self, eng):
         self.e, self.L = eng, eng.L
         self.n_isize = 0                     # begin's record_stats (the insert bins of pd_decode_record_stats)
+        self.n_row_bins = 0                  # begin's row_counts (the bins of pd_decode_row_counts)
         self._keep = []                      # arrays the C side reads during a call (and, for begin, until it returns)
         self.held = []                       # buffers acquired and not yet handed to submit / queue
 
     def begin(self, flag_mask=1796, min_mapq=-1, contig_on=None, span_off=None, spans=None, sorted=1, bytes_hint=0, batch_bytes=0,
-              batches_in_flight=0, flags=0, n_batches=0, count_deletions=False, fragments=False, frag_max=0, record_stats=0):
+              batches_in_flight=0, flags=0, n_batches=0, count_deletions=False, fragments=False, frag_max=0, record_stats=0, row_counts=None):
         """record_stats=N (1 .. 65536) adds PD_DECODE_RECORD_STATS: the session also counts its records, with N insert bins (the parameter
         "decode_isize_bins"); record_stats() returns the numbers after end().
+        row_counts=("w", W) or ("edges", edge_off, edges) adds PD_DECODE_ROW_COUNTS: the session also counts its records per bin of that table
+        (pd_decode_row_bins, set here; edge_off None: no edges, one bin per contig); row_counts() returns the bins after end().
         count_deletions adds PD_DECODE_DELETIONS to `flags`: deletions count as covered, one run per group of M/=/X/D operations.
         fragments adds PD_DECODE_FRAGMENTS: a properly paired read with tlen > 0 is the one run [pos, pos + tlen), its mate none; frag_max
         bounds |tlen| (0: no bound).  The bound travels as the parameter "decode_frag_max", set here from the argument at every call."""
@@ -676,6 +683,9 @@ class DecodeSession:
         if record_stats:
             flags = int(flags) | PD_DECODE_RECORD_STATS
             self.e.set_param("decode_isize_bins", int(record_stats))
+        if row_counts is not None:
+            flags = int(flags) | PD_DECODE_ROW_COUNTS
+            self.n_row_bins = self.row_bins(*row_counts)
         cfg = pd_decode_cfg()
         cfg.flag_mask, cfg.min_mapq, cfg.sorted = int(flag_mask), int(min_mapq), int(sorted)
         cfg.bytes_hint, cfg.batch_bytes, cfg.batches_in_flight, cfg.flags, cfg.n_batches = int(bytes_hint), int(batch_bytes), int(batches_in_flight), int(flags), int(n_batches)
@@ -764,6 +774,31 @@ class DecodeSession:
         self.held = []
         self.e._ck(self.L.pd_decode_abort(self.e.h))
         self._keep = []
+
+    def row_bins(self, form, *table):
+        """pd_decode_row_bins: ("w", W) or ("edges", edge_off, edges) -> the number of bins of that table"""
+        U64P, U32P = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)
+        if form == "w":
+            w = int(table[0])
+            self.e._ck(self.L.pd_decode_row_bins(self.e.h, w, None, None))
+            return int(self.e.window_layout(w)[-1])
+        assert form == "edges", form
+        edge_off, edges = table
+        if edge_off is None:
+            self.e._ck(self.L.pd_decode_row_bins(self.e.h, 0, None, None))
+            return self.e.n_contigs
+        off = np.ascontiguousarray(edge_off, dtype=np.uint64)
+        ed = np.ascontiguousarray(edges, dtype=np.uint32)
+        assert off.size == self.e.n_contigs + 1
+        self.e._ck(self.L.pd_decode_row_bins(self.e.h, 0, off.ctypes.data_as(U64P), ed.ctypes.data_as(U32P) if ed.size else None))
+        return int(off[-1]) + self.e.n_contigs
+
+    def row_counts(self):
+        """pd_decode_row_counts -> uint64[n_bins, PD_ROWCOUNT_WORDS] (records, passed, mapq0, kept, forward, mapq_sum per bin) of the session
+        that end() closed; PdError for a session begun without row_counts="""
+        out = np.zeros((max(self.n_row_bins, 1), PD_ROWCOUNT_WORDS), dtype=np.uint64)
+        self.e._ck(self.L.pd_decode_row_counts(self.e.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), self.n_row_bins))
+        return out[:self.n_row_bins]
 
     def record_stats(self):
         """pd_decode_record_stats -> (sums: uint64[PD_RECSTAT_FIXED + N + 1], per_contig: uint64[n_contigs, 3]) of the session that

@@ -13,6 +13,7 @@
 #include "pd_inflate_wave.h"
 #include "pd_bamwalk.h"
 #include "pd_recstats.h"
+#include "pd_rowcounts.h"
 #include "pd_kernels.h"
 #include "../../include/pandepth_amd.h"
 #include "../../include/pandepth_amd_dev.h"
@@ -140,6 +141,19 @@ __global__ __launch_bounds__(64 * RS_WAVES) void k_record_stats(const pdb2::Cfg 
     pdrs::flush_hist(hist, words, sums, threadIdx.x, 64 * RS_WAVES);
 }
 
+// The records per row of the main table (pd_rowcounts.h; sessions with PD_DECODE_ROW_COUNTS only): behind pass 2, over the same confirmed lanes, RC_WAVES
+// segments per workgroup, a wave each.  No LDS: a lane's open bin lives in registers and leaves as global 64-bit atomics.  `gate` as in k_emit_segments; a
+// segment marked RS_SKIP belongs to a unit the host takes back and counts itself.
+enum { RC_WAVES = 4 };
+__global__ __launch_bounds__(64 * RC_WAVES) void k_row_counts(const pdb2::Cfg cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes, const pdrc::Bins bins,
+                                                              unsigned long long *counts, const pdb2::ChainOut *gate)
+{
+    if (gate && gate->slow) return;
+    const uint32_t j = blockIdx.x * RC_WAVES + (threadIdx.x >> 6);
+    if (j < n_seg && segs[j].pad2 != pdrs::RS_SKIP && segs[j].n_rec != 0)
+        pdrc::rows_segment<pdw::DevWave>(cfg, segs[j], lanes + (size_t)j * 64, bins, counts);
+}
+
 // are the first runs of a batch in (tid, begin) order?  out[0] = 1 if not; out[2..3] / out[4..5] = first / last key
 __global__ __launch_bounds__(256) void k_runs_sorted(const pd_iv *runs, uint64_t n, uint32_t *out)
 {
@@ -193,6 +207,12 @@ void launch_record_stats(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *
 {
     if (!n_seg) return;
     hipLaunchKernelGGL(k_record_stats, dim3((n_seg + RS_WAVES - 1) / RS_WAVES), dim3(64 * RS_WAVES), 0, st, cfg, segs, n_seg, lanes, n_bins, sums, per_contig, gate);
+}
+void launch_row_counts(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes, const pdrc::Bins &bins,
+                       unsigned long long *counts, const pdb2::ChainOut *gate)
+{
+    if (!n_seg) return;
+    hipLaunchKernelGGL(k_row_counts, dim3((n_seg + RC_WAVES - 1) / RC_WAVES), dim3(64 * RC_WAVES), 0, st, cfg, segs, n_seg, lanes, bins, counts, gate);
 }
 void launch_spoil_segments(hipStream_t st, const pdb2::Cfg &cfg, pdb2::Seg *segs, uint32_t n_seg, pdb2::LaneOut *lanes, uint32_t k)
 {

@@ -607,11 +607,12 @@ int pd_destroy(pd_ctx *c)
         if (sl.d_tok) (void)hipFree(sl.d_tok);
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : sl.ev_rs) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : sl.ev_rc) if (e) (void)hipEventDestroy(e);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
         if (sl.st) (void)hipStreamDestroy(sl.st);
     }
     for (auto &r : c->run_segs) r.release(c);
-    for (void *p : {(void *)c->d_contig_on, (void *)c->d_span_off, (void *)c->d_spans, (void *)c->run_first, (void *)c->run_other, (void *)c->run_far, (void *)c->arena, (void *)c->d_recstat}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->d_contig_on, (void *)c->d_span_off, (void *)c->d_spans, (void *)c->run_first, (void *)c->run_other, (void *)c->run_far, (void *)c->arena, (void *)c->d_recstat, (void *)c->d_rc_off, (void *)c->d_rc_edges, (void *)c->d_rowcnt}) if (p) (void)hipFree(p);
     runs_free(c->dec_runs);
     for (void *p : {(void *)c->c8.base, (void *)c->c8.b1}) if (p) (void)hipFree(p);
     t3 = dec_now_us();
@@ -1620,6 +1621,11 @@ int pd_profile_get(pd_ctx *c, const char *name, double *ms, uint64_t *launches)
         if (!strcmp(name, "decode_record_stats")) {                                             // k_record_stats: launches of the last session, and their time where its batches were timed
             if (ms) *ms = (double)c->rs_ns.load() / 1e6;
             if (launches) *launches = c->rs_launches.load();
+            return PD_OK;
+        }
+        if (!strcmp(name, "decode_row_counts")) {                                               // k_row_counts, likewise
+            if (ms) *ms = (double)c->rc_ns.load() / 1e6;
+            if (launches) *launches = c->rc_launches.load();
             return PD_OK;
         }
         if (hit) { if (ms) *ms = 0.0; if (launches) *launches = v; return PD_OK; }

@@ -191,6 +191,7 @@ struct pd_ctx {
         hipStream_t st = nullptr;
         hipEvent_t ev[6] = {};
         hipEvent_t ev_rs[2] = {};                                 // around k_record_stats (PD_DECODE_RECORD_STATS sessions that are timed; made on first need)
+        hipEvent_t ev_rc[2] = {};                                 // around k_row_counts (PD_DECODE_ROW_COUNTS sessions, likewise)
         hipEvent_t ev_done = nullptr;                             // recorded behind everything pd_decode_queue puts on the stream: what pd_decode_collect waits for
         uint8_t *h_blob = nullptr; size_t h_cap = 0;              // page-locked (pin_alloc)
         bool h_mapped = false;                                    // ... as huge pages of its own registered with the runtime (freed by pin_free)
@@ -202,6 +203,7 @@ struct pd_ctx {
         // a batch between pd_decode_queue and pd_decode_collect (pd_decode_submit: the two back to back)
         struct Job {
             bool open = false, queued = false, c8 = false, fast = false, owes_count = false, timed = false;
+            bool rc_timed = false;                                 // ev_rc were recorded for this batch
             bool segs_sent = false, rs_timed = false;              // the host's segments (bases, RS_SKIP marks) are on the device; ev_rs were recorded for this batch
             bool collecting = false;                               // some thread is inside dec_collect on this slot (set and tested under dec_mu): one ticket, one collect
             uint64_t order = 0; size_t n_bytes = 0; uint64_t inflated = 0; uint32_t n_seg = 0;
@@ -236,6 +238,13 @@ struct pd_ctx {
     uint32_t rs_bins = 0;                                         // ... into this
     unsigned long long *d_recstat = nullptr; size_t recstat_words = 0; bool rs_ready = false;
     std::atomic<uint64_t> rs_launches{0}, rs_ns{0};               // "decode_record_stats": launches of the session, and their summed time where the batches are timed
+    // PD_DECODE_ROW_COUNTS (pd_rowcounts.h): rb_* is the table pd_decode_row_bins left for the sessions begun after it (host copies); pd_decode_begin takes
+    // it to the device as the open session's (rc_*: offsets, edges, rc_nbins bins of PD_ROWCOUNT_WORDS words, zeroed), every batch's k_row_counts adds to
+    // d_rowcnt, pd_decode_row_counts reads it between pd_decode_end and the next pd_decode_begin
+    bool rb_set = false; uint32_t rb_w = 0; std::vector<uint64_t> rb_off; std::vector<uint32_t> rb_edges; uint64_t rb_nbins = 0;
+    uint32_t rc_w = 0; uint64_t rc_nbins = 0; uint64_t *d_rc_off = nullptr; uint32_t *d_rc_edges = nullptr; size_t rc_edges_cap = 0;
+    unsigned long long *d_rowcnt = nullptr; size_t rowcnt_words = 0; bool rc_ready = false;
+    std::atomic<uint64_t> rc_launches{0}, rc_ns{0};               // "decode_row_counts": launches of the session, and their summed time where the batches are timed
     pd_decode_cfg dec_cfg{}; uint8_t *d_contig_on = nullptr; uint32_t *d_span_off = nullptr; int32_t *d_spans = nullptr;
     std::vector<RunSeg> run_segs;
     pd_iv *run_first = nullptr, *run_other = nullptr, *run_far = nullptr;   // the concatenated sample (owned until the next reset)

@@ -5,6 +5,7 @@
 // short list of steps, and every step is a function of this file.
 #include "pd_ctx.h"
 #include "pd_recstats.h"
+#include "pd_rowcounts.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // GPU-side BAM decode in asynchronous batches (include/pandepth_amd.h: pd_decode_*)
@@ -256,6 +257,30 @@ int begin_record_stats(pd_ctx *c)
     return PD_OK;
 }
 
+// PD_DECODE_ROW_COUNTS: the table pd_decode_row_bins left becomes the session's — offsets and edges go up, the bins are zeroed (on c->stream,
+// which begin_filters waits for; the host copies stay for the next session)
+int begin_row_counts(pd_ctx *c)
+{
+    const size_t words = (size_t)c->rb_nbins * PD_ROWCOUNT_WORDS;
+    const auto oom = [&]() { (void)hipGetLastError(); return fail(c, PD_ENOMEM, "pd_decode_begin: allocation failed"); };
+    if (!c->d_rc_off && hipMalloc(&c->d_rc_off, ((size_t)c->n_contigs + 1) * 8 + 64) != hipSuccess) return oom();
+    if (c->rb_edges.size() > c->rc_edges_cap) {
+        if (c->d_rc_edges) { (void)hipFree(c->d_rc_edges); c->d_rc_edges = nullptr; c->rc_edges_cap = 0; }
+        if (hipMalloc(&c->d_rc_edges, c->rb_edges.size() * 4 + 64) != hipSuccess) return oom();
+        c->rc_edges_cap = c->rb_edges.size();
+    }
+    if (words != c->rowcnt_words) {
+        if (c->d_rowcnt) { (void)hipFree(c->d_rowcnt); c->d_rowcnt = nullptr; c->rowcnt_words = 0; }
+        if (hipMalloc(&c->d_rowcnt, words * 8 + 64) != hipSuccess) return oom();
+        c->rowcnt_words = words;
+    }
+    c->rc_w = c->rb_w; c->rc_nbins = c->rb_nbins;
+    HIPOK(c, hipMemcpyAsync(c->d_rc_off, c->rb_off.data(), c->rb_off.size() * 8, hipMemcpyHostToDevice, c->stream));
+    if (!c->rb_edges.empty()) HIPOK(c, hipMemcpyAsync(c->d_rc_edges, c->rb_edges.data(), c->rb_edges.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPOK(c, hipMemsetAsync(c->d_rowcnt, 0, words * 8, c->stream));
+    return PD_OK;
+}
+
 // A sorted file read for whole-contig statistics (PD_DECODE_COMPACT), its batches numbered 0 .. n_batches - 1: the batches' runs go
 // straight to their final places in a compact sample (C8Dec).  Sized from the compressed bytes
 // (>= 32 B of BGZF per record of a real file; denser files make it grow): a first run per record, a later run for every fourth.
@@ -385,10 +410,14 @@ int pd_decode_begin(pd_ctx *c, const pd_decode_cfg *cfg)
     struct BeginMarks { const uint64_t *t; ~BeginMarks() { if (getenv("PANDEPTH_TIMING") && t[5] - t[0] > 20000) fprintf(stderr, "[timing]   pd_decode_begin: tables %.3f s, marks + compose stream %.3f s, sample arrays %.3f s, arena %.3f s, buffers %.3f s\n", (t[1] - t[0]) / 1e6, (t[2] - t[1]) / 1e6, (t[3] - t[2]) / 1e6, (t[4] - t[3]) / 1e6, (t[5] - t[4]) / 1e6); } } begin_marks{tb};
     if ((cfg->flags & PD_DECODE_RECORD_STATS) && !c->dec_isize_bins)      // (refused before anything of the context changes)
         return fail(c, PD_EINVAL, "pd_decode_begin: PD_DECODE_RECORD_STATS needs pd_set_param(\"decode_isize_bins\", N) with 1 <= N <= 65536 first");
+    if ((cfg->flags & PD_DECODE_ROW_COUNTS) && !c->rb_set)
+        return fail(c, PD_EINVAL, "pd_decode_begin: PD_DECODE_ROW_COUNTS needs a bin table: call pd_decode_row_bins first");
     c->dec_cfg = *cfg;
     c->dec_frag_bound = c->dec_frag_max ? c->dec_frag_max : 0x7FFFFFFFu;      // ("decode_frag_max" as it stands now holds for the whole session; 0: no bound)
     c->rs_ready = false; c->rs_launches = 0; c->rs_ns = 0;
     if (cfg->flags & PD_DECODE_RECORD_STATS) if (int rc = begin_record_stats(c)) return rc;
+    c->rc_ready = false; c->rc_launches = 0; c->rc_ns = 0;
+    if (cfg->flags & PD_DECODE_ROW_COUNTS) if (int rc = begin_row_counts(c)) return rc;
     if (int rc = begin_filters(c, cfg)) return rc;
     tb[1] = tb[2] = tb[3] = dec_now_us();
     if (int rc = begin_compact(c, cfg, tb)) return rc;
@@ -586,6 +615,30 @@ void dec_record_stats_time(pd_ctx *c, DecSlot &sl)
     if (hipEventElapsedTime(&ms, sl.ev_rs[0], sl.ev_rs[1]) == hipSuccess) c->rs_ns += (uint64_t)((double)ms * 1e6);
 }
 
+// The records per row of the batch's counted segments (sessions with PD_DECODE_ROW_COUNTS), at the same two places and with the same gate as
+// dec_record_stats (and behind it, where a session carries both flags)
+int dec_row_counts(pd_ctx *c, DecSlot &sl, const pdb2::Seg *d_seg, const pdb2::ChainOut *gate)
+{
+    Job &J = sl.job;
+    if (J.timed) {
+        for (auto &e : sl.ev_rc) if (!e) HIPDEC(hipEventCreate(&e));
+        HIPDEC(hipEventRecord(sl.ev_rc[0], sl.st));
+    }
+    const pdrc::Bins bins{c->rc_w, c->d_rc_off, c->d_rc_edges, c->rc_nbins};
+    launch_row_counts(sl.st, J.cfg, d_seg, J.n_seg, (const pdb2::LaneOut *)sl.d[DS_LANE], bins, c->d_rowcnt, gate);
+    if (J.timed) { HIPDEC(hipEventRecord(sl.ev_rc[1], sl.st)); J.rc_timed = true; }
+    if (!gate) ++c->rc_launches;                                          // (a gated launch counts once its batch is known to be confirmed: dec_collect)
+    return PD_OK;
+}
+
+void dec_row_counts_time(pd_ctx *c, DecSlot &sl)
+{
+    if (!sl.job.rc_timed) return;
+    sl.job.rc_timed = false;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, sl.ev_rc[0], sl.ev_rc[1]) == hipSuccess) c->rc_ns += (uint64_t)((double)ms * 1e6);
+}
+
 // Inflate, pass 1 and — where the device confirms the record chain itself — the chain and the emission; otherwise the member statuses and
 // the segments come back for the host's chain check.  *t_inflate (PANDEPTH_DEVTRACE): when the inflate kernel had been launched.
 int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t *members, unsigned n_wg, uint64_t *t_inflate)
@@ -625,6 +678,7 @@ int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t 
         HIPDEC(hipMemcpyAsync(pin + J.o.co, d_co, sizeof(pdb2::ChainOut) + (size_t)n_seg * sizeof(pdb2::SegOut), hipMemcpyDeviceToHost, st));
         if (J.timed) HIPDEC(hipEventRecord(sl.ev[4], st));
         if (c->dec_cfg.flags & PD_DECODE_RECORD_STATS) if (int rc = dec_record_stats(c, sl, d_seg, d_co)) return rc;
+        if (c->dec_cfg.flags & PD_DECODE_ROW_COUNTS) if (int rc = dec_row_counts(c, sl, d_seg, d_co)) return rc;
     } else {
         HIPDEC(hipMemcpyAsync(pin + J.o.bst, sl.d[DS_ST], (size_t)bt->n_blocks * 4, hipMemcpyDeviceToHost, st));
         HIPDEC(hipMemcpyAsync(pin + J.o.seg, d_seg, (size_t)n_seg * sizeof(pdb2::Seg), hipMemcpyDeviceToHost, st));
@@ -636,7 +690,7 @@ int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t 
 int dec_queue(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt)
 {
     Job &J = sl.job;                                                  // (claimed by dec_slot_of: J.open is set)
-    J.queued = false; J.fast = false; J.timed = false; J.segs_sent = false; J.rs_timed = false; J.t_q0 = dec_now_us(); J.order = bt->order; J.n_bytes = bt->n_bytes; J.inflated = bt->inflated_bytes; J.n_seg = 0;
+    J.queued = false; J.fast = false; J.timed = false; J.segs_sent = false; J.rs_timed = false; J.rc_timed = false; J.t_q0 = dec_now_us(); J.order = bt->order; J.n_bytes = bt->n_bytes; J.inflated = bt->inflated_bytes; J.n_seg = 0;
     J.blocks.clear(); J.units.clear(); J.segs.clear(); J.seg0.clear();
     const bool c8 = J.c8 = c->c8.on;
     J.owes_count = c8 && bt->order < c->c8.n_batches;
@@ -890,12 +944,14 @@ int dec_collect(pd_ctx *c, DecSlot &sl, int32_t *unit_status, pd_decode_result *
     J.t_mark = dec_now_us();
     if (int rc = dec_wait(c, sl)) return rc;
     dec_record_stats_time(c, sl);
+    dec_row_counts_time(c, sl);
     if (J.fast) {
         pdb2::ChainOut co;
         memcpy(&co, pin + J.o.co, sizeof co);
         c->dec_n_redo += co.n_redo;
         if (!co.slow) {
             if (c->dec_cfg.flags & PD_DECODE_RECORD_STATS) ++c->rs_launches;      // (the gated k_record_stats of dec_launch counted this batch; one the gate stopped is not a launch of the counter)
+            if (c->dec_cfg.flags & PD_DECODE_ROW_COUNTS) ++c->rc_launches;        // (k_row_counts likewise)
             return collect_confirmed(c, sl, co, res);
         }
         // ---- out of the ordinary (ChainOut::slow says why; nothing was emitted): the member statuses and the segments as they stand come
@@ -924,7 +980,7 @@ int dec_collect(pd_ctx *c, DecSlot &sl, int32_t *unit_status, pd_decode_result *
         HIPDEC(hipMemcpyAsync(pin + J.o.ord, sl.d[DS_ONLY], 24, hipMemcpyDeviceToHost, st));
     }
     if (J.timed) HIPDEC(hipEventRecord(sl.ev[4], st));
-    if ((c->dec_cfg.flags & PD_DECODE_RECORD_STATS) && counted_records(J)) {
+    if ((c->dec_cfg.flags & (PD_DECODE_RECORD_STATS | PD_DECODE_ROW_COUNTS)) && counted_records(J)) {
         // the records of the counted units (the segments of the others carry RS_SKIP); the segments go up where the emission had none to send
         pdb2::Seg *d_seg = (pdb2::Seg *)((J.d_tab ? J.d_tab : (uint8_t *)sl.d[DS_BLK]) + J.o.seg);
         if (!J.segs_sent) {
@@ -932,11 +988,13 @@ int dec_collect(pd_ctx *c, DecSlot &sl, int32_t *unit_status, pd_decode_result *
             HIPDEC(hipMemcpyAsync(d_seg, pin + J.o.seg, (size_t)J.n_seg * sizeof(pdb2::Seg), hipMemcpyHostToDevice, st));
             J.segs_sent = true;
         }
-        if (int rc = dec_record_stats(c, sl, d_seg, nullptr)) return rc;
+        if (c->dec_cfg.flags & PD_DECODE_RECORD_STATS) if (int rc = dec_record_stats(c, sl, d_seg, nullptr)) return rc;
+        if (c->dec_cfg.flags & PD_DECODE_ROW_COUNTS) if (int rc = dec_row_counts(c, sl, d_seg, nullptr)) return rc;
     }
     HIPDEC(hipStreamSynchronize(st));
     HIPDEC(hipGetLastError());
     dec_record_stats_time(c, sl);
+    dec_row_counts_time(c, sl);
     if (nf && !J.c8) {
         memcpy(order_words, pin + J.o.ord, 24);
         rs.unsorted = order_words[0];
@@ -1226,6 +1284,7 @@ int pd_decode_end(pd_ctx *c)
     if (int rs = need_state(c, 0, "pd_decode_end")) return rs;
     HIPOK(c, hipSetDevice(c->device));
     for (auto &sl : c->dec) if (sl.st) HIPOK(c, hipStreamSynchronize(sl.st));      // (the last copies of the batches' runs to their arrays)
+    c->rc_ready = (c->dec_cfg.flags & PD_DECODE_ROW_COUNTS) != 0;                  // (... and every batch's k_row_counts: pd_decode_row_counts)
     c->rs_ready = (c->dec_cfg.flags & PD_DECODE_RECORD_STATS) != 0;                // (every batch's k_record_stats is through: pd_decode_record_stats)
     std::vector<RunSeg> segs;
     { std::lock_guard<std::mutex> l2(c->dec_mu); segs.swap(c->run_segs); }
@@ -1248,6 +1307,8 @@ int pd_decode_end(pd_ctx *c)
                 (unsigned long long)c->dec_n[pd_ctx::DN_END_SCATTER], (unsigned long long)c->dec_n[pd_ctx::DN_END_UNSORTED], (unsigned long long)c->dec_n[pd_ctx::DN_END_PEND]);
     if (getenv("PANDEPTH_TIMING") && c->rs_ready)                    // (the records' statistics pass: decode_record_stats)
         fprintf(stderr, "[timing]   k_record_stats: %llu launches, %.3f ms summed over the batches\n", (unsigned long long)c->rs_launches.load(), (double)c->rs_ns.load() / 1e6);
+    if (getenv("PANDEPTH_TIMING") && c->rc_ready)                    // (the rows' pass: decode_row_counts)
+        fprintf(stderr, "[timing]   k_row_counts: %llu launches, %.3f ms summed over the batches\n", (unsigned long long)c->rc_launches.load(), (double)c->rc_ns.load() / 1e6);
     return rc;
 }
 
@@ -1262,6 +1323,11 @@ int pd_decode_abort(pd_ctx *c)
     if (c->d_recstat && (c->dec_cfg.flags & PD_DECODE_RECORD_STATS)) {            // (the statistics of the batches that are forgotten)
         for (auto &sl : c->dec) if (sl.st) (void)hipStreamSynchronize(sl.st);
         (void)hipMemset(c->d_recstat, 0, c->recstat_words * 8);
+    }
+    c->rc_ready = false;
+    if (c->d_rowcnt && (c->dec_cfg.flags & PD_DECODE_ROW_COUNTS)) {               // (... and their rows)
+        for (auto &sl : c->dec) if (sl.st) (void)hipStreamSynchronize(sl.st);
+        (void)hipMemset(c->d_rowcnt, 0, c->rowcnt_words * 8);
     }
     return PD_OK;
 }
@@ -1278,6 +1344,53 @@ int pd_decode_record_stats(pd_ctx *c, uint64_t *sums, size_t n_sums, uint64_t *p
     HIPOK(c, hipSetDevice(c->device));
     HIPOK(c, hipMemcpy(sums, c->d_recstat, want * 8, hipMemcpyDeviceToHost));
     if (c->n_contigs) HIPOK(c, hipMemcpy(per_contig, c->d_recstat + want, 3 * (size_t)c->n_contigs * 8, hipMemcpyDeviceToHost));
+    return PD_OK;
+}
+
+int pd_decode_row_bins(pd_ctx *c, uint32_t w, const uint64_t *edge_off, const uint32_t *edges)
+{
+    if (!c) return PD_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const size_t n = (size_t)c->n_contigs;
+    const uint64_t max_bins = 1ull << 28;
+    std::vector<uint64_t> off(n + 1, 0);
+    std::vector<uint32_t> ed;
+    uint64_t n_bins;
+    if (w) {
+        if (edge_off || edges) return fail(c, PD_EINVAL, "pd_decode_row_bins: w > 0 (the window form) takes no edges");
+        if (int rc = pd_window_layout(c, w, off.data())) return fail(c, rc, "pd_decode_row_bins: pd_window_layout failed");
+        n_bins = off[n];
+    } else {
+        if (edge_off) {
+            if (edge_off[0] != 0) return fail(c, PD_EINVAL, "pd_decode_row_bins: edge_off must begin at 0");
+            for (size_t t = 0; t < n; ++t) {
+                if (edge_off[t + 1] < edge_off[t]) return fail(c, PD_EINVAL, "pd_decode_row_bins: edge_off must not descend");
+                if (edge_off[t + 1] > max_bins) return fail(c, PD_EINVAL, "pd_decode_row_bins: more than 2^28 bins");
+            }
+            if (edge_off[n] && !edges) return fail(c, PD_EINVAL, "pd_decode_row_bins: edge_off names edges, edges is NULL");
+            off.assign(edge_off, edge_off + n + 1);
+            for (size_t t = 0; t < n; ++t)
+                for (uint64_t k = off[t] + 1; k < off[t + 1]; ++k)
+                    if (edges[k] <= edges[k - 1]) return fail(c, PD_EINVAL, "pd_decode_row_bins: the edges of contig " + std::to_string(t) + " are not strictly ascending");
+            ed.assign(edges, edges + off[n]);
+        }
+        n_bins = off[n] + n;
+    }
+    if (n_bins > max_bins) return fail(c, PD_EINVAL, "pd_decode_row_bins: more than 2^28 bins");
+    c->rb_w = w; c->rb_off.swap(off); c->rb_edges.swap(ed); c->rb_nbins = n_bins; c->rb_set = true;
+    return PD_OK;
+}
+
+int pd_decode_row_counts(pd_ctx *c, uint64_t *counts, size_t n_bins)
+{
+    if (!c) return PD_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!(c->dec_cfg.flags & PD_DECODE_ROW_COUNTS) || !c->rc_ready || !c->d_rowcnt)
+        return fail(c, PD_EINVAL, "pd_decode_row_counts: no session with PD_DECODE_ROW_COUNTS has been ended by pd_decode_end since the last pd_decode_begin");
+    if (n_bins != c->rc_nbins || (!counts && n_bins))
+        return fail(c, PD_EINVAL, "pd_decode_row_counts: counts must hold PD_ROWCOUNT_WORDS words for each of the session's " + std::to_string(c->rc_nbins) + " bins");
+    HIPOK(c, hipSetDevice(c->device));
+    if (n_bins) HIPOK(c, hipMemcpy(counts, c->d_rowcnt, n_bins * PD_ROWCOUNT_WORDS * 8, hipMemcpyDeviceToHost));
     return PD_OK;
 }
 

@@ -237,6 +237,7 @@ void launch_site_rows(hipStream_t st, const uint32_t *depth, uint32_t first_inde
 
 // the record walk of the device decode path (pd_bamwalk.h)
 namespace pdb2 { struct Cfg; struct Seg; struct LaneOut; struct ChainOut; }
+namespace pdrc { struct Bins; }
 namespace pdk {
 void launch_walk_segments(hipStream_t st, const pdb2::Cfg &cfg, pdb2::Seg *segs, uint32_t n_seg, pdb2::LaneOut *lanes,
                           const uint32_t *only, uint32_t n_only);
@@ -249,5 +250,8 @@ void launch_runs_sorted(hipStream_t st, const pd_iv *runs, uint64_t n, uint32_t 
 // the records' statistics of a batch's counted segments (pd_recstats.h; k_record_stats), behind the emission: n_bins insert bins, the session's sums and contig triples
 void launch_record_stats(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes, uint32_t n_bins,
                          unsigned long long *sums, unsigned long long *per_contig, const pdb2::ChainOut *gate /* as launch_emit_segments' */);
+// the records per row of the main table (pd_rowcounts.h; k_row_counts), likewise: the session's bin table and its bins of PD_ROWCOUNT_WORDS words
+void launch_row_counts(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes, const pdrc::Bins &bins,
+                       unsigned long long *counts, const pdb2::ChainOut *gate /* as launch_emit_segments' */);
 }
 #endif

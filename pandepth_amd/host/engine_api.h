@@ -86,6 +86,9 @@ typedef struct pd_engine_api {
     int (*depth_gc_bias)(pd_ctx *, const pd_region *, size_t, uint32_t, const char *const *, const uint32_t *, uint64_t *, uint64_t *, uint64_t *);
     /* optional (NULL = the host readers take an input under -readstats): the records' statistics of a decode session, see pd_decode_record_stats */
     int (*decode_record_stats)(pd_ctx *, uint64_t *, size_t, uint64_t *);
+    /* optional, both or neither (NULL = the host readers take an input under -rowreads): the records per row of a decode session, see pd_decode_row_bins */
+    int (*decode_row_bins)(pd_ctx *, uint32_t, const uint64_t *, const uint32_t *);
+    int (*decode_row_counts)(pd_ctx *, uint64_t *, size_t);
 } pd_engine_api;
 
 /* Runs one `pandepth` invocation (argv as given to main) on the engine behind `api`. */

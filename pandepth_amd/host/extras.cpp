@@ -1,4 +1,4 @@
-// extras.cpp — the outputs the reference does not have: -dist, -levels, -quantile, -thresholds and -gcbias.  Each is made after the main table is
+// extras.cpp — the outputs the reference does not have: -dist, -levels, -quantile, -thresholds, -gcbias, -readstats and -rowreads.  Each is made after the main table is
 // written and the per-site job started, so that their path and timing stay as they are; each is one entry of EXTRAS, which the
 // finish step of every table family and the exit for a PAF without targets (pipeline.cpp) walk in order.
 #include <string.h>
@@ -10,12 +10,19 @@ namespace {
 
 const char DIST_HEADER[] = "#Chr\tDepth\tSites\tAtLeast\tAtLeast(%)\n";       // -dist's table
 
-// -quantile's table: the main table's identity columns under the main table's names, the row's cell count, one column per percentage
-std::string quantile_header(const Run &r)
+// the main table's identity columns under the main table's names (-quantile's, -rowreads')
+std::string identity_header(const Run &r)
 {
     std::string h = "#Chr";
     if (r.o.mode != 0) h += "\tStart\tEnd";
     if (!r.synthetic) h += r.o.mode == 3 ? "\tRegionID" : "\tGeneID";
+    return h;
+}
+
+// -quantile's table: the identity columns, the row's cell count, one column per percentage
+std::string quantile_header(const Run &r)
+{
+    std::string h = identity_header(r);
     h += "\tCells";
     for (uint32_t p : r.o.quantile) { h += "\tQ"; h += std::to_string(p); }
     h += '\n';
@@ -599,7 +606,105 @@ bool write_readstats(Run &r)
     return true;
 }
 
+// -rowreads: the records that START in every row of the main table, in <prefix>.rowreads.stat.gz — -quantile's rows and identity columns,
+// then Records Passed MapQ0 Kept Forward MeanMapQ (rowcounts.h).  The numbers are the contexts' accumulators over the run's bins
+// (Engine::rc, fed by the device's k_row_counts or by the host readers as every input was read): nothing is asked of the engine here.
+// A window row or a contig row is one bin; a -g / -b row is the sum over its entries (the multiset: overlapping entries of one id count
+// twice, as in Length / TotalDepth) of P[bin of `second`] - P[bin of `first - 1`], P = the prefix sums over the contig's bins.
+std::string rowreads_header(const Run &r) { return identity_header(r) + "\tRecords\tPassed\tMapQ0\tKept\tForward\tMeanMapQ\n"; }
+
+bool write_rowreads(Run &r)
+{
+    const Options &o = r.o;
+    const RowBins &B = r.row_bins;
+    const int W = RowCounts::WORDS;
+    // the contexts' bins summed into the first one's (no further copy: with a small -w on a large genome the array is hundreds of MB)
+    RowCounts &all = r.eng->rc;
+    for (auto &e : r.engs) if (e.get() != r.eng) { all.merge(e->rc); e->rc.cnt.assign(e->rc.cnt.size(), 0); }
+    QPlan q;
+    quantile_rows(r, o.mode == 5 || o.mode == 6, &q);
+    GzWriter G;
+    G.set_threads(o.threads);
+    const std::string path = r.prefix + ".rowreads.stat.gz";
+    if (!G.open(path)) { r.eng->fail("cannot open " + path); return false; }
+    std::string out = rowreads_header(r);
+    std::vector<uint64_t> P;                                     // the prefix sums of one contig's bins (-g / -b)
+    int32_t p_tid = -1;
+    for (size_t i = 0; i < q.rows.size(); ++i) {
+        const QRow &row = q.rows[i];
+        uint64_t k[RowCounts::WORDS] = {0, 0, 0, 0, 0, 0};
+        if (r.synthetic) {
+            const uint64_t bin = B.w ? row.qi : (uint64_t)row.tid;
+            for (int j = 0; j < W; ++j) k[j] = all.cnt[bin * W + (size_t)j];
+        } else {
+            const size_t t = (size_t)row.tid;
+            const uint64_t first_bin = B.off[t] + t, n_b = B.off[t + 1] - B.off[t] + 1;
+            if (row.tid != p_tid) {
+                p_tid = row.tid;
+                P.assign((size_t)(n_b + 1) * W, 0);
+                for (uint64_t b = 0; b < n_b; ++b) for (int j = 0; j < W; ++j) P[(b + 1) * W + (size_t)j] = P[b * W + (size_t)j] + all.cnt[(first_bin + b) * W + (size_t)j];
+            }
+            const int64_t len = (int64_t)B.lens[t];
+            for (uint64_t s = q.roff[i]; s < q.roff[i + 1]; ++s) {
+                const int64_t b0 = std::max<int64_t>((int64_t)q.segs[s].first - 1, 0), e0 = std::min<int64_t>(q.segs[s].second, len);
+                if (b0 >= e0) continue;
+                const uint64_t jb = B.bin_of(row.tid, (uint32_t)b0) - first_bin, je = B.bin_of(row.tid, (uint32_t)e0) - first_bin;
+                // (b0 and e0 are edges: bin jb begins at b0, bin je at e0, and P[j] is the sum of the bins before j)
+                for (int j = 0; j < W; ++j) k[j] += P[je * W + (size_t)j] - P[jb * W + (size_t)j];
+            }
+        }
+        out += r.hdr.names[(size_t)row.tid];
+        if (o.mode != 0) { out += '\t'; append_i64(&out, row.start); out += '\t'; append_i64(&out, row.end); }
+        if (row.id) { out += '\t'; out += *row.id; }
+        for (int j = 0; j < RowCounts::MAPQ_SUM; ++j) { out += '\t'; append_u64(&out, k[j]); }
+        out += '\t';
+        if (k[RowCounts::KEPT]) { char t[64]; snprintf(t, sizeof t, "%.2f", (double)k[RowCounts::MAPQ_SUM] / (double)k[RowCounts::KEPT]); out += t; } else out += "NA";
+        out += '\n';
+        if (out.size() > (1u << 22)) { G.write(out); out.clear(); }
+    }
+    G.write(out);
+    if (!G.close()) { ::remove(path.c_str()); r.eng->fail("cannot write " + path); return false; }
+    r.tm.mark("row read counts");
+    return true;
+}
+
 } // namespace
+
+// -rowreads: the run's bin table, from the rows the main table will have — the window form with -w, one bin per contig for whole
+// contigs, and with -g / -b every entry's `first - 1` and `second` clipped to its contig as edges, sorted and unique per contig
+void rowreads_bins(const Run &r, RowBins *b)
+{
+    const Options &o = r.o;
+    const size_t n = r.hdr.lens.size();
+    b->lens = r.hdr.lens;
+    b->off.assign(n + 1, 0);
+    b->edges.clear();
+    b->w = 0;
+    if (o.mode == 5 || o.mode == 6) {
+        b->w = (uint32_t)o.win;
+        r.api->window_layout(r.eng->ctx, b->w, b->off.data());
+        b->n_bins = b->off[n];
+        return;
+    }
+    if (!r.synthetic) {
+        std::vector<std::vector<uint32_t>> ed(n);
+        for (auto &kv : r.rm.genes) {
+            const int64_t len = (int64_t)r.hdr.lens[(size_t)kv.first];
+            for (auto &g : kv.second)
+                for (auto &c : g.second.cds) {
+                    const int64_t b0 = std::max<int64_t>((int64_t)c.first - 1, 0), e0 = std::min<int64_t>(c.second, len);
+                    if (b0 < e0) { ed[(size_t)kv.first].push_back((uint32_t)b0); ed[(size_t)kv.first].push_back((uint32_t)e0); }
+                }
+        }
+        for (size_t t = 0; t < n; ++t) {
+            std::sort(ed[t].begin(), ed[t].end());
+            ed[t].erase(std::unique(ed[t].begin(), ed[t].end()), ed[t].end());
+            b->edges.insert(b->edges.end(), ed[t].begin(), ed[t].end());
+            b->off[t + 1] = b->edges.size();
+        }
+    }
+    b->n_bins = b->off[n] + n;
+}
 
 const Extra EXTRAS[] = {
     {".dist.stat.gz", [](const Options &o) { return o.dist != 0; }, [](const Run &) { return std::string(DIST_HEADER); }, write_dist},
@@ -608,6 +713,7 @@ const Extra EXTRAS[] = {
     {".thresholds.stat.gz", [](const Options &o) { return !o.thresholds.empty(); }, thresholds_header, write_thresholds},
     {".gcbias.stat.gz", [](const Options &o) { return o.gcbias != 0; }, gcbias_empty, write_gcbias},
     {".reads.stat.gz", [](const Options &o) { return o.readstats != 0; }, readstats_empty, write_readstats},
+    {".rowreads.stat.gz", [](const Options &o) { return o.rowreads; }, rowreads_header, write_rowreads},
 };
 const size_t N_EXTRAS = sizeof(EXTRAS) / sizeof(EXTRAS[0]);
 

@@ -251,6 +251,10 @@ int parse_options(int argc, char **argv, Options *o)
             if (!good || x < 1 || x > 65536) { std::cerr << msg << std::endl; return 0; }
             o->readstats = (uint32_t)x;
         }
+        else if (flag == "rowreads") {                                           // not in the reference: the .rowreads.stat.gz record counts of the table's rows (README)
+            if (o->rowreads) { std::cerr << "Error: -rowreads takes no value and is given once" << std::endl; return 0; }
+            o->rowreads = true;
+        }
         else if (flag == "del") o->count_del = true;                            // not in the reference: deletions count as covered (README)
         else if (flag == "frag") o->frag = true;                                 // not in the reference: whole fragments of properly paired reads (README)
         else if (flag == "fragmax") {                                            // ... and the largest |tlen| that still makes a fragment

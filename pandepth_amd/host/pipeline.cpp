@@ -202,7 +202,7 @@ bool index_exists(const std::string &p) { return file_exists(p + ".bai") || file
 // ---- readers ---------------------------------------------------------------------------------
 // records that START in [begin, stop) of an open BAM, through the host decoder
 bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter &flt, const struct SpanIndex &spans,
-                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag, RecStats *rs);
+                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag, RecStats *rs, RowCountsShare *rc);
 
 struct DevRange;
 int read_bam_device(const std::string &path, const Options &o, const AlnHeader &main_hdr, const SpanIndex &spans, const RegionModel &rm,
@@ -293,6 +293,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
                        ~Tally() { n += mine; us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count(); } }
             tally{n_rec, busy_us, my_rec, w0};
         RecStatsPart part(eng);                              // (-readstats: this thread's records, merged when it is through — like the tally)
+        RowCountsShare rows(&eng->rc);                       // (-rowreads: this thread's records go into the context's bins, its open bin flushed when it is through)
         AlnReader rd;
         std::string e2;
         if (!rd.open(path, &e2)) { eng->fail(e2); return; }
@@ -302,7 +303,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
             if (t >= n_tasks || !eng->ok()) break;
             for (size_t w = tasks[t].first; w < tasks[t].second; ++w) {
                 std::string e3;
-                if (!decode_range(rd, work[w].first, work[w].second, flt, spans, &sink, &my_rec, &e3, o.count_del, frag, part.ptr())) { eng->fail(e3 + " (" + path + ")"); return; }
+                if (!decode_range(rd, work[w].first, work[w].second, flt, spans, &sink, &my_rec, &e3, o.count_del, frag, part.ptr(), rows.ptr())) { eng->fail(e3 + " (" + path + ")"); return; }
             }
         }
     };
@@ -319,7 +320,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
 }
 
 bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter &flt, const SpanIndex &spans,
-                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag, RecStats *rs)
+                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag, RecStats *rs, RowCountsShare *rc)
 {
     if (!rd.seek(begin)) { *err = "seek failed"; return false; }
     AlnRec r;
@@ -330,6 +331,7 @@ bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter
         if (k < 0) { *err = rd.error(); return false; }
         ++*n_rec;
         if (rs) rs->add(r);
+        if (rc) rc->add(r);
         if (!flt.pass(r)) continue;
         if (!spans.hit(r, frag)) continue;
         emit_runs(r, sink, count_del, frag);
@@ -359,6 +361,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
     const auto t_enter = std::chrono::steady_clock::now();
     if (!api->decode_begin || !api->decode_acquire || !api->decode_submit || !api->decode_end || !api->decode_abort) return 0;
     if (o.readstats && (!api->decode_record_stats || !api->set_param)) return 0;      // (an engine that does not count records: the host readers do)
+    if (o.rowreads && (!api->decode_row_bins || !api->decode_row_counts)) return 0;    // (... or not per row)
     if (const char *e = tune("device_decode")) if (e[0] == '0') return 0;
     if (kind != 0 && !spans.synthetic) return 0;            // the no-index span cursor (PD:4608-4646) stays on the host
     const uint64_t F = file_size(path);
@@ -448,6 +451,12 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
     if (o.readstats) {                                       // (the bins travel as a parameter, like -fragmax)
         cfg.flags |= PD_DECODE_RECORD_STATS;
         if (api->set_param(eng->ctx, "decode_isize_bins", o.readstats) != 0) return 0;
+    }
+    if (o.rowreads) {                                        // (the run's bin table; an engine that refuses it — more than 2^28 bins — leaves the input to the host readers)
+        const RowBins &rb = *eng->rc.tab;
+        const bool edged = !rb.w && !rb.edges.empty();
+        if (api->decode_row_bins(eng->ctx, rb.w, edged ? rb.off.data() : nullptr, edged ? rb.edges.data() : nullptr) != 0) return 0;
+        cfg.flags |= PD_DECODE_ROW_COUNTS;
     }
     { uint64_t b = 0; for (auto &v : batches) for (auto &r : v) b += ((r.vend == UINT64_MAX ? F : (r.vend >> 16)) - (r.vbeg >> 16)) + 65536; cfg.bytes_hint = std::min(b, 2 * F); }
     if (!spans.synthetic) {
@@ -759,6 +768,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
         std::atomic<size_t> nb{0};
         auto host_worker = [&]() {
             RecStatsPart part(eng);                          // (-readstats: the device did not count the units it handed back; the host reader that decodes them does)
+            RowCountsShare rows(&eng->rc);                   // (-rowreads likewise, into the context's bins)
             AlnReader rd; std::string e2;
             if (!rd.open(path, &e2)) { eng->fail(e2); return; }
             RunSink sink(eng);
@@ -766,7 +776,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
                 const size_t i = nb.fetch_add(1);
                 if (i >= backlog.size() || !eng->ok()) break;
                 uint64_t nr = 0;
-                if (!decode_range(rd, backlog[i].first, backlog[i].second, flt, spans, &sink, &nr, &e2, o.count_del, frag, part.ptr())) { eng->fail(e2 + " (" + path + ")"); break; }
+                if (!decode_range(rd, backlog[i].first, backlog[i].second, flt, spans, &sink, &nr, &e2, o.count_del, frag, part.ptr(), rows.ptr())) { eng->fail(e2 + " (" + path + ")"); break; }
                 n_host += nr;
             }
         };
@@ -787,6 +797,18 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
         { std::lock_guard<std::mutex> lk(eng->rs_mu); eng->rs.merge(dev); }
         if (getenv("PANDEPTH_TIMING")) fprintf(stderr, "[timing]   record statistics: %llu records counted on the device\n", (unsigned long long)dev.sums[RecStats::RECORDS]);
     }
+    if (o.rowreads) {
+        // the session's records per bin (every unit the device counted; the backlog's records were added above)
+        // (one transient copy of the bins: the engine writes whole arrays)
+        std::vector<uint64_t> dev(eng->rc.cnt.size());
+        if (!eng->ck(api->decode_row_counts(eng->ctx, dev.data(), (size_t)eng->rc.tab->n_bins), "pd_decode_row_counts")) return -1;
+        { std::lock_guard<std::mutex> lk(eng->rc_mu); eng->rc.add_device(dev.data()); }
+        if (getenv("PANDEPTH_TIMING")) {
+            uint64_t n = 0;
+            for (size_t i = 0; i < dev.size(); i += RowCounts::WORDS) n += dev[i];
+            fprintf(stderr, "[timing]   row counts: %llu records counted on the device in %llu bins\n", (unsigned long long)n, (unsigned long long)eng->rc.tab->n_bins);
+        }
+    }
     return 1;
 }
 
@@ -802,9 +824,10 @@ bool read_sorted_stream(AlnReader *rd, const Options &o, const AlnHeader &main_h
     RunSink sink(eng);
     AlnRec r;
     int k;
-    bool over = false;                               // -readstats: every cursor has run off — the rest of the input is only counted
+    bool over = false;                               // -readstats / -rowreads: every cursor has run off — the rest of the input is only counted
     while ((k = rd->next(&r)) > 0) {
         if (eng->rs.on) eng->rs.add(r);
+        if (eng->rc.on) eng->rc.add(r);
         if (over) continue;
         if (r.tid < 0 || r.tid >= n) continue;       // the reference indexes EndChr[tid] here (UB for tid = -1)
         if (done[r.tid]) continue;
@@ -821,8 +844,8 @@ bool read_sorted_stream(AlnReader *rd, const Options &o, const AlnHeader &main_h
                 bool all = true;
                 for (int32_t i = 0; i < n; ++i) if (!done[i]) { all = false; break; }
                 if (all) {                           // this read is NOT counted (PD:4641-4644)
-                    if (!eng->rs.on) break;
-                    over = true; continue;           // (-readstats reads on to the end of the input)
+                    if (!eng->rs.on && !eng->rc.on) break;
+                    over = true; continue;           // (-readstats / -rowreads read on to the end of the input)
                 }
             }
         }
@@ -842,6 +865,7 @@ bool read_all(AlnReader *rd, const Options &o, const AlnHeader &main_hdr, const 
     int k;
     while ((k = rd->next(&r)) > 0) {
         if (eng->rs.on) eng->rs.add(r);
+        if (eng->rc.on) eng->rc.add(r);
         if (!flt.pass(r)) continue;
         if (!rm.has(r.tid)) continue;                // depth on contigs without targets is never reported
         emit_runs(r, &sink, o.count_del, frag);
@@ -1704,6 +1728,10 @@ int create_contexts(Run &r)
         }
     r.eng = r.engs[0].get();
     if (r.o.readstats) for (auto &e : r.engs) e->rs.init(r.o.flag_mask, r.o.min_mapq, r.o.readstats, (int32_t)r.hdr.names.size());
+    if (r.o.rowreads) {
+        rowreads_bins(r, &r.row_bins);
+        for (auto &e : r.engs) e->rc.init(r.o.flag_mask, r.o.min_mapq, &r.row_bins);
+    }
     r.OUT.set_parse(engine_parse(r.eng));        // the table's gzip stream: zlib's LZ77 parse on the engine (large -w tables)
     // whole-contig statistics straight from the runs when a sample ends up resident and deferred (pd_scan_reduce_windows)
     if (api->keep_deferred) for (auto &e : r.engs) api->keep_deferred(e->ctx, 1);
@@ -2102,6 +2130,18 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
                 std::cerr << "Error: -frag reads SAM and BAM only (the mate fields of " << (is_paf_path(fp) ? "PAF" : "CRAM") << " input are not available): " << fp << std::endl;
                 return 1;
             }
+    if (r.o.rowreads)
+        // -rowreads counts every record of every input that starts in a row, which takes the same: a run that reads the whole file, and records with flags
+        for (const std::string &fp : r.o.inputs) {
+            if (is_paf_path(fp) || CramReader::is_cram(fp)) {
+                std::cerr << "Error: -rowreads reads SAM and BAM only (" << (is_paf_path(fp) ? "PAF has no flags" : "CRAM input is not counted") << "): " << fp << std::endl;
+                return 1;
+            }
+            if (r.o.mode >= 1 && r.o.mode <= 4 && r.o.use_index && index_exists(fp)) {
+                std::cerr << "Error: -rowreads with -g/-b needs -s (an index fetch reads only the targets' records): " << fp << std::endl;
+                return 1;
+            }
+        }
     if (r.o.readstats)
         // -readstats counts every record of every input once, which takes a run that reads the whole file: an index fetch of -g / -b targets reads
         // only the targets' records; CRAM records come without their mate fields and PAF has neither flags nor pairs — refused per input, likewise

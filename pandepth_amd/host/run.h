@@ -22,6 +22,7 @@
 #include "recstats.h"
 #include "regions.h"
 #include "report.h"
+#include "rowcounts.h"
 
 namespace pdh {
 
@@ -45,6 +46,7 @@ struct Engine {
     std::mutex err_mu;
     std::string err;
     RecStats rs; std::mutex rs_mu;              // -readstats: the records of this context's inputs (threaded readers merge theirs under rs_mu)
+    RowCounts rc; std::mutex rc_mu;             // -rowreads: the same per bin of the run's table (Run::row_bins)
     std::atomic<bool> cancel{false};            // the run is being abandoned: a writer working behind the statistics stops where it is
     void fail(const std::string &m) { std::lock_guard<std::mutex> lk(err_mu); if (err.empty()) err = m; }
     bool ok() { std::lock_guard<std::mutex> lk(err_mu); return err.empty(); }
@@ -71,6 +73,7 @@ struct Run {
     RefSeqs ref;                                 // -c -r: the GC(%) column (PD:3506-3538); host-side text work
     RegionModel rm;
     bool gc = false, synthetic = false;          // GC column wanted and loaded; whole-contig bins (modes 0/5/6)
+    RowBins row_bins;                            // -rowreads: the elementary intervals of the table's rows (rowreads_bins, before the first input is read)
     std::string prefix, header_line;             // output names' stem (PD:4057-4090); the main table's first line
     GzWriter OUT;                                // the main table
     std::vector<std::unique_ptr<Engine>> engs;
@@ -131,13 +134,14 @@ inline std::vector<const GeneEntry *> genes_in_table_order(const std::map<std::s
     return order;
 }
 
-// extras.cpp — the outputs the reference does not have (-dist, -levels, -quantile, -thresholds, -gcbias, -readstats), one entry each
+// extras.cpp — the outputs the reference does not have (-dist, -levels, -quantile, -thresholds, -gcbias, -readstats, -rowreads), one entry each
 struct Extra {
     const char *suffix;                          // <prefix><suffix>
     bool (*enabled)(const Options &o);
     std::string (*empty_text)(const Run &r);     // what the file holds when there are no targets at all
     bool (*write)(Run &r);                       // false: the engine holds the message
 };
+void rowreads_bins(const Run &r, RowBins *b);    // -rowreads: the bin table of this run's rows (needs the first context: pd_window_layout)
 extern const Extra EXTRAS[];
 extern const size_t N_EXTRAS;
 
