@@ -423,7 +423,7 @@ int pd_synchronize(pd_ctx *ctx);
  * "decode_chain_device" / "decode_chain_host" (batches whose record chain the device / the host confirmed), "decode_segments_redone",
  * "decode_guess_units" (units submitted with PD_UNIT_GUESS), "decode_record_stats" (launches of k_record_stats that counted a batch: one per batch with counted records, 0 in a session
  * without PD_DECODE_RECORD_STATS; a launch that the chain kernel's verdict stopped at once is not among them — and, as *ms, their summed time where the batches are timed: PANDEPTH_TIMING),
- * "decode_row_counts" (the same for k_row_counts and PD_DECODE_ROW_COUNTS). */
+ * "decode_row_counts" (the same for k_row_counts and PD_DECODE_ROW_COUNTS), "decode_aln_stats" (the same for k_aln_stats and PD_DECODE_ALN_STATS). */
 int pd_profile(pd_ctx *ctx, int enable);
 int pd_profile_get(pd_ctx *ctx, const char *name, double *ms, uint64_t *launches);
 
@@ -497,6 +497,7 @@ typedef struct pd_decode_cfg {
 #define PD_DECODE_FRAGMENTS 4u
 #define PD_DECODE_RECORD_STATS 8u   /* the session also counts its RECORDS (the executable's -readstats): see pd_decode_record_stats below */
 #define PD_DECODE_ROW_COUNTS 16u    /* the session also counts its records per row of a table (the executable's -rowreads): see pd_decode_row_bins below */
+#define PD_DECODE_ALN_STATS 32u     /* the session also sums its records' CIGAR operations and read lengths (the executable's -alnstats): see pd_decode_aln_stats below */
 typedef struct pd_decode_unit { uint64_t start, stop, avail; uint32_t first_block, n_blocks, flags, pad; } pd_decode_unit;
 typedef struct pd_decode_batch {
     void *host_buf; size_t n_bytes;                              /* from pd_decode_acquire: whole BGZF members           */
@@ -583,6 +584,49 @@ int pd_decode_record_stats(pd_ctx *ctx, uint64_t *sums, size_t n_sums, uint64_t 
 #define PD_ROWCOUNT_WORDS 6
 int pd_decode_row_bins(pd_ctx *ctx, uint32_t w, const uint64_t *edge_off /* n_contigs + 1, or NULL */, const uint32_t *edges);
 int pd_decode_row_counts(pd_ctx *ctx, uint64_t *counts /* n_bins * PD_ROWCOUNT_WORDS */, size_t n_bins);
+
+/* ---- the CIGAR operations and read lengths of a session opened with PD_DECODE_ALN_STATS (csrc/pd_alnstats.h: k_aln_stats, one more pass over
+ * every batch's confirmed record chain; the first record pass that reads CIGARs — a record of COOP_MIN operations or more is walked by its whole
+ * wave — and a session without the flag does not launch it).  Every record of every unit the device COUNTED (unit_status 0) is counted exactly
+ * once: a batch adds pd_decode_result::n_reads to sums[PD_ALNSTAT_RECORDS]; the records of units that are handed back are the caller's to
+ * count.  The width W of a length bin travels as pd_set_param("decode_len_bin_width", W), 1 <= W <= 65536, which pd_decode_begin reads (and
+ * requires) as it reads "decode_isize_bins"; this keeps pd_decode_cfg's layout.
+ * THE CIGAR of a record is its own operations, or htslib's CG-tag rule where it applies: the first operation is <l_seq>S, refID >= 0 and
+ * pos >= 0, and the record's FIRST CG tag is of type B,I or B,i, has at least n_cigar_op entries and lies inside the record.  An operation is a
+ * 32-bit word: code c = word & 0xf, length len = word >> 4; its class is c for c <= 8 (M I D N S H P = X), 9 ("other") for every code 9 .. 15.
+ * An ALIGNED record has 0 <= refID < n_ref, flag & flag_mask == 0, mapq >= min_mapq (pd_decode_record_stats' `kept`: contig_on, short contigs
+ * and the spans play no part), flag & 4 == 0 and at least one operation; a PRIMARY record is an aligned one with flag & 0x900 == 0.  Per
+ * aligned record, in 64-bit arithmetic: q = the lengths of M I S = X, h = those of H, L = q + h (the read's length), a = those of M I = X (the
+ * aligned query bases), r = those of M D N = X (the reference span); it is CLIPPED when it has an S or H of length > 0.
+ * sums (n_sums = PD_ALNSTAT_WORDS), all integers:
+ *   [PD_ALNSTAT_RECORDS] all records  [.._ALIGNED]  [.._PRIMARY]  [.._CLIPPED] aligned records that are clipped
+ *   [.._READ_MAX] the maximum of L over primary records (0: none)  [.._READ_BASES] the sum of L over primary records
+ *   [.._ALIGNED_BASES] the sum of a over aligned records  [.._REF_BASES] the sum of r over aligned records
+ *   [.._OPS + 2 k], [.._OPS + 2 k + 1], k = 0 .. 9: the operations of class k of aligned records, and the sum of their lengths
+ *   [.._INS + b], [.._DEL + b], b = 0 .. PD_ALNSTAT_INDEL_BINS: the I / the D operations of aligned records with min(len, PD_ALNSTAT_INDEL_BINS) == b
+ *   [.._AF + p], p = 0 .. 100: primary records with L > 0 and floor(100 a / L) == p
+ *   [.._RL + 2 b], [.._RL + 2 b + 1], b = 0 .. PD_ALNSTAT_LEN_BINS - 1: primary records with min(L / W, PD_ALNSTAT_LEN_BINS - 1) == b, and the sum of their L
+ *   [.._AL + 2 b], [.._AL + 2 b + 1]: the same over ALL aligned records, binned by a and summing a
+ * Valid after pd_decode_end until the next pd_decode_begin (pd_decode_abort clears the numbers); PD_EINVAL with a message for a session
+ * without the flag or a wrong n_sums.  pd_push_bgzf_units does not collect these statistics. */
+#define PD_ALNSTAT_LEN_BINS 8192
+#define PD_ALNSTAT_INDEL_BINS 256
+#define PD_ALNSTAT_RECORDS 0
+#define PD_ALNSTAT_ALIGNED 1
+#define PD_ALNSTAT_PRIMARY 2
+#define PD_ALNSTAT_CLIPPED 3
+#define PD_ALNSTAT_READ_MAX 4
+#define PD_ALNSTAT_READ_BASES 5
+#define PD_ALNSTAT_ALIGNED_BASES 6
+#define PD_ALNSTAT_REF_BASES 7
+#define PD_ALNSTAT_OPS 8
+#define PD_ALNSTAT_INS (PD_ALNSTAT_OPS + 20)
+#define PD_ALNSTAT_DEL (PD_ALNSTAT_INS + PD_ALNSTAT_INDEL_BINS + 1)
+#define PD_ALNSTAT_AF (PD_ALNSTAT_DEL + PD_ALNSTAT_INDEL_BINS + 1)
+#define PD_ALNSTAT_RL (PD_ALNSTAT_AF + 101)
+#define PD_ALNSTAT_AL (PD_ALNSTAT_RL + 2 * PD_ALNSTAT_LEN_BINS)
+#define PD_ALNSTAT_WORDS (PD_ALNSTAT_AL + 2 * PD_ALNSTAT_LEN_BINS)
+int pd_decode_aln_stats(pd_ctx *ctx, uint64_t *sums, size_t n_sums);
 
 #ifdef __cplusplus
 }

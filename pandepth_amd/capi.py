@@ -24,6 +24,8 @@ PD_DECODE_DELETIONS = 2
 PD_DECODE_FRAGMENTS = 4
 PD_DECODE_RECORD_STATS = 8
 PD_DECODE_ROW_COUNTS = 16
+PD_DECODE_ALN_STATS = 32
+PD_ALNSTAT_WORDS = 8 + 20 + 2 * 257 + 101 + 4 * 8192   # pd_decode_aln_stats: the sums (include/pandepth_amd.h)
 PD_ROWCOUNT_WORDS = 6                    # pd_decode_row_counts: the words of a bin (include/pandepth_amd.h)
 PD_RECSTAT_FIXED = 275                   # pd_decode_record_stats: the sums before the insert bins (include/pandepth_amd.h)
 PD_NONE = 0xFFFFFFFFFFFFFFFF                     # pd_decode_result::first_start / next_start: no such record
@@ -163,6 +165,7 @@ def load():
         "pd_decode_record_stats": (I, [P, ctypes.POINTER(U64), SZ, ctypes.POINTER(U64)]),
         "pd_decode_row_bins": (I, [P, ctypes.c_uint32, ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_uint32)]),
         "pd_decode_row_counts": (I, [P, ctypes.POINTER(U64), SZ]),
+        "pd_decode_aln_stats": (I, [P, ctypes.POINTER(U64), SZ]),
         "pd_x_bgzf_inflate": (I, [I, P, SZ, P, SZ, ctypes.POINTER(SZ), I, I, ctypes.POINTER(ctypes.c_double),
                               ctypes.POINTER(ctypes.c_uint32)]),
         "pd_stream": (P, [P]),
@@ -183,7 +186,7 @@ EXPORTS = ["pd_abi_version", "pd_create", "pd_destroy", "pd_strerror", "pd_reset
            "pd_push_intervals_device", "pd_runs_create", "pd_runs_destroy", "pd_push_runs", "pd_stage_acquire", "pd_stage_submit", "pd_set_param", "pd_keep_deferred", "pd_scan",
            "pd_reduce_intervals", "pd_window_layout", "pd_scan_reduce_windows", "pd_reduce_windows", "pd_scan_depth_histogram", "pd_depth_histogram", "pd_depth_levels", "pd_depth_quantiles", "pd_window_quantiles", "pd_depth_thresholds", "pd_window_thresholds", "pd_depth_gc_bias",
            "pd_read_depth", "pd_format_sites", "pd_deflate_parse", "pd_host_register", "pd_host_unregister", "pd_text_open", "pd_text_close", "pd_text_append_sites", "pd_text_parse", "pd_text_read", "pd_text_release", "pd_text_append_window_rows", "pd_text_append_bytes", "pd_device_buffer", "pd_device_count", "pd_accumulate_from", "pd_device_layout", "pd_export_i8", "pd_import_i8", "pd_export_i4",
-           "pd_slice_sweep_i4", "pd_gather_windows", "pd_push_bgzf_units", "pd_decode_begin", "pd_decode_acquire", "pd_decode_submit", "pd_decode_queue", "pd_decode_collect", "pd_decode_end", "pd_decode_abort", "pd_decode_record_stats", "pd_decode_row_bins", "pd_decode_row_counts", "pd_comm_unique_id", "pd_comm_init", "pd_comm_init_all", "pd_comm_init_local", "pd_comm_preinit", "pd_comm_prepare", "pd_comm_destroy",
+           "pd_slice_sweep_i4", "pd_gather_windows", "pd_push_bgzf_units", "pd_decode_begin", "pd_decode_acquire", "pd_decode_submit", "pd_decode_queue", "pd_decode_collect", "pd_decode_end", "pd_decode_abort", "pd_decode_record_stats", "pd_decode_row_bins", "pd_decode_row_counts", "pd_decode_aln_stats", "pd_comm_unique_id", "pd_comm_init", "pd_comm_init_all", "pd_comm_init_local", "pd_comm_preinit", "pd_comm_prepare", "pd_comm_destroy",
            "pd_comm_strerror", "pd_sliced_window_sum", "pd_sliced_interval_sum", "pd_sliced_sum_start", "pd_sliced_sum_finish", "pd_x_bgzf_inflate", "pd_stream", "pd_synchronize", "pd_profile",
            "pd_profile_get", "pd_guard_check", "pd_guard_selftest", "pd_runs_pileup_tiles"]
 
@@ -666,11 +669,13 @@ class DecodeSession:
         self.held = []                       # buffers acquired and not yet handed to submit / queue
 
     def begin(self, flag_mask=1796, min_mapq=-1, contig_on=None, span_off=None, spans=None, sorted=1, bytes_hint=0, batch_bytes=0,
-              batches_in_flight=0, flags=0, n_batches=0, count_deletions=False, fragments=False, frag_max=0, record_stats=0, row_counts=None):
+              batches_in_flight=0, flags=0, n_batches=0, count_deletions=False, fragments=False, frag_max=0, record_stats=0, row_counts=None, aln_stats=0):
         """record_stats=N (1 .. 65536) adds PD_DECODE_RECORD_STATS: the session also counts its records, with N insert bins (the parameter
         "decode_isize_bins"); record_stats() returns the numbers after end().
         row_counts=("w", W) or ("edges", edge_off, edges) adds PD_DECODE_ROW_COUNTS: the session also counts its records per bin of that table
         (pd_decode_row_bins, set here; edge_off None: no edges, one bin per contig); row_counts() returns the bins after end().
+        aln_stats=W (1 .. 65536) adds PD_DECODE_ALN_STATS: the session also sums its records' CIGAR operations and read lengths, in length bins
+        of W bases (the parameter "decode_len_bin_width"); aln_stats() returns the numbers after end().
         count_deletions adds PD_DECODE_DELETIONS to `flags`: deletions count as covered, one run per group of M/=/X/D operations.
         fragments adds PD_DECODE_FRAGMENTS: a properly paired read with tlen > 0 is the one run [pos, pos + tlen), its mate none; frag_max
         bounds |tlen| (0: no bound).  The bound travels as the parameter "decode_frag_max", set here from the argument at every call."""
@@ -683,6 +688,9 @@ class DecodeSession:
         if record_stats:
             flags = int(flags) | PD_DECODE_RECORD_STATS
             self.e.set_param("decode_isize_bins", int(record_stats))
+        if aln_stats:
+            flags = int(flags) | PD_DECODE_ALN_STATS
+            self.e.set_param("decode_len_bin_width", int(aln_stats))
         if row_counts is not None:
             flags = int(flags) | PD_DECODE_ROW_COUNTS
             self.n_row_bins = self.row_bins(*row_counts)
@@ -799,6 +807,12 @@ class DecodeSession:
         out = np.zeros((max(self.n_row_bins, 1), PD_ROWCOUNT_WORDS), dtype=np.uint64)
         self.e._ck(self.L.pd_decode_row_counts(self.e.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), self.n_row_bins))
         return out[:self.n_row_bins]
+
+    def aln_stats(self):
+        """pd_decode_aln_stats -> uint64[PD_ALNSTAT_WORDS] of the session that end() closed; PdError for a session begun without aln_stats=W"""
+        sums = np.zeros(PD_ALNSTAT_WORDS, dtype=np.uint64)
+        self.e._ck(self.L.pd_decode_aln_stats(self.e.h, sums.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), sums.size))
+        return sums
 
     def record_stats(self):
         """pd_decode_record_stats -> (sums: uint64[PD_RECSTAT_FIXED + N + 1], per_contig: uint64[n_contigs, 3]) of the session that

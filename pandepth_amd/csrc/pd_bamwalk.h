@@ -135,6 +135,41 @@ PW_FN bool plausible(const Cfg &c, uint64_t p, int depth)
     return true;
 }
 
+// The tag search of htslib's CG rule (open_record below, and pd_alnstats.h): the record at p (block size bs, all of its bytes present) has a
+// first operation <l_seq>S on a placed read — the caller has seen to that.  Its FIRST CG tag decides: of type B,I or B,i, with at least
+// n_cig entries that lie inside the record, the tag's operations become the CIGAR (cig, n_cig); anything else keeps the placeholder.
+PW_FN void cg_tag_cigar(const uint8_t *buf, uint64_t p, uint32_t bs, uint32_t l_name, uint32_t l_seq, const uint8_t *&cig, uint32_t &n_cig)
+{
+    const uint64_t end = p + 4 + (uint64_t)bs;
+    uint64_t a = p + 36 + l_name + 4ull * n_cig + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq;
+    if (a > end) a = end;
+    while (a + 3 <= end) {
+        const uint8_t t0 = buf[a], t1 = buf[a + 1], ty = buf[a + 2];
+        a += 3;
+        uint64_t sz = 0;
+        if (ty == 'A' || ty == 'c' || ty == 'C') sz = 1;
+        else if (ty == 's' || ty == 'S') sz = 2;
+        else if (ty == 'i' || ty == 'I' || ty == 'f') sz = 4;
+        else if (ty == 'Z' || ty == 'H') {
+            uint64_t z = a;
+            while (z < end && buf[z] != 0) ++z;
+            if (z >= end) break;
+            sz = z - a + 1;
+        } else if (ty == 'B') {
+            if (a + 5 > end) break;
+            const uint8_t st = buf[a];
+            const uint32_t cnt = rd32(buf + a + 1);
+            const uint64_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
+            if (t0 == 'C' && t1 == 'G') {
+                if ((st == 'I' || st == 'i') && cnt >= n_cig && cnt < (1u << 29) && a + 5 + 4ull * cnt <= end) { cig = buf + a + 5; n_cig = cnt; }
+                break;
+            }
+            sz = 5 + es * cnt;
+        } else break;
+        a += sz;
+    }
+}
+
 enum { FR_NONE = 0, FR_CARRY = 1, FR_SILENT = 2 };                     // Rec::frag: not a fragment read / tlen > 0: the run [pos, fend) / tlen < 0: nothing
 struct Rec { int32_t tid, pos; uint32_t keep, n_cig; const uint8_t *cig; uint32_t flags, unmapped; uint32_t frag; int32_t fend; };
 
@@ -165,36 +200,8 @@ PW_FN Rec open_record(const Cfg &c, uint64_t p, uint32_t bs)
     // lie inside the record — then the tag's operations are the CIGAR; without such a tag the placeholder is kept.  Until round 6 the
     // lane flagged the record (WF_HOST) and the whole unit went to the host reader: every batch of a long-read file.  The record's
     // bytes all lie below c.avail (the caller has checked p + 4 + bs), so the lane may walk its tags here; one record in a hundred.
-    else if (x.n_cig >= 1 && x.tid >= 0 && x.pos >= 0 && (rd32(x.cig) & 0xf) == 4 && (rd32(x.cig) >> 4) == l_seq && x.keep && !(FRAG && x.frag)) {
-        const uint64_t end = p + 4 + (uint64_t)bs;
-        uint64_t a = p + 36 + l_name + 4ull * x.n_cig + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq;
-        if (a > end) a = end;
-        while (a + 3 <= end) {
-            const uint8_t t0 = c.buf[a], t1 = c.buf[a + 1], ty = c.buf[a + 2];
-            a += 3;
-            uint64_t sz = 0;
-            if (ty == 'A' || ty == 'c' || ty == 'C') sz = 1;
-            else if (ty == 's' || ty == 'S') sz = 2;
-            else if (ty == 'i' || ty == 'I' || ty == 'f') sz = 4;
-            else if (ty == 'Z' || ty == 'H') {
-                uint64_t z = a;
-                while (z < end && c.buf[z] != 0) ++z;
-                if (z >= end) break;
-                sz = z - a + 1;
-            } else if (ty == 'B') {
-                if (a + 5 > end) break;
-                const uint8_t st = c.buf[a];
-                const uint32_t cnt = rd32(c.buf + a + 1);
-                const uint64_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
-                if (t0 == 'C' && t1 == 'G') {
-                    if ((st == 'I' || st == 'i') && cnt >= x.n_cig && cnt < (1u << 29) && a + 5 + 4ull * cnt <= end) { x.cig = c.buf + a + 5; x.n_cig = cnt; }
-                    break;
-                }
-                sz = 5 + es * cnt;
-            } else break;
-            a += sz;
-        }
-    }
+    else if (x.n_cig >= 1 && x.tid >= 0 && x.pos >= 0 && (rd32(x.cig) & 0xf) == 4 && (rd32(x.cig) >> 4) == l_seq && x.keep && !(FRAG && x.frag))
+        cg_tag_cigar(c.buf, p, bs, l_name, l_seq, x.cig, x.n_cig);
     return x;
 }
 

@@ -14,6 +14,7 @@
 #include "pd_bamwalk.h"
 #include "pd_recstats.h"
 #include "pd_rowcounts.h"
+#include "pd_alnstats.h"
 #include "pd_kernels.h"
 #include "../../include/pandepth_amd.h"
 #include "../../include/pandepth_amd_dev.h"
@@ -154,6 +155,26 @@ __global__ __launch_bounds__(64 * RC_WAVES) void k_row_counts(const pdb2::Cfg cf
         pdrc::rows_segment<pdw::DevWave>(cfg, segs[j], lanes + (size_t)j * 64, bins, counts);
 }
 
+// The CIGAR operations and read lengths (pd_alnstats.h; sessions with PD_DECODE_ALN_STATS only): behind pass 2, over the same confirmed lanes.  AS_WAVES
+// segments per workgroup, a wave each — a record of COOP_MIN operations or more is walked by its whole wave — share one LDS copy of the fixed words, the
+// indel and aligned-fraction bins and the low length bins, as 64-bit words: 21.5 KiB, flushed once for four segments.  `gate` as in k_emit_segments; a
+// segment marked AS_SKIP belongs to a unit the host takes back and counts itself.
+enum { AS_WAVES = 4 };
+static_assert((int)pdas::AS_SKIP == (int)pdrs::RS_SKIP, "one mark in Seg::pad2 for every record pass");
+__global__ __launch_bounds__(64 * AS_WAVES) void k_aln_stats(const pdb2::Cfg cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes, uint32_t width,
+                                                             unsigned long long *sums, const pdb2::ChainOut *gate)
+{
+    __shared__ unsigned long long hist[pdas::AS_LDS_WORDS];
+    if (gate && gate->slow) return;
+    for (uint32_t i = threadIdx.x; i < (uint32_t)pdas::AS_LDS_WORDS; i += 64 * AS_WAVES) hist[i] = 0;
+    __syncthreads();
+    const uint32_t j = blockIdx.x * AS_WAVES + (threadIdx.x >> 6);
+    if (j < n_seg && segs[j].pad2 != pdas::AS_SKIP && segs[j].n_rec != 0)
+        pdas::stats_segment<pdw::DevWave>(cfg, segs[j], lanes + (size_t)j * 64, width, sums, hist);
+    __syncthreads();
+    pdas::flush_hist(hist, sums, threadIdx.x, 64 * AS_WAVES);
+}
+
 // are the first runs of a batch in (tid, begin) order?  out[0] = 1 if not; out[2..3] / out[4..5] = first / last key
 __global__ __launch_bounds__(256) void k_runs_sorted(const pd_iv *runs, uint64_t n, uint32_t *out)
 {
@@ -213,6 +234,12 @@ void launch_row_counts(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *se
 {
     if (!n_seg) return;
     hipLaunchKernelGGL(k_row_counts, dim3((n_seg + RC_WAVES - 1) / RC_WAVES), dim3(64 * RC_WAVES), 0, st, cfg, segs, n_seg, lanes, bins, counts, gate);
+}
+void launch_aln_stats(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes, uint32_t width,
+                      unsigned long long *sums, const pdb2::ChainOut *gate)
+{
+    if (!n_seg) return;
+    hipLaunchKernelGGL(k_aln_stats, dim3((n_seg + AS_WAVES - 1) / AS_WAVES), dim3(64 * AS_WAVES), 0, st, cfg, segs, n_seg, lanes, width, sums, gate);
 }
 void launch_spoil_segments(hipStream_t st, const pdb2::Cfg &cfg, pdb2::Seg *segs, uint32_t n_seg, pdb2::LaneOut *lanes, uint32_t k)
 {

@@ -608,11 +608,12 @@ int pd_destroy(pd_ctx *c)
         for (hipEvent_t e : sl.ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : sl.ev_rs) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : sl.ev_rc) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : sl.ev_as) if (e) (void)hipEventDestroy(e);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
         if (sl.st) (void)hipStreamDestroy(sl.st);
     }
     for (auto &r : c->run_segs) r.release(c);
-    for (void *p : {(void *)c->d_contig_on, (void *)c->d_span_off, (void *)c->d_spans, (void *)c->run_first, (void *)c->run_other, (void *)c->run_far, (void *)c->arena, (void *)c->d_recstat, (void *)c->d_rc_off, (void *)c->d_rc_edges, (void *)c->d_rowcnt}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->d_contig_on, (void *)c->d_span_off, (void *)c->d_spans, (void *)c->run_first, (void *)c->run_other, (void *)c->run_far, (void *)c->arena, (void *)c->d_recstat, (void *)c->d_rc_off, (void *)c->d_rc_edges, (void *)c->d_rowcnt, (void *)c->d_alnstat}) if (p) (void)hipFree(p);
     runs_free(c->dec_runs);
     for (void *p : {(void *)c->c8.base, (void *)c->c8.b1}) if (p) (void)hipFree(p);
     t3 = dec_now_us();
@@ -705,6 +706,7 @@ int pd_set_param(pd_ctx *c, const char *name, uint64_t value)
     if (!strcmp(name, "decode_deletions")) { c->dec_deletions = value != 0; return PD_OK; }
     if (!strcmp(name, "decode_fragments")) { c->dec_fragments = value != 0; return PD_OK; }
     if (!strcmp(name, "decode_frag_max")) { if (value > 0x7FFFFFFFull) return fail(c, PD_EINVAL, "decode_frag_max must be below 2^31 (0: no bound)"); c->dec_frag_max = (uint32_t)value; return PD_OK; }
+    if (!strcmp(name, "decode_len_bin_width")) { if (value < 1 || value > 65536) return fail(c, PD_EINVAL, "decode_len_bin_width must be in 1 .. 65536"); c->dec_len_bin_width = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "decode_isize_bins")) { if (value < 1 || value > 65536) return fail(c, PD_EINVAL, "decode_isize_bins must be in 1 .. 65536"); c->dec_isize_bins = (uint32_t)value; return PD_OK; }
     if (!strcmp(name, "decode_near_span")) { c->dec_near_span = value > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)value; return PD_OK; }
     return fail(c, PD_EINVAL, std::string("unknown parameter ") + name);
@@ -1626,6 +1628,11 @@ int pd_profile_get(pd_ctx *c, const char *name, double *ms, uint64_t *launches)
         if (!strcmp(name, "decode_row_counts")) {                                               // k_row_counts, likewise
             if (ms) *ms = (double)c->rc_ns.load() / 1e6;
             if (launches) *launches = c->rc_launches.load();
+            return PD_OK;
+        }
+        if (!strcmp(name, "decode_aln_stats")) {                                                // k_aln_stats, likewise
+            if (ms) *ms = (double)c->as_ns.load() / 1e6;
+            if (launches) *launches = c->as_launches.load();
             return PD_OK;
         }
         if (hit) { if (ms) *ms = 0.0; if (launches) *launches = v; return PD_OK; }

@@ -192,6 +192,7 @@ struct pd_ctx {
         hipEvent_t ev[6] = {};
         hipEvent_t ev_rs[2] = {};                                 // around k_record_stats (PD_DECODE_RECORD_STATS sessions that are timed; made on first need)
         hipEvent_t ev_rc[2] = {};                                 // around k_row_counts (PD_DECODE_ROW_COUNTS sessions, likewise)
+        hipEvent_t ev_as[2] = {};                                 // around k_aln_stats (PD_DECODE_ALN_STATS sessions, likewise)
         hipEvent_t ev_done = nullptr;                             // recorded behind everything pd_decode_queue puts on the stream: what pd_decode_collect waits for
         uint8_t *h_blob = nullptr; size_t h_cap = 0;              // page-locked (pin_alloc)
         bool h_mapped = false;                                    // ... as huge pages of its own registered with the runtime (freed by pin_free)
@@ -204,6 +205,7 @@ struct pd_ctx {
         struct Job {
             bool open = false, queued = false, c8 = false, fast = false, owes_count = false, timed = false;
             bool rc_timed = false;                                 // ev_rc were recorded for this batch
+            bool as_timed = false;                                 // ev_as were recorded for this batch
             bool segs_sent = false, rs_timed = false;              // the host's segments (bases, RS_SKIP marks) are on the device; ev_rs were recorded for this batch
             bool collecting = false;                               // some thread is inside dec_collect on this slot (set and tested under dec_mu): one ticket, one collect
             uint64_t order = 0; size_t n_bytes = 0; uint64_t inflated = 0; uint32_t n_seg = 0;
@@ -245,6 +247,12 @@ struct pd_ctx {
     uint32_t rc_w = 0; uint64_t rc_nbins = 0; uint64_t *d_rc_off = nullptr; uint32_t *d_rc_edges = nullptr; size_t rc_edges_cap = 0;
     unsigned long long *d_rowcnt = nullptr; size_t rowcnt_words = 0; bool rc_ready = false;
     std::atomic<uint64_t> rc_launches{0}, rc_ns{0};               // "decode_row_counts": launches of the session, and their summed time where the batches are timed
+    // PD_DECODE_ALN_STATS (pd_alnstats.h): the open (or last ended) session's PD_ALNSTAT_WORDS sums, zeroed by pd_decode_begin, added to by every batch's
+    // k_aln_stats, read by pd_decode_aln_stats between pd_decode_end and the next pd_decode_begin
+    uint32_t dec_len_bin_width = 0;                               // "decode_len_bin_width": the width of a length bin of the next such session (1 .. 65536), read by pd_decode_begin ...
+    uint32_t as_width = 0;                                        // ... into this
+    unsigned long long *d_alnstat = nullptr; bool as_ready = false;
+    std::atomic<uint64_t> as_launches{0}, as_ns{0};               // "decode_aln_stats": launches of the session, and their summed time where the batches are timed
     pd_decode_cfg dec_cfg{}; uint8_t *d_contig_on = nullptr; uint32_t *d_span_off = nullptr; int32_t *d_spans = nullptr;
     std::vector<RunSeg> run_segs;
     pd_iv *run_first = nullptr, *run_other = nullptr, *run_far = nullptr;   // the concatenated sample (owned until the next reset)

@@ -6,6 +6,7 @@
 #include "pd_ctx.h"
 #include "pd_recstats.h"
 #include "pd_rowcounts.h"
+#include "pd_alnstats.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // GPU-side BAM decode in asynchronous batches (include/pandepth_amd.h: pd_decode_*)
@@ -257,6 +258,15 @@ int begin_record_stats(pd_ctx *c)
     return PD_OK;
 }
 
+// PD_DECODE_ALN_STATS: the session's sums, zeroed (on c->stream, which begin_filters waits for)
+int begin_aln_stats(pd_ctx *c)
+{
+    c->as_width = c->dec_len_bin_width;
+    if (!c->d_alnstat && hipMalloc(&c->d_alnstat, (size_t)PD_ALNSTAT_WORDS * 8 + 64) != hipSuccess) { (void)hipGetLastError(); c->d_alnstat = nullptr; return fail(c, PD_ENOMEM, "pd_decode_begin: allocation failed"); }
+    HIPOK(c, hipMemsetAsync(c->d_alnstat, 0, (size_t)PD_ALNSTAT_WORDS * 8, c->stream));
+    return PD_OK;
+}
+
 // PD_DECODE_ROW_COUNTS: the table pd_decode_row_bins left becomes the session's — offsets and edges go up, the bins are zeroed (on c->stream,
 // which begin_filters waits for; the host copies stay for the next session)
 int begin_row_counts(pd_ctx *c)
@@ -410,6 +420,8 @@ int pd_decode_begin(pd_ctx *c, const pd_decode_cfg *cfg)
     struct BeginMarks { const uint64_t *t; ~BeginMarks() { if (getenv("PANDEPTH_TIMING") && t[5] - t[0] > 20000) fprintf(stderr, "[timing]   pd_decode_begin: tables %.3f s, marks + compose stream %.3f s, sample arrays %.3f s, arena %.3f s, buffers %.3f s\n", (t[1] - t[0]) / 1e6, (t[2] - t[1]) / 1e6, (t[3] - t[2]) / 1e6, (t[4] - t[3]) / 1e6, (t[5] - t[4]) / 1e6); } } begin_marks{tb};
     if ((cfg->flags & PD_DECODE_RECORD_STATS) && !c->dec_isize_bins)      // (refused before anything of the context changes)
         return fail(c, PD_EINVAL, "pd_decode_begin: PD_DECODE_RECORD_STATS needs pd_set_param(\"decode_isize_bins\", N) with 1 <= N <= 65536 first");
+    if ((cfg->flags & PD_DECODE_ALN_STATS) && !c->dec_len_bin_width)
+        return fail(c, PD_EINVAL, "pd_decode_begin: PD_DECODE_ALN_STATS needs pd_set_param(\"decode_len_bin_width\", W) with 1 <= W <= 65536 first");
     if ((cfg->flags & PD_DECODE_ROW_COUNTS) && !c->rb_set)
         return fail(c, PD_EINVAL, "pd_decode_begin: PD_DECODE_ROW_COUNTS needs a bin table: call pd_decode_row_bins first");
     c->dec_cfg = *cfg;
@@ -418,6 +430,8 @@ int pd_decode_begin(pd_ctx *c, const pd_decode_cfg *cfg)
     if (cfg->flags & PD_DECODE_RECORD_STATS) if (int rc = begin_record_stats(c)) return rc;
     c->rc_ready = false; c->rc_launches = 0; c->rc_ns = 0;
     if (cfg->flags & PD_DECODE_ROW_COUNTS) if (int rc = begin_row_counts(c)) return rc;
+    c->as_ready = false; c->as_launches = 0; c->as_ns = 0;
+    if (cfg->flags & PD_DECODE_ALN_STATS) if (int rc = begin_aln_stats(c)) return rc;
     if (int rc = begin_filters(c, cfg)) return rc;
     tb[1] = tb[2] = tb[3] = dec_now_us();
     if (int rc = begin_compact(c, cfg, tb)) return rc;
@@ -639,6 +653,29 @@ void dec_row_counts_time(pd_ctx *c, DecSlot &sl)
     if (hipEventElapsedTime(&ms, sl.ev_rc[0], sl.ev_rc[1]) == hipSuccess) c->rc_ns += (uint64_t)((double)ms * 1e6);
 }
 
+// The CIGAR operations and read lengths of the batch's counted segments (sessions with PD_DECODE_ALN_STATS), at the same two places and with the
+// same gate as dec_record_stats (and behind the other two, where a session carries several of the flags)
+int dec_aln_stats(pd_ctx *c, DecSlot &sl, const pdb2::Seg *d_seg, const pdb2::ChainOut *gate)
+{
+    Job &J = sl.job;
+    if (J.timed) {
+        for (auto &e : sl.ev_as) if (!e) HIPDEC(hipEventCreate(&e));
+        HIPDEC(hipEventRecord(sl.ev_as[0], sl.st));
+    }
+    launch_aln_stats(sl.st, J.cfg, d_seg, J.n_seg, (const pdb2::LaneOut *)sl.d[DS_LANE], c->as_width, c->d_alnstat, gate);
+    if (J.timed) { HIPDEC(hipEventRecord(sl.ev_as[1], sl.st)); J.as_timed = true; }
+    if (!gate) ++c->as_launches;                                          // (a gated launch counts once its batch is known to be confirmed: dec_collect)
+    return PD_OK;
+}
+
+void dec_aln_stats_time(pd_ctx *c, DecSlot &sl)
+{
+    if (!sl.job.as_timed) return;
+    sl.job.as_timed = false;
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, sl.ev_as[0], sl.ev_as[1]) == hipSuccess) c->as_ns += (uint64_t)((double)ms * 1e6);
+}
+
 // Inflate, pass 1 and — where the device confirms the record chain itself — the chain and the emission; otherwise the member statuses and
 // the segments come back for the host's chain check.  *t_inflate (PANDEPTH_DEVTRACE): when the inflate kernel had been launched.
 int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t *members, unsigned n_wg, uint64_t *t_inflate)
@@ -679,6 +716,7 @@ int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t 
         if (J.timed) HIPDEC(hipEventRecord(sl.ev[4], st));
         if (c->dec_cfg.flags & PD_DECODE_RECORD_STATS) if (int rc = dec_record_stats(c, sl, d_seg, d_co)) return rc;
         if (c->dec_cfg.flags & PD_DECODE_ROW_COUNTS) if (int rc = dec_row_counts(c, sl, d_seg, d_co)) return rc;
+        if (c->dec_cfg.flags & PD_DECODE_ALN_STATS) if (int rc = dec_aln_stats(c, sl, d_seg, d_co)) return rc;
     } else {
         HIPDEC(hipMemcpyAsync(pin + J.o.bst, sl.d[DS_ST], (size_t)bt->n_blocks * 4, hipMemcpyDeviceToHost, st));
         HIPDEC(hipMemcpyAsync(pin + J.o.seg, d_seg, (size_t)n_seg * sizeof(pdb2::Seg), hipMemcpyDeviceToHost, st));
@@ -690,7 +728,7 @@ int dec_launch(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt, const uint8_t 
 int dec_queue(pd_ctx *c, DecSlot &sl, const pd_decode_batch *bt)
 {
     Job &J = sl.job;                                                  // (claimed by dec_slot_of: J.open is set)
-    J.queued = false; J.fast = false; J.timed = false; J.segs_sent = false; J.rs_timed = false; J.rc_timed = false; J.t_q0 = dec_now_us(); J.order = bt->order; J.n_bytes = bt->n_bytes; J.inflated = bt->inflated_bytes; J.n_seg = 0;
+    J.queued = false; J.fast = false; J.timed = false; J.segs_sent = false; J.rs_timed = false; J.rc_timed = false; J.as_timed = false; J.t_q0 = dec_now_us(); J.order = bt->order; J.n_bytes = bt->n_bytes; J.inflated = bt->inflated_bytes; J.n_seg = 0;
     J.blocks.clear(); J.units.clear(); J.segs.clear(); J.seg0.clear();
     const bool c8 = J.c8 = c->c8.on;
     J.owes_count = c8 && bt->order < c->c8.n_batches;
@@ -945,6 +983,7 @@ int dec_collect(pd_ctx *c, DecSlot &sl, int32_t *unit_status, pd_decode_result *
     if (int rc = dec_wait(c, sl)) return rc;
     dec_record_stats_time(c, sl);
     dec_row_counts_time(c, sl);
+    dec_aln_stats_time(c, sl);
     if (J.fast) {
         pdb2::ChainOut co;
         memcpy(&co, pin + J.o.co, sizeof co);
@@ -952,6 +991,7 @@ int dec_collect(pd_ctx *c, DecSlot &sl, int32_t *unit_status, pd_decode_result *
         if (!co.slow) {
             if (c->dec_cfg.flags & PD_DECODE_RECORD_STATS) ++c->rs_launches;      // (the gated k_record_stats of dec_launch counted this batch; one the gate stopped is not a launch of the counter)
             if (c->dec_cfg.flags & PD_DECODE_ROW_COUNTS) ++c->rc_launches;        // (k_row_counts likewise)
+            if (c->dec_cfg.flags & PD_DECODE_ALN_STATS) ++c->as_launches;         // (k_aln_stats likewise)
             return collect_confirmed(c, sl, co, res);
         }
         // ---- out of the ordinary (ChainOut::slow says why; nothing was emitted): the member statuses and the segments as they stand come
@@ -980,7 +1020,7 @@ int dec_collect(pd_ctx *c, DecSlot &sl, int32_t *unit_status, pd_decode_result *
         HIPDEC(hipMemcpyAsync(pin + J.o.ord, sl.d[DS_ONLY], 24, hipMemcpyDeviceToHost, st));
     }
     if (J.timed) HIPDEC(hipEventRecord(sl.ev[4], st));
-    if ((c->dec_cfg.flags & (PD_DECODE_RECORD_STATS | PD_DECODE_ROW_COUNTS)) && counted_records(J)) {
+    if ((c->dec_cfg.flags & (PD_DECODE_RECORD_STATS | PD_DECODE_ROW_COUNTS | PD_DECODE_ALN_STATS)) && counted_records(J)) {
         // the records of the counted units (the segments of the others carry RS_SKIP); the segments go up where the emission had none to send
         pdb2::Seg *d_seg = (pdb2::Seg *)((J.d_tab ? J.d_tab : (uint8_t *)sl.d[DS_BLK]) + J.o.seg);
         if (!J.segs_sent) {
@@ -990,11 +1030,13 @@ int dec_collect(pd_ctx *c, DecSlot &sl, int32_t *unit_status, pd_decode_result *
         }
         if (c->dec_cfg.flags & PD_DECODE_RECORD_STATS) if (int rc = dec_record_stats(c, sl, d_seg, nullptr)) return rc;
         if (c->dec_cfg.flags & PD_DECODE_ROW_COUNTS) if (int rc = dec_row_counts(c, sl, d_seg, nullptr)) return rc;
+        if (c->dec_cfg.flags & PD_DECODE_ALN_STATS) if (int rc = dec_aln_stats(c, sl, d_seg, nullptr)) return rc;
     }
     HIPDEC(hipStreamSynchronize(st));
     HIPDEC(hipGetLastError());
     dec_record_stats_time(c, sl);
     dec_row_counts_time(c, sl);
+    dec_aln_stats_time(c, sl);
     if (nf && !J.c8) {
         memcpy(order_words, pin + J.o.ord, 24);
         rs.unsorted = order_words[0];
@@ -1285,6 +1327,7 @@ int pd_decode_end(pd_ctx *c)
     HIPOK(c, hipSetDevice(c->device));
     for (auto &sl : c->dec) if (sl.st) HIPOK(c, hipStreamSynchronize(sl.st));      // (the last copies of the batches' runs to their arrays)
     c->rc_ready = (c->dec_cfg.flags & PD_DECODE_ROW_COUNTS) != 0;                  // (... and every batch's k_row_counts: pd_decode_row_counts)
+    c->as_ready = (c->dec_cfg.flags & PD_DECODE_ALN_STATS) != 0;                   // (... and every batch's k_aln_stats: pd_decode_aln_stats)
     c->rs_ready = (c->dec_cfg.flags & PD_DECODE_RECORD_STATS) != 0;                // (every batch's k_record_stats is through: pd_decode_record_stats)
     std::vector<RunSeg> segs;
     { std::lock_guard<std::mutex> l2(c->dec_mu); segs.swap(c->run_segs); }
@@ -1309,6 +1352,8 @@ int pd_decode_end(pd_ctx *c)
         fprintf(stderr, "[timing]   k_record_stats: %llu launches, %.3f ms summed over the batches\n", (unsigned long long)c->rs_launches.load(), (double)c->rs_ns.load() / 1e6);
     if (getenv("PANDEPTH_TIMING") && c->rc_ready)                    // (the rows' pass: decode_row_counts)
         fprintf(stderr, "[timing]   k_row_counts: %llu launches, %.3f ms summed over the batches\n", (unsigned long long)c->rc_launches.load(), (double)c->rc_ns.load() / 1e6);
+    if (getenv("PANDEPTH_TIMING") && c->as_ready)                    // (the CIGAR pass: decode_aln_stats)
+        fprintf(stderr, "[timing]   k_aln_stats: %llu launches, %.3f ms summed over the batches\n", (unsigned long long)c->as_launches.load(), (double)c->as_ns.load() / 1e6);
     return rc;
 }
 
@@ -1329,6 +1374,24 @@ int pd_decode_abort(pd_ctx *c)
         for (auto &sl : c->dec) if (sl.st) (void)hipStreamSynchronize(sl.st);
         (void)hipMemset(c->d_rowcnt, 0, c->rowcnt_words * 8);
     }
+    c->as_ready = false;
+    if (c->d_alnstat && (c->dec_cfg.flags & PD_DECODE_ALN_STATS)) {               // (... and their CIGARs)
+        for (auto &sl : c->dec) if (sl.st) (void)hipStreamSynchronize(sl.st);
+        (void)hipMemset(c->d_alnstat, 0, (size_t)PD_ALNSTAT_WORDS * 8);
+    }
+    return PD_OK;
+}
+
+int pd_decode_aln_stats(pd_ctx *c, uint64_t *sums, size_t n_sums)
+{
+    if (!c) return PD_EINVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!(c->dec_cfg.flags & PD_DECODE_ALN_STATS) || !c->as_ready || !c->d_alnstat)
+        return fail(c, PD_EINVAL, "pd_decode_aln_stats: no session with PD_DECODE_ALN_STATS has been ended by pd_decode_end since the last pd_decode_begin");
+    if (!sums || n_sums != (size_t)PD_ALNSTAT_WORDS)
+        return fail(c, PD_EINVAL, "pd_decode_aln_stats: sums must hold PD_ALNSTAT_WORDS = " + std::to_string((size_t)PD_ALNSTAT_WORDS) + " words");
+    HIPOK(c, hipSetDevice(c->device));
+    HIPOK(c, hipMemcpy(sums, c->d_alnstat, (size_t)PD_ALNSTAT_WORDS * 8, hipMemcpyDeviceToHost));
     return PD_OK;
 }
 

@@ -253,5 +253,8 @@ void launch_record_stats(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *
 // the records per row of the main table (pd_rowcounts.h; k_row_counts), likewise: the session's bin table and its bins of PD_ROWCOUNT_WORDS words
 void launch_row_counts(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes, const pdrc::Bins &bins,
                        unsigned long long *counts, const pdb2::ChainOut *gate /* as launch_emit_segments' */);
+// the CIGAR operations and read lengths of a batch's counted segments (pd_alnstats.h; k_aln_stats), likewise: the width of a length bin, the session's PD_ALNSTAT_WORDS sums
+void launch_aln_stats(hipStream_t st, const pdb2::Cfg &cfg, const pdb2::Seg *segs, uint32_t n_seg, const pdb2::LaneOut *lanes, uint32_t width,
+                      unsigned long long *sums, const pdb2::ChainOut *gate /* as launch_emit_segments' */);
 }
 #endif

@@ -89,6 +89,8 @@ typedef struct pd_engine_api {
     /* optional, both or neither (NULL = the host readers take an input under -rowreads): the records per row of a decode session, see pd_decode_row_bins */
     int (*decode_row_bins)(pd_ctx *, uint32_t, const uint64_t *, const uint32_t *);
     int (*decode_row_counts)(pd_ctx *, uint64_t *, size_t);
+    /* optional (NULL = the host readers take an input under -alnstats): the CIGAR operations and read lengths of a decode session, see pd_decode_aln_stats */
+    int (*decode_aln_stats)(pd_ctx *, uint64_t *, size_t);
 } pd_engine_api;
 
 /* Runs one `pandepth` invocation (argv as given to main) on the engine behind `api`. */

@@ -1,4 +1,4 @@
-// extras.cpp — the outputs the reference does not have: -dist, -levels, -quantile, -thresholds, -gcbias, -readstats and -rowreads.  Each is made after the main table is
+// extras.cpp — the outputs the reference does not have: -dist, -levels, -quantile, -thresholds, -gcbias, -readstats, -rowreads and -alnstats.  Each is made after the main table is
 // written and the per-site job started, so that their path and timing stay as they are; each is one entry of EXTRAS, which the
 // finish step of every table family and the exit for a PAF without targets (pipeline.cpp) walk in order.
 #include <string.h>
@@ -606,6 +606,29 @@ bool write_readstats(Run &r)
     return true;
 }
 
+// -alnstats W: the CIGAR operations and read lengths of the records, in <prefix>.aln.stat.gz.  As -readstats: the numbers are the contexts'
+// accumulators (Engine::as, fed by the device's k_aln_stats or by the host readers as every input was read); nothing is asked of the engine here.
+std::string alnstats_empty(const Run &r)
+{
+    AlnStats z;
+    z.init(r.o.flag_mask, r.o.min_mapq, r.o.alnstats, (int32_t)r.hdr.names.size());
+    return z.text();
+}
+
+bool write_alnstats(Run &r)
+{
+    AlnStats all;
+    all.init(r.o.flag_mask, r.o.min_mapq, r.o.alnstats, (int32_t)r.hdr.names.size());
+    for (auto &e : r.engs) all.merge(e->as);
+    GzWriter G;
+    const std::string path = r.prefix + ".aln.stat.gz";
+    if (!G.open(path)) { r.eng->fail("cannot open " + path); return false; }
+    G.write(all.text());
+    if (!G.close()) { ::remove(path.c_str()); r.eng->fail("cannot write " + path); return false; }
+    r.tm.mark("alignment statistics");
+    return true;
+}
+
 // -rowreads: the records that START in every row of the main table, in <prefix>.rowreads.stat.gz — -quantile's rows and identity columns,
 // then Records Passed MapQ0 Kept Forward MeanMapQ (rowcounts.h).  The numbers are the contexts' accumulators over the run's bins
 // (Engine::rc, fed by the device's k_row_counts or by the host readers as every input was read): nothing is asked of the engine here.
@@ -714,6 +737,7 @@ const Extra EXTRAS[] = {
     {".gcbias.stat.gz", [](const Options &o) { return o.gcbias != 0; }, gcbias_empty, write_gcbias},
     {".reads.stat.gz", [](const Options &o) { return o.readstats != 0; }, readstats_empty, write_readstats},
     {".rowreads.stat.gz", [](const Options &o) { return o.rowreads; }, rowreads_header, write_rowreads},
+    {".aln.stat.gz", [](const Options &o) { return o.alnstats != 0; }, alnstats_empty, write_alnstats},
 };
 const size_t N_EXTRAS = sizeof(EXTRAS) / sizeof(EXTRAS[0]);
 

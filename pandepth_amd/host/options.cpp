@@ -251,6 +251,15 @@ int parse_options(int argc, char **argv, Options *o)
             if (!good || x < 1 || x > 65536) { std::cerr << msg << std::endl; return 0; }
             o->readstats = (uint32_t)x;
         }
+        else if (flag == "alnstats") {                                           // not in the reference: the .aln.stat.gz statistics of the records' CIGARs (README)
+            const char *msg = "Error: -alnstats should be the width of a length bin, from 1 to 65536";
+            if (i + 1 == argc) { std::cerr << msg << std::endl; return 0; }
+            v = argv[++i];
+            uint64_t x = 0; bool good = !v.empty() && v.size() <= 5;
+            for (size_t k = 0; good && k < v.size(); ++k) { if (v[k] < '0' || v[k] > '9') good = false; else x = x * 10 + (uint64_t)(v[k] - '0'); }
+            if (!good || x < 1 || x > 65536) { std::cerr << msg << std::endl; return 0; }
+            o->alnstats = (uint32_t)x;
+        }
         else if (flag == "rowreads") {                                           // not in the reference: the .rowreads.stat.gz record counts of the table's rows (README)
             if (o->rowreads) { std::cerr << "Error: -rowreads takes no value and is given once" << std::endl; return 0; }
             o->rowreads = true;

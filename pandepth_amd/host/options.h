@@ -1,4 +1,4 @@
-// options.h — the command-line surface of `pandepth` (-i -o -g -f -b -w -a -q -d -x -t -s -c -r -h; of its own: -dist -levels -quantile -thresholds -gcbias -del -frag -fragmax -readstats -rowreads);
+// options.h — the command-line surface of `pandepth` (-i -o -g -f -b -w -a -q -d -x -t -s -c -r -h; of its own: -dist -levels -quantile -thresholds -gcbias -del -frag -fragmax -readstats -rowreads -alnstats);
 // -i takes SAM / BAM / CRAM 2.1 / 3.0 / 3.1 / PAF files or a #.list of them.
 // Behaviour follows the reference's parser (PD:84-293) including its quirks: every '-' is
 // stripped from a flag, `*.list`/`*.List` expands to one input per non-empty line, -w < 1 and
@@ -37,6 +37,7 @@ struct Options {
     uint32_t frag_max = 0x7FFFFFFFu;     // -fragmax N, 1 .. 2^31 - 1 (needs -frag): pairs with |tlen| above it are two ordinary reads
     uint32_t gcbias = 0;                 // -gcbias W (not in the reference; needs -r): <out>.gcbias.stat.gz, depth by GC content of windows of W cells, 1 .. 2^20 (0: off)
     uint32_t readstats = 0;              // -readstats N (not in the reference): <out>.reads.stat.gz, what the records were — classes, flag bits, per contig, MAPQ, insert sizes 1 .. N-1 and >= N; 1 .. 65536 (0: off)
+    uint32_t alnstats = 0;               // -alnstats W (not in the reference): <out>.aln.stat.gz, the CIGAR operations, indel lengths, read lengths (N50) and aligned fractions of the records, in length bins of W bases; 1 .. 65536 (0: off)
     bool rowreads = false;               // -rowreads (not in the reference): <out>.rowreads.stat.gz, the records that start in every row of the main table — counts by filter class, strand, mean MAPQ
     std::vector<uint32_t> thresholds;    // -thresholds SPEC (not in the reference): <out>.thresholds.stat.gz, per-row counts of cells at or above each depth; 1..16 values below 2^31, strictly ascending
 };

@@ -163,6 +163,14 @@ struct RecStatsPart {
     RecStats *ptr() { return mine.on ? &mine : nullptr; }
 };
 
+// -alnstats likewise
+struct AlnStatsPart {
+    Engine *e; AlnStats mine;
+    explicit AlnStatsPart(Engine *eng) : e(eng) { mine.init_like(eng->as); }
+    ~AlnStatsPart() { if (mine.on) { std::lock_guard<std::mutex> lk(e->as_mu); e->as.merge(mine); } }
+    AlnStats *ptr() { return mine.on ? &mine : nullptr; }
+};
+
 // htslib multi-region fetch of "chr:max(s-1,1)-min(e+1,len)" for every merged span (PD:419-430):
 // a read is returned when pos < region_end && endpos > region_begin0.
 struct SpanIndex {
@@ -202,7 +210,7 @@ bool index_exists(const std::string &p) { return file_exists(p + ".bai") || file
 // ---- readers ---------------------------------------------------------------------------------
 // records that START in [begin, stop) of an open BAM, through the host decoder
 bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter &flt, const struct SpanIndex &spans,
-                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag, RecStats *rs, RowCountsShare *rc);
+                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag, RecStats *rs, RowCountsShare *rc, AlnStats *as);
 
 struct DevRange;
 int read_bam_device(const std::string &path, const Options &o, const AlnHeader &main_hdr, const SpanIndex &spans, const RegionModel &rm,
@@ -294,6 +302,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
             tally{n_rec, busy_us, my_rec, w0};
         RecStatsPart part(eng);                              // (-readstats: this thread's records, merged when it is through — like the tally)
         RowCountsShare rows(&eng->rc);                       // (-rowreads: this thread's records go into the context's bins, its open bin flushed when it is through)
+        AlnStatsPart aln(eng);                               // (-alnstats: as -readstats)
         AlnReader rd;
         std::string e2;
         if (!rd.open(path, &e2)) { eng->fail(e2); return; }
@@ -303,7 +312,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
             if (t >= n_tasks || !eng->ok()) break;
             for (size_t w = tasks[t].first; w < tasks[t].second; ++w) {
                 std::string e3;
-                if (!decode_range(rd, work[w].first, work[w].second, flt, spans, &sink, &my_rec, &e3, o.count_del, frag, part.ptr(), rows.ptr())) { eng->fail(e3 + " (" + path + ")"); return; }
+                if (!decode_range(rd, work[w].first, work[w].second, flt, spans, &sink, &my_rec, &e3, o.count_del, frag, part.ptr(), rows.ptr(), aln.ptr())) { eng->fail(e3 + " (" + path + ")"); return; }
             }
         }
     };
@@ -320,7 +329,7 @@ bool read_indexed(const std::string &path, const Options &o, const AlnHeader &ma
 }
 
 bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter &flt, const SpanIndex &spans,
-                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag, RecStats *rs, RowCountsShare *rc)
+                  RunSink *sink, uint64_t *n_rec, std::string *err, bool count_del, const FragRule &frag, RecStats *rs, RowCountsShare *rc, AlnStats *as)
 {
     if (!rd.seek(begin)) { *err = "seek failed"; return false; }
     AlnRec r;
@@ -332,6 +341,7 @@ bool decode_range(AlnReader &rd, uint64_t begin, uint64_t stop, const ReadFilter
         ++*n_rec;
         if (rs) rs->add(r);
         if (rc) rc->add(r);
+        if (as) as->add(r);
         if (!flt.pass(r)) continue;
         if (!spans.hit(r, frag)) continue;
         emit_runs(r, sink, count_del, frag);
@@ -362,6 +372,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
     if (!api->decode_begin || !api->decode_acquire || !api->decode_submit || !api->decode_end || !api->decode_abort) return 0;
     if (o.readstats && (!api->decode_record_stats || !api->set_param)) return 0;      // (an engine that does not count records: the host readers do)
     if (o.rowreads && (!api->decode_row_bins || !api->decode_row_counts)) return 0;    // (... or not per row)
+    if (o.alnstats && (!api->decode_aln_stats || !api->set_param)) return 0;           // (... or opens no CIGAR for statistics)
     if (const char *e = tune("device_decode")) if (e[0] == '0') return 0;
     if (kind != 0 && !spans.synthetic) return 0;            // the no-index span cursor (PD:4608-4646) stays on the host
     const uint64_t F = file_size(path);
@@ -451,6 +462,10 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
     if (o.readstats) {                                       // (the bins travel as a parameter, like -fragmax)
         cfg.flags |= PD_DECODE_RECORD_STATS;
         if (api->set_param(eng->ctx, "decode_isize_bins", o.readstats) != 0) return 0;
+    }
+    if (o.alnstats) {                                        // (the width of a length bin travels as a parameter, like the insert bins)
+        cfg.flags |= PD_DECODE_ALN_STATS;
+        if (api->set_param(eng->ctx, "decode_len_bin_width", o.alnstats) != 0) return 0;
     }
     if (o.rowreads) {                                        // (the run's bin table; an engine that refuses it — more than 2^28 bins — leaves the input to the host readers)
         const RowBins &rb = *eng->rc.tab;
@@ -769,6 +784,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
         auto host_worker = [&]() {
             RecStatsPart part(eng);                          // (-readstats: the device did not count the units it handed back; the host reader that decodes them does)
             RowCountsShare rows(&eng->rc);                   // (-rowreads likewise, into the context's bins)
+            AlnStatsPart aln(eng);                           // (-alnstats likewise)
             AlnReader rd; std::string e2;
             if (!rd.open(path, &e2)) { eng->fail(e2); return; }
             RunSink sink(eng);
@@ -776,7 +792,7 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
                 const size_t i = nb.fetch_add(1);
                 if (i >= backlog.size() || !eng->ok()) break;
                 uint64_t nr = 0;
-                if (!decode_range(rd, backlog[i].first, backlog[i].second, flt, spans, &sink, &nr, &e2, o.count_del, frag, part.ptr(), rows.ptr())) { eng->fail(e2 + " (" + path + ")"); break; }
+                if (!decode_range(rd, backlog[i].first, backlog[i].second, flt, spans, &sink, &nr, &e2, o.count_del, frag, part.ptr(), rows.ptr(), aln.ptr())) { eng->fail(e2 + " (" + path + ")"); break; }
                 n_host += nr;
             }
         };
@@ -796,6 +812,13 @@ int read_bam_device(const std::string &path, const Options &o, const AlnHeader &
         if (!eng->ck(api->decode_record_stats(eng->ctx, dev.sums.data(), dev.sums.size(), dev.per.data()), "pd_decode_record_stats")) return -1;
         { std::lock_guard<std::mutex> lk(eng->rs_mu); eng->rs.merge(dev); }
         if (getenv("PANDEPTH_TIMING")) fprintf(stderr, "[timing]   record statistics: %llu records counted on the device\n", (unsigned long long)dev.sums[RecStats::RECORDS]);
+    }
+    if (o.alnstats) {
+        // the session's CIGAR statistics (every unit the device counted; the backlog's records were added above)
+        AlnStats dev; dev.init_like(eng->as);
+        if (!eng->ck(api->decode_aln_stats(eng->ctx, dev.sums.data(), dev.sums.size()), "pd_decode_aln_stats")) return -1;
+        { std::lock_guard<std::mutex> lk(eng->as_mu); eng->as.merge(dev); }
+        if (getenv("PANDEPTH_TIMING")) fprintf(stderr, "[timing]   alignment statistics: %llu records counted on the device\n", (unsigned long long)dev.sums[AlnStats::RECORDS]);
     }
     if (o.rowreads) {
         // the session's records per bin (every unit the device counted; the backlog's records were added above)
@@ -828,6 +851,7 @@ bool read_sorted_stream(AlnReader *rd, const Options &o, const AlnHeader &main_h
     while ((k = rd->next(&r)) > 0) {
         if (eng->rs.on) eng->rs.add(r);
         if (eng->rc.on) eng->rc.add(r);
+        if (eng->as.on) eng->as.add(r);
         if (over) continue;
         if (r.tid < 0 || r.tid >= n) continue;       // the reference indexes EndChr[tid] here (UB for tid = -1)
         if (done[r.tid]) continue;
@@ -844,7 +868,7 @@ bool read_sorted_stream(AlnReader *rd, const Options &o, const AlnHeader &main_h
                 bool all = true;
                 for (int32_t i = 0; i < n; ++i) if (!done[i]) { all = false; break; }
                 if (all) {                           // this read is NOT counted (PD:4641-4644)
-                    if (!eng->rs.on && !eng->rc.on) break;
+                    if (!eng->rs.on && !eng->rc.on && !eng->as.on) break;
                     over = true; continue;           // (-readstats / -rowreads read on to the end of the input)
                 }
             }
@@ -866,6 +890,7 @@ bool read_all(AlnReader *rd, const Options &o, const AlnHeader &main_hdr, const 
     while ((k = rd->next(&r)) > 0) {
         if (eng->rs.on) eng->rs.add(r);
         if (eng->rc.on) eng->rc.add(r);
+        if (eng->as.on) eng->as.add(r);
         if (!flt.pass(r)) continue;
         if (!rm.has(r.tid)) continue;                // depth on contigs without targets is never reported
         emit_runs(r, &sink, o.count_del, frag);
@@ -1728,6 +1753,7 @@ int create_contexts(Run &r)
         }
     r.eng = r.engs[0].get();
     if (r.o.readstats) for (auto &e : r.engs) e->rs.init(r.o.flag_mask, r.o.min_mapq, r.o.readstats, (int32_t)r.hdr.names.size());
+    if (r.o.alnstats) for (auto &e : r.engs) e->as.init(r.o.flag_mask, r.o.min_mapq, r.o.alnstats, (int32_t)r.hdr.names.size());
     if (r.o.rowreads) {
         rowreads_bins(r, &r.row_bins);
         for (auto &e : r.engs) e->rc.init(r.o.flag_mask, r.o.min_mapq, &r.row_bins);
@@ -2139,6 +2165,19 @@ extern "C" int pandepth_main(int argc, char **argv, const pd_engine_api *api, in
             }
             if (r.o.mode >= 1 && r.o.mode <= 4 && r.o.use_index && index_exists(fp)) {
                 std::cerr << "Error: -rowreads with -g/-b needs -s (an index fetch reads only the targets' records): " << fp << std::endl;
+                return 1;
+            }
+        }
+    if (r.o.alnstats)
+        // -alnstats sums the CIGARs of every record of every input once, which takes the same run that reads the whole file; CRAM's reader rebuilds a CIGAR's
+        // shape from read features (= / X come back as M: not the file's operations) and PAF has neither flags nor clips — refused per input, likewise
+        for (const std::string &fp : r.o.inputs) {
+            if (is_paf_path(fp) || CramReader::is_cram(fp)) {
+                std::cerr << "Error: -alnstats reads SAM and BAM only (" << (is_paf_path(fp) ? "PAF has neither flags nor clips" : "the CIGARs of CRAM input are rebuilt, not the file's operations") << "): " << fp << std::endl;
+                return 1;
+            }
+            if (r.o.mode >= 1 && r.o.mode <= 4 && r.o.use_index && index_exists(fp)) {
+                std::cerr << "Error: -alnstats with -g/-b needs -s (an index fetch reads only the targets' records): " << fp << std::endl;
                 return 1;
             }
         }

@@ -19,6 +19,7 @@
 #include "engine_api.h"
 #include "fasta.h"
 #include "options.h"
+#include "alnstats.h"
 #include "recstats.h"
 #include "regions.h"
 #include "report.h"
@@ -46,6 +47,7 @@ struct Engine {
     std::mutex err_mu;
     std::string err;
     RecStats rs; std::mutex rs_mu;              // -readstats: the records of this context's inputs (threaded readers merge theirs under rs_mu)
+    AlnStats as; std::mutex as_mu;              // -alnstats: the CIGAR operations and read lengths of this context's inputs (likewise)
     RowCounts rc; std::mutex rc_mu;             // -rowreads: the same per bin of the run's table (Run::row_bins)
     std::atomic<bool> cancel{false};            // the run is being abandoned: a writer working behind the statistics stops where it is
     void fail(const std::string &m) { std::lock_guard<std::mutex> lk(err_mu); if (err.empty()) err = m; }
@@ -134,7 +136,7 @@ inline std::vector<const GeneEntry *> genes_in_table_order(const std::map<std::s
     return order;
 }
 
-// extras.cpp — the outputs the reference does not have (-dist, -levels, -quantile, -thresholds, -gcbias, -readstats, -rowreads), one entry each
+// extras.cpp — the outputs the reference does not have (-dist, -levels, -quantile, -thresholds, -gcbias, -readstats, -rowreads, -alnstats), one entry each
 struct Extra {
     const char *suffix;                          // <prefix><suffix>
     bool (*enabled)(const Options &o);
