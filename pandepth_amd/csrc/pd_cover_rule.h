@@ -227,4 +227,54 @@ PD_COVER_HD inline bool chunk_fast(const uint16_t *nar, NarState &st, int tile)
     return true;
 }
 
+// ---- the sweeps' software pipeline: three register buffers of N words in turn, no copies (the kernel's sweeps; tests/harness/sweep3_check.cpp on the CPU) ----
+// PRECONDITION: nq >= 1 (both callers ask `if (nq)`; for nq = 0 nothing would be worked on, and the kernel's loads clamp a chunk's number to nq - 1).
+// load(x, q) fills x with chunk q and also serves q >= nq (the kernel: all lanes to one place); work(x, q) is called for the chunks 0 .. min(nq - 1, the chunk
+// behind which stop() first says true), in order, each with the buffer load(., q) filled; primed() runs behind the first two loads' issue.
+// Two chunks stay in flight behind the one worked on: the wait in front of work(., q) must count the loads of chunks q + 1 and q + 2 and nothing else.
+// The loop has ONE exit, at its bottom, and every load of a rotation is issued whatever the rotation meets.  A software-pipelined loop with an exit behind every
+// chunk gets all its exits routed through the latch block by this compiler, and the pass that places the waits, which is not path-sensitive, then takes the state
+// of "left behind the first chunk" (the load into C the newest one pending) for the back edge's: it drains EVERY load (vmcnt(0)) in front of the load at the
+// loop's top, every third chunk (profiles/r20_sweep_inflight_isa.txt).  With one exit every wait counts what it should.
+// The loop runs WHOLE rotations only (q + 3 <= nq), so it loads no chunk beyond nq + 1, and the last one or two chunks, by then in A and B, are worked on
+// behind it without a load: a one-exit loop that runs to the last chunk issues up to two loads more behind it, and the wait that ends the sweep then pays
+// a whole round trip per tile — measured slower than the loop with three exits (0.693 -> 0.705 ms a step; profiles/r20_sweep_inflight_ab.txt, section 2).  A stop() inside a rotation skips the
+// rotation's remaining work, not its loads.
+// The sweep ends with nothing in flight, so that the next sweep's waits count its own loads only.
+PD_COVER_HD inline void sweep_drain()
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0)
+#endif
+}
+template <int N, class Load, class Work, class Stop, class Primed>
+PD_COVER_HD inline __attribute__((always_inline)) void sweep3(const Load &load, const Work &work, const uint32_t nq, const Stop &stop, const Primed &primed)
+{
+    uint32_t A[N], B[N], C[N];
+    uint32_t q = 0;
+    bool go = true;
+    load(A, 0u);
+    load(B, 1u);
+    primed();
+    if (nq >= 3u) {
+#pragma unroll 1
+        for (;;) {
+            load(C, q + 2u);
+            work(A, q);
+            go = !stop();
+            load(A, q + 3u);
+            if (go) { work(B, q + 1u); go = !stop(); }
+            load(B, q + 4u);
+            if (go) { work(C, q + 2u); go = !stop(); }
+            q += 3u;
+            if (!go || q + 3u > nq) break;
+        }
+    }
+    if (go && q < nq) {
+        work(A, q);
+        if (q + 1u < nq && !stop()) work(B, q + 1u);
+    }
+    sweep_drain();
+}
+
 } // namespace pdcover

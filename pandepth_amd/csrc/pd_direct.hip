@@ -1108,32 +1108,9 @@ __device__ __forceinline__ void chunk_keep_own(uint32_t (&x)[N], const int skip,
 #pragma unroll
     for (int k = 0; k < N; ++k) x[k] = k >= skip ? x[k] : neutral;
 }
-// Three register buffers of N words in turn, no copies: two chunks are in flight behind the one worked on (one wave streams a tile by itself, and a CU's 28 waves
-// must keep HBM's latency covered).  load(x, q) also serves q >= nq, all lanes to one place; primed() runs behind the first two loads' issue; stop() ends the sweep.
-template <int N, class Load, class Work, class Stop, class Primed>
-__device__ __forceinline__ void sweep3(const Load &load, const Work &work, const uint32_t nq, const Stop &stop, const Primed &primed)
-{
-    uint32_t A[N], B[N], C[N];
-    uint32_t q = 0;
-    load(A, 0u);
-    load(B, 1u);
-    primed();
-#pragma unroll 1
-    for (;;) {
-        load(C, q + 2u);
-        work(A, q);
-        if (++q >= nq || stop()) break;
-        load(A, q + 2u);
-        work(B, q);
-        if (++q >= nq || stop()) break;
-        load(B, q + 2u);
-        work(C, q);
-        if (++q >= nq || stop()) break;
-    }
-    // nothing of this tile stays in flight: the next sweep's waits then count its own loads only (left pending, the loads issued
-    // last make the compiler wait for ALL loads at the loop's top, every third chunk: measured)
-    __builtin_amdgcn_s_waitcnt(0x0F70);                            // vmcnt(0)
-}
+// The chunks go through pdcover::sweep3 (pd_cover_rule.h): three register buffers of N words in turn, no copies, two chunks in flight behind the one worked on
+// (one wave streams a tile by itself, and a CU's 28 waves must keep HBM's latency covered).  load(x, q) also serves q >= nq, all lanes to one place.
+using pdcover::sweep3;
 
 // ---- cover pass: the rule on one chunk of eight runs per lane, tile-relative begins b and ends e (pd_cover_rule.h, ONE segment) ----
 // sorted: a run that begins beyond the reach is a gap; one max-scan and one wave_shr:1 give a lane the largest end of the lanes before it, eight compares are
@@ -1366,7 +1343,9 @@ __device__ __forceinline__ GateOut cover_gate(const uint32_t (&set)[4] /* LDS */
 //  * what the cover pass derives from the lane (`ln`) and what the window path derives from the thread's number (`tix`) is formed INSIDE that part, from a number
 //    made opaque there, not kept in registers across the other part — hoisted out of the walk those values went to scratch;
 //  * the tile size a settled tile is written with (`all`) is set where it is written: as a constant it is kept in a register pair from the kernel's top, and spilled;
-//  * a sweep's three run buffers live inside sweep3, the window fill's two in the branch that uses them: never at the kernel's top;
+//  * a sweep's three run buffers live inside pdcover::sweep3, the window fill's two in the branch that uses them: never at the kernel's top;
+//  * sweep3 (pd_cover_rule.h) is whole rotations with ONE exit and a tail that works on the last one or two chunks from A and B without a load: the loop
+//    holds three copies of a sweep's work and the tail two more, in the same 61 / 64 registers (the buffers are the loop's; the tail declares none);
 //  * sweep3 ends with vmcnt(0), so that no sweep's loads are counted by the next one's waits.
 template <int WPE, int UN8, bool EXPORT, bool JOIN = false, int LW = 1, bool COVER = false, bool NARROW = false>
 __global__ __launch_bounds__(WG, WPE) void k_direct_c8(const C8Sample cs, const TileDesc *__restrict__ desc, uint32_t n_tiles,

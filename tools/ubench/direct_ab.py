@@ -45,11 +45,12 @@ for vs in variants:
     if compact: vs = vs[1:]
     v = int(vs.split("@")[0].split("/")[0])
     eng.set_param("grid_tiles", int(vs.split("@")[1]) if "@" in vs else 0)
-    opts = vs.split("/")[1:]                                  # /s64 = direct_sample 64, /l160 = lmax 160, /k0 = direct_cover 0 (k_direct_c8 without the cover pass), /m0 = direct_cover_min 0
+    opts = vs.split("/")[1:]                                  # /s64 = direct_sample 64, /l160 = lmax 160, /k0 = direct_cover 0 (k_direct_c8 without the cover pass), /m0 = direct_cover_min 0, /n0 = cover_narrow 0
     cover = next((int(o[1:]) for o in opts if o[0] == "k"), 1)
     try:
         eng.set_param("direct_cover", cover)
         eng.set_param("direct_cover_min", next((int(o[1:]) for o in opts if o[0] == "m"), 2048))
+        eng.set_param("cover_narrow", next((int(o[1:]) for o in opts if o[0] == "n"), 1))   # /n0: the wide cover sweep
     except Exception:                                         # (a library from before the knob, chosen with PANDEPTH_AMD_LIB: its kernel IS the /k0 form,
         if cover: raise                                       #  so only /k0 may be asked of it)
     eng.set_param("direct_sample", next((int(o[1:]) for o in opts if o[0] == "s"), 256))
